@@ -10,8 +10,16 @@ the reference's own witness needs its Rust + Go toolchain, so every number here 
   * SHPLONK + Blake2b as at [REF circuit-benchmarks/src/super_circuit.rs:117-132];
   * the witness columns are RESIDENT IN HBM when the timed region starts (zk_proof_advice_phase_dev).  The same proof from
     page-locked host memory (what a Rust caller hands over) is timed beside it: `pcie_inclusive_s`.
-`value` = seconds per proof over the K timed steps (lower is better), the proof checked afterwards by the oracle verifier
-(outside the timed region).  The same line carries
+`value` = seconds per proof over the K timed steps (lower is better); `ms_per_step` = the same in milliseconds.
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what that figure needs: it builds the circuit, key and
+resident witness, runs W warm-up proofs and the K timed ones, and prints one short line (metric, value, unit, ms_per_step,
+dtype, config, the last proof's size and SHA-256).  `--dump-outputs DIR` writes what the last timed proof handed its caller:
+DIR/proof.npy (the proof's bytes) and DIR/challenges.npy (the three challenges the advice phases returned, 32 little-endian
+bytes each), both float32; the inputs are seeded, so two builds can be compared output for output.
+
+`--full` adds everything else, as before: the proof checked by the oracle verifier (outside the timed region), HIP events on
+the kernel classes over the timed region, and the side measurements.  The full line carries
   * `roofline`   -- the dominant kernel class of the proof, the size-2^20 NTT (k_ntt_pass + k_ntt_last), HIP events over the
                     timed region; `rooflines` -- MSM bucket accumulation and the quotient evaluator beside it;
   * `proof_roofline` -- sum of the algorithmic bytes of the proof's stages (SURVEY 8d, K1-K10 counts) / wall-clock / 8 TB/s;
@@ -75,7 +83,7 @@ WORKLOAD = workload_text(HEADLINE_SHAPE)
 
 
 class _NoTorch:
-    """stands in for torch in a prover process that must not load it (`--proof-worker`): the library's own sync is the fence"""
+    """stands in for torch where it is not loaded (`--proof-worker`, a plain single-GPU run): the library's own sync is the fence"""
     class cuda:
         @staticmethod
         def synchronize():
@@ -89,10 +97,22 @@ def relaunch_under_launcher(args) -> int:
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch)]
-    for flag in ("no_cpu_baseline", "no_proof", "no_verify", "no_msm_ntt"):
+    for flag in ("full", "no_cpu_baseline", "no_proof", "no_verify", "no_msm_ntt"):
         if getattr(args, flag, False):
             cmd.append("--" + flag.replace("_", "-"))
+    if getattr(args, "dump_outputs", None):
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     return subprocess.call(cmd)
+
+
+def dump_outputs(out_dir, proof, challenges):
+    """what the timed path handed its caller in the last timed step, as float32 arrays (exact: every value is a byte)"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float32))
+    ch = np.ascontiguousarray(np.asarray(challenges, dtype=np.uint64).reshape(-1, 4))
+    np.save(os.path.join(out_dir, "challenges.npy"), ch.view(np.uint8).reshape(-1, 32).astype(np.float32))
 
 
 def fr_mont(v: int):
@@ -190,8 +210,9 @@ def device_sync(ctx, torch):
 
 
 # ------------------------------------------------------------------------------------ the headline, N = 1 and N > 1 alike
-def headline(args, torch, rank=0, world=1, dist=None, local_rank=0, shared_gpu=False, shape=None, side=True, project=None):
-    """One full proof per step, the same circuit / witness / phases / hand-over for every N.  N > 1: ONE proof sharded
+def headline(args, torch, rank=0, world=1, dist=None, local_rank=0, shared_gpu=False, shape=None, side=True, project=None, full=True):
+    """One full proof per step, the same circuit / witness / phases / hand-over for every N.  full=False (a plain run): the timed
+    proofs and the short line only -- no HIP events, no verification, no side measurements.  N > 1: ONE proof sharded
     over the ranks -- a rank keeps only the witness columns it OWNS resident (position j of a phase's columns, j % N == rank), commits
     them and sends them to the others device to device; the 64-byte commitments are all-gathered per transcript round; the quotient is
     split by (degree class, coset).  Exchanges: the library's own RCCL communicator (csrc/comm.hip; its 128-byte id travels over the
@@ -291,6 +312,7 @@ def headline(args, torch, rank=0, world=1, dist=None, local_rank=0, shared_gpu=F
         driver._rlc(rlc["w"], ch1[0], rlc["t"])
         t_h[:] = adv_dev[rlc["t"]].download((circ.n, 4))
         sess.advice_phase({**{i: host_cols[i] for i in range(circ.A - 2) if ph[i] == 2}, rlc["t"]: t_h})
+        state["challenges"] = list(ch0) + list(ch1)
         state["proof"] = sess.finish()
 
     # record runs (tools/gpu_r6_record.sh): ZK_BENCH_KIND=host makes the TIMED proofs the host-memory kind, so that a kernel trace holds one kind only
@@ -299,24 +321,59 @@ def headline(args, torch, rank=0, world=1, dist=None, local_rank=0, shared_gpu=F
         host_setup()
         timed_step = step_host
 
+    def teardown():
+        host_teardown()
+        driver.free()
+        for b_ in adv_dev.values():
+            b_.free()
+        pk.destroy()
+        srs.destroy()
+        if world > 1 and not shared_gpu:
+            ctx.comm_destroy()
+        ctx.close()
+
     for _ in range(args.warmup):
         timed_step()
     fence()
-    ctx.prof_reset()
-    ctx.prof_enable(2)           # HIP events around the kernel classes of the proof (MSM classes, NTT passes, quotient evaluator)
+    if full:
+        ctx.prof_reset()
+        ctx.prof_enable(2)       # HIP events around the kernel classes of the proof (MSM classes, NTT passes, quotient evaluator)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         timed_step()
     fence()
     elapsed = time.perf_counter() - t0
-    ctx.prof_enable(False)
+    if full:
+        ctx.prof_enable(False)
     if dist is not None:         # the slowest rank's clock
         box = [None] * world
         dist.all_gather_object(box, elapsed)
         elapsed = max(box)
+    per_proof = elapsed / args.steps
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, state["proof"], state.get("challenges", []))
+    config = {"workload": workload_text(shape), "k": circ.k, "advice": circ.A, "fixed": circ.F, "permutation_columns": len(circ.perm_cols), "lookups": len(circ.lookups),
+              "degree": circ.degree(), "extended_k": circ.extended_k(), "advice_phases": circ.num_phases(), "advice_columns_per_phase": [circ.advice_phase.count(p) for p in range(circ.num_phases())],
+              "challenges": len(circ.challenge_phase), "advice_queries": len(circ.advice_queries), "fixed_queries": len(circ.fixed_queries),
+              "witness_cell_distribution": dist_cells,
+              "rows_with_an_active_lookup": round(float(np.asarray(rlc["q_lk"]).reshape(-1, 4).any(axis=1).mean()), 4),
+              "rows_with_a_copy_constraint_per_column": round(len(set(r for pair in circ.copies for (_, _, r) in pair)) / circ.n, 5),
+              "witness_residency": "HBM (device buffers handed to zk_proof_advice_phase_dev, in place: the session writes its blinding rows into them)"
+                                   + ("; every rank holds the columns it owns, the others reach it device to device" if world > 1 else ""),
+              "multiopen": "shplonk", "transcript": "blake2b",
+              "vanishing_random_polynomial": "constant 1 (as the reference's own proofs)",
+              "parallelism": "single GPU" if world == 1 else
+                             f"one proof sharded x{world}: commitments by column, quotient by (degree class, coset), 64-byte commitments and witness columns all-gathered "
+                             + ("over torch.distributed gloo callbacks (the ranks share one GPU: test box)" if shared_gpu else "over the library's RCCL communicator (xGMI)")}
+    head = {"metric": METRIC, "value": round(per_proof, 4), "unit": "s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(per_proof * 1e3, 2),
+            "higher_is_better": False, "scaling": "strong", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic-shape", "config": config}
+    if not full:
+        out = dict(head, extra={"proof_bytes": len(state["proof"]), "proof_sha256": __import__("hashlib").sha256(state["proof"]).hexdigest(), "shape": shape,
+                                "keygen_pk_s": round(t_keygen, 3), "witness_upload_s_outside_timing": round(t_upload, 2), "host_circuit_build_s": round(t_build, 2)})
+        teardown()
+        return out
     prof = {name: ctx.prof_get(name) for name in ctx.prof_names()}
     prof_bytes = {name: ctx.prof_get_bytes(name) for name in prof}
-    per_proof = elapsed / args.steps
 
     # ---- outside the timed region: the same proof with the two commitment paths that read structure out of the data turned off
     # (permutation products by their run ends, lookup sums through their first differences: csrc/runs.hip) -- what a circuit
@@ -481,31 +538,7 @@ def headline(args, torch, rank=0, world=1, dist=None, local_rank=0, shared_gpu=F
     executed_total = sum(executed.values()) if transforms and world == 1 else None
     proof_traffic, tsrc_proof = committed_traffic("proof_traffic_bytes") if circ.k == 20 and world == 1 else (None, None)
     out = {
-        "metric": METRIC,
-        "value": round(per_proof, 4),
-        "unit": "s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(per_proof * 1e3, 2),
-        "higher_is_better": False,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": DTYPE,
-        "data": "synthetic-shape",
-        "config": {"workload": WORKLOAD, "k": circ.k, "advice": circ.A, "fixed": circ.F, "permutation_columns": len(circ.perm_cols), "lookups": len(circ.lookups),
-                   "degree": circ.degree(), "extended_k": circ.extended_k(), "advice_phases": circ.num_phases(), "advice_columns_per_phase": [circ.advice_phase.count(p) for p in range(circ.num_phases())],
-                   "challenges": len(circ.challenge_phase), "advice_queries": len(circ.advice_queries), "fixed_queries": len(circ.fixed_queries),
-                   "witness_cell_distribution": dist_cells,
-                   "rows_with_an_active_lookup": round(float(np.asarray(rlc["q_lk"]).reshape(-1, 4).any(axis=1).mean()), 4),
-                   "rows_with_a_copy_constraint_per_column": round(len(set(r for pair in circ.copies for (_, _, r) in pair)) / circ.n, 5),
-                   "witness_residency": "HBM (device buffers handed to zk_proof_advice_phase_dev, in place: the session writes its blinding rows into them)"
-                                        + ("; every rank holds the columns it owns, the others reach it device to device" if world > 1 else ""),
-                   "multiopen": "shplonk", "transcript": "blake2b",
-                   "vanishing_random_polynomial": "constant 1 (as the reference's own proofs)",
-                   "parallelism": "single GPU" if world == 1 else
-                                  f"one proof sharded x{world}: commitments by column, quotient by (degree class, coset), 64-byte commitments and witness columns all-gathered "
-                                  + ("over torch.distributed gloo callbacks (the ranks share one GPU: test box)" if shared_gpu else "over the library's RCCL communicator (xGMI)")},
+        **head,
         # the dominant kernel class of THIS proof by device time: the evaluator on the EVM-style shape, the NTT passes on the plain one
         "roofline": max((r for r in (roof_ntt, roof_q) if r), key=lambda r: r.get("device_ms_per_proof", 0), default=None),
         "rooflines": [r for r in (roof_ntt, roof_msm, roof_q) if r],
@@ -531,16 +564,7 @@ def headline(args, torch, rank=0, world=1, dist=None, local_rank=0, shared_gpu=F
                                 "note": "plan = zk_pk_quotient_plan: per degree class the compiled program's instructions / field products per row / columns read / values parked / parking slots alive "
                                         "at once (csrc/class_compile.hpp); a class of index e runs on 2^e cosets"}},
     }
-    out["config"]["workload"] = workload_text(shape)
-    host_teardown()
-    driver.free()
-    for b_ in adv_dev.values():
-        b_.free()
-    pk.destroy()
-    srs.destroy()
-    if world > 1 and not shared_gpu:
-        ctx.comm_destroy()
-    ctx.close()
+    teardown()
     return out
 
 
@@ -848,6 +872,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed proofs")
     ap.add_argument("--warmup", type=int, default=1, help="untimed proofs in front of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed proof returned to DIR/*.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also verify the proof, time the kernel classes and run every side measurement (the --no-* flags thin it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-proof", action="store_true", help="skip the other shapes / distributions (N = 1 only)")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle verifier's check of the last timed proof")
@@ -856,12 +882,18 @@ def main():
     ap.add_argument("--proof-worker", default="", help=argparse.SUPPRESS)      # internal: run ONE proof shape in this process and print its record
     ap.add_argument("--batch", type=int, default=32, help="msm_ntt section: columns submitted per commit_batch call")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.proof_worker:
         print(json.dumps(proof_worker(args.proof_worker)), flush=True)
         return
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_under_launcher(args))
+    if max(args.gpus, 1) == 1 and os.environ.get("WORLD_SIZE", "1") == "1" and not (args.full or args.only_msm_ntt):
+        # a plain single-GPU run: the headline alone, torch not loaded (the library's own sync is the fence, as in the proof workers)
+        print(json.dumps(headline(args, _NoTorch, full=False)), flush=True)
+        return
 
     import torch  # device plumbing + torch.distributed only
 
@@ -881,18 +913,19 @@ def main():
         print(json.dumps(msm_ntt_section(args, torch)), flush=True)
         return
     if world == 1:
-        out = headline(args, torch)
-        if not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_proof(18)
-        else:
-            out["cpu_baseline"] = None
-        if not args.no_msm_ntt:
-            try:
-                out["msm_ntt"] = msm_ntt_section(args, torch)
-            except Exception as e:
-                out["msm_ntt"] = {"error": repr(e)}
-        if not args.no_proof:
-            out["proof"] = proof_section()
+        out = headline(args, torch, full=args.full)
+        if args.full:
+            if not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_proof(18)
+            else:
+                out["cpu_baseline"] = None
+            if not args.no_msm_ntt:
+                try:
+                    out["msm_ntt"] = msm_ntt_section(args, torch)
+                except Exception as e:
+                    out["msm_ntt"] = {"error": repr(e)}
+            if not args.no_proof:
+                out["proof"] = proof_section()
         print(json.dumps(out), flush=True)
         return
 
@@ -911,9 +944,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         return
-    out = headline(args, torch, rank, world, dist, local_rank, shared_gpu)
+    out = headline(args, torch, rank, world, dist, local_rank, shared_gpu, full=args.full)
     if rank == 0:
-        out["cpu_baseline"] = None          # timed on rank 0 at N = 1 only (the N = 1 line carries it)
+        if args.full:
+            out["cpu_baseline"] = None      # timed on rank 0 at N = 1 only (the N = 1 line carries it)
         print(json.dumps(out), flush=True)
     dist.barrier()
     dist.destroy_process_group()

@@ -11,6 +11,7 @@ permutation argument over every advice column, logUp lookups) and labels every n
 usage: python bench_proof.py [--k 16] [--groups 10] [--no-verify]
 """
 import argparse
+import ctypes
 import json
 import os
 import random
@@ -216,7 +217,7 @@ def assemble_blob(ctx, c, F: int, fixed_of, copies):
     tmp = ctx.alloc(col_bytes)
     for j in range(Pn):
         ctx.fr_powers(omega_m, np.frombuffer(plonk.fr_mont_bytes(pow(plonk.FR_DELTA, j, R)), dtype=np.uint64).copy(), tmp, n)
-        sig_view[j][:] = tmp.download((n, 4))
+        ctx._ck(z.binding.lib().zk_d2h(ctx.h, sig_view[j].ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(tmp.ptr), ctypes.c_size_t(col_bytes)))
     tmp.free()
     for (ta_, ia, ra), (tb_, ib, rb) in copies:
         ja, jb = pos[(ta_, ia)], pos[(tb_, ib)]
@@ -593,7 +594,7 @@ def evm_witness(spec: dict, n: int, u: int, seed: int = 3):
     for j, pc in enumerate(spec["pair"]):
         cols[pc] = z(); cols[pc][rows[state // 2 == j]] = 1
     cols[spec["odd"]] = z(); cols[spec["odd"]][rows] = (state % 2).astype(np.uint64)
-    getc = lambda cidx: cols.setdefault(cidx, z())
+    getc = lambda cidx: cols[cidx] if cidx in cols else cols.setdefault(cidx, z())
     cval = {}
     for (cc, r) in spec["cond"]:
         v = rng.integers(0, 2, size=rows.size, dtype=np.uint64)
@@ -609,24 +610,27 @@ def evm_witness(spec: dict, n: int, u: int, seed: int = 3):
     getc(spec["ctr"])[np.concatenate([rows, [rows[-1] + 2]])] = ctr
     garbage = rng.integers(0, 256, size=(len(spec["out"]), rows.size), dtype=np.uint64)
     for s_, st in enumerate(spec["states"]):
-        m = state == s_
+        m = np.flatnonzero(state == s_)          # the steps in state s_; an operand is gathered once per state, not once per constraint
+        rows_m, iv, cv = rows[m], {}, {}
+        inp = lambda i: iv[i] if i in iv else iv.setdefault(i, ival[spec["in"][i]][m])
+        cnd = lambda x: cv[x] if x in cv else cv.setdefault(x, cval[spec["cond"][x]][m])
         for j, cn in enumerate(st["cons"]):
-            a, b, cx, dx = (ival[spec["in"][i]][m] for i in cn["in"])
+            a, b, cx, dx = (inp(i) for i in cn["in"])
             f = cn["form"]
             if f == 0: o = a * b + cx
             elif f == 1: o = a + b * np.uint64(256) + cx * np.uint64(65536)
             elif f == 2: o = a * b * cx
             elif f == 3: o = a * b * dx
-            elif f == 4: sb = cval[spec["cond"][cn["sel_bit"]]][m]; o = sb * a + (np.uint64(1) - sb) * b
+            elif f == 4: sb = cnd(cn["sel_bit"]); o = sb * a + (np.uint64(1) - sb) * b
             elif f == 5: o = a * (b + cx)
             elif f == 6: o = a + np.uint64(255) - b
             else: o = a * a + b
             holds = np.ones(o.size, dtype=bool)
             for x in cn["cond"]:
-                holds &= cval[spec["cond"][x]][m] == 1
+                holds &= cnd(x) == 1
             o = np.where(holds, o, garbage[j][m])
             oc, r = spec["out"][j]
-            getc(oc)[rows[m] + r] = o
+            getc(oc)[rows_m + r] = o
     return cols, q_usable
 
 

@@ -1,4 +1,4 @@
-"""CPU: the committed bench line (`profiles/bench_r06.json`, what `python bench.py` printed on the GPU box) keeps the driver's
+"""CPU: the committed bench line (`profiles/bench_r06.json`, the full line: what `python bench.py --full` prints) keeps the driver's
 contract as the tier framing reads it: a step is one full proof of BASELINE configs[3]'s stand-in, `value` = seconds per proof with
 the witness resident in HBM, `roofline` = the dominant kernel class with its algorithmic bytes, `cpu_baseline` = the restated CPU
 prover on a BASELINE-size sample; the side records agree with each other."""
@@ -144,3 +144,42 @@ def test_gpus_flag_without_a_launcher_starts_one_rank_per_gpu(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and int(cmd[cmd.index("--master-port") + 1]) > 0
     tail = cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:]
     assert tail[:6] == ["--gpus", "4", "--steps", "7", "--warmup", "3"] and "--no-cpu-baseline" in tail and "--no-proof" not in tail
+
+
+def test_gpus_flag_hands_full_and_dump_outputs_through(monkeypatch, tmp_path):
+    """the launched ranks run the same kind of bench as asked for: --full and --dump-outputs (as an absolute path: the ranks may
+    start elsewhere) reach them; a plain run stays plain"""
+    import argparse
+    import importlib
+    import sys
+
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    seen = []
+    monkeypatch.setattr(bench.subprocess, "call", lambda cmd: seen.append(cmd) or 0)
+    monkeypatch.chdir(tmp_path)
+    base = dict(gpus=2, steps=5, warmup=1, batch=32, no_cpu_baseline=False, no_proof=False)
+    assert bench.relaunch_under_launcher(argparse.Namespace(**base, full=True, dump_outputs="out")) == 0
+    assert bench.relaunch_under_launcher(argparse.Namespace(**base, full=False, dump_outputs=None)) == 0
+    full, plain = (cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] for cmd in seen)
+    assert full[:6] == plain[:6] == ["--gpus", "2", "--steps", "5", "--warmup", "1"]
+    assert "--full" in full and full[full.index("--dump-outputs") + 1] == str(tmp_path / "out")
+    assert "--full" not in plain and "--dump-outputs" not in plain
+
+
+def test_dump_outputs_writes_float32_bytes(tmp_path):
+    """--dump-outputs: the proof's bytes and the challenges' 32 little-endian bytes each, exact in float32"""
+    import importlib
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    proof = bytes(range(256)) * 3
+    challenges = [np.array([1, 2, 3, 1 << 63], dtype=np.uint64), np.array([(1 << 64) - 1, 0, 7, 9], dtype=np.uint64)]
+    bench.dump_outputs(str(tmp_path / "d"), proof, challenges)
+    p, c = np.load(tmp_path / "d" / "proof.npy"), np.load(tmp_path / "d" / "challenges.npy")
+    assert p.dtype == c.dtype == np.float32 and p.shape == (768,) and c.shape == (2, 32)
+    assert p.astype(np.uint8).tobytes() == proof
+    assert c.astype(np.uint8).tobytes() == np.stack(challenges).astype("<u8").tobytes()

@@ -10,7 +10,7 @@ for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
     i=$((i+1))
     envs=""; [ "$v" != "-" ] && envs="$v"
-    env $envs ZK_BENCH_QUICK=1 timeout 600 python bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps $STEPS --warmup 1 > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err
+    env $envs ZK_BENCH_QUICK=1 timeout 600 python bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps $STEPS --warmup 1 > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err
     python - "$O/v${i}_r$r.json" "variant $i [$v] round $r" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 ROOT=$(pwd); O=$ROOT/gpurun_out/arith; L=$ROOT/zkevm-circuits_amd/lib; mkdir -p $O
 export TMPDIR=/tmp
-b() { [ -s $O/bench_$1.json ] || ZKMI355_LIB=$L/libzkmi355_$1.so timeout 60 python bench.py --no-proof --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err; }
+b() { [ -s $O/bench_$1.json ] || ZKMI355_LIB=$L/libzkmi355_$1.so timeout 60 python bench.py --full --no-proof --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err; }
 q() { ZKMI355_LIB=$L/libzkmi355_$1.so timeout 40 python tools/quot_loop.py 19 100 5 > $O/quot_$1.txt 2>&1; }
 suite() { ZKMI355_LIB=$L/libzkmi355_$1.so timeout 120 python -m pytest tests -x -q -m gpu > $O/pytest_$1.log 2>&1; }
 val() { python -c "import json,sys; d=json.loads(open('$O/bench_$1.json').read().strip().splitlines()[-1]); e=d['extra']; print('$1', d['value'], 'msm', e['msm_pipelined_ms'], 'lone', e['msm_lone_ms'], 'ntt', e['ntt_only_ms'], e['kernel_avg_ms'])" 2>&1 | tail -1; }
@@ -31,7 +31,7 @@ echo "FINAL=$FINAL"
 if [ "$FINAL" != head ]; then
     ZKMI355_LIB=$L/libzkmi355_$FINAL.so timeout 60 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
     if [ $SECONDS -lt 205 ]; then
-        ZKMI355_LIB=$L/libzkmi355_$FINAL.so timeout 100 python bench.py > $O/bench_full_$FINAL.json 2> $O/bench_full_$FINAL.err
+        ZKMI355_LIB=$L/libzkmi355_$FINAL.so timeout 100 python bench.py --full > $O/bench_full_$FINAL.json 2> $O/bench_full_$FINAL.err
         python - <<PY
 import json
 d=json.loads(open("$O/bench_full_$FINAL.json").read().strip().splitlines()[-1])

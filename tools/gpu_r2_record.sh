@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 ROOT=$(pwd); O=$ROOT/gpurun_out/r2rec; mkdir -p $O
 export TMPDIR=/tmp
 run_bounded() { local secs=$1 log=$2; shift 2; setsid "$@" > "$log" 2>&1 & local pid=$!; ( sleep "$secs"; kill -TERM -- -"$pid" 2>/dev/null; sleep 3; kill -KILL -- -"$pid" 2>/dev/null ) & local wd=$!; wait "$pid"; local rc=$?; kill "$wd" 2>/dev/null; return $rc; }
-timeout 70 python bench.py > $O/bench_full.json 2> $O/bench_full.err
+timeout 70 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err
 python - <<PY
 import json
 d=json.loads(open("$O/bench_full.json").read().strip().splitlines()[-1])
@@ -16,11 +16,11 @@ print(d.get("cpu_baseline"))
 PY
 echo "bench t=${SECONDS}s"
 cd /tmp
-run_bounded 30 $O/prof_bench.log rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python $ROOT/bench.py --no-proof --no-cpu-baseline
+run_bounded 30 $O/prof_bench.log rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python $ROOT/bench.py --full --no-proof --no-cpu-baseline
 echo "kernel trace rc=$? t=${SECONDS}s"
-run_bounded 25 $O/pmc_fetch.log rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python $ROOT/bench.py --no-proof --no-cpu-baseline --steps 16 --warmup 8
+run_bounded 25 $O/pmc_fetch.log rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python $ROOT/bench.py --full --no-proof --no-cpu-baseline --steps 16 --warmup 8
 echo "pmc fetch rc=$? t=${SECONDS}s"
-run_bounded 25 $O/pmc_write.log rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python $ROOT/bench.py --no-proof --no-cpu-baseline --steps 16 --warmup 8
+run_bounded 25 $O/pmc_write.log rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python $ROOT/bench.py --full --no-proof --no-cpu-baseline --steps 16 --warmup 8
 echo "pmc write rc=$? t=${SECONDS}s"
 if [ $SECONDS -lt 62 ]; then
     run_bounded 30 $O/prof_sc.log rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sc -- python $ROOT/bench_proof.py --k 20 --shape 1000,150,150,100,9 --shplonk --pinned --repeat 2 --no-verify

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 ROOT=$(pwd); O=$ROOT/gpurun_out/r3fin; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python $ROOT/bench.py --no-proof --no-cpu-baseline --steps 32 --warmup 16 > $O/prof_bench.log 2>&1
+timeout 120 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python $ROOT/bench.py --full --no-proof --no-cpu-baseline --steps 32 --warmup 16 > $O/prof_bench.log 2>&1
 echo "bench trace rc=$? t=${SECONDS}"
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sc -- python $ROOT/bench_proof.py --k 20 --shape 1000,150,150,100,9 --shplonk --pinned --repeat 3 --no-verify > $O/prof_sc.log 2>&1
 echo "sc trace rc=$? t=${SECONDS}"

@@ -5,9 +5,9 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 ROOT=$(pwd); O=$ROOT/gpurun_out/r4rec; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
-timeout 900 python bench.py > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$? t=${SECONDS}"
+timeout 900 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$? t=${SECONDS}"
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_proof -- python $ROOT/bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify > $O/prof_proof.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_proof -- python $ROOT/bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify > $O/prof_proof.log 2>&1
 echo "proof trace rc=$? t=${SECONDS}"
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_msmntt -- python $ROOT/bench.py --only-msm-ntt --no-cpu-baseline > $O/prof_msmntt.log 2>&1
 echo "msm/ntt trace rc=$? t=${SECONDS}"
@@ -15,9 +15,9 @@ timeout 200 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch --output-format csv -- py
 echo "pmc fetch rc=$? t=${SECONDS}"
 timeout 200 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write --output-format csv -- python $ROOT/bench.py --only-msm-ntt --no-cpu-baseline > $O/pmc_write.log 2>&1
 echo "pmc write rc=$? t=${SECONDS}"
-timeout 400 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch_proof --output-format csv -- python $ROOT/bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 1 --warmup 0 > $O/pmc_fetch_proof.log 2>&1
+timeout 400 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch_proof --output-format csv -- python $ROOT/bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 1 --warmup 0 > $O/pmc_fetch_proof.log 2>&1
 echo "pmc fetch proof rc=$? t=${SECONDS}"
-timeout 400 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_proof --output-format csv -- python $ROOT/bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 1 --warmup 0 > $O/pmc_write_proof.log 2>&1
+timeout 400 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_proof --output-format csv -- python $ROOT/bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 1 --warmup 0 > $O/pmc_write_proof.log 2>&1
 echo "pmc write proof rc=$? t=${SECONDS}"
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*.db" -delete
 # the per-dispatch counter files of the proof passes are tens of MiB: keep per-kernel sums only

@@ -17,7 +17,7 @@ ZK_MSM_GM_SLAB=0 timeout 200 python tools/msm_dist.py 20 32 survey_60_30_10 > $O
 ZK_MSM_GM_REDG=8 timeout 200 python tools/msm_dist.py 20 32 survey_60_30_10 > $O/msm_dist_redg8.log 2>&1; echo "redg8 rc=$? t=${SECONDS}"
 for v in new base; do
   [ $v = base ] && export ZKMI355_LIB=$BASE || unset ZKMI355_LIB
-  ZK_PROVER_TRACE=1 timeout 400 python bench.py --no-cpu-baseline --no-proof --no-msm-ntt > $O/bench_$v.json 2> $O/bench_$v.err; echo "bench $v rc=$? t=${SECONDS}"
+  ZK_PROVER_TRACE=1 timeout 400 python bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt > $O/bench_$v.json 2> $O/bench_$v.err; echo "bench $v rc=$? t=${SECONDS}"
   head -c 300 $O/bench_$v.json; echo
 done
 cd /tmp

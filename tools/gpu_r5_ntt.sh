@@ -9,7 +9,7 @@ for f in 0 1; do
 done | tee $O/batch_time.txt
 run() {
   local name=$1; shift
-  env "$@" timeout 600 python bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 3 --warmup 1 > $O/$name.json 2> $O/$name.err
+  env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 3 --warmup 1 > $O/$name.json 2> $O/$name.err
   python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 try:

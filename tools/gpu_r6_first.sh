@@ -5,7 +5,7 @@ ROOT=$(pwd); O=$ROOT/gpurun_out/${1:-r6first}; mkdir -p $O
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests/test_gpu_evm_shape.py tests/test_gpu_quotient.py tests/test_gpu_proof.py -q -m gpu -x > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -5 $O/pytest.log
 for shape in evm plain; do
-  ZK_BENCH_SHAPE=$shape ZK_PROVER_TRACE=1 ZK_QUOTIENT_TRACE=1 timeout 900 python bench.py --no-cpu-baseline --no-proof --no-msm-ntt --steps 2 --warmup 1 > $O/$shape.json 2> $O/$shape.err
+  ZK_BENCH_SHAPE=$shape ZK_PROVER_TRACE=1 ZK_QUOTIENT_TRACE=1 timeout 900 python bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --steps 2 --warmup 1 > $O/$shape.json 2> $O/$shape.err
   echo "== $shape rc=$?"
   python tools/trace_stages.py $O/$shape.err 2>/dev/null | head -60
   grep "zk quotient\] plan" $O/$shape.err | sort | uniq -c | head

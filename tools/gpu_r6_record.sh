@@ -7,9 +7,9 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 ROOT=$(pwd); O=$ROOT/gpurun_out/r6rec; mkdir -p $O
 export TMPDIR=/tmp
 # SKIP_BENCH=1: traces and counters only (the bench line of tools/gpu_r6_bench_only.sh stays)
-if [ "$SKIP_BENCH" != 1 ]; then rm -rf $O; mkdir -p $O; timeout 1500 python bench.py > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$? t=${SECONDS}"; else rm -rf $O/prof_* $O/pmc_*; fi
+if [ "$SKIP_BENCH" != 1 ]; then rm -rf $O; mkdir -p $O; timeout 1500 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; echo "bench rc=$? t=${SECONDS}"; else rm -rf $O/prof_* $O/pmc_*; fi
 cd /tmp
-Q="--no-cpu-baseline --no-proof --no-msm-ntt --no-verify"
+Q="--full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify"
 trace() {  # name, env...
   local name=$1; shift
   env "$@" ZK_BENCH_QUICK=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python $ROOT/bench.py $Q --steps 1 --warmup 1 > $O/prof_$name.log 2>&1

@@ -3,5 +3,5 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 export TMPDIR=/tmp
 O=gpurun_out/r6shard4; mkdir -p $O
-ZK_PROVER_TRACE=1 timeout 1500 python bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 1 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+ZK_PROVER_TRACE=1 timeout 1500 python bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 1 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python tools/trace_stages.py $O/bench.err 1 2>/dev/null | head -60

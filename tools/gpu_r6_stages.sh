@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 ROOT=$(pwd); O=$ROOT/gpurun_out/${1:-r6stages}; mkdir -p $O
 export TMPDIR=/tmp
-ZK_PROVER_TRACE=1 ZK_BENCH_QUICK=1 timeout 900 python bench.py --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 2 --warmup 1 > $O/evm.json 2> $O/evm.err
+ZK_PROVER_TRACE=1 ZK_BENCH_QUICK=1 timeout 900 python bench.py --full --no-cpu-baseline --no-proof --no-msm-ntt --no-verify --steps 2 --warmup 1 > $O/evm.json 2> $O/evm.err
 python tools/trace_stages.py $O/evm.err 2 2>/dev/null | head -70
 cd /tmp
 for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VALU_INT64 SQ_INSTS_LDS" "SQ_INSTS_BRANCH SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES" "SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA" "FETCH_SIZE" "WRITE_SIZE"; do
