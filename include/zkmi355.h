@@ -470,6 +470,33 @@ typedef struct zk_transcript_vtable {
     int (*squeeze_challenge)(void* user, void* fr32_out);
 } zk_transcript_vtable;
 int zk_proof_set_transcript(zk_ctx* ctx, zk_proof* proof, const zk_transcript_vtable* vtable, void* user);
+/* ---- verifier: halo2_proofs::plonk::verify_proof (KZG) -- SURVEY 8a A6 -------------------------
+ * The reference verifies what it proves through verify_snark_shplonk [REF prover/src/common/verifier.rs:35] (its verifier
+ * services [REF prover/src/zkevm/verifier.rs:45], [REF prover/src/aggregator/verifier.rs:57]).
+ * zk_vk: halo2 VerifyingKey (keygen_vk without the columns).  h_cs_blob: the constraint-system part of a v3 key blob (what
+ * zk_pk_create reads before the column data, parsed by the same code) or the whole blob (its columns are not read); h_commitments: the F fixed then P sigma commitments,
+ * 64 B affine each, as zk_pk_vk returns them (num_commitments must be F + P); h_vk_repr_fr32: vk.transcript_repr (Montgomery
+ * Fr).  Host only, no column data, any k <= 27.  ZK_ERR_INVALID_ARG for a truncated, malformed or over-long blob.       */
+typedef struct zk_vk zk_vk;
+int zk_vk_create(const void* h_cs_blob, size_t len, const void* h_commitments, size_t num_commitments, const void* h_vk_repr_fr32, zk_vk** out);
+void zk_vk_destroy(zk_vk* vk);
+/* Proof length in bytes that this key gives under a transcript kind and multi-open scheme (host only). */
+int zk_vk_proof_len(const zk_vk* vk, int transcript_kind, int multiopen, size_t* len);
+/* The 16 words of zk_pk_shape, from the constraint system alone (host only). */
+int zk_vk_shape(const zk_vk* vk, uint32_t* out16);
+/* halo2 verify_proof, KZG, VerifierGWC / VerifierSHPLONK (multiopen), Blake2b / Poseidon / EVM transcript.  count = 1:
+ * SingleStrategy.  count > 1: AccumulatorStrategy over proofs of the same vk -- every proof's DualMSM weighted by a power of a
+ * batching scalar (Blake2b over the key, every proof and every instance: deterministic, no caller RNG) and summed, one MSM on
+ * the device, one pairing check for all.  h_instances[b][i] / h_instance_lens[b][i]: the values of instance column i of proof
+ * b (Montgomery Fr), absorbed exactly as given.  g2_128 / s_g2_128: [1]G2 and [s]G2 of the SRS (128 B, x.c0 | x.c1 | y.c0 |
+ * y.c1 Montgomery).  *ok = 1 accept, 0 reject.  A malformed proof (wrong length, a point not on the curve or not decodable, a
+ * non-canonical scalar, more instance values than usable rows) is a reject (ZK_OK, *ok = 0), not an error.
+ * ZK_ERR_INVALID_ARG only for bad arguments (null pointers, unknown kind or scheme).  A batch holds proofs of one key: a proof
+ * made with another key in it is rejected (its transcript and commitments are not this key's), never accepted.  A rejected
+ * batch does not say which proof failed: verify them one at a time for that.                                           */
+int zk_verify_proofs(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
+                     const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen, const void* g2_128,
+                     const void* s_g2_128, int* ok);
 /* Multi-GPU proving: one process per GPU, every rank runs the SAME session calls on
  * the same key, witness and seed.  Rank r then commits only columns r, r + world, ... and evaluates
  * only cosets r, r + world, ... of the quotient; commitments (64 B each) and finished cosets

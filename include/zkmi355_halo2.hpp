@@ -13,6 +13,8 @@
 //   halo2_proofs::poly::kzg::commitment::ParamsKZG-> zk::halo2::ParamsKZG
 //   halo2_proofs::plonk::{keygen_pk, create_proof}-> zk::halo2::{ProvingKey, create_proof}
 //   halo2_proofs::dev::MockProver::{run, verify_par, verify_at_rows_par} -> zk::halo2::mock_verify
+//   halo2_proofs::plonk::{VerifyingKey, verify_proof} (KZG; SingleStrategy / AccumulatorStrategy)
+//                                                 -> zk::halo2::{VerifyingKey, verify_proof}
 //   (reference call sites: circuit-benchmarks/src/super_circuit.rs:104-132, zkevm-circuits/src/test_util.rs:272,
 //    prover/src/common/prover/utils.rs:31,55, prover/src/utils.rs:77)
 #pragma once
@@ -328,6 +330,63 @@ inline std::vector<uint8_t> create_proof(const Context& c, const ProvingKey& pk,
     c.check(zk_proof_finish(c.raw(), sess, proof.data(), proof.size(), &len));
     proof.resize(len);
     return proof;
+}
+
+// plonk::VerifyingKey: the constraint system (a key blob, its column data not needed), the F fixed then P sigma commitments and
+// vk.transcript_repr; host only
+class VerifyingKey {
+   public:
+    VerifyingKey(const std::vector<uint8_t>& circuit_blob, const std::vector<G1Affine>& commitments, const Fr& transcript_repr) {
+        const int rc = zk_vk_create(circuit_blob.data(), circuit_blob.size(), commitments.data(), commitments.size(), transcript_repr.data(), &vk_);
+        if (rc) throw Error(rc, "zk_vk_create: malformed constraint system, or F + P commitments expected");
+    }
+    // the verifying key of a proving key (keygen_vk's commitments and repr, read back from the device key)
+    static VerifyingKey from_pk(const Context& c, const ProvingKey& pk, const std::vector<uint8_t>& circuit_blob) {
+        uint32_t shape[16] = {0};
+        c.check(zk_pk_shape(c.raw(), pk.raw(), shape));
+        std::vector<G1Affine> com(shape[3] + shape[6]);
+        Fr repr{};
+        c.check(zk_pk_vk(c.raw(), pk.raw(), com.data(), repr.data()));
+        return VerifyingKey(circuit_blob, com, repr);
+    }
+    VerifyingKey(VerifyingKey&& o) noexcept : vk_(o.vk_) { o.vk_ = nullptr; }
+    VerifyingKey(const VerifyingKey&) = delete;
+    VerifyingKey& operator=(const VerifyingKey&) = delete;
+    ~VerifyingKey() { zk_vk_destroy(vk_); }
+    const zk_vk* raw() const { return vk_; }
+    size_t proof_len(int transcript_kind, bool shplonk) const {
+        size_t len = 0;
+        const int rc = zk_vk_proof_len(vk_, transcript_kind, shplonk ? ZK_MULTIOPEN_SHPLONK : ZK_MULTIOPEN_GWC, &len);
+        if (rc) throw Error(rc, "zk_vk_proof_len: bad argument");
+        return len;
+    }
+   private:
+    zk_vk* vk_ = nullptr;
+};
+
+// plonk::verify_proof: one proof = SingleStrategy, several = AccumulatorStrategy (one MSM, one pairing check).  instances[b][i]:
+// the values of instance column i of proof b; g2 / s_g2 from the params (ParamsKZG::g2 / s_g2, RawBytes).  false = rejected.
+inline bool verify_proof(const Context& c, const VerifyingKey& vk, const std::vector<std::vector<uint8_t>>& proofs,
+                         const std::vector<std::vector<std::vector<Fr>>>& instances, int transcript_kind, bool shplonk,
+                         const std::vector<uint8_t>& g2, const std::vector<uint8_t>& s_g2) {
+    if (proofs.size() != instances.size() || g2.size() != 128 || s_g2.size() != 128) throw Error(ZK_ERR_INVALID_ARG, "verify_proof: one instance set per proof, 128-byte G2 points");
+    std::vector<std::vector<const void*>> cols(proofs.size());
+    std::vector<std::vector<uint32_t>> lens(proofs.size());
+    std::vector<const void* const*> col_ptrs;
+    std::vector<const uint32_t*> len_ptrs;
+    std::vector<const void*> proof_ptrs;
+    std::vector<size_t> proof_lens;
+    for (size_t b = 0; b < proofs.size(); ++b) {
+        for (const auto& col : instances[b]) { cols[b].push_back(col.data()); lens[b].push_back((uint32_t)col.size()); }
+        col_ptrs.push_back(cols[b].data());
+        len_ptrs.push_back(lens[b].data());
+        proof_ptrs.push_back(proofs[b].data());
+        proof_lens.push_back(proofs[b].size());
+    }
+    int ok = 0;
+    c.check(zk_verify_proofs(c.raw(), vk.raw(), proofs.size(), col_ptrs.data(), len_ptrs.data(), proof_ptrs.data(), proof_lens.data(), transcript_kind,
+                             shplonk ? ZK_MULTIOPEN_SHPLONK : ZK_MULTIOPEN_GWC, g2.data(), s_g2.data(), &ok));
+    return ok == 1;
 }
 
 }  // namespace halo2

@@ -62,6 +62,8 @@ def lib():
         _lib.zk_transcript_free.restype = None
         _lib.zk_transcript_free.argtypes = [ctypes.c_void_p]
         _lib.zk_transcript_proof.restype = ctypes.c_size_t
+        _lib.zk_vk_destroy.restype = None
+        _lib.zk_vk_destroy.argtypes = [ctypes.c_void_p]
     return _lib
 
 
@@ -177,6 +179,59 @@ class ProvingKey:
         if self.h:
             lib().zk_pk_destroy(self.ctx.h, self.h)
             self.h = None
+
+
+class VerifyingKey:
+    """halo2 VerifyingKey (zk_vk): the constraint system of a key blob with the key's commitments and vk_repr; host only.
+    From `cs_blob` (plonk.Circuit.cs_blob(): a shape-only circuit is enough), the F fixed then P sigma commitments ((F + P, 8)
+    u64 affine Montgomery) and vk_repr ((4,) u64 Montgomery) -- or from a ProvingKey (from_pk)."""
+
+    SHAPE_NAMES = ["k", "degree", "extended_k", "F", "A", "I", "P", "C", "L", "phases", "challenges", "blinding_factors",
+                   "advice_queries", "fixed_queries", "commitments", "evaluations"]
+
+    def __init__(self, cs_blob: bytes, commitments: np.ndarray, vk_repr: np.ndarray):
+        blob = cs_blob if isinstance(cs_blob, np.ndarray) else np.frombuffer(cs_blob, dtype=np.uint8)     # read by pointer, no copy
+        com = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)
+        rep = np.ascontiguousarray(vk_repr, dtype=np.uint64).reshape(4)
+        h = ctypes.c_void_p()
+        rc = lib().zk_vk_create(_host_ptr(blob), ctypes.c_size_t(blob.size), _host_ptr(com) if len(com) else None, ctypes.c_size_t(len(com)),
+                                _host_ptr(rep), ctypes.byref(h))
+        if rc != 0:
+            raise ZkError(f"zk_vk_create failed with status {rc} (truncated or malformed constraint system, or F + P commitments expected)")
+        self.h = h
+        self.shape_ = self.shape()
+
+    @classmethod
+    def from_pk(cls, pk: "ProvingKey", cs_blob: bytes) -> "VerifyingKey":
+        """the verifying key of a proving key made from a blob whose constraint-system part is cs_blob"""
+        sh = pk.shape()
+        com, rep = pk.vk(sh["F"] + sh["P"])
+        return cls(cs_blob, com, rep)
+
+    def shape(self) -> dict:
+        out = (ctypes.c_uint32 * 16)()
+        rc = lib().zk_vk_shape(self.h, out)
+        if rc != 0:
+            raise ZkError(f"zk_vk_shape failed with status {rc}")
+        return dict(zip(self.SHAPE_NAMES, list(out)))
+
+    def proof_len(self, transcript_kind: int = 0, multiopen: int = 0) -> int:
+        n = ctypes.c_size_t()
+        rc = lib().zk_vk_proof_len(self.h, ctypes.c_int(transcript_kind), ctypes.c_int(multiopen), ctypes.byref(n))
+        if rc != 0:
+            raise ZkError(f"zk_vk_proof_len failed with status {rc}")
+        return n.value
+
+    def destroy(self):
+        if self.h:
+            lib().zk_vk_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
 
 
 def plan_summary(words) -> dict:
@@ -712,6 +767,43 @@ class Context:
         view = np.frombuffer(blob, dtype=np.uint8)      # read-only view of the bytes object: no copy of a multi-GiB key
         self._ck(lib().zk_pk_create(self.h, srs.h, _host_ptr(view), ctypes.c_size_t(view.size), ctypes.byref(h)))
         return ProvingKey(self, h)
+
+    def verify_proofs(self, vk: "VerifyingKey", proofs: Sequence[bytes], instances: Sequence[Sequence[np.ndarray]], transcript_kind: int = 0,
+                      multiopen: int = 0, g2: bytes = b"", s_g2: bytes = b"") -> bool:
+        """halo2 verify_proof (zk_verify_proofs): one proof = SingleStrategy, several = AccumulatorStrategy (one MSM and one pairing
+        check for all).  instances[b]: proof b's instance columns, (len, 4) u64 Montgomery each, absorbed as given -- a column of
+        exactly 2^k rows is the full-column image zk_proof_begin takes and stands for its usable rows.  g2 / s_g2: [1]G2 / [s]G2,
+        128 B Montgomery.  Malformed proofs are rejected (False); bad arguments raise."""
+        sh = vk.shape_
+        n, u = 1 << sh["k"], (1 << sh["k"]) - sh["blinding_factors"] - 1
+        if len(proofs) != len(instances) or not proofs:
+            raise ZkError("verify_proofs: one instance list per proof, at least one proof")
+        keep = []
+        inst_ptrs = (ctypes.c_void_p * len(proofs))()
+        len_ptrs = (ctypes.c_void_p * len(proofs))()
+        for b, cols in enumerate(instances):
+            if len(cols) != sh["I"]:
+                raise ZkError(f"verify_proofs: proof {b} has {len(cols)} instance columns, the key {sh['I']}")
+            arrs = []
+            for c in cols:
+                a = np.ascontiguousarray(c, dtype=np.uint64).reshape(-1, 4)
+                arrs.append(a[:u] if len(a) == n else a)
+            ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+            lens = (ctypes.c_uint32 * max(len(arrs), 1))(*[len(a) for a in arrs])
+            keep += [arrs, ptrs, lens]
+            inst_ptrs[b] = ctypes.cast(ptrs, ctypes.c_void_p)
+            len_ptrs[b] = ctypes.cast(lens, ctypes.c_void_p)
+        bufs = [ctypes.create_string_buffer(bytes(p_), max(len(p_), 1)) for p_ in proofs]
+        proof_ptrs = (ctypes.c_void_p * len(proofs))(*[ctypes.cast(b_, ctypes.c_void_p) for b_ in bufs])
+        proof_lens = (ctypes.c_size_t * len(proofs))(*[len(p_) for p_ in proofs])
+        g2b, sg2b = bytes(g2), bytes(s_g2)
+        if len(g2b) != 128 or len(sg2b) != 128:
+            raise ZkError("verify_proofs: g2 and s_g2 are 128-byte G2 points")
+        ok = ctypes.c_int(-1)
+        self._ck(lib().zk_verify_proofs(self.h, vk.h, ctypes.c_size_t(len(proofs)), inst_ptrs, len_ptrs, proof_ptrs, proof_lens,
+                                        ctypes.c_int(transcript_kind), ctypes.c_int(multiopen), ctypes.c_char_p(g2b), ctypes.c_char_p(sg2b),
+                                        ctypes.byref(ok)))
+        return ok.value == 1
 
     def create_proof(self, pk: "ProvingKey", advice: Sequence[np.ndarray], instance: Sequence[np.ndarray], seed: bytes = bytes(16)) -> bytes:
         adv = [np.ascontiguousarray(a, dtype=np.uint64) for a in advice]

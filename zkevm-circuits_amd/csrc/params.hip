@@ -8,7 +8,8 @@
 //       the device as is) or 32 B (Processed: x canonical LE, bit 254 = parity of y, bit 255 = identity)
 //   G2: twice the G1 size.  The prover never touches G2; the two blobs are handed through.
 //
-// Decompression (one (p+1)/4 power per point), on-curve checks and compression run on the device:
+// Decompression (one (p+1)/4 power per point, k_g1_decode -- which also reads the verifier's proof points), on-curve checks
+// and compression run on the device:
 // 2^21 square roots are a few milliseconds there and half a minute on one host core.
 // zk_g2_setup (host only) gives unsafe_setup_with_s its G2 half: the generator and s * generator.
 #include <vector>
@@ -45,29 +46,68 @@ __device__ __forceinline__ bool g1_on_curve(const G1Affine& p) {
     return sqr(p.y) == sqr(p.x) * p.x + b3;
 }
 
-// bad[0] counts rejected encodings (x >= p, no square root, an identity flag on a non-zero image); halo2curves' flag bits:
-// bit 254 = parity of y, bit 255 = identity (host_util.hpp g1_compress has the provenance)
-__global__ void __launch_bounds__(256) k_g1_decompress(const uint8_t* __restrict__ in, G1Affine* __restrict__ out, uint64_t n, uint32_t* __restrict__ bad) {
+// One kernel for every G1 encoding the library reads (G1Enc in ctx.hpp):
+//   G1_ENC_COMPRESSED  32 B halo2curves compressed: x canonical LE, bit 254 = parity of y, bit 255 = identity (host_util.hpp
+//                      g1_compress has the provenance) -- SerdeFormat::Processed, Blake2b / Poseidon proofs; one square root each
+//   G1_ENC_RAW         64 B x | y Montgomery limbs (SerdeFormat::RawBytes): limbs below p, point on the curve; out may be NULL
+//                      (check in place)
+//   G1_ENC_BE_XY       64 B x || y canonical big-endian words (snark-verifier EvmTranscript): below p, on the curve; the
+//                      identity has no such image (0 || 0 is no point of y^2 = x^3 + 3)
+// bad[0] counts rejected encodings; bad_at (nullable) gets 1 at every rejected index, 0 elsewhere.  A rejected point is written
+// as the identity.
+__global__ void __launch_bounds__(256) k_g1_decode(const uint8_t* __restrict__ in, uint32_t enc, G1Affine* __restrict__ out, uint64_t n, uint32_t* __restrict__ bad,
+                                                   uint8_t* __restrict__ bad_at) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint4* q = reinterpret_cast<const uint4*>(in + i * 32);
-    const uint4 lo = q[0], hi = q[1];
-    Fq x{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
-    const uint32_t is_inf = x.l[7] >> 31, ysign = (x.l[7] >> 30) & 1u;
-    x.l[7] &= 0x3FFFFFFFu;
     G1Affine p{Fq::zero(), Fq::zero()};
-    if (is_inf) { if (ysign || !x.is_zero()) atomicAdd(bad, 1u); stg(out + i, p); return; }
-    if (!fq_canonical(x)) { atomicAdd(bad, 1u); stg(out + i, p); return; }
-    x = to_mont(x);
-    Fq b3 = Fq::one();
-    b3 = b3 + b3 + b3;
-    const Fq rhs = sqr(x) * x + b3;
-    Fq y = fq_sqrt_candidate(rhs);
-    if (sqr(y) != rhs) { atomicAdd(bad, 1u); stg(out + i, p); return; }
-    if ((from_mont(y).l[0] & 1u) != ysign) y = neg(y);
-    p.x = x;
-    p.y = y;
-    stg(out + i, p);
+    bool ok = true;
+    if (enc == G1_ENC_COMPRESSED) {
+        const uint4* q = reinterpret_cast<const uint4*>(in + i * 32);
+        const uint4 lo = q[0], hi = q[1];
+        Fq x{{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
+        const uint32_t is_inf = x.l[7] >> 31, ysign = (x.l[7] >> 30) & 1u;
+        x.l[7] &= 0x3FFFFFFFu;
+        if (is_inf) {
+            ok = !ysign && x.is_zero();
+        } else if (!fq_canonical(x)) {
+            ok = false;
+        } else {
+            x = to_mont(x);
+            Fq b3 = Fq::one();
+            b3 = b3 + b3 + b3;
+            const Fq rhs = sqr(x) * x + b3;
+            Fq y = fq_sqrt_candidate(rhs);
+            if (sqr(y) != rhs) ok = false;
+            else {
+                if ((from_mont(y).l[0] & 1u) != ysign) y = neg(y);
+                p.x = x;
+                p.y = y;
+            }
+        }
+    } else {
+        const uint4* q = reinterpret_cast<const uint4*>(in + i * 64);
+        const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
+        if (enc == G1_ENC_RAW) {
+            p.x = Fq{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+            p.y = Fq{{c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
+            ok = fq_canonical(p.x) && fq_canonical(p.y) && (p.is_identity() || g1_on_curve(p));
+        } else {   // big-endian words: the last 32-bit word of each half is limb 0, byte-swapped
+            Fq x{{__builtin_bswap32(b.w), __builtin_bswap32(b.z), __builtin_bswap32(b.y), __builtin_bswap32(b.x),
+                  __builtin_bswap32(a.w), __builtin_bswap32(a.z), __builtin_bswap32(a.y), __builtin_bswap32(a.x)}};
+            Fq y{{__builtin_bswap32(d.w), __builtin_bswap32(d.z), __builtin_bswap32(d.y), __builtin_bswap32(d.x),
+                  __builtin_bswap32(c.w), __builtin_bswap32(c.z), __builtin_bswap32(c.y), __builtin_bswap32(c.x)}};
+            ok = fq_canonical(x) && fq_canonical(y);
+            if (ok) {
+                p.x = to_mont(x);
+                p.y = to_mont(y);
+                ok = g1_on_curve(p);
+            }
+        }
+        if (!ok) p = G1Affine{Fq::zero(), Fq::zero()};
+    }
+    if (!ok) atomicAdd(bad, 1u);
+    if (bad_at) bad_at[i] = ok ? 0 : 1;
+    if (out) stg(out + i, p);
 }
 __global__ void __launch_bounds__(256) k_g1_compress(const G1Affine* __restrict__ in, uint8_t* __restrict__ out, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -84,14 +124,6 @@ __global__ void __launch_bounds__(256) k_g1_compress(const G1Affine* __restrict_
     q[0] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]);
     q[1] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]);
 }
-// SerdeFormat::RawBytes reads check what RawBytesUnchecked skips: limbs below p, point on the curve
-__global__ void __launch_bounds__(256) k_g1_check(const G1Affine* __restrict__ pts, uint64_t n, uint32_t* __restrict__ bad) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const G1Affine p = ldg(pts + i);
-    if (!fq_canonical(p.x) || !fq_canonical(p.y) || !(p.is_identity() || g1_on_curve(p))) atomicAdd(bad, 1u);
-}
-
 // ---- host: Fq2 = Fq[u] / (u^2 + 1) and the G2 group law (XYZZ formulas hold over any field, a = 0)
 namespace host {
 struct F2 { F4 c0, c1; };
@@ -149,6 +181,17 @@ inline F4 fq_from_words(const uint64_t (&w)[4]) {         // canonical -> Montgo
 
 using namespace zk;
 
+namespace zk {
+// n points of one encoding from d_in (n x 32 or 64 B) into d_out (nullable for G1_ENC_RAW): enqueued on ctx->stream;
+// *d_bad (one u32, zeroed by the caller) counts rejects, d_bad_at (nullable, n bytes) flags them
+int g1_decode_run(zk_ctx* ctx, const void* d_in, int enc, G1Affine* d_out, uint64_t n, uint32_t* d_bad, uint8_t* d_bad_at) {
+    if (!n) return ZK_OK;
+    hipLaunchKernelGGL(k_g1_decode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint8_t*)d_in, (uint32_t)enc, d_out, n, d_bad, d_bad_at);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+}  // namespace zk
+
 static size_t g1_len(int format) { return format == ZK_SERDE_PROCESSED ? 32 : 64; }
 
 extern "C" {
@@ -186,16 +229,16 @@ int zk_params_read(zk_ctx* ctx, const void* h_file, size_t len, int format, zk_s
         if (e == hipSuccess && hipMalloc(&d_in, 2 * n * 32) != hipSuccess) { (void)hipGetLastError(); return fail(ctx->fail(ZK_ERR_OOM, "SRS staging allocation failed")); }
         if (e == hipSuccess) e = hipMemcpyAsync(d_in, fg, 2 * n * 32, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_g1_decompress, grid, block, 0, ctx->stream, (const uint8_t*)d_in, s->g, (uint64_t)n, d_bad);
-            hipLaunchKernelGGL(k_g1_decompress, grid, block, 0, ctx->stream, (const uint8_t*)d_in + n * 32, s->g_lagrange, (uint64_t)n, d_bad);
+            hipLaunchKernelGGL(k_g1_decode, grid, block, 0, ctx->stream, (const uint8_t*)d_in, (uint32_t)G1_ENC_COMPRESSED, s->g, (uint64_t)n, d_bad, (uint8_t*)nullptr);
+            hipLaunchKernelGGL(k_g1_decode, grid, block, 0, ctx->stream, (const uint8_t*)d_in + n * 32, (uint32_t)G1_ENC_COMPRESSED, s->g_lagrange, (uint64_t)n, d_bad, (uint8_t*)nullptr);
             e = hipGetLastError();
         }
     } else {
         if (e == hipSuccess) e = hipMemcpyAsync(s->g, fg, n * 64, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(s->g_lagrange, fl, n * 64, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess && format == ZK_SERDE_RAW) {
-            hipLaunchKernelGGL(k_g1_check, grid, block, 0, ctx->stream, (const G1Affine*)s->g, (uint64_t)n, d_bad);
-            hipLaunchKernelGGL(k_g1_check, grid, block, 0, ctx->stream, (const G1Affine*)s->g_lagrange, (uint64_t)n, d_bad);
+            hipLaunchKernelGGL(k_g1_decode, grid, block, 0, ctx->stream, (const uint8_t*)s->g, (uint32_t)G1_ENC_RAW, (G1Affine*)nullptr, (uint64_t)n, d_bad, (uint8_t*)nullptr);
+            hipLaunchKernelGGL(k_g1_decode, grid, block, 0, ctx->stream, (const uint8_t*)s->g_lagrange, (uint32_t)G1_ENC_RAW, (G1Affine*)nullptr, (uint64_t)n, d_bad, (uint8_t*)nullptr);
             e = hipGetLastError();
         }
     }

@@ -42,9 +42,11 @@
 #include <functional>
 #include "ctx.hpp"
 #include "host_hash.hpp"
+#include "cs.hpp"
 
 using namespace zk;
 using zk::host::F4;
+using namespace zk::cs;
 
 extern "C" int zk_quotient_eval(zk_ctx*, const uint32_t*, uint32_t, const void* const*, uint32_t, const void*, uint32_t, uint32_t, uint32_t, int, void*);
 extern "C" int zk_fr_powers(zk_ctx*, const void*, const void*, void*, size_t);
@@ -61,19 +63,6 @@ extern "C" int zk_poly_eval_batch(zk_ctx*, const void* const*, size_t, size_t, c
 extern "C" int zk_poly_eval_pairs(zk_ctx*, const void* const*, const uint32_t*, size_t, const void*, size_t, size_t, void*);
 
 namespace {
-
-enum ColType : uint32_t { CT_FIXED = 0, CT_ADVICE = 1, CT_INSTANCE = 2, CT_SPECIAL = 3, CT_PERM_Z = 4, CT_SIGMA = 5, CT_LK_M = 6, CT_LK_PHI = 7, CT_RANDOM = 8, CT_H = 9, CT_SPLIT_R = 10 /* remainder polynomials of the additive split (zk_proof_finish) */ };
-enum Special : uint32_t { SP_X = 0, SP_L0 = 1, SP_LLAST = 2, SP_LACTIVE = 3 };
-enum QOp : uint32_t { Q_END = 0, Q_PUSH_COL = 1, Q_PUSH_CONST = 2, Q_ADD = 3, Q_SUB = 4, Q_MUL = 5, Q_NEG = 6, Q_SQUARE = 7, Q_DOUBLE = 8, Q_FOLD = 9, Q_MUL_CONST = 10, Q_ADD_CONST = 11, Q_TEE_TMP = 12, Q_PUSH_TMP = 13 };
-// abstract constant operands: user constants are [0, num_consts); challenges live above
-constexpr uint32_t C_THETA = 0xFFFF0000u, C_BETA = 0xFFFF0001u, C_GAMMA = 0xFFFF0002u, C_Y = 0xFFFF0003u, C_ONE = 0xFFFF0004u, C_ZERO = 0xFFFF0005u, C_DELTA0 = 0xFFFE0000u,   // C_DELTA0 + j = beta * delta^j
-                   C_CHAL0 = 0xFFFD0000u,                                                                                      // C_CHAL0 + i = user challenge i
-                   C_YPOW0 = 0xFFFC0000u;                                                                                      // C_YPOW0 + g = y^g (folding constraints that are g positions apart)
-
-inline uint32_t colref(uint32_t type, uint32_t idx) { return (type << 24) | idx; }
-
-struct Instr { uint32_t op, a, b; };
-typedef std::vector<Instr> Prog;
 
 // Inside a PoolScope (the proof-session entry points) DevBuf blocks come from and return to the
 // context's block pool; outside (key generation: buffers that live as long as the key) they are
@@ -129,7 +118,6 @@ struct PinnedBuf {
     bool alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess; }
 };
 
-struct Query { uint32_t type, idx; int32_t rot; };
 
 // ZK_PROVER_TRACE=1: wall-clock per prover stage on stderr (device drained at every mark)
 struct StageTrace {
@@ -147,18 +135,7 @@ struct StageTrace {
 }  // namespace
 
 struct QuotientPlan;
-struct zk_pk {
-    uint32_t k = 0, bf = 0, d = 0, ext_k = 0, F = 0, A = 0, I = 0, P = 0, L = 0;
-    uint32_t chunk = 0, C = 0, u = 0;   // permutation chunk size, #chunks, last usable row index
-    std::vector<std::pair<uint32_t, uint32_t>> perm_cols;
-    std::vector<F4> consts;
-    std::vector<Prog> gates;
-    struct Lookup { std::vector<Prog> tables; std::vector<std::vector<Prog>> inputs; };      // mv_lookup::Argument: table_expressions, inputs_expressions
-    std::vector<Lookup> lookups;
-    std::vector<Query> adv_q, fix_q;         // evaluation queries, in proof order
-    uint32_t num_phases = 1;
-    std::vector<uint32_t> adv_phase;         // phase of every advice column (halo2 FirstPhase/SecondPhase/...)
-    std::vector<uint32_t> chal_phase;        // challenge i becomes available after this phase
+struct zk_pk : zk::cs::ConstraintSystem {   // the constraint system (cs.hpp) and what keygen derives from it
     // device-resident key material
     std::vector<DevBuf> fixed_lag, fixed_coeff, sigma_lag, sigma_coeff;
     DevBuf omega_lag, l0_lag, llast_lag, lactive_lag, l0_coeff, llast_coeff, lactive_coeff;
@@ -171,7 +148,6 @@ struct zk_pk {
     mutable size_t part_cache_bytes = 0;     // what this key's slots hold of the context's shared budget (zk_ctx::coset_cache_bytes)
     std::vector<G1Affine> fixed_com, sigma_com;
     F4 vk_repr;                              // vk.transcript_repr: the default, or what zk_pk_set_transcript_repr installed
-    std::vector<Query> inst_q;               // instance queries (verifier side; carried for the vk)
     const zk_srs* srs = nullptr;
     mutable std::shared_ptr<const QuotientPlan> qplan;      // the quotient's plan (degree classes, class programs), made on first use
 };
@@ -210,40 +186,6 @@ struct zk_proof {
 namespace {
 
 #define PK_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
-
-struct Reader {
-    const uint8_t* p; size_t left; bool ok = true;
-    uint32_t u32() { if (left < 4) { ok = false; return 0; } uint32_t v; memcpy(&v, p, 4); p += 4; left -= 4; return v; }
-    const uint8_t* bytes(size_t n) { if (left < n) { ok = false; return nullptr; } const uint8_t* r = p; p += n; left -= n; return r; }
-    // a count of records of `each` bytes that the rest of the blob can actually hold (a truncated or
-    // hostile header must not drive allocations)
-    uint32_t count(size_t each) { const uint32_t c = u32(); if (ok && (size_t)c * each > left) ok = false; return ok ? c : 0; }
-    Prog prog() { Prog g; const uint32_t len = count(12); g.reserve(len); for (uint32_t i = 0; i < len && ok; ++i) { Instr in; in.op = u32(); in.a = u32(); in.b = u32(); g.push_back(in); } return g; }
-    void queries(std::vector<Query>* out, uint32_t type, uint32_t ncols) {
-        const uint32_t cnt = count(8);
-        for (uint32_t i = 0; i < cnt && ok; ++i) { const uint32_t c = u32(); const int32_t rot = (int32_t)u32(); if (c >= ncols) ok = false; out->push_back(Query{type, c, rot}); }
-    }
-};
-
-// Degree of a postfix program as halo2's Expression::degree computes it (columns 1, constants and
-// challenges 0, sums the maximum, products the sum); -1 on a malformed program.
-int program_degree(const Prog& g, std::vector<int>* tmp_degree) {
-    std::vector<int> st;
-    for (const Instr& in : g) {
-        switch (in.op) {
-            case Q_PUSH_COL: st.push_back(1); break;
-            case Q_PUSH_CONST: st.push_back(0); break;
-            case Q_ADD: case Q_SUB: if (st.size() < 2) return -1; { const int b_ = st.back(); st.pop_back(); st.back() = std::max(st.back(), b_); } break;
-            case Q_MUL: if (st.size() < 2) return -1; { const int b_ = st.back(); st.pop_back(); st.back() += b_; } break;
-            case Q_NEG: case Q_DOUBLE: case Q_ADD_CONST: case Q_MUL_CONST: if (st.empty()) return -1; break;
-            case Q_SQUARE: if (st.empty()) return -1; st.back() *= 2; break;
-            case Q_TEE_TMP: if (st.empty()) return -1; if (in.a >= tmp_degree->size()) tmp_degree->resize(in.a + 1, 0); (*tmp_degree)[in.a] = st.back(); break;
-            case Q_PUSH_TMP: if (in.a >= tmp_degree->size()) return -1; st.push_back((*tmp_degree)[in.a]); break;
-            default: return -1;
-        }
-    }
-    return st.size() == 1 ? st[0] : -1;
-}
 
 int commit_lagrange(zk_ctx* ctx, const zk_srs* srs, const Fr* d_vals, size_t n, G1Affine* out) { return zk_commit(ctx, srs, 1, d_vals, n, out); }
 int commit_coeff(zk_ctx* ctx, const zk_srs* srs, const Fr* d_vals, size_t n, G1Affine* out) { return zk_commit(ctx, srs, 0, d_vals, n, out); }
@@ -495,18 +437,10 @@ int upload(zk_ctx* ctx, DevBuf* b, const void* h, size_t bytes) {
 
 }  // namespace
 
-extern "C" {
-
-void zk_pk_destroy(zk_ctx* ctx, zk_pk* pk) {
-    if (ctx) (void)zk_ctx_sync(ctx);
-    if (ctx && pk) ctx->coset_cache_bytes -= std::min(ctx->coset_cache_bytes, pk->part_cache_bytes);     // its slots go back to the shared budget
-    delete pk;
-}
-
-// The constraint-system part of a key blob (everything before the column data) into `pk`: shape, phases, query lists,
+// The constraint-system part of a key blob (everything before the column data) into `cs`: shape, phases, query lists,
 // permutation columns, constants, gate and lookup programs -- with every count checked against what the blob can hold and the
-// declared degree against what the programs need.  No device, no SRS (zk_pk_create goes on from here; the host-only hooks stop here).
-static int parse_cs(Reader& r, zk_pk* pk, size_t blob_len, bool with_columns, std::string* err) {
+// declared degree against what the programs need.  No device, no SRS (zk_pk_create goes on from here; zk_vk_create and the host-only hooks stop here).
+int zk::cs::parse_cs(Reader& r, ConstraintSystem* pk, size_t blob_len, bool with_columns, std::string* err) {
     char msg[256];
     auto fail = [&](int code, const char* fmt, auto... args) { snprintf(msg, sizeof msg, fmt, args...); *err = msg; return code; };
     if (r.u32() != 0x4B505A4Bu) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad magic");
@@ -545,7 +479,7 @@ static int parse_cs(Reader& r, zk_pk* pk, size_t blob_len, bool with_columns, st
     for (uint32_t i = 0; i < nconsts && r.ok; ++i) { const uint8_t* b = r.bytes(32); F4 v; if (b) memcpy(v.l, b, 32); pk->consts.push_back(v); }
     for (uint32_t i = 0; i < ngates && r.ok; ++i) pk->gates.push_back(r.prog());
     for (uint32_t i = 0; i < pk->L && r.ok; ++i) {
-        zk_pk::Lookup lk;
+        ConstraintSystem::Lookup lk;
         const uint32_t m = r.u32(), ninputs = r.count(4);
         if (!r.ok || m == 0 || ninputs == 0 || (size_t)m * 4 > r.left || (size_t)m * ninputs > r.left / 4) { r.ok = false; break; }
         for (uint32_t j = 0; j < m && r.ok; ++j) lk.tables.push_back(r.prog());
@@ -589,6 +523,14 @@ static int parse_cs(Reader& r, zk_pk* pk, size_t blob_len, bool with_columns, st
         if (!seen) return fail(ZK_ERR_INVALID_ARG, "pk blob: permutation column (%u, %u) is not queried at rotation 0", pc.first, pc.second);
     }
     return ZK_OK;
+}
+
+extern "C" {
+
+void zk_pk_destroy(zk_ctx* ctx, zk_pk* pk) {
+    if (ctx) (void)zk_ctx_sync(ctx);
+    if (ctx && pk) ctx->coset_cache_bytes -= std::min(ctx->coset_cache_bytes, pk->part_cache_bytes);     // its slots go back to the shared budget
+    delete pk;
 }
 
 // keygen_pk: parse the blob, make the key material device resident, commit fixed / sigma columns.
