@@ -96,7 +96,8 @@ int zk_prof_names(zk_ctx* ctx, char* buf, size_t len);
 /* Self-test of the device's Montgomery products (no reference counterpart: halo2curves' `Fr::mul` has one form; here the device runs
  * generated gfx950 asm -- csrc/mul29_asm.hip.hpp -- and the host / the definition the C forms of csrc/ff29.hip.hpp): `operand_sets`
  * lanes each run mul29 / mul29_ub / sqr29 / mul2add29 in both forms on pseudo-random operands AT the documented lazy-reduction
- * bounds and compare every limb.  out3 = {lanes with a difference, OR of the differing routines (1, 2, 4, 8), lanes run}. */
+ * bounds and compare every limb, and so do the evaluator's in-place forms mul29_ipa / mul29_ipb / mul29_ub_ipa / mul2add29_ub_ipa.
+ * out3 = {lanes with a difference, OR of the differing routines (1, 2, 4, 8; in-place 16, 32, 64, 128), lanes run}. */
 int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t seed, uint32_t* out3);
 
 /* ---- field vectors (halo2curves Fr/Fq Add/Sub/Mul, element-wise)  -- SURVEY 8a K4/K10 ---------- */
@@ -176,7 +177,9 @@ int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr,
 /* Host only (no device): the instruction stream the evaluator's kernel runs for `program` -- memory operands fused
  * into the operations (ADD_COL 16, SUB_COL 17, RSUB_COL 18, MUL_COL 19, FOLD_COL 20 | const << 12, NOP 21), bit 8 / 9
  * of word 0 = "settle t0 / t1 first", parked intermediates as columns num_cols + slot.  fuse = 0 keeps the caller's
- * sequence.  out_words may be NULL (sizes only).  For tests and for inspecting what a key's gates compile to. */
+ * sequence; fuse & 2 also fuses Horner steps  (S MUL_CONST c) + X * mem (+ chain)  into MAC_COL 22 | const << 16 (t0 = t0 * mem + S * c,
+ * one reduction), as zk_quotient_eval does unless ZK_QUOTIENT_MAC=0.  out_words may be NULL (sizes only).  For tests and for inspecting
+ * what a key's gates compile to. */
 int zk_host_quotient_lower(const uint32_t* program, uint32_t num_instr, uint32_t num_cols, int fuse, uint32_t* out_words, size_t cap_words,
                            uint32_t* out_instr, int* out_depth);
 /* Host only (no device): where zk_quotient_eval would cut `program` into slices for 2^ext_k rows (round 6: a large sum of terms
@@ -227,7 +230,9 @@ int zk_host_compile_class(const uint32_t* words, const uint32_t* lens, const uin
  * program -- exactly as zk_proof_finish will follow it; cs_blob = the constraint-system part of a zk_pk_create blob (column data
  * not needed).  out_summary: [0] ext_k - k, [1] constraints, [2] classes on, [3] additive split on, [4] expression graph on,
  * [5] remainder polynomials, [6] cost estimate, [7] columns read; then 8 words per class: used, instructions, products, columns,
- * values parked, slots alive at once, factor groups, last.  class_index / out_words / out_instr: one class's program (optional). */
+ * values parked, slots alive at once, factor groups, last.  With cap_summary >= 8 + 10 (E + 1): 2 more words per class after those,
+ * reductions and fused multiply-accumulates (Horner steps evaluated as two products under one reduction; 0 with ZK_QUOTIENT_MAC=0).
+ * class_index / out_words / out_instr: one class's program (optional). */
 int zk_host_quotient_plan(const void* cs_blob, size_t blob_len, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words,
                           uint32_t* out_instr);
 

@@ -109,6 +109,61 @@ def product_inplace(kind, on):
     return lines
 
 
+def product_inplace2():
+    """x <- mul2add29(x, y, s, c) with the RESULT IN x'S REGISTERS (the evaluator's fused Horner step  t0 * B + S * c): x * y vector x vector,
+    s * c vector x scalar (c wave-uniform, in scalar registers).  Same column sums in the same order as mul2add29_c; limb j of x is last read
+    in column j + 8 and result limb j is written in column j + 9, as in product_inplace.
+    Operands: 0..8 = x (in / out), 9..17 = scratch (m), 18..26 = y, 27..35 = s, 36..44 = c, 45..53 = the modulus, 54 INV, 55 MASK."""
+    x = list(range(9))
+    m = list(range(9, 18))
+    y = list(range(18, 27))
+    s = list(range(27, 36))
+    c = list(range(36, 45))
+    M = list(range(45, 54))
+    INV, MASK = 54, 55
+    lines = []
+    first = True
+    def mad(p, q):
+        nonlocal first
+        src2 = "0" if first else ACC
+        first = False
+        lines.append(f"v_mad_u64_u32 {ACC}, vcc, %{p}, %{q}, {src2}")
+    for k in range(17):
+        lo, hi = (0, k) if k < 9 else (k - 8, 8)
+        for i in range(lo, hi + 1):
+            mad(x[i], y[k - i])
+        for i in range(lo, hi + 1):
+            mad(s[i], c[k - i])
+        for i in range(lo, (k - 1 if k < 9 else 8) + 1):
+            mad(m[i], M[k - i])
+        if k < 9:
+            lines.append(f"v_mul_lo_u32 %{m[k]}, {LO}, %{INV}")
+            lines.append(f"v_and_b32 %{m[k]}, %{MASK}, %{m[k]}")
+            mad(m[k], M[0])
+        else:
+            lines.append(f"v_and_b32 %{x[k - 9]}, %{MASK}, {LO}")
+        lines.append(f"v_lshrrev_b64 {ACC}, 29, {ACC}")
+    lines.append(f"v_mov_b32 %{x[8]}, {LO}")
+    return lines
+
+
+def emit_inplace2(name):
+    body = "\\n\\t\"\n        \"".join(product_inplace2())
+    out = []
+    out.append(f"template <class P>\n__device__ __forceinline__ void {name}(F29<P>& x, const F29<P>& y, const F29<P>& s, const F29<P>& c) {{")
+    out.append("    uint32_t m0, m1, m2, m3, m4, m5, m6, m7, m8;")
+    out.append(f"    asm(\"{body}\"")
+    out.append("        : " + ", ".join(f"\"+v\"(x.l[{i}])" for i in range(9)) + ",")
+    out.append("          " + ", ".join(f"\"=&v\"(m{i})" for i in range(9)))
+    out.append("        : " + ", ".join(f"\"v\"(y.l[{i}])" for i in range(9)) + ",")
+    out.append("          " + ", ".join(f"\"v\"(s.l[{i}])" for i in range(9)) + ",")
+    out.append("          " + ", ".join(f"\"s\"(c.l[{i}])" for i in range(9)) + ",")
+    out.append("          " + ", ".join(f"\"s\"(P::M({i}))" for i in range(9)) + ", \"s\"(P::INV), \"s\"(MASK29)")
+    out.append(f"        : \"vcc\", \"v{AL}\", \"v{AH}\");")
+    out.append("}")
+    return "\n".join(out)
+
+
 def emit_inplace(name, kind, on):
     lines = product_inplace(kind, on)
     body = "\\n\\t\"\n        \"".join(lines)
@@ -168,6 +223,9 @@ def main():
     print()
     print("// x <- mul29_ub(x, y): y wave-uniform, in scalar registers")
     print(emit_inplace("mul29_ub_ipa_asm", "vs", "a"))
+    print()
+    print("// x <- mul2add29(x, y, s, c): c wave-uniform, in scalar registers (the evaluator's fused Horner step)")
+    print(emit_inplace2("mul2add29_ub_ipa_asm"))
 
 
 if __name__ == "__main__":

@@ -1496,7 +1496,7 @@ static bool quotient_split_enabled(bool sharded, bool gates_share_tmps) {
 // phases (which cosets read which column) and zk_proof_finish.  Candidates: degree classes with the additive split, degree
 // classes alone, one class -- the cheapest by a count of what each would execute (below) is taken; ZK_QUOTIENT_COSTGATE=0 takes
 // the most split one the knobs allow, as rounds 3-5 did.
-struct QPlanClass { Prog prog; std::vector<uint32_t> refs; uint32_t last = 0; bool used = false; uint32_t products = 0, parked = 0, max_live = 0, groups = 0; };
+struct QPlanClass { Prog prog; std::vector<uint32_t> refs; uint32_t last = 0; bool used = false; uint32_t products = 0, parked = 0, max_live = 0, groups = 0, fused = 0; };
 struct QPlanRem { uint32_t t = 0, e = 0; Prog prog; uint32_t last = 0; bool used = false; uint32_t products = 0; };
 struct QuotientPlan {
     std::string key;                 // the knob values the plan was made under
@@ -1512,6 +1512,26 @@ static uint32_t count_products(const Prog& g) {
     for (const Instr& in : g) c += in.op == Q_MUL || in.op == Q_SQUARE || in.op == Q_MUL_CONST || in.op == Q_FOLD;
     return c;
 }
+// Horner steps of a class program that the evaluator runs as one fused multiply-accumulate (K_MAC_COL of csrc/quotient.hip: two products, one
+// reduction) when ZK_QUOTIENT_MAC is on: the program lowered as zk_quotient_eval lowers it, constants numbered densely first
+static uint32_t count_fused(const Prog& g) {
+    std::vector<uint32_t> w;
+    w.reserve(3 * g.size() + 3);
+    std::unordered_map<uint32_t, uint32_t> cix;
+    for (const Instr& in : g) {
+        const bool c = in.op == Q_PUSH_CONST || in.op == Q_MUL_CONST || in.op == Q_ADD_CONST || in.op == Q_FOLD;
+        w.push_back(in.op); w.push_back(c ? cix.emplace(in.a, (uint32_t)cix.size()).first->second : in.a); w.push_back(in.b);
+    }
+    uint32_t n = 0;
+    int depth = 0;
+    if (zk_host_quotient_lower(w.data(), (uint32_t)g.size(), 0x80000000u, 3, nullptr, 0, &n, &depth)) return 0;
+    std::vector<uint32_t> out(3 * (size_t)n);
+    if (zk_host_quotient_lower(w.data(), (uint32_t)g.size(), 0x80000000u, 3, out.data(), out.size(), &n, &depth)) return 0;
+    uint32_t f = 0;
+    for (uint32_t i = 0; i < n; ++i) f += (out[3 * i] & 0xffu) == 22u;
+    return f;
+}
+static bool quotient_mac_enabled() { const char* e = getenv("ZK_QUOTIENT_MAC"); return !(e && atoi(e) == 0); }
 static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req, QuotientPlan& qp, std::string* err) {
     std::vector<Prog> cons;
     bool gates_share_tmps = false;
@@ -1584,6 +1604,7 @@ static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req
             }
         }
         c.products = count_products(c.prog);
+        c.fused = quotient_mac_enabled() ? count_fused(c.prog) : 0;
     }
     for (QPlanClass& c : qp.cls) {
         std::unordered_set<uint32_t> seen;
@@ -1610,7 +1631,7 @@ static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req
 }
 static std::string quotient_plan_key() {
     std::string k;
-    for (const char* name : {"ZK_QUOTIENT_SPLIT", "ZK_QUOTIENT_ADDSPLIT", "ZK_QUOTIENT_GROUP", "ZK_QUOTIENT_DAG", "ZK_QUOTIENT_COSTGATE"}) { const char* v = getenv(name); k += v ? v : "-"; k += '|'; }
+    for (const char* name : {"ZK_QUOTIENT_SPLIT", "ZK_QUOTIENT_ADDSPLIT", "ZK_QUOTIENT_GROUP", "ZK_QUOTIENT_DAG", "ZK_QUOTIENT_COSTGATE", "ZK_QUOTIENT_MAC"}) { const char* v = getenv(name); k += v ? v : "-"; k += '|'; }
     return k;
 }
 static int quotient_plan(const zk_pk* pk, std::shared_ptr<const QuotientPlan>* out, std::string* err) {
@@ -1900,6 +1921,11 @@ static int write_plan_summary(const std::shared_ptr<const QuotientPlan>& qp, uin
         uint32_t* o = out_summary + 8 + 8 * e;
         o[0] = c.used; o[1] = (uint32_t)c.prog.size(); o[2] = c.products; o[3] = (uint32_t)c.refs.size(); o[4] = c.parked; o[5] = c.max_live; o[6] = c.groups; o[7] = c.last;
     }
+    if (cap_summary >= 8 + 10 * (size_t)(qp->E + 1))         // a caller that asks for them: 2 more words per class -- reductions, fused multiply-accumulates
+        for (uint32_t e = 0; e <= qp->E; ++e) {
+            uint32_t* o = out_summary + 8 + 8 * (qp->E + 1) + 2 * e;
+            o[0] = qp->cls[e].products - qp->cls[e].fused; o[1] = qp->cls[e].fused;
+        }
     if (out_instr && class_index <= qp->E) {
         const Prog& g = qp->cls[class_index].prog;
         *out_instr = (uint32_t)g.size();

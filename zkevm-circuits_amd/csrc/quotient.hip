@@ -126,7 +126,10 @@ __device__ __forceinline__ Q29 q_mul(const Q29& a, const Q29& b) { return mul29(
 
 enum QOp : uint32_t { Q_END = 0, Q_PUSH_COL = 1, Q_PUSH_CONST = 2, Q_ADD = 3, Q_SUB = 4, Q_MUL = 5, Q_NEG = 6, Q_SQUARE = 7, Q_DOUBLE = 8, Q_FOLD = 9, Q_MUL_CONST = 10, Q_ADD_CONST = 11, Q_TEE_TMP = 12, Q_PUSH_TMP = 13,
                       // produced by the lowering only (never part of a caller's program): the second operand comes from memory
-                      K_ADD_COL = 16, K_SUB_COL = 17, K_RSUB_COL = 18, K_MUL_COL = 19, K_FOLD_COL = 20, K_NOP = 21 };
+                      K_ADD_COL = 16, K_SUB_COL = 17, K_RSUB_COL = 18, K_MUL_COL = 19, K_FOLD_COL = 20, K_NOP = 21,
+                      // t0 <- t0 * 32 mem + st[sp - 2] * const, pop (the constant index in word 0 above K_CONST_SHIFT, as K_FOLD_COL): a Horner step
+                      // S y^gap + X mem in one reduction (lower_fuse with mac; k_quotient_eval2 only)
+                      K_MAC_COL = 22 };
 constexpr uint32_t K_SETTLE0 = 0x100, K_SETTLE1 = 0x200;      // word 0 of a lowered instruction: settle t0 / t1 before executing
 constexpr uint32_t K_NORM0 = 0x400, K_NORM1 = 0x800;          // ... or only propagate its carries (limbs back below 2^29, value unchanged): a third of a settle
 constexpr uint32_t K_SETTLE0_8 = 0x1000, K_SETTLE1_8 = 0x2000; // ... or settle a value that may have reached 8p (q_settle8)
@@ -175,11 +178,11 @@ __device__ __forceinline__ Q29 unpack29_x32(const Fr& a) {
 }
 static inline bool k_has_mem_host(uint32_t w0) {
     const uint32_t o = w0 & 0xffu;
-    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL);
+    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL) || o == K_MAC_COL;
 }
 __device__ __forceinline__ bool k_has_mem(uint32_t w0) {
     const uint32_t o = w0 & 0xffu;
-    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL);
+    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL) || o == K_MAC_COL;
 }
 
 // Runs a LOWERED program (lower_program below): `prog` holds prog_len instructions followed by two END triples.
@@ -409,6 +412,7 @@ enum QClass : uint32_t {
     C_MULS = 1u << 16,       // t0 <- B * t0 (stack product)               MUL
     C_NEG = 1u << 17, C_SQ = 1u << 18, C_DBL = 1u << 19, C_TEE = 1u << 20,
     C_FOLD = 1u << 21,       // acc <- acc * const + t0, pop               FOLD
+    C_MACC = 1u << 22,       // t0 <- t0 * B + (entry below) * const, pop  MAC_COL
 };
 static uint32_t q_class_mask(uint32_t w0) {
     uint32_t m = 0;
@@ -430,6 +434,7 @@ static uint32_t q_class_mask(uint32_t w0) {
         case K_RSUB_COL: m = C_UNPACK_B | C_HASMEM | C_RARE | C_RSUB; break;
         case K_MUL_COL: m = C_UNPACK_B32 | C_HASMEM | C_MULV; break;
         case K_FOLD_COL: m = C_UNPACK_B | C_HASMEM | C_FOLDC; break;
+        case K_MAC_COL: m = C_UNPACK_B32 | C_HASMEM | C_MACC; break;
         default: break;            // K_NOP, Q_END
     }
     if (w0 & (K_SETTLE0 | K_SETTLE1 | K_NORM0 | K_NORM1 | K_SETTLE0_8 | K_SETTLE1_8)) m |= C_FLAGS;
@@ -558,6 +563,12 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
         // 3. the operation, on t0 in place
         if (w3 & C_MULV) mul29_ipa(t0, B);
         if (w3 & C_MULC) mul29_ub_ipa(t0, cst(consts_rp, w1));
+        if (w3 & C_MACC) {                                                  // S = the entry below the top: its bounds never ask for a settle (lower_bounds)
+            Q29 S;
+            st_get(sp - 2, S);
+            --sp;
+            mul2add29_ub_ipa(t0, B, S, cst(consts_rp, w0 >> K_CONST_SHIFT));
+        }
         if (w3 & C_ADDV) {
 #pragma unroll
             for (int q = 0; q < 9; ++q) t0.l[q] += B.l[q];
@@ -622,21 +633,59 @@ struct LNode {
 };
 struct LowInstr { uint32_t w0, a, b; };
 
-// expression trees of the program, re-emitted with memory operands (see the header comment)
-static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, std::vector<LowInstr>* out) {
+// expression trees of the program, re-emitted with memory operands (see the header comment).
+// mac (k_quotient_eval2 only): a Horner step of a compiled class program, (S MUL_CONST c) + T with T = X * mem followed by a chain of sums with
+// memory / constant operands (T = X * m - n, the regrouped `sel * expr`, ...), is re-associated into  K_MAC_COL(m, c)  (t0 = X * m + S * c, ONE
+// reduction for both products) followed by T's chain: every operand is read in the order it was, only the product by c moves.
+static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, std::vector<LowInstr>* out, bool mac = false) {
     std::vector<LNode> nodes;
     nodes.reserve(len);
     std::vector<int32_t> st;
     auto add = [&](LNode n) { nodes.push_back(n); return (int32_t)nodes.size() - 1; };
     auto leafish = [&](int32_t n) { return nodes[n].kind == LNode::MEM || nodes[n].kind == LNode::CONST; };
-    struct Work { int32_t node; int plan; };
+    struct Work { int32_t node; int plan; LowInstr raw; };        // plan 5: emit `raw` as it stands
     std::vector<Work> work;
     // plans of a BIN node after its operands: 0 = stack op, 1 = y from memory, 2 = y constant, 3 = x from memory (operands swapped), 4 = x constant (swapped)
+    auto bin_plan = [&](const LNode& n) {
+        const LNode &x = nodes[n.x], &y = nodes[n.y];
+        if (y.kind == LNode::MEM) return 1;
+        if (y.kind == LNode::CONST && (n.op == Q_ADD || n.op == Q_MUL)) return 2;
+        if (x.kind == LNode::MEM && !leafish(n.y) && !(x.is_tmp && y.has_tee)) return 3;
+        if (x.kind == LNode::CONST && !leafish(n.y) && (n.op == Q_ADD || n.op == Q_MUL)) return 4;
+        return 0;
+    };
+    // mac: T = X * mem under a chain of sums with a memory / constant operand, emitted the way the plans above emit it -> X, the product's
+    // memory operand, the chain's instructions innermost last
+    std::vector<LowInstr> chain;
+    auto mac_shape = [&](int32_t t, int32_t* xo, LowInstr* mo) -> bool {
+        chain.clear();
+        for (int guard = 0; guard < 64; ++guard) {
+            const LNode& n = nodes[t];
+            if (n.kind == LNode::CONSTOP && n.op == Q_ADD_CONST) { chain.push_back({Q_ADD_CONST, n.a, 0}); t = n.x; continue; }
+            if (n.kind != LNode::BIN) return false;
+            const int plan = bin_plan(n);
+            const LNode &x = nodes[n.x], &y = nodes[n.y];
+            if (n.op == Q_MUL) {
+                if (plan == 1) { *xo = n.x; *mo = {K_MAC_COL, y.a, y.b}; return true; }
+                if (plan == 3) { *xo = n.y; *mo = {K_MAC_COL, x.a, x.b}; return true; }
+                return false;
+            }
+            if (n.op == Q_SUB && plan == 1) { chain.push_back({K_SUB_COL, y.a, y.b}); t = n.x; continue; }
+            if (n.op != Q_ADD) return false;
+            if (plan == 1) { chain.push_back({K_ADD_COL, y.a, y.b}); t = n.x; }
+            else if (plan == 2) { chain.push_back({Q_ADD_CONST, y.a, 0}); t = n.x; }
+            else if (plan == 3) { chain.push_back({K_ADD_COL, x.a, x.b}); t = n.y; }
+            else if (plan == 4) { chain.push_back({Q_ADD_CONST, x.a, 0}); t = n.y; }
+            else return false;
+        }
+        return false;
+    };
     auto emit = [&](int32_t root) {
-        work.push_back({root, -1});
+        work.push_back({root, -1, {}});
         while (!work.empty()) {
             const Work wk = work.back();
             work.pop_back();
+            if (wk.plan == 5) { out->push_back(wk.raw); continue; }
             const LNode& n = nodes[wk.node];
             switch (n.kind) {
                 case LNode::MAT: break;
@@ -657,11 +706,17 @@ static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, st
                 case LNode::BIN: {
                     const LNode &x = nodes[n.x], &y = nodes[n.y];
                     if (wk.plan < 0) {
-                        int plan = 0;
-                        if (y.kind == LNode::MEM) plan = 1;
-                        else if (y.kind == LNode::CONST && (n.op == Q_ADD || n.op == Q_MUL)) plan = 2;
-                        else if (x.kind == LNode::MEM && !leafish(n.y) && !(x.is_tmp && y.has_tee)) plan = 3;
-                        else if (x.kind == LNode::CONST && !leafish(n.y) && (n.op == Q_ADD || n.op == Q_MUL)) plan = 4;
+                        int32_t xm = -1;
+                        LowInstr mi{};
+                        if (mac && n.op == Q_ADD && x.kind == LNode::CONSTOP && x.op == Q_MUL_CONST && x.a < (1u << (32 - K_CONST_SHIFT)) && mac_shape(n.y, &xm, &mi)) {
+                            // S, X, MAC_COL(m, c), the chain: pushed in reverse
+                            for (const LowInstr& c : chain) work.push_back({-1, 5, c});
+                            work.push_back({-1, 5, {mi.w0 | (x.a << K_CONST_SHIFT), mi.a, mi.b}});
+                            work.push_back({xm, -1, {}});
+                            work.push_back({x.x, -1, {}});
+                            break;
+                        }
+                        const int plan = bin_plan(n);
                         work.push_back({wk.node, plan});
                         if (plan == 0) { work.push_back({n.y, -1}); work.push_back({n.x, -1}); }
                         else if (plan == 1 || plan == 2) work.push_back({n.x, -1});
@@ -739,7 +794,7 @@ static int lower_bounds(std::vector<LowInstr>* prog_io, uint32_t num_cols, int* 
             if (bs.back().L + dL > 4) norm0();
             if (bs.back().V + dV > capV) settle0();
         };
-        const size_t need = (op == Q_ADD || op == Q_SUB || op == Q_MUL) ? 2 : (op == Q_PUSH_COL || op == Q_PUSH_CONST || op == K_FOLD_COL || op == K_NOP) ? 0 : 1;
+        const size_t need = (op == Q_ADD || op == Q_SUB || op == Q_MUL || op == K_MAC_COL) ? 2 : (op == Q_PUSH_COL || op == Q_PUSH_CONST || op == K_FOLD_COL || op == K_NOP) ? 0 : 1;
         if (bs.size() < need) return -1;
         switch (op) {
             case Q_PUSH_COL: case Q_PUSH_CONST: bs.push_back({1, 1}); break;
@@ -778,6 +833,14 @@ static int lower_bounds(std::vector<LowInstr>* prog_io, uint32_t num_cols, int* 
             case K_SUB_COL: room0(2, 2); bs.back() = {bs.back().V + 2, bs.back().L + 2}; break;
             case K_RSUB_COL: settled0(); bs.back() = {3, 1}; break;
             case K_MUL_COL: if (bs.back().V > 5) settle0(); bs.back() = {2, 1}; break;
+            case K_MAC_COL: {
+                // t0 * 32 m + S c' < (32 V_t0 + V_S) p^2 <= 168 p^2 < 2^261 p (V_t0 <= 5 as for MUL_COL, V_S <= 8); columns below
+                // 9 (L_t0 + L_S + 1) 2^58 + 2^35 < 2^64 for L_t0 + L_S <= 6 -- carries of t0 propagated where not (L_S <= 4): S never needs a flag
+                if (bs.back().V > 5) settle0();
+                if (bs.back().L + bs[bs.size() - 2].L > 6) norm0();
+                bs.pop_back(); bs.back() = {2, 1};
+                break;
+            }
             case K_FOLD_COL: case K_NOP: break;
             default: return -1;
         }
@@ -868,7 +931,7 @@ extern "C" int zk_host_quotient_lower(const uint32_t* h_program, uint32_t num_in
         }
     }
     std::vector<LowInstr> low;
-    if (fuse) lower_fuse(h_program, num_instr, num_cols, &low);
+    if (fuse) lower_fuse(h_program, num_instr, num_cols, &low, (fuse & 2) != 0);      // bit 1: the fused Horner steps (K_MAC_COL); fuse = 1 is the stream without them
     else
         for (uint32_t pc = 0; pc < num_instr && h_program[3 * pc] != Q_END; ++pc) {
             const uint32_t op = h_program[3 * pc], a_ = h_program[3 * pc + 1], b_ = h_program[3 * pc + 2];
@@ -979,6 +1042,8 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
     if (rc) return rc;
     const int kernel_knob = getenv("ZK_QUOTIENT_KERNEL") ? atoi(getenv("ZK_QUOTIENT_KERNEL")) : 2;       // 2: fixed register roles (k_quotient_eval2: one stack entry in registers, 4-word instructions); 1: round 5's kernel
     const bool v2 = kernel_knob != 1;
+    // fused Horner steps (K_MAC_COL; k_quotient_eval2 only).  ZK_QUOTIENT_MAC=0: the instruction stream without them (A/B runs, byte-equality tests)
+    const bool mac = v2 && !(getenv("ZK_QUOTIENT_MAC") && atoi(getenv("ZK_QUOTIENT_MAC")) == 0);
     const uint64_t ne = 1ull << ext_k;
     // a large sum of terms whose operands are read many times is cut into slices that share their rows' operands through the caches (plan_slices)
     SlicePlan plan;
@@ -1008,10 +1073,10 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
                 }
                 if (op == Q_PUSH_COL || op == Q_PUSH_CONST || op == Q_PUSH_TMP) ++spd;
                 else if (op == Q_ADD || op == Q_SUB || op == Q_MUL) --spd;
-                else if (op == Q_FOLD) { --spd; if (spd == 0) slice_k[sl] = slice_k[sl] * ((const Fr*)h_consts)[sub[3 * q + 1]]; }
+                else if (op == Q_FOLD) { --spd; slice_k[sl] = slice_k[sl] * ((const Fr*)h_consts)[sub[3 * q + 1]]; }       // EVERY fold multiplies the accumulator, whatever lies below it on the stack
             }
             sub.push_back(Q_END); sub.push_back(0); sub.push_back(0);
-            lower_fuse(sub.data(), (uint32_t)(sub.size() / 3), num_cols, &lows[sl]);
+            lower_fuse(sub.data(), (uint32_t)(sub.size() / 3), num_cols, &lows[sl], mac);
             int dsl = 0;
             if (lower_bounds(&lows[sl], num_cols, &dsl)) return ctx->fail(ZK_ERR_INVALID_ARG, "quotient program: lowering failed");
             dmax = std::max(dmax, dsl);
@@ -1027,7 +1092,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
                 if (op == Q_PUSH_TMP) low.push_back({Q_PUSH_COL, num_cols + a_, 0});
                 else low.push_back({op, a_, b_});
             }
-        } else lower_fuse(h_program, num_instr, num_cols, &low);
+        } else lower_fuse(h_program, num_instr, num_cols, &low, mac);
         if (lower_bounds(&low, num_cols, &depth)) return ctx->fail(ZK_ERR_INVALID_ARG, "quotient program: lowering failed");
     }
     if (depth > Q_MAX_STACK) return ctx->fail(ZK_ERR_UNSUPPORTED, "quotient program: stack deeper than %d", Q_MAX_STACK);
@@ -1061,12 +1126,12 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
         if (!d_part) return ZK_ERR_OOM;
     }
     if (getenv("ZK_QUOTIENT_TRACE") && low_len >= 64) {        // what the kernel will run: lowered instructions by opcode, settle bits, stack depth
-        static const char* names[22] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "SQUARE", "DOUBLE", "FOLD", "MUL_CONST", "ADD_CONST", "TEE_TMP", "PUSH_TMP", "?", "?",
-                                        "ADD_COL", "SUB_COL", "RSUB_COL", "MUL_COL", "FOLD_COL", "NOP"};
-        uint32_t hist[22] = {0}, settles = 0, norms = 0;
-        for (const std::vector<LowInstr>& low : lows) for (const LowInstr& in : low) { const uint32_t o = in.w0 & 0xffu; if (o < 22) ++hist[o]; settles += ((in.w0 & (K_SETTLE0 | K_SETTLE0_8)) ? 1 : 0) + ((in.w0 & (K_SETTLE1 | K_SETTLE1_8)) ? 1 : 0); norms += ((in.w0 & K_NORM0) ? 1 : 0) + ((in.w0 & K_NORM1) ? 1 : 0); }
+        static const char* names[23] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "SQUARE", "DOUBLE", "FOLD", "MUL_CONST", "ADD_CONST", "TEE_TMP", "PUSH_TMP", "?", "?",
+                                        "ADD_COL", "SUB_COL", "RSUB_COL", "MUL_COL", "FOLD_COL", "NOP", "MAC_COL"};
+        uint32_t hist[23] = {0}, settles = 0, norms = 0;
+        for (const std::vector<LowInstr>& low : lows) for (const LowInstr& in : low) { const uint32_t o = in.w0 & 0xffu; if (o < 23) ++hist[o]; settles += ((in.w0 & (K_SETTLE0 | K_SETTLE0_8)) ? 1 : 0) + ((in.w0 & (K_SETTLE1 | K_SETTLE1_8)) ? 1 : 0); norms += ((in.w0 & K_NORM0) ? 1 : 0) + ((in.w0 & K_NORM1) ? 1 : 0); }
         fprintf(stderr, "[zk quotient] 2^%u rows, %u lowered instructions%s, depth %d, %u settles, %u carry propagations:", ext_k, low_len, sliced ? (" in " + std::to_string(S) + " slices").c_str() : "", depth, settles, norms);
-        for (int o = 0; o < 22; ++o) if (hist[o]) fprintf(stderr, " %s %u", names[o], hist[o]);
+        for (int o = 0; o < 23; ++o) if (hist[o]) fprintf(stderr, " %s %u", names[o], hist[o]);
         if (sliced) { fprintf(stderr, "; slice lengths"); for (const std::vector<LowInstr>& low : lows) fprintf(stderr, " %zu", low.size()); fprintf(stderr, "; %u parking slots", num_tmp); }
         fprintf(stderr, "\n");
     }

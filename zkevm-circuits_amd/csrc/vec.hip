@@ -657,6 +657,12 @@ __global__ void k_selftest_products(uint32_t* bad, uint32_t seed) {
     cmp(mul29_ub(a, u), mul29_ub_c(a, u), 2u);
     cmp(sqr29(an), sqr29_c(an), 4u);
     cmp(mul2add29(an, b, c, d), mul2add29_c(an, b, c, d), 8u);
+    // the in-place forms the evaluator's interpreter runs (k_quotient_eval2): first factor / accumulated operand with limbs below 2^30,
+    // the constant factor workgroup-uniform (scalar registers)
+    { F29<P> x = a; mul29_ipa(x, b); cmp(x, mul29_c(a, b), 16u); }
+    { F29<P> x = b; mul29_ipb(x, a); cmp(x, mul29_c(a, b), 32u); }
+    { F29<P> x = a; mul29_ub_ipa(x, u); cmp(x, mul29_ub_c(a, u), 64u); }
+    { F29<P> x = a; mul2add29_ub_ipa(x, b, d, u); cmp(x, mul2add29_c(a, b, d, u), 128u); }
     // and the product against the definition: a b 2^-261 mod p through the 8 x 32 CIOS routine is covered by the NTT / MSM parity
     // tests; here the two forms of the SAME column sums must agree in every limb
     if (diff) { atomicAdd(bad, 1u); atomicOr(bad + 1, diff); }
