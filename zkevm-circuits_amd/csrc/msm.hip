@@ -1750,14 +1750,14 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
             const int p = (int)(it % GP);
             const int kind = (any_narrow && narrow[it] == 1) ? 0 : ((binsort && !(narrow && narrow[it] == 2)) ? 1 : 2);
             ctx->stream = P[p];
-            // a graph is tied to every address baked into its kernel arguments
-            uint64_t key = 1469598103934665603ull;
-            for (uint64_t v : {(uint64_t)kind, (uint64_t)p, (uint64_t)n, (uint64_t)pl.c, (uint64_t)pn.c, (uint64_t)(uintptr_t)d_table, (uint64_t)(uintptr_t)d_table_n, (uint64_t)tab_stride,
-                               (uint64_t)(uintptr_t)ws, (uint64_t)words, (uint64_t)(uintptr_t)bk[p], (uint64_t)(uintptr_t)desc, (uint64_t)staged_scatter, (uint64_t)range_bits, n_narrow})
-                key = (key ^ v) * 1099511628211ull;
-            hipGraphExec_t exec = nullptr;
+            // a graph is tied to every address and every plan parameter baked into its kernel arguments: ZK_MSM_TOP_SHIFT and
+            // ZK_MSM_CHUNK change the top-window shift and the partition grid without changing any address
             const std::vector<uint64_t> key_tuple = {(uint64_t)kind, (uint64_t)p, (uint64_t)n, (uint64_t)pl.c, (uint64_t)pn.c, (uint64_t)(uintptr_t)d_table, (uint64_t)(uintptr_t)d_table_n, (uint64_t)tab_stride,
-                                                     (uint64_t)(uintptr_t)ws, (uint64_t)words, (uint64_t)(uintptr_t)bk[p], (uint64_t)(uintptr_t)desc, (uint64_t)staged_scatter, (uint64_t)range_bits, n_narrow};
+                                                     (uint64_t)(uintptr_t)ws, (uint64_t)words, (uint64_t)(uintptr_t)bk[p], (uint64_t)(uintptr_t)desc, (uint64_t)staged_scatter, (uint64_t)range_bits, n_narrow,
+                                                     (uint64_t)pl.top_shift, (uint64_t)nwg};
+            uint64_t key = 1469598103934665603ull;
+            for (uint64_t v : key_tuple) key = (key ^ v) * 1099511628211ull;
+            hipGraphExec_t exec = nullptr;
             auto found = ctx->msm_graphs.find(key);
             if (found != ctx->msm_graphs.end() && ctx->msm_graph_keys[key] != key_tuple) {       // a 64-bit hash collision: the stale graph goes
                 (void)hipGraphExecDestroy((hipGraphExec_t)found->second);
@@ -1781,11 +1781,19 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
                 if (ok) ok = hipStreamEndCapture(P[p], &graph) == hipSuccess && graph != nullptr;
                 ok = ok && rc_e == ZK_OK && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
                 if (graph) (void)hipGraphDestroy(graph);
-                if (!ok) { (void)hipGetLastError(); ctx->msm_graph_broken = true; fallback = true; break; }
+                if (!ok) {
+                    const hipError_t e = hipGetLastError();
+                    if (getenv("ZK_MSM_TRACE")) fprintf(stderr, "[zk msm] graph capture failed (rc %d, %s): plain launches from now on\n", rc_e, hipGetErrorString(e));
+                    ctx->msm_graph_broken = true; fallback = true; break;
+                }
                 ctx->msm_graphs[key] = (void*)exec;
                 ctx->msm_graph_keys[key] = key_tuple;
             }
-            if (hipGraphLaunch(exec, P[p]) != hipSuccess) { (void)hipGetLastError(); ctx->msm_graph_broken = true; fallback = true; break; }
+            if (hipGraphLaunch(exec, P[p]) != hipSuccess) {
+                const hipError_t e = hipGetLastError();
+                if (getenv("ZK_MSM_TRACE")) fprintf(stderr, "[zk msm] graph replay failed (%s): plain launches from now on\n", hipGetErrorString(e));
+                ctx->msm_graph_broken = true; fallback = true; break;
+            }
             if (stage && it + 1 < count) { ctx->stream = P[(it + 1) % GP]; int rc = stage(stage_user, it + 1); if (rc) return rc; }
         }
         ctx->stream = P[0];
@@ -2281,13 +2289,16 @@ int srs_window_table(zk_ctx* ctx, const zk_srs* srs, int basis, size_t n, const 
     const char* env = getenv("ZK_MSM_TABLE_GB");
     const double cap_gb = env ? atof(env) : 32.0;
     if (n < 64 || (double)bytes > cap_gb * (double)(1ull << 30) || (uint64_t)pl.W * ns >= (1ull << 31)) return ZK_OK;
-    if (s->tab[basis] && s->tab_c[basis] != pl.c) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(s->tab[basis]); s->tab[basis] = nullptr; }   // plan changed (measurement knob)
+    // plan changed (measurement knobs): the top window's entries carry c - top_shift doublings, so a table is only valid for the
+    // (c, top_shift) it was built for
+    if (s->tab[basis] && (s->tab_c[basis] != pl.c || s->tab_shift[basis] != pl.top_shift)) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(s->tab[basis]); s->tab[basis] = nullptr; }
     if (!s->tab[basis]) {
         const G1Affine* rp = nullptr;
         int rc = srs_bases_rp(ctx, srs, basis, &rp);
         if (rc) return rc;
         if (hipMalloc(&s->tab[basis], bytes) != hipSuccess) { (void)hipGetLastError(); s->tab[basis] = nullptr; return ZK_OK; }   // no memory: per-window path
         s->tab_c[basis] = pl.c;
+        s->tab_shift[basis] = pl.top_shift;
         hipLaunchKernelGGL(k_build_window_tables, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, rp, ns, pl.c, pl.W, s->tab[basis], pl.top_shift);
         ZK_CHECK_LAUNCH(ctx);
     }
