@@ -91,6 +91,36 @@ def test_plan_of_a_key_is_reported(ctx, cref):
         srs.destroy()
 
 
+def test_the_plan_cache_follows_the_chunk_knob(ctx, cref, monkeypatch):
+    """ZK_QUOTIENT_CHUNK changes the class programs the compiler emits (tests/test_quotient_compile.py checks that it does on this key): the
+    plan a key keeps must be made again when it flips -- it is part of the plan key -- and be the plan zk_host_quotient_plan makes under
+    the same knob.  The proof stays the oracle prover's under both settings."""
+    from oracle import plonk_prover as pp
+    from test_quotient_compile import host_plan_summary
+    circ, adv, inst = build_evm_circuit(6, seed=2)
+    blob = circ.cs_blob()
+    srs = ctx.srs_setup_with_s(6, cref.fr_const(S_SECRET))
+    pk = ctx.pk_create(srs, circ.blob())
+    seed = bytes(range(5, 21))
+    try:
+        _, rep = pk.vk(circ.F + len(circ.perm_cols))
+        want = pp.create_proof(circ, pp.Srs(6, S_SECRET), adv, inst, cref.from_mont(rep.reshape(1, 4))[0], seed, "shplonk")
+        shape = {}
+        for chunk in ("0", "1", "0"):
+            monkeypatch.setenv("ZK_QUOTIENT_CHUNK", chunk)
+            classes = pk.quotient_plan()["classes"]
+            assert classes == host_plan_summary(blob)["classes"], chunk
+            shape.setdefault(chunk, [(c["instructions"], c["values_parked"]) for c in classes if c["used"]])
+            sess = ctx.proof_session(pk, [plonk.column_to_mont(c) for c in inst], seed)
+            sess.set_multiopen(1)
+            sess.advice_phase({i: plonk.column_to_mont(c) for i, c in enumerate(adv)})
+            assert sess.finish() == want, chunk
+        assert shape["0"] != shape["1"]
+    finally:
+        pk.destroy()
+        srs.destroy()
+
+
 def test_the_benched_evm_configuration_at_k20(ctx, cref):
     from test_gpu_headline_config import require_host_memory
     require_host_memory(64)

@@ -320,3 +320,30 @@ def test_the_plan_of_an_evm_style_constraint_system(zk):
         finally:
             for k_ in env:
                 os.environ.pop(k_)
+
+
+def host_plan_summary(blob):
+    """zk_host_quotient_plan's summary of a constraint system under the knobs in force (a fresh plan on every call)"""
+    from zkevm_circuits_amd import binding
+    lib = binding.lib()
+    summ = np.zeros(8 + 8 * 16, dtype=np.uint32)
+    n_ = ctypes.c_uint32()
+    assert lib.zk_host_quotient_plan(blob, ctypes.c_size_t(len(blob)), summ.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(summ.size),
+                                     ctypes.c_uint32(0xFFFFFFFF), None, ctypes.c_size_t(0), ctypes.byref(n_)) == 0
+    return binding.plan_summary(list(summ))
+
+
+def test_the_chunk_knob_changes_the_small_evm_key_plan(monkeypatch):
+    """the precondition of tests/test_gpu_evm_shape.py::test_the_plan_cache_follows_the_chunk_knob: on that small key ZK_QUOTIENT_CHUNK=1 makes
+    the compiler emit other class programs than ZK_QUOTIENT_CHUNK=0 (or no setting: the key is below the size that chunks by itself)"""
+    from plonk_fixtures import build_evm_circuit
+    circ, _, _ = build_evm_circuit(6, seed=2)
+    blob = circ.cs_blob()
+    shape = {}
+    for chunk in ("0", "1", None):
+        if chunk is None:
+            monkeypatch.delenv("ZK_QUOTIENT_CHUNK", raising=False)
+        else:
+            monkeypatch.setenv("ZK_QUOTIENT_CHUNK", chunk)
+        shape[chunk] = [(c["instructions"], c["values_parked"]) for c in host_plan_summary(blob)["classes"] if c["used"]]
+    assert shape["0"] != shape["1"] and shape[None] == shape["0"]

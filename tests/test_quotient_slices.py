@@ -99,3 +99,43 @@ def test_a_value_parked_across_the_whole_program_forbids_every_cut(monkeypatch):
     prog = [(PUSH_COL, 0, 0), (PUSH_COL, 1, 0), (MUL, 0, 0), (TEE, 0, 0), (FOLD, 0, 0)] + terms(rng, 500, 8) + [(PUSH_TMP, 0, 0), (FOLD, 1, 0)]
     assert cuts_of(prog, 20) == []
     assert len(cuts_of(terms(rng, 500, 8), 20)) == 9            # the same terms without it: the eight slices asked for
+
+
+def test_nested_folds_are_no_cut_points_and_count_in_the_slice_constant(monkeypatch):
+    """A FOLD while a value waits below it (PUSH a; <term>; FOLD c1; FOLD c2) multiplies the accumulator like any other fold: plan_slices cuts
+    only where the stack is empty, and the constant that carries the incoming accumulator through a slice is the product of EVERY fold
+    constant of the slice, the nested ones included (zk_quotient_eval's slice_k)."""
+    monkeypatch.setenv("ZK_QUOTIENT_SLICES", "8")
+    rng = random.Random(5)
+    prog = []
+    for t in range(300):
+        if t % 3 == 0:           # a term with a nested fold inside
+            prog += [(PUSH_COL, rng.randrange(8), 0), (PUSH_COL, rng.randrange(8), 0), (MUL, 0, 0),
+                     (PUSH_COL, rng.randrange(8), 0), (PUSH_COL, rng.randrange(8), 0), (SUB, 0, 0), (FOLD, rng.randrange(4), 0), (FOLD, rng.randrange(4), 0)]
+        else:
+            prog += terms(rng, 1, 8)
+    sp, top_level, nested = 0, set(), set()
+    for pc, (op, a, _) in enumerate(prog):
+        sp += 1 if op in (PUSH_COL, PUSH_CONST, PUSH_TMP) else -1 if op in (ADD, SUB, MUL, FOLD) else 0
+        if op == FOLD:
+            (top_level if sp == 0 else nested).add(pc + 1)
+    assert len(nested) == 100
+    cuts = cuts_of(prog, 20)
+    assert len(cuts) == 9
+    assert set(cuts[1:-1]) <= top_level and not set(cuts) & nested
+    consts = [rng.randrange(R) for _ in range(4)]
+    row = [rng.randrange(R) for _ in range(8)]
+    acc = acc_top_only = 0
+    for x, y in zip(cuts, cuts[1:]):
+        sl = prog[x:y]
+        every, top = 1, 1
+        sp = 0
+        for op, a, _ in sl:
+            sp += 1 if op in (PUSH_COL, PUSH_CONST, PUSH_TMP) else -1 if op in (ADD, SUB, MUL, FOLD) else 0
+            if op == FOLD:
+                every = every * consts[a] % R
+                top = top * consts[a] % R if sp == 0 else top
+        acc = (acc * every + run(sl, row, consts)) % R
+        acc_top_only = (acc_top_only * top + run(sl, row, consts)) % R
+    assert acc == run(prog, row, consts)
+    assert acc_top_only != acc            # a slice constant without the nested folds would be wrong

@@ -1631,7 +1631,7 @@ static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req
 }
 static std::string quotient_plan_key() {
     std::string k;
-    for (const char* name : {"ZK_QUOTIENT_SPLIT", "ZK_QUOTIENT_ADDSPLIT", "ZK_QUOTIENT_GROUP", "ZK_QUOTIENT_DAG", "ZK_QUOTIENT_COSTGATE", "ZK_QUOTIENT_MAC"}) { const char* v = getenv(name); k += v ? v : "-"; k += '|'; }
+    for (const char* name : {"ZK_QUOTIENT_SPLIT", "ZK_QUOTIENT_ADDSPLIT", "ZK_QUOTIENT_GROUP", "ZK_QUOTIENT_DAG", "ZK_QUOTIENT_COSTGATE", "ZK_QUOTIENT_MAC", "ZK_QUOTIENT_CHUNK"}) { const char* v = getenv(name); k += v ? v : "-"; k += '|'; }
     return k;
 }
 static int quotient_plan(const zk_pk* pk, std::shared_ptr<const QuotientPlan>* out, std::string* err) {
