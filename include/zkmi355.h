@@ -182,6 +182,13 @@ int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr,
  * what a key's gates compile to. */
 int zk_host_quotient_lower(const uint32_t* program, uint32_t num_instr, uint32_t num_cols, int fuse, uint32_t* out_words, size_t cap_words,
                            uint32_t* out_instr, int* out_depth);
+/* The same, and *out_declined (may be NULL) = the sums of two column products left unfused because fusing them would have taken the
+ * stack deeper than the fuse = 3 stream goes.  fuse & 4 (with fuse & 2; zk_quotient_eval unless ZK_QUOTIENT_MAC=0 or 1): a Horner step over a sum
+ * of two column products, S c + X * m1 + Y * m2, becomes  S, X, PUSH_COL32 23 (m1: pushes 32 m1; its settle bits act on the entry it spills, X), Y,
+ * MAC2_COL 24 | const << 16 (m2)  -- three products, one reduction, three entries popped -- and one over a product of two computed values,
+ * S c + U * V, becomes  S, U, V, MAC_STK 25 | const << 16  (two entries popped).  fuse = 0 ... 3 are unaffected by bit 2's existence. */
+int zk_host_quotient_lower2(const uint32_t* program, uint32_t num_instr, uint32_t num_cols, int fuse, uint32_t* out_words, size_t cap_words,
+                            uint32_t* out_instr, int* out_depth, uint32_t* out_declined);
 /* Host only (no device): where zk_quotient_eval would cut `program` into slices for 2^ext_k rows (round 6: a large sum of terms
  * acc = acc * c_f + term_f whose operands are read many times is evaluated slice by slice over the same rows at the same time so
  * that the slices find each other's operands in the caches; cuts only at top-level FOLDs that no parked intermediate is alive
@@ -232,6 +239,10 @@ int zk_host_compile_class(const uint32_t* words, const uint32_t* lens, const uin
  * [5] remainder polynomials, [6] cost estimate, [7] columns read; then 8 words per class: used, instructions, products, columns,
  * values parked, slots alive at once, factor groups, last.  With cap_summary >= 8 + 10 (E + 1): 2 more words per class after those,
  * reductions and fused multiply-accumulates (Horner steps evaluated as two products under one reduction; 0 with ZK_QUOTIENT_MAC=0).
+ * Those two words describe the K_MAC_COL-only (fuse = 3) stream whatever the knob's other values: reductions + fused = products.  With
+ * cap_summary >= 8 + 14 (E + 1): 4 more words per class after those, for the stream in force (ZK_QUOTIENT_MAC unset / 2: fuse = 7; 1: fuse = 3;
+ * 0: none): sums of two column products fused (MAC2_COL), stack products fused (MAC_STK), MAC2_COL fusions declined for stack depth, reductions
+ * of that stream (products - MAC_COL - 2 MAC2_COL - MAC_STK).  No word depends on the room given beyond its own presence.
  * class_index / out_words / out_instr: one class's program (optional). */
 int zk_host_quotient_plan(const void* cs_blob, size_t blob_len, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words,
                           uint32_t* out_instr);

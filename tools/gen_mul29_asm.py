@@ -164,6 +164,62 @@ def emit_inplace2(name):
     return "\n".join(out)
 
 
+def product_inplace_sum(prods):
+    """x <- (sum of the products) / 2^261 with the RESULT IN x'S REGISTERS: `prods` lists (first factor, second factor) as operand-number lists,
+    x = operands 0..8 being a factor of the first product, operands 9..17 the scratch registers of the Montgomery multipliers, the modulus, INV
+    and MASK behind the last factor.  One product after the other joins each column sum (the column accumulator is the only wide value alive),
+    then the reduction's terms; limb j of x is last read in column j + 8 and result limb j is written in column j + 9, as in product_inplace."""
+    x = list(range(9))
+    m = list(range(9, 18))
+    last = max(max(f) for pr in prods for f in pr)
+    M = list(range(last + 1, last + 10))
+    INV, MASK = last + 10, last + 11
+    lines = []
+    first = True
+    def mad(p, q):
+        nonlocal first
+        src2 = "0" if first else ACC
+        first = False
+        lines.append(f"v_mad_u64_u32 {ACC}, vcc, %{p}, %{q}, {src2}")
+    for k in range(17):
+        lo, hi = (0, k) if k < 9 else (k - 8, 8)
+        for a, b in prods:
+            for i in range(lo, hi + 1):
+                mad(a[i], b[k - i])
+        for i in range(lo, (k - 1 if k < 9 else 8) + 1):
+            mad(m[i], M[k - i])
+        if k < 9:
+            lines.append(f"v_mul_lo_u32 %{m[k]}, {LO}, %{INV}")
+            lines.append(f"v_and_b32 %{m[k]}, %{MASK}, %{m[k]}")
+            mad(m[k], M[0])
+        else:
+            lines.append(f"v_and_b32 %{x[k - 9]}, %{MASK}, {LO}")
+        lines.append(f"v_lshrrev_b64 {ACC}, 29, {ACC}")
+    lines.append(f"v_mov_b32 %{x[8]}, {LO}")
+    return lines
+
+
+def emit_inplace_sum(name, args, prods):
+    """args: the inputs behind x in operand order, (name, 'v' | 's'); prods: pairs of names ('x' included)"""
+    num = {"x": list(range(9))}
+    for j, (a, _) in enumerate(args):
+        num[a] = list(range(18 + 9 * j, 27 + 9 * j))
+    body = "\\n\\t\"\n        \"".join(product_inplace_sum([(num[a], num[b]) for a, b in prods]))
+    out = []
+    sig = ", ".join(f"const F29<P>& {a}" for a, _ in args)
+    out.append(f"template <class P>\n__device__ __forceinline__ void {name}(F29<P>& x, {sig}) {{")
+    out.append("    uint32_t m0, m1, m2, m3, m4, m5, m6, m7, m8;")
+    out.append(f"    asm(\"{body}\"")
+    out.append("        : " + ", ".join(f"\"+v\"(x.l[{i}])" for i in range(9)) + ",")
+    out.append("          " + ", ".join(f"\"=&v\"(m{i})" for i in range(9)))
+    for j, (a, c) in enumerate(args):
+        out.append(("        : " if j == 0 else "          ") + ", ".join(f"\"{c}\"({a}.l[{i}])" for i in range(9)) + ",")
+    out.append("          " + ", ".join(f"\"s\"(P::M({i}))" for i in range(9)) + ", \"s\"(P::INV), \"s\"(MASK29)")
+    out.append(f"        : \"vcc\", \"v{AL}\", \"v{AH}\");")
+    out.append("}")
+    return "\n".join(out)
+
+
 def emit_inplace(name, kind, on):
     lines = product_inplace(kind, on)
     body = "\\n\\t\"\n        \"".join(lines)
@@ -226,6 +282,12 @@ def main():
     print()
     print("// x <- mul2add29(x, y, s, c): c wave-uniform, in scalar registers (the evaluator's fused Horner step)")
     print(emit_inplace2("mul2add29_ub_ipa_asm"))
+    print()
+    print("// x <- mul2add29(y, x, s, c): x is the SECOND factor of the first product (normalised), c wave-uniform (the evaluator's Horner step over a stack product)")
+    print(emit_inplace_sum("mul2add29_ub_ipb_asm", [("y", "v"), ("s", "v"), ("c", "s")], [("y", "x"), ("s", "c")]))
+    print()
+    print("// x <- mul3add29(x, y, a, b, s, c) = (x y + a b + s c) / 2^261: c wave-uniform (the evaluator's Horner step over a sum of two column products)")
+    print(emit_inplace_sum("mul3add29_ub_ipa_asm", [("y", "v"), ("a", "v"), ("b", "v"), ("s", "v"), ("c", "s")], [("x", "y"), ("a", "b"), ("s", "c")]))
 
 
 if __name__ == "__main__":

@@ -423,6 +423,35 @@ __host__ __device__ __forceinline__ F29<P> mul2add29_c(const F29<P>& a, const F2
     t.l[8] = (uint32_t)acc;
     return t;
 }
+// (a*b + c*d + e*f) * 2^-261 mod p in one pass: three products in the same column sums, one reduction (the evaluator's Horner step over a
+// sum of two column products, csrc/quotient.hip K_MAC2_COL).  b, d, f normalised; limbs of a, c, e below L_a 2^29, L_c 2^29, L_e 2^29 with
+// L_a + L_c + L_e <= 6: a column holds below 9 (L_a + L_c + L_e + 1) 2^58 + 2^35 < 2^64.  a*b + c*d + e*f < 2^261 p.  Result normalised, below 2p.
+template <class P>
+__host__ __device__ __forceinline__ F29<P> mul3add29_c(const F29<P>& a, const F29<P>& b, const F29<P>& c, const F29<P>& d, const F29<P>& e, const F29<P>& f) {
+    uint32_t m[9];
+    F29<P> t;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 17; ++k) {
+        const int lo = k < 9 ? 0 : k - 8, hi = k < 9 ? k : 8, nm = k < 9 ? k : 17 - k;
+        uint32_t ys[9], ds[9], fs[9], ks[9];
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) { ys[i - lo] = b.l[k - i]; ds[i - lo] = d.l[k - i]; fs[i - lo] = f.l[k - i]; ks[i - lo] = P::M(k - i); }
+        acc = dotv(a.l + lo, ys, hi - lo + 1, acc);
+        acc = dotv(c.l + lo, ds, hi - lo + 1, acc);
+        acc = dotv(e.l + lo, fs, hi - lo + 1, acc);
+        acc = dotk(m + lo, ks, nm, acc);
+        if (k < 9) {
+            m[k] = ((uint32_t)acc * P::INV) & MASK29;
+            acc += (uint64_t)m[k] * P::M(0);
+        } else {
+            t.l[k - 9] = (uint32_t)acc & MASK29;
+        }
+        acc >>= 29;
+    }
+    t.l[8] = (uint32_t)acc;
+    return t;
+}
 // K*p - b taken limb by limb (b normalised, top limb of b below the top limb of K*p, i.e. b < K*p - 2^232): the value is
 // K*p - b, limbs are non-negative and below 2^30, not normalised -- what mul2add29 takes as its last operand.
 template <int K, class P>
@@ -553,6 +582,26 @@ __host__ __device__ __forceinline__ void mul2add29_ub_ipa(F29<P>& x, const F29<P
     mul2add29_ub_ipa_asm<P>(x, y, s, c);
 #else
     x = mul2add29_c<P>(x, y, s, c);
+#endif
+}
+// x <- mul2add29(y, x, s, c): x is the SECOND factor of the first product (normalised; a stack product's top entry, shifted), y its first
+// (limbs below L_y 2^29, L_y + L_s <= 6): the Horner step over a product of two computed values, K_MAC_STK.
+template <class P>
+__host__ __device__ __forceinline__ void mul2add29_ub_ipb(F29<P>& x, const F29<P>& y, const F29<P>& s, const F29<P>& c) {
+#if ZK_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
+    mul2add29_ub_ipb_asm<P>(x, y, s, c);
+#else
+    x = mul2add29_c<P>(y, x, s, c);
+#endif
+}
+// x <- mul3add29(x, y, a, b, s, c) = (x y + a b + s c) / 2^261 mod p, c wave-uniform: K_MAC2_COL's  t0 * 32 m2 + X * 32 m1 + S y^gap.
+// y, b, c normalised; limbs of x, a, s below L 2^29 each with L_x + L_a + L_s <= 6 (mul3add29_c).
+template <class P>
+__host__ __device__ __forceinline__ void mul3add29_ub_ipa(F29<P>& x, const F29<P>& y, const F29<P>& a, const F29<P>& b, const F29<P>& s, const F29<P>& c) {
+#if ZK_MUL_ASM && defined(__HIP_DEVICE_COMPILE__)
+    mul3add29_ub_ipa_asm<P>(x, y, a, b, s, c);
+#else
+    x = mul3add29_c<P>(x, y, a, b, s, c);
 #endif
 }
 

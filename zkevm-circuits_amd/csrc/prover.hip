@@ -1496,7 +1496,7 @@ static bool quotient_split_enabled(bool sharded, bool gates_share_tmps) {
 // phases (which cosets read which column) and zk_proof_finish.  Candidates: degree classes with the additive split, degree
 // classes alone, one class -- the cheapest by a count of what each would execute (below) is taken; ZK_QUOTIENT_COSTGATE=0 takes
 // the most split one the knobs allow, as rounds 3-5 did.
-struct QPlanClass { Prog prog; std::vector<uint32_t> refs; uint32_t last = 0; bool used = false; uint32_t products = 0, parked = 0, max_live = 0, groups = 0, fused = 0; };
+struct QPlanClass { Prog prog; std::vector<uint32_t> refs; uint32_t last = 0; bool used = false; uint32_t products = 0, parked = 0, max_live = 0, groups = 0, fused = 0, mac2 = 0, mac_stk = 0, declined = 0, reductions = 0; };
 struct QPlanRem { uint32_t t = 0, e = 0; Prog prog; uint32_t last = 0; bool used = false; uint32_t products = 0; };
 struct QuotientPlan {
     std::string key;                 // the knob values the plan was made under
@@ -1514,7 +1514,8 @@ static uint32_t count_products(const Prog& g) {
 }
 // Horner steps of a class program that the evaluator runs as one fused multiply-accumulate (K_MAC_COL of csrc/quotient.hip: two products, one
 // reduction) when ZK_QUOTIENT_MAC is on: the program lowered as zk_quotient_eval lowers it, constants numbered densely first
-static uint32_t count_fused(const Prog& g) {
+// fuse = 3: K_MAC_COL alone (out4 unused); fuse = 7: out4 = { MAC2_COL, MAC_STK, MAC2_COL fusions declined for stack depth, MAC_COL } of that stream
+static uint32_t count_fused(const Prog& g, int fuse = 3, uint32_t* out4 = nullptr) {
     std::vector<uint32_t> w;
     w.reserve(3 * g.size() + 3);
     std::unordered_map<uint32_t, uint32_t> cix;
@@ -1524,14 +1525,17 @@ static uint32_t count_fused(const Prog& g) {
     }
     uint32_t n = 0;
     int depth = 0;
-    if (zk_host_quotient_lower(w.data(), (uint32_t)g.size(), 0x80000000u, 3, nullptr, 0, &n, &depth)) return 0;
+    uint32_t decl = 0;
+    if (zk_host_quotient_lower2(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, nullptr, 0, &n, &depth, &decl)) return 0;
     std::vector<uint32_t> out(3 * (size_t)n);
-    if (zk_host_quotient_lower(w.data(), (uint32_t)g.size(), 0x80000000u, 3, out.data(), out.size(), &n, &depth)) return 0;
-    uint32_t f = 0;
-    for (uint32_t i = 0; i < n; ++i) f += (out[3 * i] & 0xffu) == 22u;
+    if (zk_host_quotient_lower2(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, out.data(), out.size(), &n, &depth, &decl)) return 0;
+    uint32_t f = 0, f2 = 0, fs = 0;
+    for (uint32_t i = 0; i < n; ++i) { const uint32_t o = out[3 * i] & 0xffu; f += o == 22u; f2 += o == 24u; fs += o == 25u; }
+    if (out4) { out4[0] = f2; out4[1] = fs; out4[2] = decl; out4[3] = f; }
     return f;
 }
-static bool quotient_mac_enabled() { const char* e = getenv("ZK_QUOTIENT_MAC"); return !(e && atoi(e) == 0); }
+static int quotient_mac_level() { const char* e = getenv("ZK_QUOTIENT_MAC"); return e ? atoi(e) : 2; }      // 0: no fused steps, 1: K_MAC_COL alone, otherwise all (csrc/quotient.hip)
+static bool quotient_mac_enabled() { return quotient_mac_level() != 0; }
 static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req, QuotientPlan& qp, std::string* err) {
     std::vector<Prog> cons;
     bool gates_share_tmps = false;
@@ -1605,6 +1609,13 @@ static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req
         }
         c.products = count_products(c.prog);
         c.fused = quotient_mac_enabled() ? count_fused(c.prog) : 0;
+        c.reductions = c.products - c.fused;
+        if (quotient_mac_enabled() && quotient_mac_level() != 1) {
+            uint32_t f4[4] = {0, 0, 0, 0};
+            count_fused(c.prog, 7, f4);
+            c.mac2 = f4[0]; c.mac_stk = f4[1]; c.declined = f4[2];
+            c.reductions = c.products - f4[3] - 2 * f4[0] - f4[1];
+        }
     }
     for (QPlanClass& c : qp.cls) {
         std::unordered_set<uint32_t> seen;
@@ -1888,6 +1899,9 @@ int zk_host_compile_class(const uint32_t* words, const uint32_t* lens, const uin
 // [2] degree classes on, [3] additive split on, [4] compiled through the expression graph, [5] remainder polynomials, [6] the cost
 // estimate the candidates were compared by, [7] columns read; then 8 words per class e <= E: used, instructions, products, columns
 // read, values parked, parking slots alive at once, factor groups, last.  class_index <= E with out_words: that class's program.
+// With room for 8 + 10 (E + 1) words: per class the reductions and K_MAC_COL steps of the fuse = 3 stream (reductions + fused = products, whatever
+// else the knob turns on); with room for 8 + 14 (E + 1): per class, for the stream ZK_QUOTIENT_MAC puts in force, MAC2_COL steps, MAC_STK steps,
+// MAC2_COL fusions declined for stack depth, reductions.  Earlier words never depend on the room given.
 static int write_plan_summary(const std::shared_ptr<const QuotientPlan>& qp, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr);
 int zk_host_quotient_plan(const void* cs_blob, size_t blob_len, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr) {
     if (!cs_blob || !out_summary) return ZK_ERR_INVALID_ARG;
@@ -1925,6 +1939,11 @@ static int write_plan_summary(const std::shared_ptr<const QuotientPlan>& qp, uin
         for (uint32_t e = 0; e <= qp->E; ++e) {
             uint32_t* o = out_summary + 8 + 8 * (qp->E + 1) + 2 * e;
             o[0] = qp->cls[e].products - qp->cls[e].fused; o[1] = qp->cls[e].fused;
+        }
+    if (cap_summary >= 8 + 14 * (size_t)(qp->E + 1))         // ... and 4 more for the stream in force: MAC2_COL, MAC_STK, fusions declined for stack depth, its reductions
+        for (uint32_t e = 0; e <= qp->E; ++e) {
+            uint32_t* o = out_summary + 8 + 10 * (qp->E + 1) + 4 * e;
+            o[0] = qp->cls[e].mac2; o[1] = qp->cls[e].mac_stk; o[2] = qp->cls[e].declined; o[3] = qp->cls[e].reductions;
         }
     if (out_instr && class_index <= qp->E) {
         const Prog& g = qp->cls[class_index].prog;

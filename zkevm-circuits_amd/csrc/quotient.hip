@@ -58,6 +58,13 @@
 //                  K = 1 for canonical b, 2 for settled b
 //   FOLD           acc = mul29(acc, y) + t: acc is only ever the first operand of a product by a
 //                  constant, so it is never settled: L_t <= 3
+//   MAC_COL        t0 * 32 m + S c' under one reduction: 32 V_t0 + V_S <= 168 < 2^261 / p = 169.3 (V_t0 <= 5, V_S <= 8); a column
+//                  holds 18 limb products + 9 of the reduction, below 9 (L_t0 + L_S + 1) 2^58 + 2^35 < 2^64 for L_t0 + L_S <= 6
+//   MAC2_COL       t0 * 32 m2 + X * 32 m1 + S c' (t0 = Y): 32 (V_X + V_Y) + V_S <= 168 needs V_X + V_Y <= 5; 27 limb products + 9 a
+//                  column, below 9 (L_X + L_Y + L_S + 1) 2^58 + 2^35 < 2^64 for L_X + L_Y + L_S <= 6.  X and S are in LDS by then: X is
+//                  brought to V <= 3, L_X + L_S <= 5 by requests on the PUSH_COL32 that spills it, Y by MAC2_COL's own (lower_bounds)
+//   MAC_STK        B * 32 t0 + S c' (t0 settled, B popped into registers): V_B V_t0 <= 5 as for MUL, L_B + L_S <= 6
+//   No request is ever made for an entry that is in LDS when the instruction runs: the kernel has no step for it.
 #include "ctx.hpp"
 #include "ff29.hip.hpp"
 #include <unordered_map>
@@ -129,7 +136,14 @@ enum QOp : uint32_t { Q_END = 0, Q_PUSH_COL = 1, Q_PUSH_CONST = 2, Q_ADD = 3, Q_
                       K_ADD_COL = 16, K_SUB_COL = 17, K_RSUB_COL = 18, K_MUL_COL = 19, K_FOLD_COL = 20, K_NOP = 21,
                       // t0 <- t0 * 32 mem + st[sp - 2] * const, pop (the constant index in word 0 above K_CONST_SHIFT, as K_FOLD_COL): a Horner step
                       // S y^gap + X mem in one reduction (lower_fuse with mac; k_quotient_eval2 only)
-                      K_MAC_COL = 22 };
+                      K_MAC_COL = 22,
+                      // Sums of two column products under one reduction (lower_fuse with mac2; k_quotient_eval2 only).  The stream of such a term is
+                      //   <S> <X> PUSH_COL32 m1 <Y> MAC2_COL(m2, const):  t0 <- t0 * 32 m2 + st[sp - 3] * st[sp - 2] + st[sp - 4] * const, three entries popped
+                      // (t0 = Y, st[sp - 2] = 32 m1 as PUSH_COL32 left it, st[sp - 3] = X, st[sp - 4] = S): one memory operand per instruction, m1 travels over
+                      // the stack.  PUSH_COL32 pushes 32 x its memory operand; ITS settle / carry bits (bit 0 forms only) act on the entry it spills, X.
+                      K_PUSH_COL32 = 23, K_MAC2_COL = 24,
+                      // t0 <- st[sp - 2] * 32 t0 + st[sp - 3] * const, two entries popped: a Horner step over a stack product, S y^gap + U V
+                      K_MAC_STK = 25 };
 constexpr uint32_t K_SETTLE0 = 0x100, K_SETTLE1 = 0x200;      // word 0 of a lowered instruction: settle t0 / t1 before executing
 constexpr uint32_t K_NORM0 = 0x400, K_NORM1 = 0x800;          // ... or only propagate its carries (limbs back below 2^29, value unchanged): a third of a settle
 constexpr uint32_t K_SETTLE0_8 = 0x1000, K_SETTLE1_8 = 0x2000; // ... or settle a value that may have reached 8p (q_settle8)
@@ -178,11 +192,11 @@ __device__ __forceinline__ Q29 unpack29_x32(const Fr& a) {
 }
 static inline bool k_has_mem_host(uint32_t w0) {
     const uint32_t o = w0 & 0xffu;
-    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL) || o == K_MAC_COL;
+    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL) || o == K_MAC_COL || o == K_PUSH_COL32 || o == K_MAC2_COL;
 }
 __device__ __forceinline__ bool k_has_mem(uint32_t w0) {
     const uint32_t o = w0 & 0xffu;
-    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL) || o == K_MAC_COL;
+    return o == Q_PUSH_COL || (o >= K_ADD_COL && o <= K_FOLD_COL) || o == K_MAC_COL || o == K_PUSH_COL32 || o == K_MAC2_COL;
 }
 
 // Runs a LOWERED program (lower_program below): `prog` holds prog_len instructions followed by two END triples.
@@ -413,6 +427,9 @@ enum QClass : uint32_t {
     C_NEG = 1u << 17, C_SQ = 1u << 18, C_DBL = 1u << 19, C_TEE = 1u << 20,
     C_FOLD = 1u << 21,       // acc <- acc * const + t0, pop               FOLD
     C_MACC = 1u << 22,       // t0 <- t0 * B + (entry below) * const, pop  MAC_COL
+    C_UNPACK_T32 = 1u << 23, // spill (word 0's flags on the spilled entry), t0 <- 32 x memory operand     PUSH_COL32
+    C_MAC2 = 1u << 24,       // t0 <- t0 * B + X * m1 + S * const, pop 3   MAC2_COL
+    C_MACS = 1u << 25,       // t0 <- B * 32 t0 + S * const, pop (B popped by C_POP_B)   MAC_STK (under C_RARE)
 };
 static uint32_t q_class_mask(uint32_t w0) {
     uint32_t m = 0;
@@ -435,6 +452,9 @@ static uint32_t q_class_mask(uint32_t w0) {
         case K_MUL_COL: m = C_UNPACK_B32 | C_HASMEM | C_MULV; break;
         case K_FOLD_COL: m = C_UNPACK_B | C_HASMEM | C_FOLDC; break;
         case K_MAC_COL: m = C_UNPACK_B32 | C_HASMEM | C_MACC; break;
+        case K_PUSH_COL32: return C_UNPACK_T32 | C_HASMEM;       // its flags are X's: handled where X is spilled, not by the C_FLAGS step
+        case K_MAC2_COL: m = C_UNPACK_B32 | C_HASMEM | C_MAC2; break;
+        case K_MAC_STK: m = C_POP_B | C_RARE | C_MACS; break;
         default: break;            // K_NOP, Q_END
     }
     if (w0 & (K_SETTLE0 | K_SETTLE1 | K_NORM0 | K_NORM1 | K_SETTLE0_8 | K_SETTLE1_8)) m |= C_FLAGS;
@@ -547,6 +567,14 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
         //    takes the entry below the top
         if (w3 & C_SPILL) { if (sp >= 1) st_put(sp - 1, t0); ++sp; }
         if (w3 & C_UNPACK_T) q_unpack_to(t0, raw_fr(m));
+        if (w3 & C_UNPACK_T32) {                                            // PUSH_COL32: the flags are for the entry that leaves the registers (X of the MAC2_COL to come)
+            if (w0 & K_SETTLE0) q_settle_ip(t0);
+            if (w0 & K_NORM0) normalize29(t0);
+            if (w0 & K_SETTLE0_8) q_settle8_ip(t0);
+            st_put(sp - 1, t0);
+            ++sp;
+            q_unpack_x32_to(t0, raw_fr(m));
+        }
         if (w3 & C_UNPACK_B) q_unpack_to(B, raw_fr(m));
         if (w3 & C_UNPACK_B32) q_unpack_x32_to(B, raw_fr(m));
         if (w3 & C_POP_B) { st_get(sp - 2, B); --sp; }
@@ -568,6 +596,14 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
             st_get(sp - 2, S);
             --sp;
             mul2add29_ub_ipa(t0, B, S, cst(consts_rp, w0 >> K_CONST_SHIFT));
+        }
+        if (w3 & C_MAC2) {                                                  // below the top: 32 m1, X, S -- none of them ever carries a settle request here (lower_bounds)
+            Q29 M1, X, S;
+            st_get(sp - 2, M1);
+            st_get(sp - 3, X);
+            st_get(sp - 4, S);
+            sp -= 3;
+            mul3add29_ub_ipa(t0, B, X, M1, S, cst(consts_rp, w0 >> K_CONST_SHIFT));
         }
         if (w3 & C_ADDV) {
 #pragma unroll
@@ -595,6 +631,13 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
                 normalize29(t0);
             }
             if (w3 & C_MULS) { q_shl5_ip(t0); mul29_ipb(t0, B); }            // t0 <- mul29(B, 32 t0)
+            if (w3 & C_MACS) {                                              // t0 <- mul2add29(B, 32 t0, S, const): t0 settled, B popped above, S below it
+                Q29 S;
+                st_get(sp - 2, S);
+                --sp;
+                q_shl5_ip(t0);
+                mul2add29_ub_ipb(t0, B, S, cst(consts_rp, w0 >> K_CONST_SHIFT));
+            }
             if (w3 & C_NEG) {
 #pragma unroll
                 for (int q = 0; q < 9; ++q) t0.l[q] = kp_balanced<Fr29P>(2, q) - t0.l[q];
@@ -637,16 +680,22 @@ struct LowInstr { uint32_t w0, a, b; };
 // mac (k_quotient_eval2 only): a Horner step of a compiled class program, (S MUL_CONST c) + T with T = X * mem followed by a chain of sums with
 // memory / constant operands (T = X * m - n, the regrouped `sel * expr`, ...), is re-associated into  K_MAC_COL(m, c)  (t0 = X * m + S * c, ONE
 // reduction for both products) followed by T's chain: every operand is read in the order it was, only the product by c moves.
-static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, std::vector<LowInstr>* out, bool mac = false) {
+// mac2 (with mac): where T's chain ends in a SUM OF TWO products by memory operands, X * m1 + Y * m2, the step becomes
+//   S, X, PUSH_COL32 m1, Y, MAC2_COL(m2, c)   (three products, one reduction; operands read in the order they were),
+// and where it ends in a product of two computed values, U * V:  S, U, V, MAC_STK(c)  (two products, one reduction).  MAC2_COL holds one entry
+// more on the stack while Y is computed than the unfused stream does.  The LDS stack caps the waves per SIMD of a class launch, so a fusion
+// that would take the program deeper than its mac-only stream goes is declined (first tried with the two products swapped, where no parked
+// intermediate pins the order); *declined counts them.
+static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, std::vector<LowInstr>* out, bool mac = false, bool mac2 = false, uint32_t* declined = nullptr) {
     std::vector<LNode> nodes;
     nodes.reserve(len);
     std::vector<int32_t> st;
-    auto add = [&](LNode n) { nodes.push_back(n); return (int32_t)nodes.size() - 1; };
     auto leafish = [&](int32_t n) { return nodes[n].kind == LNode::MEM || nodes[n].kind == LNode::CONST; };
-    struct Work { int32_t node; int plan; LowInstr raw; };        // plan 5: emit `raw` as it stands
-    std::vector<Work> work;
-    // plans of a BIN node after its operands: 0 = stack op, 1 = y from memory, 2 = y constant, 3 = x from memory (operands swapped), 4 = x constant (swapped)
-    auto bin_plan = [&](const LNode& n) {
+    // per node: du = entries the mac-only emission of the subtree holds at its peak, above those there when it starts; net = by how many the
+    // stack has grown when it is done (1, less the already materialised entries it consumes).  Children precede parents, so one pass makes them.
+    std::vector<int16_t> du, net;
+    du.reserve(len); net.reserve(len);
+    auto plan_of = [&](const LNode& n) {         // bin_plan below, needed here first
         const LNode &x = nodes[n.x], &y = nodes[n.y];
         if (y.kind == LNode::MEM) return 1;
         if (y.kind == LNode::CONST && (n.op == Q_ADD || n.op == Q_MUL)) return 2;
@@ -654,31 +703,114 @@ static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, st
         if (x.kind == LNode::CONST && !leafish(n.y) && (n.op == Q_ADD || n.op == Q_MUL)) return 4;
         return 0;
     };
+    auto add = [&](LNode n) {
+        int d = 0, g = 0;
+        switch (n.kind) {
+            case LNode::MAT: break;
+            case LNode::MEM: case LNode::CONST: d = 1; g = 1; break;
+            case LNode::UN: case LNode::CONSTOP: case LNode::TEE: d = du[n.x]; g = net[n.x]; break;
+            case LNode::BIN: {
+                const int plan = plan_of(n);
+                if (plan == 0) { d = std::max<int>(du[n.x], net[n.x] + du[n.y]); g = net[n.x] + net[n.y] - 1; }
+                else if (plan == 1 || plan == 2) { d = du[n.x]; g = net[n.x]; }
+                else { d = du[n.y]; g = net[n.y]; }
+                break;
+            }
+        }
+        nodes.push_back(n); du.push_back((int16_t)d); net.push_back((int16_t)g);
+        return (int32_t)nodes.size() - 1;
+    };
+    struct Work { int32_t node; int plan; LowInstr raw; };        // plan 5: emit `raw` as it stands
+    std::vector<Work> work;
+    // plans of a BIN node after its operands: 0 = stack op, 1 = y from memory, 2 = y constant, 3 = x from memory (operands swapped), 4 = x constant (swapped)
+    auto bin_plan = [&](const LNode& n) { return plan_of(n); };
     // mac: T = X * mem under a chain of sums with a memory / constant operand, emitted the way the plans above emit it -> X, the product's
     // memory operand, the chain's instructions innermost last
     std::vector<LowInstr> chain;
-    auto mac_shape = [&](int32_t t, int32_t* xo, LowInstr* mo) -> bool {
-        chain.clear();
+    // a product by a memory operand: the other factor, the operand
+    auto mul_mem = [&](int32_t t, int32_t* xo, LowInstr* mo) -> bool {
+        const LNode& n = nodes[t];
+        if (n.kind != LNode::BIN || n.op != Q_MUL) return false;
+        const int plan = bin_plan(n);
+        if (plan == 1) { *xo = n.x; *mo = {0, nodes[n.y].a, nodes[n.y].b}; return true; }
+        if (plan == 3) { *xo = n.y; *mo = {0, nodes[n.x].a, nodes[n.x].b}; return true; }
+        return false;
+    };
+    int32_t yo2 = -1;             // mac_shape's second outputs: MAC2_COL's Y and m2, MAC_STK's V
+    LowInstr mo2{};
+    uint32_t cur_depth = 0;       // stack entries of the stream emitted so far (kept by depth_now)
+    size_t counted = out->size();
+    int limit = 0;                // mac2: the mac-only stream's depth
+    auto depth_now = [&]() {
+        for (; counted < out->size(); ++counted) {
+            const uint32_t o = (*out)[counted].w0 & 0xffu;
+            if (o == Q_PUSH_COL || o == Q_PUSH_CONST || o == K_PUSH_COL32) ++cur_depth;
+            else if (o == Q_ADD || o == Q_SUB || o == Q_MUL || o == Q_FOLD || o == K_MAC_COL) --cur_depth;
+            else if (o == K_MAC_STK) cur_depth -= 2;
+            else if (o == K_MAC2_COL) cur_depth -= 3;
+        }
+        return (int)cur_depth;
+    };
+    // walks down a chain of sums with a memory / constant operand (pushed on `ch`, outermost first, as the plans above emit them); returns the node under it
+    auto walk = [&](int32_t t, std::vector<LowInstr>& ch) -> int32_t {
         for (int guard = 0; guard < 64; ++guard) {
             const LNode& n = nodes[t];
-            if (n.kind == LNode::CONSTOP && n.op == Q_ADD_CONST) { chain.push_back({Q_ADD_CONST, n.a, 0}); t = n.x; continue; }
-            if (n.kind != LNode::BIN) return false;
+            if (n.kind == LNode::CONSTOP && n.op == Q_ADD_CONST) { ch.push_back({Q_ADD_CONST, n.a, 0}); t = n.x; continue; }
+            if (n.kind != LNode::BIN) return t;
             const int plan = bin_plan(n);
             const LNode &x = nodes[n.x], &y = nodes[n.y];
-            if (n.op == Q_MUL) {
-                if (plan == 1) { *xo = n.x; *mo = {K_MAC_COL, y.a, y.b}; return true; }
-                if (plan == 3) { *xo = n.y; *mo = {K_MAC_COL, x.a, x.b}; return true; }
-                return false;
-            }
-            if (n.op == Q_SUB && plan == 1) { chain.push_back({K_SUB_COL, y.a, y.b}); t = n.x; continue; }
-            if (n.op != Q_ADD) return false;
-            if (plan == 1) { chain.push_back({K_ADD_COL, y.a, y.b}); t = n.x; }
-            else if (plan == 2) { chain.push_back({Q_ADD_CONST, y.a, 0}); t = n.x; }
-            else if (plan == 3) { chain.push_back({K_ADD_COL, x.a, x.b}); t = n.y; }
-            else if (plan == 4) { chain.push_back({Q_ADD_CONST, x.a, 0}); t = n.y; }
-            else return false;
+            if (n.op == Q_SUB && plan == 1) { ch.push_back({K_SUB_COL, y.a, y.b}); t = n.x; continue; }
+            if (n.op != Q_ADD) return t;
+            if (plan == 1) { ch.push_back({K_ADD_COL, y.a, y.b}); t = n.x; }
+            else if (plan == 2) { ch.push_back({Q_ADD_CONST, y.a, 0}); t = n.x; }
+            else if (plan == 3) { ch.push_back({K_ADD_COL, x.a, x.b}); t = n.y; }
+            else if (plan == 4) { ch.push_back({Q_ADD_CONST, x.a, 0}); t = n.y; }
+            else return t;
         }
-        return false;
+        return -1;
+    };
+    std::vector<LowInstr> chain_a, chain_b, chain_in;      // chain_in: shape 4's sums right behind its MAC_COL
+    int32_t z_node = -1;                                    // shape 4's other addend
+    // returns 0: no fusable shape, 1: MAC_COL (xo, mo), 2: MAC2_COL (xo, mo = X, m1; yo2, mo2 = Y, m2), 3: MAC_STK (xo, yo2 = U, V),
+    // 4 (mac2): T = (X * m [sums]) + Z with any Z, run as  S, X, MAC_COL(m, c), [sums], Z, ADD  -- what a sum of two column products falls back to
+    // when MAC2_COL would deepen the stack, and what serves when only one addend is a product by memory: one reduction fewer, never deeper
+    auto mac_shape = [&](int32_t t, int32_t s_node, int32_t* xo, LowInstr* mo) -> int {
+        chain.clear();
+        t = walk(t, chain);
+        if (t < 0 || nodes[t].kind != LNode::BIN) return 0;
+        const LNode& n = nodes[t];
+        const int plan = bin_plan(n);
+        const LNode &x = nodes[n.x], &y = nodes[n.y];
+        if (n.op == Q_MUL) {
+            if (plan == 1) { *xo = n.x; *mo = {K_MAC_COL, y.a, y.b}; return 1; }
+            if (plan == 3) { *xo = n.y; *mo = {K_MAC_COL, x.a, x.b}; return 1; }
+            if (plan == 0 && mac2) { *xo = n.x; yo2 = n.y; return 3; }          // same depth as S MUL_CONST, U, V, MUL, ADD
+            return 0;
+        }
+        if (n.op != Q_ADD || plan != 0 || !mac2) return 0;
+        chain_a.clear(); chain_b.clear();
+        int32_t xa = -1, xb = -1;
+        LowInstr ma{}, mb{};
+        const int32_t ta = walk(n.x, chain_a), tb = walk(n.y, chain_b);
+        const bool ok_a = ta >= 0 && mul_mem(ta, &xa, &ma), ok_b = tb >= 0 && mul_mem(tb, &xb, &mb);
+        const bool free_order = !x.has_tee && !y.has_tee;          // no parked intermediate pins the order of the two addends' reads
+        if (ok_a && ok_b && (chain_a.empty() || free_order)) {
+            // Y is computed on top of S, X and 32 m1
+            const int base = depth_now() + net[s_node];
+            const bool fits = base + net[xa] + 1 + du[xb] <= limit;
+            const bool swapped = !fits && free_order && base + net[xb] + 1 + du[xa] <= limit;
+            if (fits || swapped) {
+                if (fits) { *xo = xa; *mo = ma; yo2 = xb; mo2 = mb; }
+                else { *xo = xb; *mo = mb; yo2 = xa; mo2 = ma; }
+                chain.insert(chain.end(), chain_b.begin(), chain_b.end());       // all the sums run behind the product, the inner ones first
+                chain.insert(chain.end(), chain_a.begin(), chain_a.end());
+                return 2;
+            }
+            if (declined) ++*declined;
+        }
+        if (ok_a) { *xo = xa; *mo = {K_MAC_COL, ma.a, ma.b}; chain_in = chain_a; z_node = n.y; return 4; }
+        if (ok_b && free_order) { *xo = xb; *mo = {K_MAC_COL, mb.a, mb.b}; chain_in = chain_b; z_node = n.x; return 4; }
+        return 0;
     };
     auto emit = [&](int32_t root) {
         work.push_back({root, -1, {}});
@@ -708,11 +840,29 @@ static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, st
                     if (wk.plan < 0) {
                         int32_t xm = -1;
                         LowInstr mi{};
-                        if (mac && n.op == Q_ADD && x.kind == LNode::CONSTOP && x.op == Q_MUL_CONST && x.a < (1u << (32 - K_CONST_SHIFT)) && mac_shape(n.y, &xm, &mi)) {
+                        const int shape = mac && n.op == Q_ADD && x.kind == LNode::CONSTOP && x.op == Q_MUL_CONST && x.a < (1u << (32 - K_CONST_SHIFT)) ? mac_shape(n.y, x.x, &xm, &mi) : 0;
+                        if (shape) {
                             // S, X, MAC_COL(m, c), the chain: pushed in reverse
                             for (const LowInstr& c : chain) work.push_back({-1, 5, c});
-                            work.push_back({-1, 5, {mi.w0 | (x.a << K_CONST_SHIFT), mi.a, mi.b}});
-                            work.push_back({xm, -1, {}});
+                            if (shape == 1) {
+                                work.push_back({-1, 5, {mi.w0 | (x.a << K_CONST_SHIFT), mi.a, mi.b}});
+                                work.push_back({xm, -1, {}});
+                            } else if (shape == 4) {      // S, X, MAC_COL(m, c), its sums, Z, ADD
+                                work.push_back({-1, 5, {Q_ADD, 0, 0}});
+                                work.push_back({z_node, -1, {}});
+                                for (const LowInstr& c : chain_in) work.push_back({-1, 5, c});
+                                work.push_back({-1, 5, {mi.w0 | (x.a << K_CONST_SHIFT), mi.a, mi.b}});
+                                work.push_back({xm, -1, {}});
+                            } else if (shape == 2) {      // S, X, PUSH_COL32 m1, Y, MAC2_COL(m2, c)
+                                work.push_back({-1, 5, {K_MAC2_COL | (x.a << K_CONST_SHIFT), mo2.a, mo2.b}});
+                                work.push_back({yo2, -1, {}});
+                                work.push_back({-1, 5, {K_PUSH_COL32, mi.a, mi.b}});
+                                work.push_back({xm, -1, {}});
+                            } else {                      // S, U, V, MAC_STK(c)
+                                work.push_back({-1, 5, {K_MAC_STK | (x.a << K_CONST_SHIFT), 0, 0}});
+                                work.push_back({yo2, -1, {}});
+                                work.push_back({xm, -1, {}});
+                            }
                             work.push_back({x.x, -1, {}});
                             break;
                         }
@@ -731,9 +881,13 @@ static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, st
             }
         }
     };
+    // the statements in order: an expression to emit (node >= 0) or an instruction as it stands.  Kept until the whole program is read: the
+    // depth the mac-only stream reaches (the limit of mac2's fusions) is known only then.
+    struct Ev { int32_t node; LowInstr raw; };
+    std::vector<Ev> evs;
     auto materialise_pending = [&]() {
         for (int32_t& e : st)
-            if (nodes[e].kind != LNode::MAT) { emit(e); e = add({LNode::MAT, false, false, 0, 0, 0, -1, -1}); }
+            if (nodes[e].kind != LNode::MAT) { evs.push_back({e, {}}); e = add({LNode::MAT, false, false, 0, 0, 0, -1, -1}); }
     };
     for (uint32_t pc = 0; pc < len; ++pc) {
         const uint32_t op = prog[3 * pc], a = prog[3 * pc + 1], b = prog[3 * pc + 2];
@@ -754,14 +908,25 @@ static void lower_fuse(const uint32_t* prog, uint32_t len, uint32_t num_cols, st
             case Q_FOLD: {
                 const int32_t r = st.back(); st.pop_back();
                 materialise_pending();
-                if (nodes[r].kind == LNode::MEM && a < (1u << (32 - K_CONST_SHIFT))) out->push_back({K_FOLD_COL | (a << K_CONST_SHIFT), nodes[r].a, nodes[r].b});
-                else { emit(r); out->push_back({Q_FOLD, a, 0}); }
+                if (nodes[r].kind == LNode::MEM && a < (1u << (32 - K_CONST_SHIFT))) evs.push_back({-1, {K_FOLD_COL | (a << K_CONST_SHIFT), nodes[r].a, nodes[r].b}});
+                else { evs.push_back({r, {}}); evs.push_back({-1, {Q_FOLD, a, 0}}); }
                 break;
             }
             default: break;     // validate_program has refused everything else
         }
     }
     materialise_pending();
+    if (mac2) {
+        int cur = 0;
+        for (const Ev& e : evs) {
+            if (e.node >= 0) { limit = std::max(limit, cur + du[e.node]); cur += net[e.node]; }
+            else if ((e.raw.w0 & 0xffu) == Q_FOLD) --cur;
+        }
+    }
+    for (const Ev& e : evs) {
+        if (e.node >= 0) emit(e.node);
+        else out->push_back(e.raw);
+    }
 }
 
 // Settle / normalise bits, prefetch hazards and stack depth of a fused program (bounds: header comment).  V in units of p, L in
@@ -794,7 +959,7 @@ static int lower_bounds(std::vector<LowInstr>* prog_io, uint32_t num_cols, int* 
             if (bs.back().L + dL > 4) norm0();
             if (bs.back().V + dV > capV) settle0();
         };
-        const size_t need = (op == Q_ADD || op == Q_SUB || op == Q_MUL || op == K_MAC_COL) ? 2 : (op == Q_PUSH_COL || op == Q_PUSH_CONST || op == K_FOLD_COL || op == K_NOP) ? 0 : 1;
+        const size_t need = op == K_MAC2_COL ? 4 : op == K_MAC_STK ? 3 : (op == Q_ADD || op == Q_SUB || op == Q_MUL || op == K_MAC_COL || op == K_PUSH_COL32) ? 2 : (op == Q_PUSH_COL || op == Q_PUSH_CONST || op == K_FOLD_COL || op == K_NOP) ? 0 : 1;
         if (bs.size() < need) return -1;
         switch (op) {
             case Q_PUSH_COL: case Q_PUSH_CONST: bs.push_back({1, 1}); break;
@@ -839,6 +1004,37 @@ static int lower_bounds(std::vector<LowInstr>* prog_io, uint32_t num_cols, int* 
                 if (bs.back().V > 5) settle0();
                 if (bs.back().L + bs[bs.size() - 2].L > 6) norm0();
                 bs.pop_back(); bs.back() = {2, 1};
+                break;
+            }
+            // The three-product step  t0 * 32 m2 + X * 32 m1 + S c'  (t0 = Y; m1, m2, c' canonical):
+            //   value   (32 (V_X + V_Y) + V_S) p^2 must stay below 2^261 p = 169.3 p^2: V_X + V_Y <= 5 with V_S <= 8 (168);
+            //   columns 27 limb products + 9 of the reduction: 9 (L_Y + L_X + L_S + 1) 2^58 + 2^35 < 2^64 for L_X + L_Y + L_S <= 6.
+            // X and S are in LDS when the product runs and the kernel has no step that settles them there.  S is whatever the stack holds (V <= 8, L <= 4).
+            // X is still in registers when PUSH_COL32 spills it, so the requests for X ride on that instruction: V_X <= 3 and L_X + L_S <= 5 leave
+            // room for a Y that MAC2_COL's own bit-0 requests can always reach (settled: V 2, L 1).
+            case K_PUSH_COL32: {
+                if (bs.back().V > 3) settle0();
+                if (bs.back().L + bs[bs.size() - 2].L > 5) norm0();
+                bs.push_back({32, 1});
+                break;
+            }
+            case K_MAC2_COL: {
+                const Bd S = bs[bs.size() - 4], X = bs[bs.size() - 3];
+                if (X.V + bs.back().V > 5) settle0();
+                if (X.L + S.L + bs.back().L > 6) norm0();
+                if (X.V + bs.back().V > 5 || X.L + S.L + bs.back().L > 6 || S.V > 8) return -1;
+                bs.pop_back(); bs.pop_back(); bs.pop_back(); bs.back() = {2, 1};
+                break;
+            }
+            // B * 32 t0 + S c'  (B = the entry below the top, popped into registers: bit-1 requests reach it; t0 settled, then shifted in place --
+            // 17 instructions on 211 steps a row; a constant in another Montgomery form instead would leave U V a factor 32 short of S c', and
+            // carrying that factor to a later product by a constant needs a form tag on every stack entry: not worth 0.1 % of the instructions):
+            //   value (32 V_B V_t0 + V_S) p^2 <= 168 p^2 for V_B V_t0 <= 5 (Q_MUL's rule); columns 9 (L_B + L_S + 1) 2^58 + 2^35 < 2^64 for L_B + L_S <= 6
+            case K_MAC_STK: {
+                settled0();
+                if (bs[bs.size() - 2].V * bs.back().V > 5) settle1();
+                if (bs[bs.size() - 2].L + bs[bs.size() - 3].L > 6) norm1();
+                bs.pop_back(); bs.pop_back(); bs.back() = {2, 1};
                 break;
             }
             case K_FOLD_COL: case K_NOP: break;
@@ -918,7 +1114,13 @@ using namespace zk;
 // CPU tests, which execute the lowered stream limb by limb and check every bound the kernel relies on.
 extern "C" int zk_host_quotient_lower(const uint32_t* h_program, uint32_t num_instr, uint32_t num_cols, int fuse, uint32_t* out_words, size_t cap_words,
                                       uint32_t* out_instr, int* out_depth) {
+    return zk_host_quotient_lower2(h_program, num_instr, num_cols, fuse, out_words, cap_words, out_instr, out_depth, nullptr);
+}
+// ... and how many MAC2_COL fusions (fuse & 4) were declined because they would have deepened the stack
+extern "C" int zk_host_quotient_lower2(const uint32_t* h_program, uint32_t num_instr, uint32_t num_cols, int fuse, uint32_t* out_words, size_t cap_words,
+                                       uint32_t* out_instr, int* out_depth, uint32_t* out_declined) {
     if (!h_program || !out_instr || !out_depth) return ZK_ERR_INVALID_ARG;
+    if (out_declined) *out_declined = 0;
     {   // stack discipline of the caller's program (zk_quotient_eval checks the same, with messages, in validate_program)
         int sp = 0;
         for (uint32_t pc = 0; pc < num_instr && h_program[3 * pc] != Q_END; ++pc) {
@@ -931,7 +1133,8 @@ extern "C" int zk_host_quotient_lower(const uint32_t* h_program, uint32_t num_in
         }
     }
     std::vector<LowInstr> low;
-    if (fuse) lower_fuse(h_program, num_instr, num_cols, &low, (fuse & 2) != 0);      // bit 1: the fused Horner steps (K_MAC_COL); fuse = 1 is the stream without them
+    // bit 1: the fused Horner steps (K_MAC_COL); fuse = 1 is the stream without them; bit 2 (with bit 1): sums of two column products and stack products too
+    if (fuse) lower_fuse(h_program, num_instr, num_cols, &low, (fuse & 2) != 0, (fuse & 6) == 6, out_declined);
     else
         for (uint32_t pc = 0; pc < num_instr && h_program[3 * pc] != Q_END; ++pc) {
             const uint32_t op = h_program[3 * pc], a_ = h_program[3 * pc + 1], b_ = h_program[3 * pc + 2];
@@ -1042,8 +1245,10 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
     if (rc) return rc;
     const int kernel_knob = getenv("ZK_QUOTIENT_KERNEL") ? atoi(getenv("ZK_QUOTIENT_KERNEL")) : 2;       // 2: fixed register roles (k_quotient_eval2: one stack entry in registers, 4-word instructions); 1: round 5's kernel
     const bool v2 = kernel_knob != 1;
-    // fused Horner steps (K_MAC_COL; k_quotient_eval2 only).  ZK_QUOTIENT_MAC=0: the instruction stream without them (A/B runs, byte-equality tests)
-    const bool mac = v2 && !(getenv("ZK_QUOTIENT_MAC") && atoi(getenv("ZK_QUOTIENT_MAC")) == 0);
+    // fused Horner steps (k_quotient_eval2 only).  ZK_QUOTIENT_MAC=0: the instruction stream without them; 1: K_MAC_COL alone; unset / 2: K_MAC2_COL and
+    // K_MAC_STK as well (A/B runs, byte-equality tests)
+    const int mac_level = getenv("ZK_QUOTIENT_MAC") ? atoi(getenv("ZK_QUOTIENT_MAC")) : 2;
+    const bool mac = v2 && mac_level != 0, mac2 = mac && mac_level != 1;
     const uint64_t ne = 1ull << ext_k;
     // a large sum of terms whose operands are read many times is cut into slices that share their rows' operands through the caches (plan_slices)
     SlicePlan plan;
@@ -1076,7 +1281,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
                 else if (op == Q_FOLD) { --spd; slice_k[sl] = slice_k[sl] * ((const Fr*)h_consts)[sub[3 * q + 1]]; }       // EVERY fold multiplies the accumulator, whatever lies below it on the stack
             }
             sub.push_back(Q_END); sub.push_back(0); sub.push_back(0);
-            lower_fuse(sub.data(), (uint32_t)(sub.size() / 3), num_cols, &lows[sl], mac);
+            lower_fuse(sub.data(), (uint32_t)(sub.size() / 3), num_cols, &lows[sl], mac, mac2);
             int dsl = 0;
             if (lower_bounds(&lows[sl], num_cols, &dsl)) return ctx->fail(ZK_ERR_INVALID_ARG, "quotient program: lowering failed");
             dmax = std::max(dmax, dsl);
@@ -1092,7 +1297,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
                 if (op == Q_PUSH_TMP) low.push_back({Q_PUSH_COL, num_cols + a_, 0});
                 else low.push_back({op, a_, b_});
             }
-        } else lower_fuse(h_program, num_instr, num_cols, &low, mac);
+        } else lower_fuse(h_program, num_instr, num_cols, &low, mac, mac2);
         if (lower_bounds(&low, num_cols, &depth)) return ctx->fail(ZK_ERR_INVALID_ARG, "quotient program: lowering failed");
     }
     if (depth > Q_MAX_STACK) return ctx->fail(ZK_ERR_UNSUPPORTED, "quotient program: stack deeper than %d", Q_MAX_STACK);
@@ -1126,12 +1331,12 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
         if (!d_part) return ZK_ERR_OOM;
     }
     if (getenv("ZK_QUOTIENT_TRACE") && low_len >= 64) {        // what the kernel will run: lowered instructions by opcode, settle bits, stack depth
-        static const char* names[23] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "SQUARE", "DOUBLE", "FOLD", "MUL_CONST", "ADD_CONST", "TEE_TMP", "PUSH_TMP", "?", "?",
-                                        "ADD_COL", "SUB_COL", "RSUB_COL", "MUL_COL", "FOLD_COL", "NOP", "MAC_COL"};
-        uint32_t hist[23] = {0}, settles = 0, norms = 0;
-        for (const std::vector<LowInstr>& low : lows) for (const LowInstr& in : low) { const uint32_t o = in.w0 & 0xffu; if (o < 23) ++hist[o]; settles += ((in.w0 & (K_SETTLE0 | K_SETTLE0_8)) ? 1 : 0) + ((in.w0 & (K_SETTLE1 | K_SETTLE1_8)) ? 1 : 0); norms += ((in.w0 & K_NORM0) ? 1 : 0) + ((in.w0 & K_NORM1) ? 1 : 0); }
+        static const char* names[26] = {"END", "PUSH_COL", "PUSH_CONST", "ADD", "SUB", "MUL", "NEG", "SQUARE", "DOUBLE", "FOLD", "MUL_CONST", "ADD_CONST", "TEE_TMP", "PUSH_TMP", "?", "?",
+                                        "ADD_COL", "SUB_COL", "RSUB_COL", "MUL_COL", "FOLD_COL", "NOP", "MAC_COL", "PUSH_COL32", "MAC2_COL", "MAC_STK"};
+        uint32_t hist[26] = {0}, settles = 0, norms = 0;
+        for (const std::vector<LowInstr>& low : lows) for (const LowInstr& in : low) { const uint32_t o = in.w0 & 0xffu; if (o < 26) ++hist[o]; settles += ((in.w0 & (K_SETTLE0 | K_SETTLE0_8)) ? 1 : 0) + ((in.w0 & (K_SETTLE1 | K_SETTLE1_8)) ? 1 : 0); norms += ((in.w0 & K_NORM0) ? 1 : 0) + ((in.w0 & K_NORM1) ? 1 : 0); }
         fprintf(stderr, "[zk quotient] 2^%u rows, %u lowered instructions%s, depth %d, %u settles, %u carry propagations:", ext_k, low_len, sliced ? (" in " + std::to_string(S) + " slices").c_str() : "", depth, settles, norms);
-        for (int o = 0; o < 23; ++o) if (hist[o]) fprintf(stderr, " %s %u", names[o], hist[o]);
+        for (int o = 0; o < 26; ++o) if (hist[o]) fprintf(stderr, " %s %u", names[o], hist[o]);
         if (sliced) { fprintf(stderr, "; slice lengths"); for (const std::vector<LowInstr>& low : lows) fprintf(stderr, " %zu", low.size()); fprintf(stderr, "; %u parking slots", num_tmp); }
         fprintf(stderr, "\n");
     }

@@ -639,15 +639,16 @@ __device__ __forceinline__ uint32_t st_hash32(uint32_t x) { x ^= x >> 16; x *= 0
 template <class P>
 __global__ void k_selftest_products(uint32_t* bad, uint32_t seed) {
     const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    F29<P> a, b, c, d, u;
+    F29<P> a, b, c, d, u, e;
     for (int i = 0; i < 9; ++i) {
         const uint32_t top = i == 8;
         a.l[i] = st_hash32(seed + tid * 41 + i) & (top ? 0x3ffffffu : 0x3fffffffu);          // limbs < 2^30, value < 2^258
         b.l[i] = st_hash32(seed + tid * 43 + i + 100) & (top ? 0xffffffu : 0x1fffffffu);     // normalised, < 2^256
         c.l[i] = st_hash32(seed + tid * 47 + i + 200) & (top ? 0xffffffu : 0x1fffffffu);
         d.l[i] = st_hash32(seed + tid * 53 + i + 300) & (top ? 0xffffffu : 0x3fffffffu);     // limbs < 2^30
+        e.l[i] = st_hash32(seed + tid * 61 + i + 500) & (top ? 0xffffffu : 0x3fffffffu);     // limbs < 2^30
         u.l[i] = st_hash32(seed + blockIdx.x * 59 + i + 400) & (top ? 0xffffffu : 0x1fffffffu);   // workgroup-uniform second factor (scalar registers)
-        if ((tid & 15) == 3 && i < 8) { a.l[i] = 0x3fffffffu; b.l[i] = 0x1fffffffu; c.l[i] = 0x1fffffffu; d.l[i] = 0x3fffffffu; }
+        if ((tid & 15) == 3 && i < 8) { a.l[i] = 0x3fffffffu; b.l[i] = 0x1fffffffu; c.l[i] = 0x1fffffffu; d.l[i] = 0x3fffffffu; e.l[i] = 0x3fffffffu; }
     }
     F29<P> an = a;
     for (int i = 0; i < 8; ++i) an.l[i] &= 0x1fffffffu;
@@ -663,6 +664,10 @@ __global__ void k_selftest_products(uint32_t* bad, uint32_t seed) {
     { F29<P> x = b; mul29_ipb(x, a); cmp(x, mul29_c(a, b), 32u); }
     { F29<P> x = a; mul29_ub_ipa(x, u); cmp(x, mul29_ub_c(a, u), 64u); }
     { F29<P> x = a; mul2add29_ub_ipa(x, b, d, u); cmp(x, mul2add29_c(a, b, d, u), 128u); }
+    // the sums of products of the evaluator's MAC_STK / MAC2_COL steps, at the limb bounds its lowering admits: first factors with limbs below
+    // 2^30 (L = 2 each: L_x + L_a + L_s = 6), second factors normalised, the constant workgroup-uniform
+    { F29<P> x = b; mul2add29_ub_ipb(x, a, d, u); cmp(x, mul2add29_c(a, b, d, u), 256u); }
+    { F29<P> x = a; mul3add29_ub_ipa(x, b, d, c, e, u); cmp(x, mul3add29_c(a, b, d, c, e, u), 512u); }
     // and the product against the definition: a b 2^-261 mod p through the 8 x 32 CIOS routine is covered by the NTT / MSM parity
     // tests; here the two forms of the SAME column sums must agree in every limb
     if (diff) { atomicAdd(bad, 1u); atomicOr(bad + 1, diff); }
