@@ -299,6 +299,15 @@ const void* zk_srs_g_lagrange(const zk_srs* srs); /* device pointer or NULL     
 /* sum_i scalars[i] * bases[i] over device buffers; the affine result (64 B) is written to the
  * host.  Scalars are Montgomery-form Fr exactly as halo2 holds them.                             */
 int zk_msm_g1(zk_ctx* ctx, const void* d_scalars, const void* d_bases, size_t n, void* h_out_affine);
+/* num_segments independent MSMs in one pass: out[s] = sum of scalars[i] * bases[i] over i in [h_seg_offsets[s],
+ * h_seg_offsets[s + 1]) (num_segments + 1 offsets on the host, the first 0, non-decreasing).  Scalars: Montgomery Fr; bases: 64 B
+ * affine Montgomery, arbitrary points (no table is built, nothing is cached), the identity as all zeros.  h_out_affine
+ * receives num_segments x 64 B (identity: all zeros; an empty segment gives the identity).  All segments share one sequence
+ * of three launches and one download -- no launch and no synchronisation per segment: what many sums of a few to a few
+ * thousand points need (zk_verify_accumulators: two per proof), where one zk_msm_g1 call per sum would pay its sort, its
+ * launches and its host tail every time.  It spends about one addition per scalar bit and point: one large sum belongs to
+ * zk_msm_g1.                                                                                                            */
+int zk_msm_g1_segments(zk_ctx* ctx, const void* d_scalars, const void* d_bases, const uint32_t* h_seg_offsets, size_t num_segments, void* h_out_affine);
 /* ParamsKZG::commit (basis = 0, over g) / commit_lagrange (basis = 1, over g_lagrange).          */
 int zk_commit(zk_ctx* ctx, const zk_srs* srs, int basis, const void* d_scalars, size_t n, void* h_out_affine);
 /* `count` commitments over the same basis (ParamsKZG::commit_lagrange over every advice column
@@ -513,6 +522,26 @@ int zk_vk_shape(const zk_vk* vk, uint32_t* out16);
 int zk_verify_proofs(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
                      const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen, const void* g2_128,
                      const void* s_g2_128, int* ok);
+/* Succinct verification -- snark-verifier's PlonkSuccinctVerifier::verify as extract_accumulators_and_proof runs it on the
+ * child snarks of an aggregation layer [REF aggregator/src/core.rs:48-107] (decider variant :111-147) -- for `count` proofs of
+ * one key.  The arguments up to multiopen are zk_verify_proofs'.  acc_indices: for each of the num_prior accumulators a snark
+ * of this key carries in its instances, 12 cells as {column, row} pairs (12 x num_prior x 2 words; snark-verifier's
+ * accumulator_indices; limb layout of zk_host_accumulator_limbs); NULL with num_prior = 0.
+ * Outputs: proof b writes 1 + num_prior accumulators at index b * (1 + num_prior) of h_lhs / h_rhs (64 B affine each, the
+ * convention of zk_host_accumulator_check: e(lhs, g2) == e(rhs, s_g2)): first the accumulator of the proof's own openings,
+ * then the carried ones in the order of acc_indices.  ok[b] (count entries) = 1 when proof b is well formed and every carried
+ * accumulator decodes; 0, with all of that proof's outputs zeroed, for every reject reason of zk_verify_proofs, a limb of
+ * 2^88 or more, a coordinate of p or more, a point off the curve, or an index outside the given instance values.  A reject
+ * is ZK_OK, not an error status.
+ * NO PAIRING IS DONE: ok[b] = 1 is NOT acceptance.  The caller decides each accumulator with zk_host_accumulator_check, or
+ * first combines them with zk_host_accumulate and decides the result (then encodes it with zk_host_accumulator_limbs as the
+ * next layer's instances).  The verdict is per proof, so this is also the way to find which proof of a batch that
+ * zk_verify_proofs rejected is the bad one.
+ * The points of all proofs are decoded in one launch, the proofs replayed on up to 16 host threads, and the 2 * count
+ * coefficient vectors go through one zk_msm_g1_segments pass.                                                            */
+int zk_verify_accumulators(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
+                           const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen, const uint32_t* acc_indices,
+                           size_t num_prior, void* h_lhs, void* h_rhs, int* ok);
 /* Multi-GPU proving: one process per GPU, every rank runs the SAME session calls on
  * the same key, witness and seed.  Rank r then commits only columns r, r + world, ... and evaluates
  * only cosets r, r + world, ... of the quotient; commitments (64 B each) and finished cosets
@@ -608,6 +637,9 @@ int zk_host_pairing_check(const void* g1_points, const void* g2_points, size_t n
 int zk_host_accumulate(const void* lhs_in, const void* rhs_in, size_t n, void* lhs_out, void* rhs_out, void* r_out);
 int zk_host_accumulator_check(const void* lhs, const void* rhs, const void* g2, const void* s_g2, int* ok);
 int zk_host_accumulator_limbs(const void* lhs, const void* rhs, void* out12_fr);
+/* the inverse (LimbsEncoding::from_repr [REF aggregator/src/core.rs:120-135]): 12 Montgomery Fr cells -> lhs, rhs.  *ok = 0 and
+ * both points zeroed for a limb of 2^88 or more, a coordinate of p or more, or a point off the curve (ZK_OK either way)   */
+int zk_host_accumulator_from_limbs(const void* limbs12_fr, void* lhs, void* rhs, int* ok);
 
 /* ---- G1 element-wise (tests of the group law; halo2curves G1 Add / Double / Mul) --------------- */
 /* out[i] = a[i] + b[i], all affine (n x 64 B) */

@@ -389,5 +389,57 @@ inline bool verify_proof(const Context& c, const VerifyingKey& vk, const std::ve
     return ok == 1;
 }
 
+// PlonkSuccinctVerifier::verify for a batch (zk_verify_accumulators): per proof the KZG accumulator of its own openings, then the
+// accumulators its instances carry at acc_indices (12 {column, row} cells each).  NO pairing is done: ok[b] says proof b is well
+// formed, not that it is accepted -- decide every accumulator with zk_host_accumulator_check, or combine them with
+// zk_host_accumulate first.
+struct Accumulators {
+    size_t per_proof = 0;                              // 1 + the number of carried accumulators
+    std::vector<std::array<uint64_t, 8>> lhs, rhs;     // proofs x per_proof, 64 B affine Montgomery; zero where ok is false
+    std::vector<bool> ok;
+};
+inline Accumulators verify_accumulators(const Context& c, const VerifyingKey& vk, const std::vector<std::vector<uint8_t>>& proofs,
+                                        const std::vector<std::vector<std::vector<Fr>>>& instances, int transcript_kind, bool shplonk,
+                                        const std::vector<std::array<std::array<uint32_t, 2>, 12>>& acc_indices = {}) {
+    if (proofs.size() != instances.size()) throw Error(ZK_ERR_INVALID_ARG, "verify_accumulators: one instance set per proof");
+    std::vector<std::vector<const void*>> cols(proofs.size());
+    std::vector<std::vector<uint32_t>> lens(proofs.size());
+    std::vector<const void* const*> col_ptrs;
+    std::vector<const uint32_t*> len_ptrs;
+    std::vector<const void*> proof_ptrs;
+    std::vector<size_t> proof_lens;
+    for (size_t b = 0; b < proofs.size(); ++b) {
+        for (const auto& col : instances[b]) { cols[b].push_back(col.data()); lens[b].push_back((uint32_t)col.size()); }
+        col_ptrs.push_back(cols[b].data());
+        len_ptrs.push_back(lens[b].data());
+        proof_ptrs.push_back(proofs[b].data());
+        proof_lens.push_back(proofs[b].size());
+    }
+    Accumulators out;
+    out.per_proof = 1 + acc_indices.size();
+    out.lhs.resize(proofs.size() * out.per_proof);
+    out.rhs.resize(proofs.size() * out.per_proof);
+    std::vector<int> ok(proofs.size(), 0);
+    c.check(zk_verify_accumulators(c.raw(), vk.raw(), proofs.size(), col_ptrs.data(), len_ptrs.data(), proof_ptrs.data(), proof_lens.data(), transcript_kind,
+                                   shplonk ? ZK_MULTIOPEN_SHPLONK : ZK_MULTIOPEN_GWC, acc_indices.empty() ? nullptr : &acc_indices[0][0][0], acc_indices.size(),
+                                   out.lhs.data(), out.rhs.data(), ok.data()));
+    for (int v : ok) out.ok.push_back(v == 1);
+    return out;
+}
+// the inverse of zk_host_accumulator_limbs; false (points zeroed) for a limb of 2^88 or more, a coordinate of p or more, a point off the curve
+inline bool accumulator_from_limbs(const std::array<Fr, 12>& limbs, std::array<uint64_t, 8>& lhs, std::array<uint64_t, 8>& rhs) {
+    int ok = 0;
+    const int rc = zk_host_accumulator_from_limbs(limbs.data(), lhs.data(), rhs.data(), &ok);
+    if (rc) throw Error(rc, "zk_host_accumulator_from_limbs: bad argument");
+    return ok == 1;
+}
+// num_segments independent MSMs over arbitrary device bases in one pass (zk_msm_g1_segments): offsets.size() - 1 results
+inline std::vector<std::array<uint64_t, 8>> msm_segments(const Context& c, const void* d_scalars, const void* d_bases, const std::vector<uint32_t>& offsets) {
+    if (offsets.empty()) throw Error(ZK_ERR_INVALID_ARG, "msm_segments: one offset more than there are segments");
+    std::vector<std::array<uint64_t, 8>> out(offsets.size() - 1);
+    c.check(zk_msm_g1_segments(c.raw(), d_scalars, d_bases, offsets.data(), out.size(), out.data()));
+    return out;
+}
+
 }  // namespace halo2
 }  // namespace zk

@@ -25,6 +25,10 @@ pub struct zk_pk {
 pub struct zk_proof {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct zk_vk {
+    _private: [u8; 0],
+}
 
 pub const ZK_OK: c_int = 0;
 pub const ZK_ERR_INVALID_ARG: c_int = -1;
@@ -108,4 +112,11 @@ extern "C" {
     // ---- pinned host memory for witness columns (optional: uploads at link rate)
     pub fn zk_host_register(ctx: *mut zk_ctx, ptr: *mut c_void, bytes: usize) -> c_int;
     pub fn zk_host_unregister(ctx: *mut zk_ctx, ptr: *mut c_void) -> c_int;
+
+    // ---- succinct verification of child snarks (aggregation layers): accumulators per proof, no pairing
+    pub fn zk_msm_g1_segments(ctx: *mut zk_ctx, d_scalars: *const c_void, d_bases: *const c_void, h_seg_offsets: *const u32, num_segments: usize, h_out_affine: *mut c_void) -> c_int;
+    pub fn zk_verify_accumulators(ctx: *mut zk_ctx, vk: *const zk_vk, count: usize, h_instances: *const *const *const c_void, h_instance_lens: *const *const u32,
+                                  h_proofs: *const *const c_void, h_proof_lens: *const usize, transcript_kind: c_int, multiopen: c_int, acc_indices: *const u32,
+                                  num_prior: usize, h_lhs: *mut c_void, h_rhs: *mut c_void, ok: *mut c_int) -> c_int;
+    pub fn zk_host_accumulator_from_limbs(limbs12_fr: *const c_void, lhs: *mut c_void, rhs: *mut c_void, ok: *mut c_int) -> c_int;
 }

@@ -12,7 +12,7 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -720,6 +720,16 @@ class Context:
         self._ck(lib().zk_msm_g1(self.h, ctypes.c_void_p(scalars_ptr), ctypes.c_void_p(bases_ptr), ctypes.c_size_t(n), _host_ptr(out)))
         return out
 
+    def msm_segments(self, scalars_ptr: int, bases_ptr: int, seg_offsets: Sequence[int]) -> np.ndarray:
+        """zk_msm_g1_segments: out[s] = sum of scalars[i] * bases[i] over [seg_offsets[s], seg_offsets[s + 1]), all segments in one
+        pass; device pointers, arbitrary bases; returns (len(seg_offsets) - 1, 8) u64 affine Montgomery."""
+        off = np.ascontiguousarray(seg_offsets, dtype=np.uint32)
+        if off.ndim != 1 or off.size < 1:
+            raise ZkError("msm_segments: seg_offsets holds one offset more than there are segments")
+        out = np.zeros((max(off.size - 1, 1), 8), dtype=np.uint64)
+        self._ck(lib().zk_msm_g1_segments(self.h, ctypes.c_void_p(scalars_ptr), ctypes.c_void_p(bases_ptr), _host_ptr(off), ctypes.c_size_t(off.size - 1), _host_ptr(out)))
+        return out[:off.size - 1]
+
     def commit(self, srs: Srs, scalars: DeviceBuffer, n: int, lagrange: bool = False) -> np.ndarray:
         out = np.empty(8, dtype=np.uint64)
         self._ck(lib().zk_commit(self.h, srs.h, ctypes.c_int(1 if lagrange else 0), ctypes.c_void_p(scalars.ptr), ctypes.c_size_t(n), _host_ptr(out)))
@@ -768,22 +778,19 @@ class Context:
         self._ck(lib().zk_pk_create(self.h, srs.h, _host_ptr(view), ctypes.c_size_t(view.size), ctypes.byref(h)))
         return ProvingKey(self, h)
 
-    def verify_proofs(self, vk: "VerifyingKey", proofs: Sequence[bytes], instances: Sequence[Sequence[np.ndarray]], transcript_kind: int = 0,
-                      multiopen: int = 0, g2: bytes = b"", s_g2: bytes = b"") -> bool:
-        """halo2 verify_proof (zk_verify_proofs): one proof = SingleStrategy, several = AccumulatorStrategy (one MSM and one pairing
-        check for all).  instances[b]: proof b's instance columns, (len, 4) u64 Montgomery each, absorbed as given -- a column of
-        exactly 2^k rows is the full-column image zk_proof_begin takes and stands for its usable rows.  g2 / s_g2: [1]G2 / [s]G2,
-        128 B Montgomery.  Malformed proofs are rejected (False); bad arguments raise."""
+    def _proof_args(self, who: str, vk: "VerifyingKey", proofs: Sequence[bytes], instances: Sequence[Sequence[np.ndarray]]):
+        """the (instances, lengths, proofs, proof lengths) arguments zk_verify_proofs and zk_verify_accumulators share; the first
+        item returned keeps the buffers alive"""
         sh = vk.shape_
         n, u = 1 << sh["k"], (1 << sh["k"]) - sh["blinding_factors"] - 1
         if len(proofs) != len(instances) or not proofs:
-            raise ZkError("verify_proofs: one instance list per proof, at least one proof")
+            raise ZkError(f"{who}: one instance list per proof, at least one proof")
         keep = []
         inst_ptrs = (ctypes.c_void_p * len(proofs))()
         len_ptrs = (ctypes.c_void_p * len(proofs))()
         for b, cols in enumerate(instances):
             if len(cols) != sh["I"]:
-                raise ZkError(f"verify_proofs: proof {b} has {len(cols)} instance columns, the key {sh['I']}")
+                raise ZkError(f"{who}: proof {b} has {len(cols)} instance columns, the key {sh['I']}")
             arrs = []
             for c in cols:
                 a = np.ascontiguousarray(c, dtype=np.uint64).reshape(-1, 4)
@@ -796,6 +803,35 @@ class Context:
         bufs = [ctypes.create_string_buffer(bytes(p_), max(len(p_), 1)) for p_ in proofs]
         proof_ptrs = (ctypes.c_void_p * len(proofs))(*[ctypes.cast(b_, ctypes.c_void_p) for b_ in bufs])
         proof_lens = (ctypes.c_size_t * len(proofs))(*[len(p_) for p_ in proofs])
+        return keep + [bufs], inst_ptrs, len_ptrs, proof_ptrs, proof_lens
+
+    def verify_accumulators(self, vk: "VerifyingKey", proofs: Sequence[bytes], instances: Sequence[Sequence[np.ndarray]], transcript_kind: int = 0,
+                            multiopen: int = 0, acc_indices: Sequence[Sequence[Tuple[int, int]]] = ()):
+        """succinct verification (zk_verify_accumulators): per proof the KZG accumulator of its openings, then the accumulators its
+        instances carry at acc_indices (per accumulator 12 (column, row) cells).  Returns (lhs, rhs, ok): lhs / rhs of shape
+        (count, 1 + len(acc_indices), 8) u64 affine Montgomery, ok a list of bools.  NO pairing is done: decide every accumulator
+        with accumulator_check, or combine them with zk_host_accumulate first.  ok[b] False: proof b is malformed or a carried
+        accumulator does not decode; its outputs are zero."""
+        keep, inst_ptrs, len_ptrs, proof_ptrs, proof_lens = self._proof_args("verify_accumulators", vk, proofs, instances)
+        num_prior = len(acc_indices)
+        idx = np.ascontiguousarray([[int(c), int(r)] for acc in acc_indices for c, r in acc], dtype=np.uint32).reshape(-1, 2)
+        if len(idx) != 12 * num_prior:
+            raise ZkError("verify_accumulators: an accumulator is 12 (column, row) cells")
+        lhs = np.zeros((len(proofs), 1 + num_prior, 8), dtype=np.uint64)
+        rhs = np.zeros_like(lhs)
+        ok = (ctypes.c_int * len(proofs))()
+        self._ck(lib().zk_verify_accumulators(self.h, vk.h, ctypes.c_size_t(len(proofs)), inst_ptrs, len_ptrs, proof_ptrs, proof_lens,
+                                              ctypes.c_int(transcript_kind), ctypes.c_int(multiopen), _host_ptr(idx) if num_prior else None,
+                                              ctypes.c_size_t(num_prior), _host_ptr(lhs), _host_ptr(rhs), ok))
+        return lhs, rhs, [v == 1 for v in ok]
+
+    def verify_proofs(self, vk: "VerifyingKey", proofs: Sequence[bytes], instances: Sequence[Sequence[np.ndarray]], transcript_kind: int = 0,
+                      multiopen: int = 0, g2: bytes = b"", s_g2: bytes = b"") -> bool:
+        """halo2 verify_proof (zk_verify_proofs): one proof = SingleStrategy, several = AccumulatorStrategy (one MSM and one pairing
+        check for all).  instances[b]: proof b's instance columns, (len, 4) u64 Montgomery each, absorbed as given -- a column of
+        exactly 2^k rows is the full-column image zk_proof_begin takes and stands for its usable rows.  g2 / s_g2: [1]G2 / [s]G2,
+        128 B Montgomery.  Malformed proofs are rejected (False); bad arguments raise."""
+        keep, inst_ptrs, len_ptrs, proof_ptrs, proof_lens = self._proof_args("verify_proofs", vk, proofs, instances)
         g2b, sg2b = bytes(g2), bytes(s_g2)
         if len(g2b) != 128 or len(sg2b) != 128:
             raise ZkError("verify_proofs: g2 and s_g2 are 128-byte G2 points")
@@ -855,6 +891,18 @@ def mock_challenges(count: int) -> np.ndarray:
     if rc != 0:
         raise ZkError(f"zk_host_mock_challenges failed with status {rc}")
     return out[:count]
+
+
+def accumulator_from_limbs(limbs: np.ndarray):
+    """zk_host_accumulator_from_limbs: 12 Montgomery Fr cells, (12, 4) u64 -> (lhs, rhs, ok); lhs / rhs (8,) u64 affine Montgomery,
+    zero when ok is False (a limb of 2^88 or more, a coordinate of p or more, a point off the curve).  Host only."""
+    cells = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(12, 4)
+    lhs, rhs = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    ok = ctypes.c_int(-1)
+    rc = lib().zk_host_accumulator_from_limbs(_host_ptr(cells), _host_ptr(lhs), _host_ptr(rhs), ctypes.byref(ok))
+    if rc != 0:
+        raise ZkError(f"zk_host_accumulator_from_limbs failed with status {rc}")
+    return lhs, rhs, ok.value == 1
 
 
 def version() -> str:

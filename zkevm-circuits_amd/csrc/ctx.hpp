@@ -235,6 +235,8 @@ int g1_decode_run(zk_ctx* ctx, const void* d_in, int enc, G1Affine* d_out, uint6
 int msm_run(zk_ctx* ctx, const Fr* d_scalars, const G1Affine* d_bases, size_t n, G1Affine* h_out);
 int msm_run_rp(zk_ctx* ctx, const Fr* d_scalars, const G1Affine* d_bases, const G1Affine* d_bases_rp, size_t n, G1Affine* h_out);
 int msm_batch_rp(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_bases, const G1Affine* d_bases_rp, size_t n, G1Affine* h_out);
+// out[s] = sum over [h_off[s], h_off[s + 1]) of scalars[i] * bases[i], arbitrary bases, one pass and one download for all segments
+int msm_segments_run(zk_ctx* ctx, const Fr* d_scalars, const G1Affine* d_bases, const uint32_t* h_off, size_t num_segments, G1Affine* h_out);
 int srs_bases_rp(zk_ctx* ctx, const zk_srs* srs, int basis, const G1Affine** out);
 int srs_window_table(zk_ctx* ctx, const zk_srs* srs, int basis, size_t n, const G1Affine** out, size_t* stride);
 // stage(user, it) makes the scalars of MSM `it` available (ordered before the main stream's next

@@ -2334,7 +2334,130 @@ int srs_bases_rp(zk_ctx* ctx, const zk_srs* srs, int basis, const G1Affine** out
     return ZK_OK;
 }
 
+// ---- segmented MSM: many independent small sums in one pass (zk_msm_g1_segments) ------------------------------------
+// out[s] = sum_{i in [off[s], off[s+1])} scalars[i] * bases[i] for arbitrary bases.  The caller is the succinct verifier:
+// 2 * count sums of a few to a few thousand points each, every base used once, so there is no table to amortise and the
+// sort + bucket + reduce pipeline above (a dozen launches and a host tail per sum) costs more than the additions it saves.
+// Mapping: a workgroup takes SEG_T * T consecutive points of one segment, lane l the points lo + l + j * SEG_T.  The lane
+// runs ONE double-and-add chain over all of its points (bit by bit from the top: double the accumulator, add every point
+// whose scalar has the bit set), so the 254 doublings are paid per lane, not per point; the lanes are summed by an LDS
+// tree; a second launch sums the workgroups of a segment and normalises.  T grows with the total so that the device is
+// filled before the chains get longer: the call is bound by the latency of one chain (254 doublings + 254 T additions),
+// the same floor any on-device Horner over the windows of a bucket method would have.
+constexpr int SEG_T = 256;
+constexpr uint32_t SEG_MAX_T = 32;
+struct SegTask { uint32_t lo, hi; };       // the points [lo, hi) of one segment
+
+// scalars leave Montgomery form once; bases go to R' form.  A term that adds nothing (zero scalar, identity base) gets a
+// zero scalar: the chains test scalar bits only.
+__global__ void __launch_bounds__(256) k_msm_seg_prepare(const Fr* __restrict__ scalars, const G1Affine* __restrict__ bases, uint32_t n, Fr* __restrict__ canon, G1Affine* __restrict__ bases_rp) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1Affine p = ldg(bases + i);
+    const bool skip = p.is_identity();
+    stg(canon + i, skip ? Fr::zero() : from_mont(ldg(scalars + i)));
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { p.x = dbl(p.x); p.y = dbl(p.y); }
+    stg(bases_rp + i, p);
+}
+__global__ void __launch_bounds__(SEG_T) k_msm_seg_partial(const Fr* __restrict__ canon, const G1Affine* __restrict__ bases_rp, const SegTask* __restrict__ tasks, G1Xyzz29* __restrict__ partial) {
+    __shared__ G1Xyzz29 sh[SEG_T];
+    const SegTask t = tasks[blockIdx.x];
+    const uint32_t first = t.lo + threadIdx.x;
+    int top = -1;                              // highest set bit over the lane's scalars
+    for (uint32_t i = first; i < t.hi; i += SEG_T)
+        for (int w = 7; w >= 0; --w) {
+            const uint32_t v = canon[i].l[w];
+            if (v) { top = max(top, 32 * w + 31 - __clz(v)); break; }
+        }
+    G1Xyzz29 acc = identity29();
+#pragma unroll 1
+    for (int bit = top; bit >= 0; --bit) {
+        acc = dbl29pt(acc);
+#pragma unroll 1
+        for (uint32_t i = first; i < t.hi; i += SEG_T)
+            if ((canon[i].l[bit >> 5] >> (bit & 31)) & 1u) acc = madd29(acc, load_affine29(bases_rp + i));
+    }
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = SEG_T / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] = add29pt(sh[threadIdx.x], sh[threadIdx.x + off]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) stg29(partial + blockIdx.x, sh[0]);
+}
+// one wave per segment: the sum of its workgroups' partials [seg_first[s], seg_first[s + 1]) as a canonical affine point in
+// the R = 2^256 form of the ABI (identity: all zeros)
+__global__ void __launch_bounds__(64) k_msm_seg_finish(const G1Xyzz29* __restrict__ partial, const uint32_t* __restrict__ seg_first, G1Affine* __restrict__ out) {
+    __shared__ G1Xyzz29 sh[64];
+    const uint32_t s = blockIdx.x, lo = seg_first[s], hi = seg_first[s + 1];
+    G1Xyzz29 acc = identity29();
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += 64) acc = add29pt(acc, ldg29(partial + i));
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) sh[threadIdx.x] = add29pt(sh[threadIdx.x], sh[threadIdx.x + off]);
+        __syncthreads();
+    }
+    if (threadIdx.x) return;
+    const G1Xyzz29 p = sh[0];
+    if (is_identity29(p)) { stg(out + s, G1Affine{Fq::zero(), Fq::zero()}); return; }
+    const Fq29 t = inv29(mul29(p.zz, p.zzz)), c = unpack29<Fq29P>(Fq::one());     // c: the integer 2^256 mod p takes R' to R
+    const Fq29 x = mul29(p.x, mul29(t, p.zzz)), y = mul29(p.y, mul29(t, p.zz));
+    stg(out + s, G1Affine{pack29_lt2p(mul29(x, c)), pack29_lt2p(mul29(y, c))});
+}
+
+int msm_segments_run(zk_ctx* ctx, const Fr* d_scalars, const G1Affine* d_bases, const uint32_t* h_off, size_t num_segments, G1Affine* h_out) {
+    if (num_segments == 0) return ZK_OK;
+    if (num_segments >= (1ull << 31)) return ctx->fail(ZK_ERR_UNSUPPORTED, "more than 2^31-1 segments");
+    for (size_t s = 0; s < num_segments; ++s)
+        if (h_off[s] > h_off[s + 1]) return ctx->fail(ZK_ERR_INVALID_ARG, "invalid argument: segment offsets decrease at segment %zu", s);
+    if (h_off[0] != 0) return ctx->fail(ZK_ERR_INVALID_ARG, "invalid argument: the first segment offset is not 0");
+    const uint32_t n = h_off[num_segments];
+    if (n == 0) { memset(h_out, 0, sizeof(G1Affine) * num_segments); return ZK_OK; }
+    if (!d_scalars || !d_bases) return ctx->fail(ZK_ERR_INVALID_ARG, "invalid argument: null pointer");
+    // points per lane: one while every point finds a lane among the waves the device holds at two workgroups per CU
+    const uint64_t lanes = (uint64_t)std::max(ctx->prop.multiProcessorCount, 1) * 2 * SEG_T;
+    const uint32_t T = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + lanes - 1) / lanes, 1), SEG_MAX_T), chunk = SEG_T * T;
+    std::vector<SegTask> tasks;
+    std::vector<uint32_t> seg_first(num_segments + 1);
+    for (size_t s = 0; s < num_segments; ++s) {
+        seg_first[s] = (uint32_t)tasks.size();
+        for (uint64_t lo = h_off[s]; lo < h_off[s + 1]; lo += chunk) tasks.push_back({(uint32_t)lo, (uint32_t)std::min<uint64_t>(lo + chunk, h_off[s + 1])});
+    }
+    seg_first[num_segments] = (uint32_t)tasks.size();
+    // workspace: canonical scalars | R' bases | tasks | seg_first; partial sums; results
+    const size_t task_bytes = (tasks.size() * sizeof(SegTask) + 15) & ~(size_t)15;
+    char* ws = (char*)ctx->get_scratch(SC_MSM_KEYS, (size_t)n * (sizeof(Fr) + sizeof(G1Affine)) + task_bytes + seg_first.size() * 4);
+    G1Xyzz29* partial = (G1Xyzz29*)ctx->get_scratch(SC_MSM_BUCKETS, sizeof(G1Xyzz29) * tasks.size());
+    G1Affine* d_out = (G1Affine*)ctx->get_scratch(SC_MSM_RESULTS, sizeof(G1Affine) * num_segments);
+    if (!ws || !partial || !d_out) return ZK_ERR_OOM;
+    G1Affine* bases_rp = (G1Affine*)ws;
+    Fr* canon = (Fr*)(bases_rp + n);
+    SegTask* d_tasks = (SegTask*)(canon + n);
+    uint32_t* d_first = (uint32_t*)((char*)d_tasks + task_bytes);
+    ZK_HIP(ctx, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(SegTask), hipMemcpyHostToDevice, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(d_first, seg_first.data(), seg_first.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    {
+        ZkProfScope ps(ctx, "msm_segments");
+        hipLaunchKernelGGL(k_msm_seg_prepare, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_scalars, d_bases, n, canon, bases_rp);
+        hipLaunchKernelGGL(k_msm_seg_partial, dim3((unsigned)tasks.size()), dim3(SEG_T), 0, ctx->stream, (const Fr*)canon, (const G1Affine*)bases_rp, (const SegTask*)d_tasks, partial);
+        hipLaunchKernelGGL(k_msm_seg_finish, dim3((unsigned)num_segments), dim3(64), 0, ctx->stream, (const G1Xyzz29*)partial, (const uint32_t*)d_first, d_out);
+        ZK_CHECK_LAUNCH(ctx);
+    }
+    ZK_HIP(ctx, hipMemcpyAsync(h_out, d_out, sizeof(G1Affine) * num_segments, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the one download of the call; tasks / seg_first are host vectors that end here
+    return ZK_OK;
+}
+
 }  // namespace zk
+
+// num_segments independent MSMs over arbitrary bases in one pass: see the section above and zkmi355.h
+extern "C" int zk_msm_g1_segments(zk_ctx* ctx, const void* d_scalars, const void* d_bases, const uint32_t* h_seg_offsets, size_t num_segments, void* h_out_affine) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    ZK_REQUIRE(ctx, (h_seg_offsets && h_out_affine) || num_segments == 0, "null pointer");
+    return zk::msm_segments_run(ctx, (const zk::Fr*)d_scalars, (const zk::G1Affine*)d_bases, h_seg_offsets, num_segments, (zk::G1Affine*)h_out_affine);
+}
 
 // Host only: the merged-window plan of an SRS of 2^k points -- window bits, windows, and the shift the top window's digit is
 // scaled by (MsmPlan::top_shift).  For the CPU tests, which check the invariant the recoding relies on: the scaled top digit of

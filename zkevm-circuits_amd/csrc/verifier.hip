@@ -7,7 +7,8 @@
 // What runs where:
 //   device : decoding every point of every proof of the batch (one k_g1_decode launch: a square root per compressed point,
 //            a range and curve check per EVM point) and the final DualMSM of the whole batch (proofs weighted by powers of
-//            a batching scalar, the key's commitments once with summed coefficients)
+//            a batching scalar, the key's commitments once with summed coefficients); for zk_verify_accumulators the DualMSM
+//            of every proof on its own, all of them in one segmented MSM
 //   host   : transcript replay and the scalar work of one proof (instance and Lagrange evaluations, the folded identity at
 //            x, the multi-open's rotation sets) -- proofs are independent up to the MSM and are replayed on up to 16
 //            threads; the 2-term pairing check
@@ -455,7 +456,8 @@ struct DevMem {
     bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
 };
 
-// ZK_VERIFY_TRACE=1: wall-clock per step of zk_verify_proofs on stderr (tools/verify_time.py reads it)
+// ZK_VERIFY_TRACE=1: wall-clock per step of zk_verify_proofs (setup, decode, replay, msm, pairing) and zk_verify_accumulators (setup,
+// decode, replay, carried, gather, msm_seg -- msm_loop under ZK_ACC_MSM_LOOP=1) on stderr (tools/verify_time.py, tools/acc_time.py read it)
 struct VerifyTrace {
     bool on = getenv("ZK_VERIFY_TRACE") != nullptr;
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -466,6 +468,109 @@ struct VerifyTrace {
         t0 = t1;
     }
 };
+
+// What zk_verify_proofs and zk_verify_accumulators share: every point of every proof decoded on the device in one launch
+// (the key's commitments and the generator follow them in d_bases), every proof replayed on the host.
+struct Front {
+    Layout lo;
+    uint32_t M = 0, KP = 0;
+    size_t npts = 0, nbases = 0;
+    DevMem d_enc, d_bases;
+    std::vector<G1Affine> pts, tail;       // decoded proof points; fixed and sigma commitments, then the generator
+    std::vector<uint8_t> bad;
+    std::vector<ProofWork> work;
+};
+
+int check_verify_args(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
+                      const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen) {
+    ZK_REQUIRE(ctx, vk && h_proofs && h_proof_lens, "null pointer");
+    ZK_REQUIRE(ctx, count >= 1, "no proofs");
+    ZK_REQUIRE(ctx, !vk->I || (h_instances && h_instance_lens), "null instance pointer");
+    ZK_REQUIRE(ctx, transcript_kind == ZK_TRANSCRIPT_BLAKE2B || transcript_kind == ZK_TRANSCRIPT_POSEIDON || transcript_kind == ZK_TRANSCRIPT_EVM, "unknown transcript kind");
+    ZK_REQUIRE(ctx, multiopen == ZK_MULTIOPEN_GWC || multiopen == ZK_MULTIOPEN_SHPLONK, "unknown multi-open scheme");
+    for (size_t b = 0; b < count; ++b) {
+        ZK_REQUIRE(ctx, h_proofs[b] || !h_proof_lens[b], "null proof");
+        if (vk->I) {
+            ZK_REQUIRE(ctx, h_instances[b] && h_instance_lens[b], "null instance pointer");
+            for (uint32_t i = 0; i < vk->I; ++i) ZK_REQUIRE(ctx, h_instances[b][i] || !h_instance_lens[b][i], "null instance column");
+        }
+    }
+    return ZK_OK;
+}
+
+// f.lo is set.  A proof whose length is not the layout's is not looked at: its points decode from zero bytes and its work stays !ok.
+int decode_and_replay(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
+                      const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen, VerifyTrace& trace, Front& f) {
+    const Layout& lo = f.lo;
+    const uint32_t M = f.M = lo.points(), KP = f.KP = vk->F + vk->P;
+    // ---- every point of every proof: gathered, decoded in one launch; the key's commitments and the generator follow them,
+    // so the MSM reads its bases where the decoder left them
+    const size_t npts = f.npts = count * M, enc_bytes = npts * lo.point_len;
+    f.nbases = npts + KP + 1;
+    if (!f.d_enc.alloc(enc_bytes + npts) || !f.d_bases.alloc(f.nbases * sizeof(G1Affine))) {
+        (void)hipGetLastError();
+        return ctx->fail(ZK_ERR_OOM, "verifier: device allocation failed");
+    }
+    std::vector<uint8_t> enc(enc_bytes);
+    for (size_t b = 0; b < count; ++b) {
+        if (h_proof_lens[b] != lo.len()) continue;
+        for (uint32_t j = 0; j < M; ++j) memcpy(&enc[(b * M + j) * lo.point_len], (const uint8_t*)h_proofs[b] + lo.point_offset(j), lo.point_len);
+    }
+    std::vector<G1Affine>& tail = f.tail;
+    tail.resize(KP + 1);
+    for (uint32_t i = 0; i < vk->F; ++i) tail[i] = vk->fixed_com[i];
+    for (uint32_t i = 0; i < vk->P; ++i) tail[vk->F + i] = vk->sigma_com[i];
+    {   // the generator (1, 2)
+        F4 gx = fone<FqC>(), gy = fadd<FqC>(gx, gx);
+        memcpy(&tail[KP].x, gx.l, 32);
+        memcpy(&tail[KP].y, gy.l, 32);
+    }
+    uint8_t* d_in = (uint8_t*)f.d_enc.p;
+    uint8_t* d_bad_at = d_in + enc_bytes;
+    G1Affine* bases = (G1Affine*)f.d_bases.p;
+    std::vector<G1Affine>& pts = f.pts;
+    std::vector<uint8_t>& bad = f.bad;
+    pts.resize(npts);
+    bad.resize(npts);
+    trace.mark("setup");
+    {
+        DevMem d_cnt;
+        if (!d_cnt.alloc(4)) { (void)hipGetLastError(); return ctx->fail(ZK_ERR_OOM, "verifier: device allocation failed"); }
+        ZK_HIP(ctx, hipMemsetAsync(d_cnt.p, 0, 4, ctx->stream));
+        if (enc_bytes) ZK_HIP(ctx, hipMemcpyAsync(d_in, enc.data(), enc_bytes, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(ctx, hipMemcpyAsync(bases + npts, tail.data(), tail.size() * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = g1_decode_run(ctx, d_in, transcript_kind == ZK_TRANSCRIPT_EVM ? G1_ENC_BE_XY : G1_ENC_COMPRESSED, bases, npts, (uint32_t*)d_cnt.p, d_bad_at)) return rc;
+        if (npts) {
+            ZK_HIP(ctx, hipMemcpyAsync(pts.data(), bases, npts * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
+            ZK_HIP(ctx, hipMemcpyAsync(bad.data(), d_bad_at, npts, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    trace.mark("decode");
+
+    // ---- transcript replay, one proof per task, up to 16 threads
+    Replay rp{*vk, lo, transcript_kind, multiopen, fr_from_device(fr_root_of_unity(vk->k)), host::fr_pow(host::fr_from_u64(7), 1ull << 28), M, M + KP};
+    std::vector<ProofWork>& work = f.work;
+    work.resize(count);
+    {
+        std::atomic<size_t> next{0};
+        auto worker = [&]() {
+            for (size_t b; (b = next.fetch_add(1)) < count;) {
+                if (h_proof_lens[b] != lo.len()) continue;
+                const F4* const* inst = vk->I ? (const F4* const*)h_instances[b] : nullptr;
+                const uint32_t* lens = vk->I ? h_instance_lens[b] : nullptr;
+                rp.run((const uint8_t*)h_proofs[b], pts.data() + b * M, bad.data() + b * M, inst, lens, &work[b]);
+            }
+        };
+        const size_t nthreads = std::min<size_t>(count, 16);
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < nthreads; ++t) pool.emplace_back(worker);
+        worker();
+        for (auto& t : pool) t.join();
+    }
+    trace.mark("replay");
+    return ZK_OK;
+}
 
 }  // namespace
 
@@ -521,85 +626,26 @@ int zk_vk_shape(const zk_vk* vk, uint32_t* out16) {
 int zk_verify_proofs(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
                      const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen, const void* g2_128, const void* s_g2_128, int* ok) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
-    ZK_REQUIRE(ctx, vk && ok && h_proofs && h_proof_lens && g2_128 && s_g2_128, "null pointer");
-    ZK_REQUIRE(ctx, count >= 1, "no proofs");
-    ZK_REQUIRE(ctx, !vk->I || (h_instances && h_instance_lens), "null instance pointer");
-    ZK_REQUIRE(ctx, transcript_kind == ZK_TRANSCRIPT_BLAKE2B || transcript_kind == ZK_TRANSCRIPT_POSEIDON || transcript_kind == ZK_TRANSCRIPT_EVM, "unknown transcript kind");
-    ZK_REQUIRE(ctx, multiopen == ZK_MULTIOPEN_GWC || multiopen == ZK_MULTIOPEN_SHPLONK, "unknown multi-open scheme");
-    for (size_t b = 0; b < count; ++b) {
-        ZK_REQUIRE(ctx, h_proofs[b] || !h_proof_lens[b], "null proof");
-        if (vk->I) {
-            ZK_REQUIRE(ctx, h_instances[b] && h_instance_lens[b], "null instance pointer");
-            for (uint32_t i = 0; i < vk->I; ++i) ZK_REQUIRE(ctx, h_instances[b][i] || !h_instance_lens[b][i], "null instance column");
-        }
-    }
+    ZK_REQUIRE(ctx, ok && g2_128 && s_g2_128, "null pointer");
+    if (int rc = check_verify_args(ctx, vk, count, h_instances, h_instance_lens, h_proofs, h_proof_lens, transcript_kind, multiopen)) return rc;
     *ok = 0;
     VerifyTrace trace;
-    const Layout lo = layout_of(*vk, transcript_kind, multiopen);
-    const uint32_t M = lo.points(), KP = vk->F + vk->P;
+    Front f;
+    f.lo = layout_of(*vk, transcript_kind, multiopen);
     // a proof of the wrong length is a reject before anything else is looked at
-    for (size_t b = 0; b < count; ++b) if (h_proof_lens[b] != lo.len()) return ZK_OK;
-
-    // ---- every point of every proof: gathered, decoded in one launch; the key's commitments and the generator follow them,
-    // so the MSM reads its bases where the decoder left them
-    const size_t npts = count * M, nbases = npts + KP + 1, enc_bytes = npts * lo.point_len;
-    DevMem d_enc, d_bases, d_scalars;
-    if (!d_enc.alloc(enc_bytes + npts) || !d_bases.alloc(nbases * sizeof(G1Affine)) || !d_scalars.alloc(2 * nbases * sizeof(Fr))) {
+    for (size_t b = 0; b < count; ++b) if (h_proof_lens[b] != f.lo.len()) return ZK_OK;
+    if (int rc = decode_and_replay(ctx, vk, count, h_instances, h_instance_lens, h_proofs, h_proof_lens, transcript_kind, multiopen, trace, f)) return rc;
+    const uint32_t M = f.M, KP = f.KP;
+    const size_t npts = f.npts, nbases = f.nbases;
+    const std::vector<G1Affine>&pts = f.pts, &tail = f.tail;
+    const std::vector<ProofWork>& work = f.work;
+    G1Affine* bases = (G1Affine*)f.d_bases.p;
+    for (const ProofWork& w : work) if (!w.ok) return ZK_OK;
+    DevMem d_scalars;
+    if (!d_scalars.alloc(2 * nbases * sizeof(Fr))) {
         (void)hipGetLastError();
         return ctx->fail(ZK_ERR_OOM, "verifier: device allocation failed");
     }
-    std::vector<uint8_t> enc(enc_bytes);
-    for (size_t b = 0; b < count; ++b)
-        for (uint32_t j = 0; j < M; ++j) memcpy(&enc[(b * M + j) * lo.point_len], (const uint8_t*)h_proofs[b] + lo.point_offset(j), lo.point_len);
-    std::vector<G1Affine> tail(KP + 1);
-    for (uint32_t i = 0; i < vk->F; ++i) tail[i] = vk->fixed_com[i];
-    for (uint32_t i = 0; i < vk->P; ++i) tail[vk->F + i] = vk->sigma_com[i];
-    {   // the generator (1, 2)
-        F4 gx = fone<FqC>(), gy = fadd<FqC>(gx, gx);
-        memcpy(&tail[KP].x, gx.l, 32);
-        memcpy(&tail[KP].y, gy.l, 32);
-    }
-    uint8_t* d_in = (uint8_t*)d_enc.p;
-    uint8_t* d_bad_at = d_in + enc_bytes;
-    G1Affine* bases = (G1Affine*)d_bases.p;
-    std::vector<G1Affine> pts(npts);
-    std::vector<uint8_t> bad(npts);
-    trace.mark("setup");
-    {
-        DevMem d_cnt;
-        if (!d_cnt.alloc(4)) { (void)hipGetLastError(); return ctx->fail(ZK_ERR_OOM, "verifier: device allocation failed"); }
-        ZK_HIP(ctx, hipMemsetAsync(d_cnt.p, 0, 4, ctx->stream));
-        if (enc_bytes) ZK_HIP(ctx, hipMemcpyAsync(d_in, enc.data(), enc_bytes, hipMemcpyHostToDevice, ctx->stream));
-        ZK_HIP(ctx, hipMemcpyAsync(bases + npts, tail.data(), tail.size() * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
-        if (int rc = g1_decode_run(ctx, d_in, transcript_kind == ZK_TRANSCRIPT_EVM ? G1_ENC_BE_XY : G1_ENC_COMPRESSED, bases, npts, (uint32_t*)d_cnt.p, d_bad_at)) return rc;
-        if (npts) {
-            ZK_HIP(ctx, hipMemcpyAsync(pts.data(), bases, npts * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream));
-            ZK_HIP(ctx, hipMemcpyAsync(bad.data(), d_bad_at, npts, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    trace.mark("decode");
-
-    // ---- transcript replay, one proof per task, up to 16 threads
-    Replay rp{*vk, lo, transcript_kind, multiopen, fr_from_device(fr_root_of_unity(vk->k)), host::fr_pow(host::fr_from_u64(7), 1ull << 28), M, M + KP};
-    std::vector<ProofWork> work(count);
-    {
-        std::atomic<size_t> next{0};
-        auto worker = [&]() {
-            for (size_t b; (b = next.fetch_add(1)) < count;) {
-                const F4* const* inst = vk->I ? (const F4* const*)h_instances[b] : nullptr;
-                const uint32_t* lens = vk->I ? h_instance_lens[b] : nullptr;
-                rp.run((const uint8_t*)h_proofs[b], pts.data() + b * M, bad.data() + b * M, inst, lens, &work[b]);
-            }
-        };
-        const size_t nthreads = std::min<size_t>(count, 16);
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-        worker();
-        for (auto& t : pool) t.join();
-    }
-    trace.mark("replay");
-    for (const ProofWork& w : work) if (!w.ok) return ZK_OK;
 
     // ---- one DualMSM for the batch: proof b weighted by rho^b, rho from Blake2b over the key, every proof and every instance
     F4 rho = fr_one();
@@ -657,6 +703,100 @@ int zk_verify_proofs(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* con
     memcpy(&Q[1], s_g2_128, 128);
     *ok = pairing_check(P, Q, 2) ? 1 : 0;
     trace.mark("pairing");
+    return ZK_OK;
+}
+
+// PlonkSuccinctVerifier::verify for a batch, as extract_accumulators_and_proof runs it on the child snarks of an aggregation
+// layer [REF aggregator/src/core.rs:48-107]: per proof the KZG accumulator of its own openings (lhs = MSM of `right`, rhs = MSM of
+// `left`, Replay::run's normalisation) and the accumulators its instances carry, NO pairing.  The statement followed is
+// oracle/snark_verifier.py:succinct_verify.  Decode and replay are zk_verify_proofs'; the 2 * count coefficient vectors then go
+// through ONE segmented MSM (zero coefficients and identity points dropped, so `left` is one to a few terms).
+// ZK_ACC_MSM_LOOP=1 (measurement only) sends the same vectors through 2 * count zk_msm_g1 calls instead, the only route there
+// was before zk_msm_g1_segments.
+int zk_verify_accumulators(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* const* const* h_instances, const uint32_t* const* h_instance_lens,
+                           const void* const* h_proofs, const size_t* h_proof_lens, int transcript_kind, int multiopen, const uint32_t* acc_indices, size_t num_prior,
+                           void* h_lhs, void* h_rhs, int* ok) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    ZK_REQUIRE(ctx, ok && h_lhs && h_rhs && (acc_indices || !num_prior), "null pointer");
+    if (int rc = check_verify_args(ctx, vk, count, h_instances, h_instance_lens, h_proofs, h_proof_lens, transcript_kind, multiopen)) return rc;
+    const size_t per = 1 + num_prior;
+    G1Affine* lhs = (G1Affine*)h_lhs;
+    G1Affine* rhs = (G1Affine*)h_rhs;
+    memset(h_lhs, 0, count * per * sizeof(G1Affine));
+    memset(h_rhs, 0, count * per * sizeof(G1Affine));
+    for (size_t b = 0; b < count; ++b) ok[b] = 0;
+    VerifyTrace trace;
+    Front f;
+    f.lo = layout_of(*vk, transcript_kind, multiopen);
+    if (int rc = decode_and_replay(ctx, vk, count, h_instances, h_instance_lens, h_proofs, h_proof_lens, transcript_kind, multiopen, trace, f)) return rc;
+    const uint32_t M = f.M, KP = f.KP;
+
+    // ---- the accumulators carried in the instances: 12 limbs each, cell (column, row) per limb
+    for (size_t b = 0; b < count; ++b) {
+        bool good = f.work[b].ok;
+        for (size_t a = 0; a < num_prior && good; ++a) {
+            F4 limbs[12];
+            for (int l = 0; l < 12 && good; ++l) {
+                const uint32_t col = acc_indices[(a * 12 + l) * 2], row = acc_indices[(a * 12 + l) * 2 + 1];
+                good = col < vk->I && row < h_instance_lens[b][col];
+                if (good) memcpy(limbs[l].l, (const uint8_t*)h_instances[b][col] + (size_t)32 * row, 32);
+            }
+            int dec = 0;
+            if (good) (void)zk_host_accumulator_from_limbs(limbs, &lhs[b * per + 1 + a], &rhs[b * per + 1 + a], &dec);
+            good = good && dec;
+        }
+        ok[b] = good ? 1 : 0;
+    }
+    trace.mark("carried");
+
+    // ---- segment 2b: `right` over [the proof's points | the key's commitments | the generator]; segment 2b + 1: `left` over
+    // the proof's points.  A rejected proof has two empty segments.
+    std::vector<uint32_t> off(2 * count + 1, 0);
+    std::vector<F4> sc;
+    std::vector<G1Affine> bs;
+    for (size_t b = 0; b < count; ++b) {
+        if (ok[b]) {
+            const ProofWork& w = f.work[b];
+            auto term = [&](const F4& c, const G1Affine& p) { if (!fr_is_zero(c) && !p.is_identity()) { sc.push_back(c); bs.push_back(p); } };
+            for (uint32_t j = 0; j < M; ++j) term(w.right[j], f.pts[b * M + j]);
+            for (uint32_t t = 0; t <= KP; ++t) term(w.right[M + t], f.tail[t]);
+            off[2 * b + 1] = (uint32_t)sc.size();
+            for (uint32_t j = 0; j < M; ++j) term(w.left[j], f.pts[b * M + j]);
+        } else {
+            off[2 * b + 1] = (uint32_t)sc.size();
+        }
+        off[2 * b + 2] = (uint32_t)sc.size();
+    }
+    std::vector<G1Affine> sums(2 * count);
+    if (!sc.empty()) {
+        DevMem d_sc, d_bs;
+        if (!d_sc.alloc(sc.size() * sizeof(F4)) || !d_bs.alloc(bs.size() * sizeof(G1Affine))) {
+            (void)hipGetLastError();
+            return ctx->fail(ZK_ERR_OOM, "verifier: device allocation failed");
+        }
+        ZK_HIP(ctx, hipMemcpyAsync(d_sc.p, sc.data(), sc.size() * sizeof(F4), hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(ctx, hipMemcpyAsync(d_bs.p, bs.data(), bs.size() * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream));
+        trace.mark("gather");
+        const char* loop = getenv("ZK_ACC_MSM_LOOP");
+        if (loop && atoi(loop) == 1) {
+            for (size_t s = 0; s < 2 * count; ++s)
+                if (int rc = zk_msm_g1(ctx, (const F4*)d_sc.p + off[s], (const G1Affine*)d_bs.p + off[s], off[s + 1] - off[s], &sums[s])) return rc;
+            if (int rc = zk_ctx_sync(ctx)) return rc;
+            trace.mark("msm_loop");
+        } else {
+            if (int rc = msm_segments_run(ctx, (const Fr*)d_sc.p, (const G1Affine*)d_bs.p, off.data(), 2 * count, sums.data())) return rc;
+            trace.mark("msm_seg");
+        }
+    }
+    for (size_t b = 0; b < count; ++b) {
+        if (!ok[b]) {       // nothing of a rejected proof goes out, carried accumulators that did decode included
+            memset((void*)&lhs[b * per], 0, per * sizeof(G1Affine));
+            memset((void*)&rhs[b * per], 0, per * sizeof(G1Affine));
+            continue;
+        }
+        lhs[b * per] = sums[2 * b];
+        rhs[b * per] = sums[2 * b + 1];
+    }
     return ZK_OK;
 }
 

@@ -232,6 +232,44 @@ int zk_host_accumulator_limbs(const void* lhs, const void* rhs, void* out12_fr) 
     }
     return ZK_OK;
 }
+// The inverse (LimbsEncoding::from_repr as the aggregation layers read an accumulator off a snark's instances
+// [REF aggregator/src/core.rs:120-135]): 12 Fr cells (Montgomery) -> lhs, rhs.  *ok = 0, with both points zeroed, when a
+// cell is not a canonical Fr, a limb is 2^88 or more, a coordinate is p or more, or a point is not on the curve (the
+// identity has no encoding).  A malformed accumulator is a verdict, not an error status.
+int zk_host_accumulator_from_limbs(const void* limbs12_fr, void* lhs, void* rhs, int* ok) {
+    if (!limbs12_fr || !lhs || !rhs || !ok) return ZK_ERR_INVALID_ARG;
+    *ok = 0;
+    memset(lhs, 0, 64);
+    memset(rhs, 0, 64);
+    static const uint64_t Q_R2[4] = {0xf32cfc5b538afa89ULL, 0xb5e71911d44501fbULL, 0x47ab1eff0a417ff6ULL, 0x06d89f71cab8351fULL};
+    F4 r2, coord[4];
+    memcpy(r2.l, Q_R2, 32);
+    for (int c = 0; c < 4; ++c) {
+        uint8_t b[33 + 8] = {0};                                       // 3 x 11 bytes; the 33rd must stay zero
+        for (int limb = 0; limb < 3; ++limb) {
+            F4 m;
+            memcpy(m.l, (const uint8_t*)limbs12_fr + 32 * (3 * c + limb), 32);
+            if (geq_mod<FrC>(m.l)) return ZK_OK;
+            const F4 v = fr_canon(m);
+            if ((v.l[1] >> 24) | v.l[2] | v.l[3]) return ZK_OK;        // limb >= 2^88
+            memcpy(b + 11 * limb, v.l, 11);
+        }
+        F4 x;
+        memcpy(x.l, b, 32);
+        if (b[32] || geq_mod<FqC>(x.l)) return ZK_OK;                  // coordinate >= p
+        coord[c] = fmul<FqC>(x, r2);
+    }
+    for (int j = 0; j < 2; ++j) {
+        const F4 &x = coord[2 * j], &y = coord[2 * j + 1];
+        if (memcmp(q_mul(y, y).l, q_add(q_mul(q_mul(x, x), x), q_from_u64(3)).l, 32) != 0) return ZK_OK;
+    }
+    memcpy(lhs, coord[0].l, 32);
+    memcpy((uint8_t*)lhs + 32, coord[1].l, 32);
+    memcpy(rhs, coord[2].l, 32);
+    memcpy((uint8_t*)rhs + 32, coord[3].l, 32);
+    *ok = 1;
+    return ZK_OK;
+}
 
 // ---- the prover's `Proof` wire object [REF prover/src/proof.rs:25-35, 99-104]: what `dump_as_json` writes to
 // full_proof_<name>.json -- {"proof": base64, "instances": base64 of the 32-byte big-endian words, "vk": base64 of
