@@ -188,11 +188,11 @@ def _mixed_batch(pool, count, offset):
 
 
 def _pipeline_settings():
-    return [(p, g, sa) for p in ("1", "2") for g in ("0", "1") for sa in ("0", "1")]
+    return [(p, g) for p in ("1", "2") for g in ("0", "1")]
 
 
 def test_batches_pipelines_and_graph_replay(ctx, cref, srs12, bases12, monkeypatch, capfd):
-    """Batches of 1, 2, 3, 4, 5 and 9 mixed columns under ZK_MSM_PIPES x ZK_MSM_GRAPH x ZK_MSM_SORT_AHEAD: each column = its own
+    """Batches of 1, 2, 3, 4, 5 and 9 mixed columns under ZK_MSM_PIPES x ZK_MSM_GRAPH: each column = its own
     oracle.  Where graph replay is due (4+ columns, 1024 <= n <= 2^19) the trace must say it ran: the session's context keeps a
     graph failure for good, and the fallback alone would pass every comparison."""
     pool = _cols(cref, 12, 1 << 12, 4000)
@@ -202,14 +202,13 @@ def test_batches_pipelines_and_graph_replay(ctx, cref, srs12, bases12, monkeypat
         for count in (1, 2, 3, 4, 5, 9):
             names = _mixed_batch(pool, count, count + n)
             want = [_want(cref, pool[nm], bases12[True], ("k12", True), n) for nm in names]
-            for pipes, graph, sa in _pipeline_settings():
+            for pipes, graph in _pipeline_settings():
                 monkeypatch.setenv("ZK_MSM_PIPES", pipes)
                 monkeypatch.setenv("ZK_MSM_GRAPH", graph)
-                monkeypatch.setenv("ZK_MSM_SORT_AHEAD", sa)
                 capfd.readouterr()
                 got = ctx.commit_batch(srs12, [bufs[nm].ptr for nm in names], n, lagrange=True, narrow=[0] * count)
                 err = capfd.readouterr().err
-                label = f"n = {n}, {count} columns, PIPES={pipes} GRAPH={graph} SORT_AHEAD={sa}"
+                label = f"n = {n}, {count} columns, PIPES={pipes} GRAPH={graph}"
                 bad = [f"{i}:{nm}" for i, nm in enumerate(names) if not np.array_equal(got[i], want[i])]
                 assert not bad, f"{label}: columns {bad} differ from best_multiexp"
                 assert ("(graph replay)" in err) == (graph == "1" and count >= 4), f"{label}: graph replay expected {graph == '1' and count >= 4}, trace: {err!r}"
@@ -218,8 +217,8 @@ def test_batches_pipelines_and_graph_replay(ctx, cref, srs12, bases12, monkeypat
 
 
 def test_batches_at_2_19(ctx, cref, monkeypatch, capfd):
-    """The largest batch size of the graph mode (2^19 rows over an SRS of 2^19, c = 19): mixed columns under a subset of the
-    pipeline / graph / sort-ahead settings, each against the closed form over the coefficient basis."""
+    """The largest batch size of the graph mode (2^19 rows over an SRS of 2^19, c = 19): mixed columns under each of the
+    four pipeline x graph settings, each against the closed form over the coefficient basis."""
     k = 19
     n = 1 << k
     s = S_SRS + 19
@@ -229,15 +228,14 @@ def test_batches_at_2_19(ctx, cref, monkeypatch, capfd):
     want = {nm: _closed_form(cref, pool[nm], s) for nm in names}
     bufs = {nm: ctx.to_device(col) for nm, col in pool.items()}
     monkeypatch.setenv("ZK_MSM_TRACE", "1")
-    for count, (pipes, graph, sa) in ((5, ("2", "1", "0")), (4, ("1", "1", "1")), (5, ("2", "0", "1")), (3, ("1", "0", "0"))):
+    for count, (pipes, graph) in ((5, ("2", "1")), (4, ("1", "1")), (5, ("2", "0")), (3, ("1", "0"))):
         monkeypatch.setenv("ZK_MSM_PIPES", pipes)
         monkeypatch.setenv("ZK_MSM_GRAPH", graph)
-        monkeypatch.setenv("ZK_MSM_SORT_AHEAD", sa)
         batch = _mixed_batch(pool, count, count)
         capfd.readouterr()
         got = ctx.commit_batch(srs, [bufs[nm].ptr for nm in batch], n, narrow=[0] * count)
         err = capfd.readouterr().err
-        label = f"2^19, {count} columns, PIPES={pipes} GRAPH={graph} SORT_AHEAD={sa}"
+        label = f"2^19, {count} columns, PIPES={pipes} GRAPH={graph}"
         bad = [f"{i}:{nm}" for i, nm in enumerate(batch) if not np.array_equal(got[i], want[nm])]
         assert not bad, f"{label}: columns {bad} differ from the closed form"
         assert ("(graph replay)" in err) == (graph == "1" and count >= 4), f"{label}: trace {err!r}"

@@ -1,5 +1,5 @@
 """Dense commit batches at small k through the graph-replay path (no profiling events: they switch it off): ms per MSM for
-batches of 8 and 16 columns.  usage: [ZK_MSM_GRAPH_PIPES=N] python tools/msm_graph_pipes.py [k]"""
+batches of 8 and 16 columns.  usage: python tools/msm_graph_pipes.py [k]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,5 +23,5 @@ for cnt in (8, 16):
             t0 = time.perf_counter()
             ctx.commit_batch(srs, ptrs, n, lagrange=basis)
             best = min(best, (time.perf_counter() - t0) / cnt)
-        print(f"k={k} pipes={os.environ.get('ZK_MSM_GRAPH_PIPES', '4')} batch of {cnt} dense columns, {'lagrange' if basis else 'coefficient'} basis: {best * 1e3:.3f} ms per MSM")
+        print(f"k={k} batch of {cnt} dense columns, {'lagrange' if basis else 'coefficient'} basis: {best * 1e3:.3f} ms per MSM")
 ctx.close()

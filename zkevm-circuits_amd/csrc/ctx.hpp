@@ -43,7 +43,6 @@ struct zk_ctx {
     uint32_t msm_blinded_tail = 0;          // set by the prover around a commit batch: this many rows at the end of the hint-1 (small-valued) columns
                                             // hold field-sized blinding values; they are committed apart (k_msm_tails) so that the main MSM sees small values only
     bool msm_graph_broken = false;          // a capture or replay failed once: the plain launch path from then on
-    hipEvent_t ev_sorted[2] = {nullptr, nullptr};   // sort-ahead of msm_batch_merged: workspace copy i holds a finished sort
     hipEvent_t ev_pipe = nullptr;        // joins the second MSM pipeline of small batches (msm_batch_merged)
     // copy stream: host -> device staging of the next column under the current MSM (api.hip)
     hipStream_t stream_copy = nullptr;

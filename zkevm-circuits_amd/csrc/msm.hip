@@ -29,6 +29,7 @@
 //                dependent doubling chain is issue-bound on one GPU lane) and the affine
 //                normalisation; with window tables only the normalisation is left.
 #include <chrono>
+#include <climits>
 #include <cmath>
 
 #include "ctx.hpp"
@@ -69,7 +70,7 @@ static MsmPlan make_plan(size_t n) {
 // 1. k_msm_digits: every scalar leaves Montgomery form once and is recoded; digit codes go to a
 //    window-major u16 matrix dig[w][i] (row stride n_pad, multiple of 64):
 //      0xFFFF = zero digit, otherwise bit 15 = sign, bits 0..14 = bucket (|d| - 1).
-// 2. k_msm_lds_count / k_msm_lds_scatter: workgroup (r, w) owns bucket range r of window w
+// 2. k_msm_lds_sweep<SCATTER> (count, then scatter): workgroup (r, w) owns bucket range r of window w
 //    (<= 2048 buckets).  It streams the whole digit row (2 MiB at 2^20, L2-resident, 16 B/lane)
 //    and keeps only digits in its range: counters / cursors live in LDS (ds_add_rtn_u32), so the
 //    sort needs no global atomics, and a workgroup's slice of `idx` is written by that workgroup
@@ -1187,6 +1188,197 @@ static int wsum_enqueue(zk_ctx* ctx, hipStream_t st, const G1Xyzz29* buckets, ui
     return ZK_OK;
 }
 
+// ---- host side -----------------------------------------------------------------------------------
+// msm_batch_tab and msm_batch_merged -- its plain launches and its graph capture alike -- are sequences of the stage
+// functions below over one SortWs; no other code launches the sort, accumulation, combination or reduction kernels.
+#define PK_TRY_MSM(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
+
+// Measurement knobs.  read_knobs() is called at the top of every call that applies one and its result is never kept: a
+// process may change the environment between two calls.  A field is the variable's atoi, KNOB_UNSET when it is not
+// set; the range of a knob is checked where it is applied.
+constexpr int KNOB_UNSET = INT_MIN;
+struct MsmKnobs {
+    int c, top_shift;                                       // ZK_MSM_C, ZK_MSM_TOP_SHIFT: the merged plan (make_plan_merged)
+    int binsort, staged, chunk;                             // ZK_MSM_BINSORT, ZK_MSM_STAGED, ZK_MSM_CHUNK: the merged sort
+    int pipes, graph;                                       // ZK_MSM_PIPES, ZK_MSM_GRAPH: pipelines of a small batch
+    int narrow, narrow_group, narrow_gm, gm_sets;           // ZK_MSM_NARROW, ZK_MSM_NARROW_GROUP, ZK_MSM_NARROW_GM, ZK_MSM_GM_SETS: small-valued columns
+    double table_gb;                                        // ZK_MSM_TABLE_GB: largest window table per basis (default 32 GiB)
+    bool trace;                                             // ZK_MSM_TRACE (set at all): host enqueue / device drain times of every batch on stderr
+};
+static MsmKnobs read_knobs() {
+    auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : KNOB_UNSET; };
+    MsmKnobs k;
+    k.c = num("ZK_MSM_C");
+    k.top_shift = num("ZK_MSM_TOP_SHIFT");
+    k.binsort = num("ZK_MSM_BINSORT");
+    k.staged = num("ZK_MSM_STAGED");
+    k.chunk = num("ZK_MSM_CHUNK");
+    k.pipes = num("ZK_MSM_PIPES");
+    k.graph = num("ZK_MSM_GRAPH");
+    k.narrow = num("ZK_MSM_NARROW");
+    k.narrow_group = num("ZK_MSM_NARROW_GROUP");
+    k.narrow_gm = num("ZK_MSM_NARROW_GM");
+    k.gm_sets = num("ZK_MSM_GM_SETS");
+    const char* gb = getenv("ZK_MSM_TABLE_GB");
+    k.table_gb = gb ? atof(gb) : 32.0;
+    k.trace = getenv("ZK_MSM_TRACE") != nullptr;
+    return k;
+}
+
+// Sort workspace.  A bump allocator over u32 words describes a layout once: over a null base it only counts -- the size
+// to ask for --, over the workspace it hands out the pointers, so the two cannot disagree.
+struct WsCarver {
+    uint32_t* base;
+    size_t at = 0;
+    uint32_t* take(size_t nwords, size_t align_words = 1) {
+        at = (at + align_words - 1) / align_words * align_words;
+        uint32_t* p = base ? base + at : nullptr;
+        at += nwords;
+        return p;
+    }
+};
+static inline uint32_t scan_blocks_of(uint32_t cnt) { return (cnt + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS); }
+// size_hist[SIZE_BINS] | nmulti[4] | window flags[MSM_WFLAGS] | done-counters[TASK_DONE_MAX]: the kernels find the flags
+// and the counters behind nmulti, and every sort starts by clearing the four with ONE memset -- they are one region
+constexpr uint32_t MSM_CLEARED_WORDS = SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX;
+// The three layouts by their dimensions:
+//   per-window "N" (msm_batch_tab, small-valued columns):  slices, idx[n * windows], digit matrix
+//   merged "M":                                            slices (the sliced sort), partition histogram, idx and entries[n * W]
+//   grouped "GM":                                          partition histogram, idx and entries[n * W * columns]
+struct SortDims {
+    uint32_t nb;            // buckets
+    bool slices;            // [bucket][slice] counters and offsets of a sort by MSM_SLICES workgroups per bucket range
+    uint32_t hist_cnt;      // partition histogram: partitions x workgroups (0: no partition pass)
+    uint64_t idx_cnt;       // sorted indices, worst case
+    size_t dig_words;       // u16 digit matrix, in words (0: none)
+    bool entries;           // u64 (bucket, table index) entries, idx_cnt of them
+};
+struct SortWs {
+    uint32_t *slice_counts, *slice_off, *block_tot_s;       // slices (both 16-B aligned: k_scan_u32_c reads the MSM_SLICES words of a bucket as one uint4)
+    uint32_t *counts, *offsets, *order, *ntasks, *toff, *block_tot;
+    uint32_t *cleared, *size_hist, *nmulti, *wflag;         // the cleared region and its named parts
+    uint32_t *hist, *hist_off, *block_tot_h;                // partition pass
+    uint32_t* idx;
+    uint16_t* dig;                                          // 16-B aligned
+    uint64_t* entries;                                      // 8-B aligned
+    size_t words;                                           // of the whole layout
+};
+static SortWs carve_sort_ws(const SortDims& d, uint32_t* base) {
+    WsCarver c{base};
+    SortWs w{};
+    if (d.slices) {
+        w.slice_counts = c.take((size_t)d.nb * MSM_SLICES, 4);
+        w.slice_off = c.take((size_t)d.nb * MSM_SLICES + 4, 4);
+    }
+    w.counts = c.take(d.nb);
+    w.cleared = c.take(MSM_CLEARED_WORDS);
+    w.size_hist = w.cleared;
+    w.nmulti = w.size_hist + SIZE_BINS;
+    w.wflag = w.nmulti + 4;
+    w.offsets = c.take((size_t)d.nb + 1);
+    w.order = c.take(d.nb);
+    w.ntasks = c.take(d.nb);
+    w.toff = c.take((size_t)d.nb + 1);
+    if (d.slices) w.block_tot_s = c.take(scan_blocks_of(d.nb * MSM_SLICES));
+    w.block_tot = c.take(scan_blocks_of(d.nb));
+    if (d.hist_cnt) {
+        w.block_tot_h = c.take(scan_blocks_of(d.hist_cnt));
+        w.hist = c.take(d.hist_cnt);
+        w.hist_off = c.take((size_t)d.hist_cnt + 1);
+    }
+    w.idx = c.take(d.idx_cnt);
+    if (d.dig_words) w.dig = reinterpret_cast<uint16_t*>(c.take(d.dig_words, 4));
+    if (d.entries) w.entries = reinterpret_cast<uint64_t*>(c.take(2 * (size_t)d.idx_cnt, 2));
+    w.words = c.at;
+    return w;
+}
+
+// exclusive scan of in[cnt] into out[cnt], the total to *total_out (nullable); block_tot: scan_blocks_of(cnt) words.
+// Block-local offsets: k_task_offsets (exclusive_scan) or the slice scan's own last pass adds the block totals.
+static void scan_blocks(hipStream_t st, const uint32_t* in, uint32_t cnt, uint32_t* out, uint32_t* block_tot, uint32_t* total_out) {
+    const uint32_t sb = scan_blocks_of(cnt);
+    hipLaunchKernelGGL(k_scan_u32_a, dim3(sb), dim3(SCAN_T), 0, st, in, cnt, out, block_tot);
+    hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, block_tot, sb, out, cnt, total_out);
+}
+static int exclusive_scan(zk_ctx* ctx, hipStream_t st, const uint32_t* in, uint32_t cnt, uint32_t* out, uint32_t* block_tot) {
+    scan_blocks(st, in, cnt, out, block_tot, nullptr);
+    hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks_of(cnt)), dim3(SCAN_T), 0, st, cnt, out, (const uint32_t*)block_tot);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// [bucket][slice] counters -> slice offsets, bucket offsets (total behind them), bucket counts and the size histogram
+static int slice_scan(zk_ctx* ctx, hipStream_t st, const SortWs& w, uint32_t nb) {
+    scan_blocks(st, w.slice_counts, nb * MSM_SLICES, w.slice_off, w.block_tot_s, w.offsets + nb);
+    hipLaunchKernelGGL(k_scan_u32_c, dim3(scan_blocks_of(nb * MSM_SLICES)), dim3(SCAN_T), 0, st, (const uint32_t*)w.slice_counts, nb, w.slice_off, (const uint32_t*)w.block_tot_s, w.offsets, w.counts,
+                       w.size_hist);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// skew-proof work split: buckets ordered by size, split into tasks, task offsets per position
+static int task_split(zk_ctx* ctx, hipStream_t st, const SortWs& w, uint32_t nb) {
+    hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, st, w.size_hist, (const uint32_t*)(w.offsets + nb));
+    hipLaunchKernelGGL(k_order_buckets, dim3(scan_blocks_of(nb)), dim3(SCAN_T), 0, st, (const uint32_t*)w.counts, nb, w.size_hist, w.order, w.ntasks);
+    return exclusive_scan(ctx, st, w.ntasks, nb, w.toff, w.block_tot);
+}
+// Per-window sort of `ncols` columns that share one launch sequence: digits, LDS-privatised counting sort with empty
+// windows skipped; column j owns windows [j W, (j + 1) W) of the digit matrix and of the flags.  The scalars come from
+// scalars[j], or (graph mode, one column) from cols[*ctr].
+static int sort_digits(zk_ctx* ctx, hipStream_t st, const SortWs& w, const MsmPlan& pl, const Fr* const* scalars, uint32_t ncols, uint64_t n, uint64_t n_pad, const MsmCol* cols, const uint32_t* ctr) {
+    const uint32_t wins = ncols * (uint32_t)pl.W, nb = wins * pl.B;
+    const int range_bits = std::min(pl.c - 1, MSM_RANGE_MAX_BITS);
+    const dim3 sweep_grid(8u * ((wins + 7) / 8) * (pl.B >> range_bits) * MSM_SLICES);
+    ZK_HIP(ctx, hipMemsetAsync(w.cleared, 0, (size_t)MSM_CLEARED_WORDS * 4, st));
+    for (uint32_t j = 0; j < ncols; ++j)
+        launch_digits(pl.c, dim3((unsigned)((n_pad / 2 + 255) / 256)), st, scalars ? scalars[j] : nullptr, n, n_pad, w.dig + (size_t)j * pl.W * n_pad, w.wflag + j * pl.W, cols, ctr);
+    hipLaunchKernelGGL((k_msm_lds_sweep<false>), sweep_grid, dim3(1024), 0, st, (const uint16_t*)w.dig, n_pad, range_bits, pl.B, w.slice_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)w.wflag, wins);
+    ZK_CHECK_LAUNCH(ctx);
+    PK_TRY_MSM(slice_scan(ctx, st, w, nb));
+    PK_TRY_MSM(task_split(ctx, st, w, nb));
+    hipLaunchKernelGGL((k_msm_lds_sweep<true>), sweep_grid, dim3(1024), 0, st, (const uint16_t*)w.dig, n_pad, range_bits, pl.B, (uint32_t*)nullptr, (const uint32_t*)w.slice_off, w.idx, (const uint32_t*)w.wflag, wins);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// Bucket accumulation of a finished sort, then the combination of the buckets that were split into tasks.
+// log_b / tab_stride / wflag / tab_windows: the per-window paths, see k_msm_buckets; with idx holding table indices (M, GM)
+// there is no window offset and no per-window skip: all zero.  perm: the GM sort's bucket numbering.
+static int accumulate_combine(zk_ctx* ctx, hipStream_t st, const char* label, const G1Affine* table, const SortWs& w, uint32_t nb, size_t max_tasks, G1Xyzz29* buckets, G1Xyzz29* task_partial,
+                              int log_b, uint64_t tab_stride, const uint32_t* wflag, uint32_t tab_windows, uint32_t perm) {
+    {
+        ZkProfScope ps(ctx, label, st);
+        // multi-task buckets first (they are the long poles), then one lane per ordinary bucket
+        hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((max_tasks + 255) / 256)), dim3(256), 0, st, table, (const uint32_t*)w.offsets, (const uint32_t*)w.idx,
+                           (const uint32_t*)w.order, (const uint32_t*)w.toff, (const uint32_t*)w.nmulti, nb, buckets, task_partial, log_b, tab_stride, wflag, tab_windows, perm);
+    }
+    {
+        ZkProfScope ps(ctx, "msm_combine", st);
+        hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((max_tasks + 255) / 256)), dim3(256), 0, st, (const uint32_t*)w.nmulti, (const uint32_t*)w.toff, task_partial);
+        hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nb + 255) / 256)), dim3(256), 0, st, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
+                           (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partial, buckets, perm);
+        hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, st, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
+                           (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partial, buckets, perm);
+        ZK_CHECK_LAUNCH(ctx);
+    }
+    return ZK_OK;
+}
+// `sums` weighted bucket sums by running sums + LDS tree, each over `sets` consecutive bucket sets of B buckets; with
+// fold_W != 0 a sum's fold_W windows (those whose flag is set) are folded into one set first.  short_chain: the caller
+// waits for this very reduction.  The result goes to out[sum], or (graph mode, one sum) to cols[*ctr].out, and *ctr
+// moves on by ctr_step.
+static int reduce_window(zk_ctx* ctx, hipStream_t st, const G1Xyzz29* buckets, uint32_t B, int fold_W, G1Xyzz29* folded, const uint32_t* wflag, uint32_t sums, uint32_t sets, bool short_chain,
+                         G1Xyzz29* partial, G1Xyzz* out, const MsmCol* cols, uint32_t* ctr, uint32_t ctr_step) {
+    const uint32_t red_blocks = ((B + (short_chain ? RED_G_FOLDED : RED_G_WIDE) - 1) / (short_chain ? RED_G_FOLDED : RED_G_WIDE) + RED_THREADS - 1) / RED_THREADS;
+    if (fold_W) {
+        hipLaunchKernelGGL(k_msm_fold_windows, dim3((B + 63) / 64, sums), dim3(256), 0, st, buckets, B, fold_W, folded, wflag);
+        buckets = folded;
+    }
+    if (short_chain) hipLaunchKernelGGL((k_msm_reduce<RED_G_FOLDED>), dim3(red_blocks, sums * sets), dim3(RED_THREADS), 0, st, buckets, B, partial);
+    else hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(red_blocks, sums * sets), dim3(RED_THREADS), 0, st, buckets, B, partial);
+    ZK_CHECK_LAUNCH(ctx);
+    hipLaunchKernelGGL(k_msm_window_sum, dim3(sums), dim3(RED_THREADS), 0, st, (const G1Xyzz29*)partial, red_blocks * sets, out, cols, ctr, ctr_step);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+
 // bases_rp: device bases already in R' form (SRS cache) or nullptr -> converted into scratch
 // d_table (nullable): fixed-base window table for exactly this plan (W windows of tab_stride points)
 int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_bases, const G1Affine* d_bases_rp, const G1Affine* d_table, size_t tab_stride,
@@ -1199,34 +1391,11 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     // bucket offsets and task cursors are 32-bit: n * W (point, window) entries must stay below 2^32 (n <= 2^27 at 16 windows)
     if ((uint64_t)n * pl.W >= (1ull << 32)) return ctx->fail(ZK_ERR_UNSUPPORTED, "MSM of %zu points x %d windows exceeds 2^32 index entries: split it", n, pl.W);
 
-    // u32 workspace: slice_counts[4 nb] | slice_off[4 nb + 4] (both 16-B aligned) | counts[nb] | size_hist[256] nmulti[4] wflag[64] |
-    //                offsets[nb+1] | order[nb] | ntasks[nb] | toff[nb+1] | block_tot[scan_blocks_s + scan_blocks] | idx[n*W] |
-    //                (16-B aligned) dig[W*n_pad u16]
-    const uint32_t scan_blocks = (nb + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS);
-    const uint32_t scan_blocks_s = (nb + SCAN_T - 1) / SCAN_T;                    // scan over the [bucket][slice] counters: one bucket per thread
     const uint64_t n_pad = ((uint64_t)n + 16 * MSM_SLICES - 1) & ~(uint64_t)(16 * MSM_SLICES - 1);
-    const size_t dig_words = (size_t)(n_pad * pl.W + 1) / 2 + 4;
-    const size_t head_words = (size_t)nb * (2 * MSM_SLICES + 5) + 4 + 2 + SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX + (size_t)scan_blocks_s + scan_blocks + (size_t)n * pl.W;
-    const size_t words = head_words + 4 + dig_words;
-    uint32_t* ws = (uint32_t*)ctx->get_scratch(SC_MSM_KEYS, words * 4);
+    const SortDims dims{nb, true, 0, (uint64_t)n * pl.W, (size_t)(n_pad * pl.W + 1) / 2 + 4, false};      // per-window layout
+    uint32_t* ws = (uint32_t*)ctx->get_scratch(SC_MSM_KEYS, carve_sort_ws(dims, nullptr).words * 4);
     if (!ws) return ZK_ERR_OOM;
-    uint32_t* slice_counts = ws;
-    uint32_t* slice_off = slice_counts + (size_t)nb * MSM_SLICES;
-    uint32_t* counts = slice_off + (size_t)nb * MSM_SLICES + 4;
-    uint32_t* size_hist = counts + nb;
-    uint32_t* nmulti = size_hist + SIZE_BINS;
-    uint32_t* wflag = nmulti + 4;          // MSM_WFLAGS words: W <= 64 windows (c >= 4)
-    uint32_t* offsets = wflag + MSM_WFLAGS + TASK_DONE_MAX;
-    uint32_t* order = offsets + nb + 1;
-    uint32_t* ntasks = order + nb;
-    uint32_t* toff = ntasks + nb;
-    uint32_t* block_tot = toff + nb + 1;
-    uint32_t* block_tot2 = block_tot + scan_blocks_s;
-    uint32_t* idx = block_tot2 + scan_blocks;
-    uint16_t* dig = reinterpret_cast<uint16_t*>(ws + ((head_words + 3) & ~(size_t)3));   // 16-B aligned
-    int range_bits = pl.c - 1;
-    if (range_bits > MSM_RANGE_MAX_BITS) range_bits = MSM_RANGE_MAX_BITS;
-    const dim3 sweep_grid(8u * ((pl.W + 7) / 8) * (pl.B >> range_bits) * MSM_SLICES);
+    const SortWs w = carve_sort_ws(dims, ws);
     // a lone MSM is latency-bound (short chains: G = 2); in a batch the reduction hides under the
     // next MSM and only its work counts (G = 8)
     const bool short_chain = d_table && count == 1;
@@ -1263,7 +1432,6 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     if (stage) { int rc = stage(stage_user, 0); if (rc) return rc; }
   for (size_t it = 0; it < count; ++it) {
     const int par = (int)(it & 1);
-    const Fr* d_scalars = d_scalar_ptrs[it];
     G1Xyzz29* buckets = (G1Xyzz29*)bkbuf[par];
     G1Xyzz29* partial = buckets + nb;
     G1Xyzz29* task_partial = partial + (size_t)pl.W * red_blocks;
@@ -1273,52 +1441,15 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     if (it >= 2) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[par], 0));   // reduce(it-2) must be done with this buffer
     {
         ZkProfScope ps(ctx, "msm_sort");
-        ZK_HIP(ctx, hipMemsetAsync(size_hist, 0, (size_t)(SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX) * 4, ctx->stream));   // size_hist + nmulti + wflag
-        launch_digits(pl.c, dim3((unsigned)((n_pad / 2 + 255) / 256)), ctx->stream, d_scalars, (uint64_t)n, n_pad, dig, wflag);
-        hipLaunchKernelGGL((k_msm_lds_sweep<false>), sweep_grid, dim3(1024), 0, ctx->stream, (const uint16_t*)dig, n_pad, range_bits, pl.B, slice_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)wflag, (uint32_t)pl.W);
-        ZK_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_s), dim3(SCAN_T), 0, ctx->stream, (const uint32_t*)slice_counts, nb * MSM_SLICES, slice_off, block_tot);
-        hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, ctx->stream, block_tot, scan_blocks_s, slice_off, nb * MSM_SLICES, offsets + nb);
-        hipLaunchKernelGGL(k_scan_u32_c, dim3(scan_blocks_s), dim3(SCAN_T), 0, ctx->stream, (const uint32_t*)slice_counts, nb, slice_off, (const uint32_t*)block_tot, offsets, counts, size_hist);
-        hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, ctx->stream, size_hist, (const uint32_t*)(offsets + nb));
-        hipLaunchKernelGGL(k_order_buckets, dim3(scan_blocks), dim3(SCAN_T), 0, ctx->stream, (const uint32_t*)counts, nb, size_hist, order, ntasks);
-        hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks), dim3(SCAN_T), 0, ctx->stream, (const uint32_t*)ntasks, nb, toff, block_tot2);
-        hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, ctx->stream, block_tot2, scan_blocks, toff, nb, (uint32_t*)nullptr);
-        hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks), dim3(SCAN_T), 0, ctx->stream, nb, toff, (const uint32_t*)block_tot2);
-        ZK_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL((k_msm_lds_sweep<true>), sweep_grid, dim3(1024), 0, ctx->stream, (const uint16_t*)dig, n_pad, range_bits, pl.B, (uint32_t*)nullptr, (const uint32_t*)slice_off, idx, (const uint32_t*)wflag, (uint32_t)pl.W);
-        ZK_CHECK_LAUNCH(ctx);
+        PK_TRY_MSM(sort_digits(ctx, ctx->stream, w, pl, d_scalar_ptrs + it, 1, (uint64_t)n, n_pad, nullptr, nullptr));
     }
-    ZK_HIP(ctx, hipMemcpyAsync(wflag_it, wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    {
-        ZkProfScope ps(ctx, "msm_buckets");
-        // multi-task buckets first (they are the long poles), then one lane per ordinary bucket
-        hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((max_tasks + 255) / 256)), dim3(256), 0, ctx->stream, d_bases_rp, (const uint32_t*)offsets, (const uint32_t*)idx,
-                           (const uint32_t*)order, (const uint32_t*)toff, (const uint32_t*)nmulti, nb, buckets, task_partial, pl.c - 1, (uint64_t)tab_stride, (const uint32_t*)wflag);
-    }
-    {
-        ZkProfScope ps(ctx, "msm_combine");
-        hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((max_tasks + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)nmulti, (const uint32_t*)toff, task_partial);
-        hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nb + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)nmulti, (const uint32_t*)order,
-                           (const uint32_t*)ntasks, (const uint32_t*)toff, (const G1Xyzz29*)task_partial, buckets);
-        hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)nmulti, (const uint32_t*)order,
-                           (const uint32_t*)ntasks, (const uint32_t*)toff, (const G1Xyzz29*)task_partial, buckets);
-        ZK_CHECK_LAUNCH(ctx);
-    }
+    ZK_HIP(ctx, hipMemcpyAsync(wflag_it, w.wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets", d_bases_rp, w, nb, max_tasks, buckets, task_partial, pl.c - 1, (uint64_t)tab_stride, w.wflag, 0, 0));
     ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
     ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_p1[par], 0));
     {   // latency-bound tail on the side stream: it hides under the next MSM's phase 1
         ZkProfScope ps(ctx, "msm_reduce", ctx->stream2);
-        const G1Xyzz29* red_in = buckets;
-        if (d_table) {
-            hipLaunchKernelGGL(k_msm_fold_windows, dim3((pl.B + 63) / 64), dim3(256), 0, ctx->stream2, (const G1Xyzz29*)buckets, pl.B, pl.W, folded, (const uint32_t*)wflag_it);
-            red_in = folded;
-        }
-        if (short_chain) hipLaunchKernelGGL((k_msm_reduce<RED_G_FOLDED>), dim3(red_blocks, red_W), dim3(RED_THREADS), 0, ctx->stream2, red_in, pl.B, partial);
-        else hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(red_blocks, red_W), dim3(RED_THREADS), 0, ctx->stream2, red_in, pl.B, partial);
-        ZK_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_msm_window_sum, dim3(red_W), dim3(RED_THREADS), 0, ctx->stream2, (const G1Xyzz29*)partial, red_blocks, wsum);
-        ZK_CHECK_LAUNCH(ctx);
+        PK_TRY_MSM(reduce_window(ctx, ctx->stream2, buckets, pl.B, d_table ? pl.W : 0, folded, wflag_it, (uint32_t)red_W, 1, short_chain, partial, wsum, nullptr, nullptr, 0));
     }
     ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], ctx->stream2));
     if (stage && it + 1 < count) { int rc = stage(stage_user, it + 1); if (rc) return rc; }
@@ -1332,7 +1463,6 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     for (size_t it = 0; it < count; ++it) host::msm_tail(hw.data() + it * pl.W, red_W, pl.c, h_out + it);
     return ZK_OK;
 }
-#define PK_TRY_MSM(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
 // Blinded tails.  A witness column of small values ends in a few rows of field-sized blinding values (halo2: the last
 // blinding_factors + 1 rows); inside the main MSM they would put a handful of entries into EVERY window and undo what the
 // per-window path gains by skipping empty ones (2^18 bit columns: 0.34 instead of 0.21 ms).  They are committed here instead:
@@ -1374,11 +1504,11 @@ __global__ void __launch_bounds__(1024) k_msm_tails(const Fr* const* __restrict_
     }
 }
 // ---- merged-window MSM over an SRS window table ----------------------------------------------------
-static MsmPlan make_plan_merged(uint32_t k_srs) {
+static MsmPlan make_plan_merged(uint32_t k_srs, const MsmKnobs& kn) {
     int c = (int)k_srs;
     if (c < MSM_M_MIN_C) c = MSM_M_MIN_C;
     if (c > MSM_M_MAX_C) c = MSM_M_MAX_C;
-    if (const char* e = getenv("ZK_MSM_C")) { const int v = atoi(e); if (v >= MSM_M_MIN_C && v <= MSM_M_MAX_C) c = v; }   // measurement knob
+    if (kn.c >= MSM_M_MIN_C && kn.c <= MSM_M_MAX_C) c = kn.c;   // measurement knob
     MsmPlan p;
     p.c = c;
     p.W = (256 + c - 1) / c;
@@ -1398,7 +1528,7 @@ static MsmPlan make_plan_merged(uint32_t k_srs) {
     }
     p.top_shift = 0;
     while (p.top_shift + 1 <= c - 1 && (top_max << (p.top_shift + 1)) <= (1ull << (c - 1))) ++p.top_shift;
-    if (const char* e = getenv("ZK_MSM_TOP_SHIFT")) { const int v = atoi(e); if (v >= 0 && v <= p.top_shift) p.top_shift = v; }   // measurement knob
+    if (kn.top_shift >= 0 && kn.top_shift <= p.top_shift) p.top_shift = kn.top_shift;   // measurement knob
     return p;
 }
 template <bool SCATTER>
@@ -1432,15 +1562,62 @@ static int launch_scatter_staged(zk_ctx* ctx, int c, int W, dim3 grid, const Fr*
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
+// Counting sort inside every partition of scattered entries, then the task split.  binsort: one launch (bucket offsets,
+// counts, size histogram, sorted table indices); otherwise the sliced count / scan / scatter sequence, four
+// slice-workgroups per partition.
+static int sort_entries(zk_ctx* ctx, hipStream_t st, const SortWs& w, uint32_t nbins, uint32_t nwg, int range_bits, uint32_t nb, bool binsort) {
+    if (binsort) {
+        hipLaunchKernelGGL(k_msm_m_binsort, dim3(nbins), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwg, range_bits, nb, w.offsets, w.counts, w.size_hist, w.idx);
+        ZK_CHECK_LAUNCH(ctx);
+        return task_split(ctx, st, w, nb);
+    }
+    hipLaunchKernelGGL((k_msm_m_bin<false>), dim3(nbins * MSM_SLICES), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwg, range_bits, w.slice_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    ZK_CHECK_LAUNCH(ctx);
+    PK_TRY_MSM(slice_scan(ctx, st, w, nb));
+    PK_TRY_MSM(task_split(ctx, st, w, nb));
+    hipLaunchKernelGGL((k_msm_m_bin<true>), dim3(nbins * MSM_SLICES), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwg, range_bits, (uint32_t*)nullptr, (const uint32_t*)w.slice_off, w.idx);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// Merged-window sort of one column: partition by the high bucket bits while recoding (histogram, scan, scatter -- direct
+// or with LDS-staged runs), then sort_entries.  The scalars come from `scalars`, or (graph mode) from cols[*ctr].
+static int sort_partitioned(zk_ctx* ctx, hipStream_t st, const SortWs& w, const MsmPlan& pl, const Fr* scalars, uint64_t n, uint64_t tab_stride, int range_bits, uint32_t nwg, bool staged_scatter, bool binsort,
+                            const MsmCol* cols, const uint32_t* ctr) {
+    const uint32_t nbins = pl.B >> range_bits;
+    ZK_HIP(ctx, hipMemsetAsync(w.cleared, 0, (size_t)MSM_CLEARED_WORDS * 4, st));
+    launch_partition<false>(pl.c, dim3(nwg), st, scalars, n, range_bits, w.hist, (const uint32_t*)nullptr, (uint64_t*)nullptr, tab_stride, pl.top_shift, cols, ctr);
+    ZK_CHECK_LAUNCH(ctx);
+    PK_TRY_MSM(exclusive_scan(ctx, st, w.hist, nbins * nwg, w.hist_off, w.block_tot_h));
+    if (staged_scatter) PK_TRY_MSM(launch_scatter_staged(ctx, pl.c, pl.W, dim3(nwg), scalars, n, range_bits, (const uint32_t*)w.hist_off, w.entries, tab_stride, pl.top_shift, cols, ctr, st));
+    else launch_partition<true>(pl.c, dim3(nwg), st, scalars, n, range_bits, (uint32_t*)nullptr, (const uint32_t*)w.hist_off, w.entries, tab_stride, pl.top_shift, cols, ctr);
+    ZK_CHECK_LAUNCH(ctx);
+    return sort_entries(ctx, st, w, nbins, nwg, range_bits, pl.B, binsort);
+}
+// GM sort of a group of `cnt` small-valued columns: per column a histogram and a scatter pass over its scalars into the
+// group's shared partition space (column j owns partitions [j * bpc, (j + 1) * bpc)), then ONE counting sort, size
+// ordering and task split over the cnt * sets * B buckets of the group
+static int sort_gm(zk_ctx* ctx, hipStream_t st, const SortWs& w, const MsmPlan& pl, const Fr* const* scalars, uint32_t cnt, uint64_t n, uint64_t tab_stride, int range_bits, uint32_t nwg, uint32_t bpc, uint32_t sets) {
+    const uint32_t nbins = cnt * bpc;
+    ZK_HIP(ctx, hipMemsetAsync(w.cleared, 0, (size_t)MSM_CLEARED_WORDS * 4, st));
+    GmCols gcols{};
+    for (uint32_t j = 0; j < cnt; ++j) gcols.p[j] = scalars[j];
+    launch_gm_partition<false>(pl.c, dim3(nwg, cnt), st, gcols, n, range_bits, w.hist, (const uint32_t*)nullptr, (uint64_t*)nullptr, tab_stride, bpc, sets - 1);
+    ZK_CHECK_LAUNCH(ctx);
+    PK_TRY_MSM(exclusive_scan(ctx, st, w.hist, nbins * nwg, w.hist_off, w.block_tot_h));
+    launch_gm_partition<true>(pl.c, dim3(nwg, cnt), st, gcols, n, range_bits, (uint32_t*)nullptr, (const uint32_t*)w.hist_off, w.entries, tab_stride, bpc, sets - 1);
+    ZK_CHECK_LAUNCH(ctx);
+    return sort_entries(ctx, st, w, nbins, nwg, range_bits, cnt * sets * pl.B, true);
+}
 // d_table: [W][tab_stride] affine points, table[w][i] = 2^(c w) * P_i in R' form, built for plan `pl`.
 // Same pipelining as msm_batch_tab: the reduction of MSM i runs on the side stream under MSM i + 1.
 // narrow[it] != 0 (with d_table_n, the per-window table of plan pl_n): column `it` is expected to fill
 // only a few windows (witness columns of small values, selectors, lookup multiplicities) and takes the
 // per-window path -- bucket sets of empty windows are never touched there, whereas the merged path
 // always pays for its 2^(c-1) shared buckets.  The two paths alternate freely inside one pipelined batch.
-static thread_local uint32_t tl_gm_group_cap = 0;       // upper bound on the columns of a GM group while a batch is retried with smaller groups (0 = none)
-int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_table, size_t tab_stride, const MsmPlan& pl,
-                     size_t n, G1Affine* h_out, MsmStageFn stage, void* stage_user, const G1Affine* d_table_n = nullptr, const MsmPlan* pl_n = nullptr, const uint8_t* narrow = nullptr) {
+// group_cap != 0: upper bound on the columns of a GM group.  When the sort workspace of the groups does not fit,
+// *smaller_cap receives the next cap to try (see msm_batch_merged) and nothing has been enqueued.
+static int msm_batch_merged_capped(zk_ctx* ctx, const MsmKnobs& kn, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_table, size_t tab_stride, const MsmPlan& pl,
+                                   size_t n, G1Affine* h_out, MsmStageFn stage, void* stage_user, const G1Affine* d_table_n, const MsmPlan* pl_n, const uint8_t* narrow, uint32_t group_cap, uint32_t* smaller_cap) {
     if (count == 0) return ZK_OK;
     if (n == 0) { memset(h_out, 0, sizeof(G1Affine) * count); return ZK_OK; }
     const auto t_batch0 = std::chrono::steady_clock::now();
@@ -1464,18 +1641,15 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
     if (any_narrow) {
         NG = std::min<uint32_t>((uint32_t)GM_MAX_COLS, MSM_WFLAGS / (uint32_t)pn.W);       // sixteen at c = 16: a group's dozen short launches (scans, size bins, task split) cost the same for eight
                                                                                             // columns or sixteen -- 60/30/10 columns 0.265 -> 0.255 ms each in a batch, the sort 0.81 ms per eight -> 1.45 per sixteen
-        if (const char* e = getenv("ZK_MSM_NARROW_GROUP")) { const int v = atoi(e); if (v >= 1 && v <= GM_MAX_COLS) NG = std::min<uint32_t>((uint32_t)v, MSM_WFLAGS / (uint32_t)pn.W); }
-        if (const char* e = getenv("ZK_MSM_SORT_AHEAD")) if (atoi(e) == 1) NG = 1;
-        if (tl_gm_group_cap && NG > tl_gm_group_cap) NG = tl_gm_group_cap;            // a retry after the group's sort workspace did not fit (below)
+        if (kn.narrow_group >= 1 && kn.narrow_group <= GM_MAX_COLS) NG = std::min<uint32_t>((uint32_t)kn.narrow_group, MSM_WFLAGS / (uint32_t)pn.W);
+        if (group_cap && NG > group_cap) NG = group_cap;
         while (NG > 1 && (uint64_t)n * pn.W * NG >= (1ull << 32)) --NG;
         if (NG < 1) NG = 1;
     }
     const uint32_t Wg = (uint32_t)pn.W * NG;
     const uint32_t nbN = Wg * pn.B;
-    const uint32_t scan_blocks_N = (nbN + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS), scan_blocks_sN = (nbN + SCAN_T - 1) / SCAN_T;
     const uint64_t n_pad = ((uint64_t)n + 16 * MSM_SLICES - 1) & ~(uint64_t)(16 * MSM_SLICES - 1);
-    const size_t dig_words = (size_t)(n_pad * Wg + 1) / 2 + 4;
-    const size_t head_words_N = (size_t)nbN * (2 * MSM_SLICES + 5) + 4 + 2 + SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX + (size_t)scan_blocks_sN + scan_blocks_N + (size_t)n * Wg;
+    const SortDims dims_N{nbN, true, 0, (uint64_t)n * Wg, (size_t)(n_pad * Wg + 1) / 2 + 4, false};
     // Groups of small-valued columns, sorted like the merged path ("GM"; ZK_MSM_NARROW_GM=0 keeps the digit matrix + LDS sweeps):
     // the digit matrix of a group is 16 x n codes per column of which a witness-like column fills a tenth, and every row of it
     // was streamed by sixteen range workgroups, twice -- 0.22 ms of sort per column for 0.12 ms of accumulation.  Here the non-zero
@@ -1483,29 +1657,20 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
     // column needs ONE set of 2^(c-1) buckets, not one per window -- and go through the merged path's partition / one-launch
     // counting sort: column j of the group owns partitions [j * bpc, (j + 1) * bpc) and buckets [j B, (j + 1) B); the fold of the
     // windows disappears (the accumulation already sums them), reduction and window sum run per column as before.
-    const bool gm = any_narrow && pn.c >= MSM_M_MIN_C && pn.c <= 16 && NG <= (uint32_t)GM_MAX_COLS && !(getenv("ZK_MSM_NARROW_GM") && atoi(getenv("ZK_MSM_NARROW_GM")) == 0);
+    const bool gm = any_narrow && pn.c >= MSM_M_MIN_C && pn.c <= 16 && NG <= (uint32_t)GM_MAX_COLS && kn.narrow_gm != 0;
     // A column's windows are dealt over SG bucket sets (window w -> set w mod SG): a witness-like column (10 % field-sized cells) puts
     // ~2 M entries into its buckets -- 61 per bucket with one set of 2^15, every bucket split into two unequal tasks and put together
     // again afterwards (accumulation + combination 2.2 ms per group of eight against the 1.0 ms the additions cost); with two sets
     // the buckets hold 26-35 entries, one task each.  ZK_MSM_GM_SETS = 1 / 2 / 4 (measurement knob).
     uint32_t SG = 2;
-    if (const char* e = getenv("ZK_MSM_GM_SETS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) SG = (uint32_t)v; }
+    if (kn.gm_sets == 1 || kn.gm_sets == 2 || kn.gm_sets == 4) SG = (uint32_t)kn.gm_sets;
     int range_bits_G = pn.c - 1 - 7;                                  // 128 * SG partitions per column of 2^(c-8) buckets each
     if (range_bits_G < 0) range_bits_G = 0;
     const uint32_t bpcG = (SG * pn.B) >> range_bits_G;                // partitions per column
     const uint32_t perm_G = ((uint32_t)range_bits_G << 8) | (uint32_t)(pn.c - 1 - range_bits_G);      // the GM sort numbers buckets low bits first (perm_true)
     const uint32_t nwgG = (uint32_t)((n_narrow + MSM_M_CHUNK - 1) / MSM_M_CHUNK);      // partition workgroups per column
-    const uint32_t nbG = NG * SG * pn.B;
-    const uint64_t entG = (uint64_t)n * pn.W * NG;                    // worst case: every digit of every column non-zero
-    const uint32_t hist_cnt_G = NG * bpcG * nwgG;
-    const uint32_t scan_blocks_G = (nbG + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS), scan_blocks_hG = (hist_cnt_G + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS);
-    // u32 workspace of the GM sort: counts[nbG] | size_hist nmulti wflags done | offsets[nbG + 1] | order[nbG] | ntasks[nbG] | toff[nbG + 1] | block_tot2 | block_tot3 |
-    //                               hist[hist_cnt_G] | hist_off[hist_cnt_G + 1] | idx[entG] | (8-B aligned) entries[entG] u64
-    const size_t head_words_G = (size_t)nbG * 5 + 2 + SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX + scan_blocks_G + scan_blocks_hG + 2 * (size_t)hist_cnt_G + 2 + (size_t)entG;
-    const size_t words_G = gm ? head_words_G + 4 + 2 * (size_t)entG : 0;
-    const size_t words_N = any_narrow ? std::max(head_words_N + 4 + dig_words, words_G) : 0;
-    int range_bits_N = pn.c - 1;
-    if (range_bits_N > MSM_RANGE_MAX_BITS) range_bits_N = MSM_RANGE_MAX_BITS;
+    const SortDims dims_G{NG * SG * pn.B, false, NG * bpcG * nwgG, (uint64_t)n * pn.W * NG, 0, true};      // entries, worst case: every digit of every column non-zero
+    const size_t words_N = any_narrow ? std::max(carve_sort_ws(dims_N, nullptr).words, gm ? carve_sort_ws(dims_G, nullptr).words : 0) : 0;
     const uint32_t red_blocks_N = ((pn.B + RED_G_WIDE - 1) / RED_G_WIDE + RED_THREADS - 1) / RED_THREADS;
     const size_t max_tasks_N = (size_t)nbN + std::max(((size_t)n * Wg) / TASK_CAP, (size_t)TASK_TARGET) + 1;
     const size_t npts29_N = any_narrow ? (size_t)nbN + (size_t)red_blocks_N * NG * 4 + max_tasks_N + (size_t)pn.B * NG : 0;      // x 4: the GM path reduces up to four bucket sets per column
@@ -1517,8 +1682,7 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
     if (range_bits > MSM_RANGE_MAX_BITS) range_bits = MSM_RANGE_MAX_BITS;
     // one-launch partition sort (k_msm_m_binsort) when 1024 partitions are small enough for its LDS staging buffer;
     // ZK_MSM_BINSORT=0 keeps the sliced count / scan / scatter sequence (measurement knob)
-    const char* env_bs = getenv("ZK_MSM_BINSORT");
-    bool binsort = !(env_bs && atoi(env_bs) == 0);
+    bool binsort = kn.binsort != 0;
     if (binsort) {
         int rb = pl.c - 1 - 10;
         if (rb < 0) rb = 0;
@@ -1526,60 +1690,32 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
         if (per_partition + per_partition / 8 <= MSM_M_STAGE) range_bits = rb;
         else binsort = false;
     }
-    const uint32_t nbins = nb >> range_bits;
     uint32_t chunk = MSM_M_CHUNK;
-    if (const char* e = getenv("ZK_MSM_CHUNK")) { const int v = atoi(e); if (v >= 256 && v <= 65536) chunk = (uint32_t)v; }   // measurement knob
+    if (kn.chunk >= 256 && kn.chunk <= 65536) chunk = (uint32_t)kn.chunk;   // measurement knob
     // scatter with LDS-staged runs (k_msm_m_scatter_staged): window sizes whose 1024 x W entries fit the LDS, and only next to the
     // one-launch partition sort (same 1024-partition layout); ZK_MSM_STAGED=0 keeps the direct scatter (measurement knob)
-    const char* env_ss = getenv("ZK_MSM_STAGED");
-    const bool staged_scatter = binsort && pl.c >= 19 && scatter_staged_lds(pl.W) <= (size_t)150 * 1024 && !(env_ss && atoi(env_ss) == 0);
+    const bool staged_scatter = binsort && pl.c >= 19 && scatter_staged_lds(pl.W) <= (size_t)150 * 1024 && kn.staged != 0;
     if (staged_scatter) chunk = MSM_M_SCHUNK;
     const uint32_t nwg = (uint32_t)((n + chunk - 1) / chunk);
-    const uint32_t hist_cnt = nbins * nwg;
-    const uint32_t scan_blocks = (nb + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS);
-    const uint32_t scan_blocks_s = (nb + SCAN_T - 1) / SCAN_T;
-    const uint32_t scan_blocks_h = (hist_cnt + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS);
-    // u32 workspace: slice_counts[4 nb] | slice_off[4 nb + 4] | counts[nb] | size_hist[256] nmulti[4] pad[64] | offsets[nb+1] | order[nb] |
-    //                ntasks[nb] | toff[nb+1] | block_tot[...] | hist[hist_cnt] | hist_off[hist_cnt + 1] | idx[n W] | (8-B aligned) entries[n W] u64
-    const size_t head_words = (size_t)nb * (2 * MSM_SLICES + 5) + 4 + 2 + SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX + (size_t)scan_blocks_s + scan_blocks + scan_blocks_h + 2 * (size_t)hist_cnt + 2 + max_entries;
-    const size_t words = (std::max(head_words + 4 + 2 * max_entries, words_N) + 63) & ~(size_t)63;
+    const SortDims dims_M{nb, true, (nb >> range_bits) * nwg, max_entries, 0, true};
+    const size_t words_M = carve_sort_ws(dims_M, nullptr).words;
+    const size_t words = (std::max(words_M, words_N) + 63) & ~(size_t)63;      // per copy: every copy starts 256-B aligned
     // Below 2^20 points an MSM does not fill the device: its sort / accumulation / combination is a chain of some twenty
     // short launches.  Two such chains then run side by side -- even columns on the context's stream, odd columns on the
     // third side stream, each with its own sort workspace -- and hide each other's latency.  ZK_MSM_PIPES overrides.
     int npipe = (n <= ((size_t)1 << 19) && count >= 2) ? 2 : 1;
-    if (const char* e = getenv("ZK_MSM_PIPES")) { const int v = atoi(e); if (v == 1 || (v == 2 && count >= 2)) npipe = v; }
+    if (kn.pipes == 1 || (kn.pipes == 2 && count >= 2)) npipe = kn.pipes;
     // Graph mode (below): the launch sequence of a column is captured once per pipeline and replayed -- at these sizes the
     // host's launch rate, ~30 API calls per column, is what bounds a batch.  ZK_MSM_GRAPH=0 disables it.
-    const char* env_graph = getenv("ZK_MSM_GRAPH");
-    const bool want_graph = n <= ((size_t)1 << 19) && n >= 1024 && count >= 4 && !ctx->prof_on && !ctx->msm_graph_broken && !(env_graph && atoi(env_graph) == 0) && !(any_narrow && NG > 1);
+    const bool want_graph = n <= ((size_t)1 << 19) && n >= 1024 && count >= 4 && !ctx->prof_on && !ctx->msm_graph_broken && kn.graph != 0 && !(any_narrow && NG > 1);
     constexpr int GP = 4;                     // pipelines of the graph mode: the context's stream and the three side streams
-    const char* env_sa = getenv("ZK_MSM_SORT_AHEAD");
-    const int ws_copies = want_graph ? GP : ((npipe == 2 || (count >= 2 && env_sa && atoi(env_sa) == 1)) ? 2 : 1);
-    uint32_t* ws = (uint32_t*)ctx->get_scratch(SC_MSM_KEYS, words * 4 * ws_copies);
-    if (!ws && any_narrow && NG > 1 && words_N > head_words + 4 + 2 * max_entries) {
-        // the group sort's workspace is sized for the worst case (every digit of all NG columns non-zero: 3 GiB per copy at 2^20 rows and
-        // sixteen columns): with memory short, smaller groups are tried before the batch is given up
-        struct Cap { uint32_t prev; explicit Cap(uint32_t v) : prev(tl_gm_group_cap) { tl_gm_group_cap = v; } ~Cap() { tl_gm_group_cap = prev; } } cap(NG / 2);
+    uint32_t* ws = (uint32_t*)ctx->get_scratch(SC_MSM_KEYS, words * 4 * (want_graph ? GP : npipe));      // one copy per pipeline
+    if (!ws && any_narrow && NG > 1 && words_N > words_M) {
         (void)hipGetLastError();
-        return msm_batch_merged(ctx, d_scalar_ptrs, count, d_table, tab_stride, pl, n, h_out, stage, stage_user, d_table_n, pl_n, narrow);
+        *smaller_cap = NG / 2;
+        return ZK_ERR_OOM;
     }
     if (!ws) return ZK_ERR_OOM;
-    uint32_t* slice_counts = ws;
-    uint32_t* slice_off = slice_counts + (size_t)nb * MSM_SLICES;
-    uint32_t* counts = slice_off + (size_t)nb * MSM_SLICES + 4;
-    uint32_t* size_hist = counts + nb;
-    uint32_t* nmulti = size_hist + SIZE_BINS;
-    uint32_t* offsets = nmulti + 4 + MSM_WFLAGS + TASK_DONE_MAX;
-    uint32_t* order = offsets + nb + 1;
-    uint32_t* ntasks = order + nb;
-    uint32_t* toff = ntasks + nb;
-    uint32_t* block_tot = toff + nb + 1;
-    uint32_t* block_tot2 = block_tot + scan_blocks_s;
-    uint32_t* block_tot3 = block_tot2 + scan_blocks;
-    uint32_t* hist = block_tot3 + scan_blocks_h;
-    uint32_t* hist_off = hist + hist_cnt;
-    uint32_t* idx = hist_off + hist_cnt + 1;
-    uint64_t* entries = reinterpret_cast<uint64_t*>(ws + ((head_words + 3) & ~(size_t)3));
     const uint32_t red_pts = nb / 4 + 1024;       // scratch of the weighted bucket sum (group sums of every level, partials)
     const size_t max_tasks = (size_t)nb + std::max((size_t)(max_entries / TASK_CAP), (size_t)TASK_TARGET) + 1;
     const size_t npts29 = std::max((size_t)nb + red_pts + max_tasks, npts29_N);
@@ -1619,6 +1755,25 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
         ZK_CHECK_LAUNCH(ctx);
         return ZK_OK;
     };
+    // the batch is enqueued: one download of the window sums (and tails) behind everything on the context's stream, host tails
+    auto finish = [&](const char* how) -> int {
+        PK_TRY_MSM(enqueue_tails());
+        std::vector<G1Xyzz> hw(count), ht(tail_rows ? count : 0);
+        if (tail_rows) ZK_HIP(ctx, hipMemcpyAsync(ht.data(), tails_dev, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
+        ZK_HIP(ctx, hipMemcpyAsync(hw.data(), wsum_all, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
+        const auto t_enq = std::chrono::steady_clock::now();
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (kn.trace) {
+            const auto t_done = std::chrono::steady_clock::now();
+            fprintf(stderr, "[zk msm] batch of %zu x 2^%.0f%s: host enqueue %.3f ms, device drained %.3f ms later\n", count, log2((double)n), how,
+                    std::chrono::duration<double, std::milli>(t_enq - t_batch0).count(), std::chrono::duration<double, std::milli>(t_done - t_enq).count());
+        }
+        for (size_t it = 0; it < count; ++it) {
+            if (tail_rows && narrow[it] == 1) host::msm_tail2(hw.data() + it, ht.data() + it, h_out + it);
+            else host::msm_tail(hw.data() + it, 1, pl.c, h_out + it);
+        }
+        return ZK_OK;
+    };
     if (want_graph) {
         // ---- graph mode: GP linear pipelines, column it on pipeline it % GP (stream, sort workspace and bucket buffer of its own;
         // the reduction runs on the same stream: one launch, short chain), one hipGraphLaunch per column.
@@ -1639,110 +1794,29 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
         ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, P[0]));
         for (int p = 1; p < GP; ++p) ZK_HIP(ctx, hipStreamWaitEvent(P[p], ctx->ev_pipe, 0));
         struct StreamRestoreG { zk_ctx* c; hipStream_t s; ~StreamRestoreG() { c->stream = s; } } restore_g{ctx, ctx->stream};
-        // the launch sequence of one column of `kind` on pipeline p, enqueued on ctx->stream (being captured)
+        // the launch sequence of one column of `kind` on pipeline p, enqueued on ctx->stream (being captured): the stage functions
+        // of the plain path as one linear chain, the column read through (cols_dev, ctr_dev + p); groups are off here (NG == 1)
         auto enqueue = [&](int kind, int p) -> int {
             hipStream_t st = ctx->stream;
-            uint32_t* wsb = ws + (size_t)p * words;
             G1Xyzz29* buckets = (G1Xyzz29*)bk[p];
-            const uint32_t* ctr = ctr_dev + p;
+            uint32_t* ctr = ctr_dev + p;
             if (kind == 0) {           // per-window path over the narrow table
-                uint32_t* slice_countsN = wsb;
-                uint32_t* slice_offN = slice_countsN + (size_t)nbN * MSM_SLICES;
-                uint32_t* countsN = slice_offN + (size_t)nbN * MSM_SLICES + 4;
-                uint32_t* size_histN = countsN + nbN;
-                uint32_t* nmultiN = size_histN + SIZE_BINS;
-                uint32_t* wflag = nmultiN + 4;
-                uint32_t* offsetsN = wflag + MSM_WFLAGS + TASK_DONE_MAX;
-                uint32_t* orderN = offsetsN + nbN + 1;
-                uint32_t* ntasksN = orderN + nbN;
-                uint32_t* toffN = ntasksN + nbN;
-                uint32_t* block_totN = toffN + nbN + 1;
-                uint32_t* block_tot2N = block_totN + scan_blocks_sN;
-                uint32_t* idxN = block_tot2N + scan_blocks_N;
-                uint16_t* dig = reinterpret_cast<uint16_t*>(wsb + ((head_words_N + 3) & ~(size_t)3));
+                const SortWs w = carve_sort_ws(dims_N, ws + (size_t)p * words);
                 G1Xyzz29* partialN = buckets + nbN;
                 G1Xyzz29* task_partialN = partialN + (size_t)red_blocks_N * NG;
                 G1Xyzz29* folded = task_partialN + max_tasks_N;
-                const dim3 sweep_grid(8u * ((pn.W + 7) / 8) * (pn.B >> range_bits_N) * MSM_SLICES);
-                ZK_HIP(ctx, hipMemsetAsync(size_histN, 0, (size_t)(SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX) * 4, st));
-                launch_digits(pn.c, dim3((unsigned)((n_pad / 2 + 255) / 256)), st, (const Fr*)nullptr, n_narrow, n_pad, dig, wflag, cols_dev, ctr);
-                hipLaunchKernelGGL((k_msm_lds_sweep<false>), sweep_grid, dim3(1024), 0, st, (const uint16_t*)dig, n_pad, range_bits_N, pn.B, slice_countsN, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)wflag, (uint32_t)pn.W);
-                hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_sN), dim3(SCAN_T), 0, st, (const uint32_t*)slice_countsN, nbN * MSM_SLICES, slice_offN, block_totN);
-                hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, block_totN, scan_blocks_sN, slice_offN, nbN * MSM_SLICES, offsetsN + nbN);
-                hipLaunchKernelGGL(k_scan_u32_c, dim3(scan_blocks_sN), dim3(SCAN_T), 0, st, (const uint32_t*)slice_countsN, nbN, slice_offN, (const uint32_t*)block_totN, offsetsN, countsN, size_histN);
-                hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, st, size_histN, (const uint32_t*)(offsetsN + nbN));
-                hipLaunchKernelGGL(k_order_buckets, dim3(scan_blocks_N), dim3(SCAN_T), 0, st, (const uint32_t*)countsN, nbN, size_histN, orderN, ntasksN);
-                hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_N), dim3(SCAN_T), 0, st, (const uint32_t*)ntasksN, nbN, toffN, block_tot2N);
-                hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, block_tot2N, scan_blocks_N, toffN, nbN, (uint32_t*)nullptr);
-                hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks_N), dim3(SCAN_T), 0, st, nbN, toffN, (const uint32_t*)block_tot2N);
-                hipLaunchKernelGGL((k_msm_lds_sweep<true>), sweep_grid, dim3(1024), 0, st, (const uint16_t*)dig, n_pad, range_bits_N, pn.B, (uint32_t*)nullptr, (const uint32_t*)slice_offN, idxN, (const uint32_t*)wflag, (uint32_t)pn.W);
-                hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((max_tasks_N + 255) / 256)), dim3(256), 0, st, d_table_n, (const uint32_t*)offsetsN, (const uint32_t*)idxN,
-                                   (const uint32_t*)orderN, (const uint32_t*)toffN, (const uint32_t*)nmultiN, nbN, buckets, task_partialN, pn.c - 1, (uint64_t)tab_stride, (const uint32_t*)wflag);
-                hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((max_tasks_N + 255) / 256)), dim3(256), 0, st, (const uint32_t*)nmultiN, (const uint32_t*)toffN, task_partialN);
-                hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nbN + 255) / 256)), dim3(256), 0, st, (const uint32_t*)nmultiN, (const uint32_t*)orderN,
-                                   (const uint32_t*)ntasksN, (const uint32_t*)toffN, (const G1Xyzz29*)task_partialN, buckets);
-                hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, st, (const uint32_t*)nmultiN, (const uint32_t*)orderN,
-                                   (const uint32_t*)ntasksN, (const uint32_t*)toffN, (const G1Xyzz29*)task_partialN, buckets);
+                PK_TRY_MSM(sort_digits(ctx, st, w, pn, nullptr, 1, n_narrow, n_pad, cols_dev, ctr));
+                PK_TRY_MSM(accumulate_combine(ctx, st, "msm_buckets_narrow", d_table_n, w, nbN, max_tasks_N, buckets, task_partialN, pn.c - 1, (uint64_t)tab_stride, w.wflag, 0, 0));
                 // the window flags are still this column's when the fold reads them: the next column of this pipeline comes behind it on the same stream
-                hipLaunchKernelGGL(k_msm_fold_windows, dim3((pn.B + 63) / 64), dim3(256), 0, st, (const G1Xyzz29*)buckets, pn.B, pn.W, folded, (const uint32_t*)wflag);
-                hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(red_blocks_N, 1), dim3(RED_THREADS), 0, st, (const G1Xyzz29*)folded, pn.B, partialN);
-                hipLaunchKernelGGL(k_msm_window_sum, dim3(1), dim3(RED_THREADS), 0, st, (const G1Xyzz29*)partialN, red_blocks_N, (G1Xyzz*)nullptr, cols_dev, ctr_dev + p, (uint32_t)GP);
-                ZK_CHECK_LAUNCH(ctx);
-                return ZK_OK;
+                return reduce_window(ctx, st, buckets, pn.B, pn.W, folded, w.wflag, 1, 1, false, partialN, nullptr, cols_dev, ctr, (uint32_t)GP);
             }
             // merged-window path (kind 1: one-launch partition sort, kind 2: sliced sort)
-            uint32_t* slice_counts = wsb;
-            uint32_t* slice_off = slice_counts + (size_t)nb * MSM_SLICES;
-            uint32_t* counts = slice_off + (size_t)nb * MSM_SLICES + 4;
-            uint32_t* size_hist = counts + nb;
-            uint32_t* nmulti = size_hist + SIZE_BINS;
-            uint32_t* offsets = nmulti + 4 + MSM_WFLAGS + TASK_DONE_MAX;
-            uint32_t* order = offsets + nb + 1;
-            uint32_t* ntasks = order + nb;
-            uint32_t* toff = ntasks + nb;
-            uint32_t* block_tot = toff + nb + 1;
-            uint32_t* block_tot2 = block_tot + scan_blocks_s;
-            uint32_t* block_tot3 = block_tot2 + scan_blocks;
-            uint32_t* hist = block_tot3 + scan_blocks_h;
-            uint32_t* hist_off = hist + hist_cnt;
-            uint32_t* idx = hist_off + hist_cnt + 1;
-            uint64_t* entries = reinterpret_cast<uint64_t*>(wsb + ((head_words + 3) & ~(size_t)3));
+            const SortWs w = carve_sort_ws(dims_M, ws + (size_t)p * words);
             G1Xyzz29* partial = buckets + nb;
             G1Xyzz29* task_partial = partial + red_pts;
-            const bool bs_it = kind == 1;
-            ZK_HIP(ctx, hipMemsetAsync(size_hist, 0, (size_t)(SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX) * 4, st));
-            launch_partition<false>(pl.c, dim3(nwg), st, (const Fr*)nullptr, (uint64_t)n, range_bits, hist, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)tab_stride, pl.top_shift, cols_dev, ctr);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_h), dim3(SCAN_T), 0, st, (const uint32_t*)hist, hist_cnt, hist_off, block_tot3);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, block_tot3, scan_blocks_h, hist_off, hist_cnt, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks_h), dim3(SCAN_T), 0, st, hist_cnt, hist_off, (const uint32_t*)block_tot3);
-            if (staged_scatter) PK_TRY_MSM(launch_scatter_staged(ctx, pl.c, pl.W, dim3(nwg), (const Fr*)nullptr, (uint64_t)n, range_bits, (const uint32_t*)hist_off, entries, (uint64_t)tab_stride, pl.top_shift, cols_dev, ctr));
-            else launch_partition<true>(pl.c, dim3(nwg), st, (const Fr*)nullptr, (uint64_t)n, range_bits, (uint32_t*)nullptr, (const uint32_t*)hist_off, entries, (uint64_t)tab_stride, pl.top_shift, cols_dev, ctr);
-            if (bs_it) {
-                hipLaunchKernelGGL(k_msm_m_binsort, dim3(nbins), dim3(1024), 0, st, (const uint64_t*)entries, (const uint32_t*)hist_off, nwg, range_bits, nb, offsets, counts, size_hist, idx);
-            } else {
-                hipLaunchKernelGGL((k_msm_m_bin<false>), dim3(nbins * MSM_SLICES), dim3(1024), 0, st, (const uint64_t*)entries, (const uint32_t*)hist_off, nwg, range_bits, slice_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-                hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_s), dim3(SCAN_T), 0, st, (const uint32_t*)slice_counts, nb * MSM_SLICES, slice_off, block_tot);
-                hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, block_tot, scan_blocks_s, slice_off, nb * MSM_SLICES, offsets + nb);
-                hipLaunchKernelGGL(k_scan_u32_c, dim3(scan_blocks_s), dim3(SCAN_T), 0, st, (const uint32_t*)slice_counts, nb, slice_off, (const uint32_t*)block_tot, offsets, counts, size_hist);
-            }
-            hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, st, size_hist, (const uint32_t*)(offsets + nb));
-            hipLaunchKernelGGL(k_order_buckets, dim3(scan_blocks), dim3(SCAN_T), 0, st, (const uint32_t*)counts, nb, size_hist, order, ntasks);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks), dim3(SCAN_T), 0, st, (const uint32_t*)ntasks, nb, toff, block_tot2);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, block_tot2, scan_blocks, toff, nb, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks), dim3(SCAN_T), 0, st, nb, toff, (const uint32_t*)block_tot2);
-            if (!bs_it) hipLaunchKernelGGL((k_msm_m_bin<true>), dim3(nbins * MSM_SLICES), dim3(1024), 0, st, (const uint64_t*)entries, (const uint32_t*)hist_off, nwg, range_bits, (uint32_t*)nullptr, (const uint32_t*)slice_off, idx);
-            hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((max_tasks + 255) / 256)), dim3(256), 0, st, d_table, (const uint32_t*)offsets, (const uint32_t*)idx,
-                               (const uint32_t*)order, (const uint32_t*)toff, (const uint32_t*)nmulti, nb, buckets, task_partial, 0, (uint64_t)0, (const uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((max_tasks + 255) / 256)), dim3(256), 0, st, (const uint32_t*)nmulti, (const uint32_t*)toff, task_partial);
-            hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nb + 255) / 256)), dim3(256), 0, st, (const uint32_t*)nmulti, (const uint32_t*)order,
-                               (const uint32_t*)ntasks, (const uint32_t*)toff, (const G1Xyzz29*)task_partial, buckets);
-            hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, st, (const uint32_t*)nmulti, (const uint32_t*)order,
-                               (const uint32_t*)ntasks, (const uint32_t*)toff, (const G1Xyzz29*)task_partial, buckets);
-            const uint32_t rb = ((nb + RED_G_WIDE - 1) / RED_G_WIDE + RED_THREADS - 1) / RED_THREADS;
-            hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(rb, 1), dim3(RED_THREADS), 0, st, (const G1Xyzz29*)buckets, nb, partial);
-            hipLaunchKernelGGL(k_msm_window_sum, dim3(1), dim3(RED_THREADS), 0, st, (const G1Xyzz29*)partial, rb, (G1Xyzz*)nullptr, cols_dev, ctr_dev + p, (uint32_t)GP);
-            ZK_CHECK_LAUNCH(ctx);
-            return ZK_OK;
+            PK_TRY_MSM(sort_partitioned(ctx, st, w, pl, nullptr, (uint64_t)n, (uint64_t)tab_stride, range_bits, nwg, staged_scatter, kind == 1, cols_dev, ctr));
+            PK_TRY_MSM(accumulate_combine(ctx, st, "msm_buckets", d_table, w, nb, max_tasks, buckets, task_partial, 0, 0, nullptr, 0, 0));
+            return reduce_window(ctx, st, buckets, nb, 0, nullptr, nullptr, 1, 1, false, partial, nullptr, cols_dev, ctr, (uint32_t)GP);
         };
         if (stage) { int rc = stage(stage_user, 0); if (rc) return rc; }
         bool fallback = false;
@@ -1750,8 +1824,12 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
             const int p = (int)(it % GP);
             const int kind = (any_narrow && narrow[it] == 1) ? 0 : ((binsort && !(narrow && narrow[it] == 2)) ? 1 : 2);
             ctx->stream = P[p];
-            // a graph is tied to every address and every plan parameter baked into its kernel arguments: ZK_MSM_TOP_SHIFT and
-            // ZK_MSM_CHUNK change the top-window shift and the partition grid without changing any address
+            // A graph is tied to every value baked into a kernel argument or a grid of `enqueue`, and the key holds them all.  They are
+            // the arguments of the stage functions there: the two plans (c fixes W, B and the sweep's range bits; top_shift apart), both
+            // tables and their stride, n and n_narrow (n_pad, the task bounds), the merged sort's range_bits, nwg and staged scatter
+            // (kind holds binsort), the column table and counters (desc), the bucket buffer, and the workspace: its base, the
+            // stride of a copy and the pipeline give the copy, the dimensions above (functions of the plans, n, range_bits and nwg)
+            // every pointer into it.  ZK_MSM_TOP_SHIFT and ZK_MSM_CHUNK change top_shift and nwg without changing any address.
             const std::vector<uint64_t> key_tuple = {(uint64_t)kind, (uint64_t)p, (uint64_t)n, (uint64_t)pl.c, (uint64_t)pn.c, (uint64_t)(uintptr_t)d_table, (uint64_t)(uintptr_t)d_table_n, (uint64_t)tab_stride,
                                                      (uint64_t)(uintptr_t)ws, (uint64_t)words, (uint64_t)(uintptr_t)bk[p], (uint64_t)(uintptr_t)desc, (uint64_t)staged_scatter, (uint64_t)range_bits, n_narrow,
                                                      (uint64_t)pl.top_shift, (uint64_t)nwg};
@@ -1783,7 +1861,7 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
                 if (graph) (void)hipGraphDestroy(graph);
                 if (!ok) {
                     const hipError_t e = hipGetLastError();
-                    if (getenv("ZK_MSM_TRACE")) fprintf(stderr, "[zk msm] graph capture failed (rc %d, %s): plain launches from now on\n", rc_e, hipGetErrorString(e));
+                    if (kn.trace) fprintf(stderr, "[zk msm] graph capture failed (rc %d, %s): plain launches from now on\n", rc_e, hipGetErrorString(e));
                     ctx->msm_graph_broken = true; fallback = true; break;
                 }
                 ctx->msm_graphs[key] = (void*)exec;
@@ -1791,7 +1869,7 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
             }
             if (hipGraphLaunch(exec, P[p]) != hipSuccess) {
                 const hipError_t e = hipGetLastError();
-                if (getenv("ZK_MSM_TRACE")) fprintf(stderr, "[zk msm] graph replay failed (%s): plain launches from now on\n", hipGetErrorString(e));
+                if (kn.trace) fprintf(stderr, "[zk msm] graph replay failed (%s): plain launches from now on\n", hipGetErrorString(e));
                 ctx->msm_graph_broken = true; fallback = true; break;
             }
             if (stage && it + 1 < count) { ctx->stream = P[(it + 1) % GP]; int rc = stage(stage_user, it + 1); if (rc) return rc; }
@@ -1801,24 +1879,7 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
             ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[p - 1], P[p]));
             ZK_HIP(ctx, hipStreamWaitEvent(P[0], ctx->ev_p2[p - 1], 0));
         }
-        if (!fallback) {
-            PK_TRY_MSM(enqueue_tails());
-            std::vector<G1Xyzz> hw(count), ht(tail_rows ? count : 0);
-            if (tail_rows) ZK_HIP(ctx, hipMemcpyAsync(ht.data(), tails_dev, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
-            ZK_HIP(ctx, hipMemcpyAsync(hw.data(), wsum_all, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
-            const auto t_enq = std::chrono::steady_clock::now();
-            ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (getenv("ZK_MSM_TRACE")) {
-                const auto t_done = std::chrono::steady_clock::now();
-                fprintf(stderr, "[zk msm] batch of %zu x 2^%.0f (graph replay): host enqueue %.3f ms, device drained %.3f ms later\n", count, log2((double)n),
-                        std::chrono::duration<double, std::milli>(t_enq - t_batch0).count(), std::chrono::duration<double, std::milli>(t_done - t_enq).count());
-            }
-            for (size_t it = 0; it < count; ++it) {
-                if (tail_rows && narrow[it] == 1) host::msm_tail2(hw.data() + it, ht.data() + it, h_out + it);
-                else host::msm_tail(hw.data() + it, 1, pl.c, h_out + it);
-            }
-            return ZK_OK;
-        }
+        if (!fallback) return finish(" (graph replay)");
         // capture or replay failed: drain what was launched and take the plain path below for the whole batch (a staging
         // callback is simply asked again: uploading a column twice and redoing its transform are idempotent)
         ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1829,88 +1890,7 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
         ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, mains[0]));
         ZK_HIP(ctx, hipStreamWaitEvent(mains[1], ctx->ev_pipe, 0));
     }
-    // Sort-ahead (one pipeline, >= 2 columns): the sort of MSM it + 1 (recoding, partition, counting sort, task split: a third
-    // of an MSM's time on the main stream, bound by memory and launch latency) runs on the auxiliary stream UNDER the bucket
-    // accumulation of MSM it (bound by integer issue), on the second copy of the sort workspace.  OFF by default
-    // (ZK_MSM_SORT_AHEAD=1 enables): measured in round 3 (profiles/r03_sort_ahead.md) it LOSES 11-15 % -- beside a kernel with
-    // thousands of workgroups pending, the sort's 1024-thread / 104 KiB-LDS workgroups rarely find a CU with room, its dozen
-    // dependent launches stretch from 0.29 to 0.8-1.3 ms, and the accumulation slows by the slots they do get; a
-    // high-priority stream changes nothing.  Kept as a knob because the refactoring it needed (sort / accumulate as separate
-    // steps over workspace slots) is what a future partition-level pipeline would start from.
-    const bool sort_ahead = npipe == 1 && ws_copies == 2;
-    hipStream_t sort_st = nullptr;
-    if (sort_ahead) {
-        if (!ctx->ensure_aux()) return ctx->fail(ZK_ERR_HIP, "could not create the auxiliary stream");
-        sort_st = ctx->stream_aux;
-        for (int i = 0; i < 2; ++i) if (!ctx->ev_sorted[i]) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_sorted[i], hipEventDisableTiming));
-        ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, mains[0]));          // the sorts start behind everything already enqueued on the context's stream
-        ZK_HIP(ctx, hipStreamWaitEvent(sort_st, ctx->ev_pipe, 0));
-    }
-    // the sort workspace of a slot, merged-window layout (see above) and per-window layout
-    struct WsM { uint32_t *slice_counts, *slice_off, *counts, *size_hist, *nmulti, *offsets, *order, *ntasks, *toff, *block_tot, *block_tot2, *block_tot3, *hist, *hist_off, *idx; uint64_t* entries; };
-    struct WsN { uint32_t *slice_counts, *slice_off, *counts, *size_hist, *nmulti, *wflag, *offsets, *order, *ntasks, *toff, *block_tot, *block_tot2, *idx; uint16_t* dig; };
-    auto ws_merged = [&](int slot) {
-        WsM w;
-        uint32_t* wsb = ws + (size_t)slot * words;
-        w.slice_counts = wsb;
-        w.slice_off = w.slice_counts + (size_t)nb * MSM_SLICES;
-        w.counts = w.slice_off + (size_t)nb * MSM_SLICES + 4;
-        w.size_hist = w.counts + nb;
-        w.nmulti = w.size_hist + SIZE_BINS;
-        w.offsets = w.nmulti + 4 + MSM_WFLAGS + TASK_DONE_MAX;
-        w.order = w.offsets + nb + 1;
-        w.ntasks = w.order + nb;
-        w.toff = w.ntasks + nb;
-        w.block_tot = w.toff + nb + 1;
-        w.block_tot2 = w.block_tot + scan_blocks_s;
-        w.block_tot3 = w.block_tot2 + scan_blocks;
-        w.hist = w.block_tot3 + scan_blocks_h;
-        w.hist_off = w.hist + hist_cnt;
-        w.idx = w.hist_off + hist_cnt + 1;
-        w.entries = reinterpret_cast<uint64_t*>(wsb + ((head_words + 3) & ~(size_t)3));
-        return w;
-    };
-    auto ws_narrow = [&](int slot) {
-        WsN w;
-        uint32_t* wsb = ws + (size_t)slot * words;
-        w.slice_counts = wsb;
-        w.slice_off = w.slice_counts + (size_t)nbN * MSM_SLICES;
-        w.counts = w.slice_off + (size_t)nbN * MSM_SLICES + 4;
-        w.size_hist = w.counts + nbN;
-        w.nmulti = w.size_hist + SIZE_BINS;
-        w.wflag = w.nmulti + 4;
-        w.offsets = w.wflag + MSM_WFLAGS + TASK_DONE_MAX;
-        w.order = w.offsets + nbN + 1;
-        w.ntasks = w.order + nbN;
-        w.toff = w.ntasks + nbN;
-        w.block_tot = w.toff + nbN + 1;
-        w.block_tot2 = w.block_tot + scan_blocks_sN;
-        w.idx = w.block_tot2 + scan_blocks_N;
-        w.dig = reinterpret_cast<uint16_t*>(wsb + ((head_words_N + 3) & ~(size_t)3));
-        return w;
-    };
-    struct WsG { uint32_t *counts, *size_hist, *nmulti, *offsets, *order, *ntasks, *toff, *block_tot2, *block_tot3, *hist, *hist_off, *idx; uint64_t* entries; };
-    auto ws_gm = [&](int slot) {
-        WsG w;
-        uint32_t* wsb = ws + (size_t)slot * words;
-        w.counts = wsb;
-        w.size_hist = w.counts + nbG;
-        w.nmulti = w.size_hist + SIZE_BINS;
-        w.offsets = w.nmulti + 4 + MSM_WFLAGS + TASK_DONE_MAX;
-        w.order = w.offsets + nbG + 1;
-        w.ntasks = w.order + nbG;
-        w.toff = w.ntasks + nbG;
-        w.block_tot2 = w.toff + nbG + 1;
-        w.block_tot3 = w.block_tot2 + scan_blocks_G;
-        w.hist = w.block_tot3 + scan_blocks_hG;
-        w.hist_off = w.hist + hist_cnt_G;
-        w.idx = w.hist_off + hist_cnt_G + 1;
-        w.entries = reinterpret_cast<uint64_t*>(wsb + ((head_words_G + 3) & ~(size_t)3));
-        return w;
-    };
-    const dim3 sweep_grid(8u * ((pn.W + 7) / 8) * (pn.B >> range_bits_N) * MSM_SLICES);
     auto is_narrow = [&](size_t it) { return any_narrow && narrow[it] == 1; };
-    // ---- the sort of MSM `it` into workspace `slot`, enqueued on `st`
     // the group of columns column `it` starts: up to NG consecutive small-valued columns, or the column alone
     auto group_of = [&](size_t it) -> size_t {
         if (!is_narrow(it)) return 1;
@@ -1918,239 +1898,66 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
         while (g < NG && it + g < count && is_narrow(it + g)) ++g;
         return g;
     };
-    auto enqueue_sort = [&](size_t it, int slot, hipStream_t st) -> int {
-        const Fr* d_scalars = d_scalar_ptrs[it];
-        ZkProfScope ps(ctx, "msm_sort", st);
-        if (is_narrow(it) && gm) {
-            // GM sort of the group (see above): per column a histogram and a scatter pass over its scalars into the group's shared
-            // partition space, then ONE counting sort, size ordering and task split over the cnt * B buckets of the group
-            const uint32_t cnt = (uint32_t)group_of(it), nbc = cnt * SG * pn.B, nbins_c = cnt * bpcG, hist_c = nbins_c * nwgG;
-            const uint32_t sb = (nbc + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS), sb_h = (hist_c + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS);
-            const WsG w = ws_gm(slot);
-            ZK_HIP(ctx, hipMemsetAsync(w.size_hist, 0, (size_t)(SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX) * 4, st));
-            GmCols gcols{};
-            for (uint32_t j = 0; j < cnt; ++j) gcols.p[j] = d_scalar_ptrs[it + j];
-            launch_gm_partition<false>(pn.c, dim3(nwgG, cnt), st, gcols, n_narrow, range_bits_G, w.hist, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)tab_stride, bpcG, SG - 1);
-            ZK_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(sb_h), dim3(SCAN_T), 0, st, (const uint32_t*)w.hist, hist_c, w.hist_off, w.block_tot3);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot3, sb_h, w.hist_off, hist_c, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_task_offsets, dim3(sb_h), dim3(SCAN_T), 0, st, hist_c, w.hist_off, (const uint32_t*)w.block_tot3);
-            launch_gm_partition<true>(pn.c, dim3(nwgG, cnt), st, gcols, n_narrow, range_bits_G, (uint32_t*)nullptr, (const uint32_t*)w.hist_off, w.entries, (uint64_t)tab_stride, bpcG, SG - 1);
-            ZK_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_msm_m_binsort, dim3(nbins_c), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwgG, range_bits_G, nbc, w.offsets, w.counts, w.size_hist, w.idx);
-            ZK_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, st, w.size_hist, (const uint32_t*)(w.offsets + nbc));
-            hipLaunchKernelGGL(k_order_buckets, dim3(sb), dim3(SCAN_T), 0, st, (const uint32_t*)w.counts, nbc, w.size_hist, w.order, w.ntasks);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(sb), dim3(SCAN_T), 0, st, (const uint32_t*)w.ntasks, nbc, w.toff, w.block_tot2);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot2, sb, w.toff, nbc, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_task_offsets, dim3(sb), dim3(SCAN_T), 0, st, nbc, w.toff, (const uint32_t*)w.block_tot2);
-            ZK_CHECK_LAUNCH(ctx);
-            return ZK_OK;
-        }
-        if (is_narrow(it)) {
-            // per-window path over the narrow table (see msm_batch_tab): digits, LDS-privatised sort with empty windows skipped;
-            // the columns of a group are windows [j W, (j + 1) W) of one sort
-            const uint32_t cnt = (uint32_t)group_of(it), wins = cnt * (uint32_t)pn.W, nbc = wins * pn.B;      // this group's windows and buckets
-            const uint32_t sb_s = (nbc + SCAN_T - 1) / SCAN_T, sb = (nbc + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS);
-            const dim3 grid_sw(8u * ((wins + 7) / 8) * (pn.B >> range_bits_N) * MSM_SLICES);
-            const WsN w = ws_narrow(slot);
-            uint32_t* wflag_it = reinterpret_cast<uint32_t*>(wsum_all + count) + it * MSM_WFLAGS;
-            ZK_HIP(ctx, hipMemsetAsync(w.size_hist, 0, (size_t)(SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX) * 4, st));
-            for (uint32_t j = 0; j < cnt; ++j)
-                launch_digits(pn.c, dim3((unsigned)((n_pad / 2 + 255) / 256)), st, d_scalar_ptrs[it + j], n_narrow, n_pad, w.dig + (size_t)j * pn.W * n_pad, w.wflag + j * pn.W);
-            hipLaunchKernelGGL((k_msm_lds_sweep<false>), grid_sw, dim3(1024), 0, st, (const uint16_t*)w.dig, n_pad, range_bits_N, pn.B, w.slice_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)w.wflag, wins);
-            ZK_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(sb_s), dim3(SCAN_T), 0, st, (const uint32_t*)w.slice_counts, nbc * MSM_SLICES, w.slice_off, w.block_tot);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot, sb_s, w.slice_off, nbc * MSM_SLICES, w.offsets + nbc);
-            hipLaunchKernelGGL(k_scan_u32_c, dim3(sb_s), dim3(SCAN_T), 0, st, (const uint32_t*)w.slice_counts, nbc, w.slice_off, (const uint32_t*)w.block_tot, w.offsets, w.counts, w.size_hist);
-            hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, st, w.size_hist, (const uint32_t*)(w.offsets + nbc));
-            hipLaunchKernelGGL(k_order_buckets, dim3(sb), dim3(SCAN_T), 0, st, (const uint32_t*)w.counts, nbc, w.size_hist, w.order, w.ntasks);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(sb), dim3(SCAN_T), 0, st, (const uint32_t*)w.ntasks, nbc, w.toff, w.block_tot2);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot2, sb, w.toff, nbc, (uint32_t*)nullptr);
-            hipLaunchKernelGGL(k_task_offsets, dim3(sb), dim3(SCAN_T), 0, st, nbc, w.toff, (const uint32_t*)w.block_tot2);
-            ZK_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL((k_msm_lds_sweep<true>), grid_sw, dim3(1024), 0, st, (const uint16_t*)w.dig, n_pad, range_bits_N, pn.B, (uint32_t*)nullptr, (const uint32_t*)w.slice_off, w.idx, (const uint32_t*)w.wflag, wins);
-            ZK_CHECK_LAUNCH(ctx);
-            ZK_HIP(ctx, hipMemcpyAsync(wflag_it, w.wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            return ZK_OK;
-        }
-        const WsM w = ws_merged(slot);
-        ZK_HIP(ctx, hipMemsetAsync(w.size_hist, 0, (size_t)(SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX) * 4, st));
-        // 1. partition by the high bucket bits while recoding: histogram, scan, scatter
-        launch_partition<false>(pl.c, dim3(nwg), st, d_scalars, (uint64_t)n, range_bits, w.hist, (const uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)tab_stride, pl.top_shift);
-        ZK_CHECK_LAUNCH(ctx);
-        hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_h), dim3(SCAN_T), 0, st, (const uint32_t*)w.hist, hist_cnt, w.hist_off, w.block_tot3);
-        hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot3, scan_blocks_h, w.hist_off, hist_cnt, (uint32_t*)nullptr);
-        hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks_h), dim3(SCAN_T), 0, st, hist_cnt, w.hist_off, (const uint32_t*)w.block_tot3);
-        if (staged_scatter) PK_TRY_MSM(launch_scatter_staged(ctx, pl.c, pl.W, dim3(nwg), d_scalars, (uint64_t)n, range_bits, (const uint32_t*)w.hist_off, w.entries, (uint64_t)tab_stride, pl.top_shift, nullptr, nullptr, st));
-        else launch_partition<true>(pl.c, dim3(nwg), st, d_scalars, (uint64_t)n, range_bits, (uint32_t*)nullptr, (const uint32_t*)w.hist_off, w.entries, (uint64_t)tab_stride, pl.top_shift);
-        ZK_CHECK_LAUNCH(ctx);
-        // 2. counting sort inside every partition, one launch (bucket offsets, counts, size histogram, sorted table indices);
-        //    ZK_MSM_BINSORT=0 keeps the sliced count / scan / scatter sequence (measurement knob)
-        const bool bs_it = binsort && !(narrow && narrow[it] == 2);       // hint 2: long runs of equal scalars (running products) put whole runs into
-                                                                          // one partition; four slice-workgroups per partition stream them faster than one
-        if (bs_it) {
-            hipLaunchKernelGGL(k_msm_m_binsort, dim3(nbins), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwg, range_bits, nb, w.offsets, w.counts, w.size_hist, w.idx);
-            ZK_CHECK_LAUNCH(ctx);
-        } else {
-            hipLaunchKernelGGL((k_msm_m_bin<false>), dim3(nbins * MSM_SLICES), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwg, range_bits, w.slice_counts, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-            ZK_CHECK_LAUNCH(ctx);
-            hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks_s), dim3(SCAN_T), 0, st, (const uint32_t*)w.slice_counts, nb * MSM_SLICES, w.slice_off, w.block_tot);
-            hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot, scan_blocks_s, w.slice_off, nb * MSM_SLICES, w.offsets + nb);
-            hipLaunchKernelGGL(k_scan_u32_c, dim3(scan_blocks_s), dim3(SCAN_T), 0, st, (const uint32_t*)w.slice_counts, nb, w.slice_off, (const uint32_t*)w.block_tot, w.offsets, w.counts, w.size_hist);
-        }
-        hipLaunchKernelGGL(k_size_bins_scan, dim3(1), dim3(64), 0, st, w.size_hist, (const uint32_t*)(w.offsets + nb));
-        hipLaunchKernelGGL(k_order_buckets, dim3(scan_blocks), dim3(SCAN_T), 0, st, (const uint32_t*)w.counts, nb, w.size_hist, w.order, w.ntasks);
-        hipLaunchKernelGGL(k_scan_u32_a, dim3(scan_blocks), dim3(SCAN_T), 0, st, (const uint32_t*)w.ntasks, nb, w.toff, w.block_tot2);
-        hipLaunchKernelGGL(k_scan_u32_b, dim3(1), dim3(SCAN_T), 0, st, w.block_tot2, scan_blocks, w.toff, nb, (uint32_t*)nullptr);
-        hipLaunchKernelGGL(k_task_offsets, dim3(scan_blocks), dim3(SCAN_T), 0, st, nb, w.toff, (const uint32_t*)w.block_tot2);
-        ZK_CHECK_LAUNCH(ctx);
-        if (!bs_it) hipLaunchKernelGGL((k_msm_m_bin<true>), dim3(nbins * MSM_SLICES), dim3(1024), 0, st, (const uint64_t*)w.entries, (const uint32_t*)w.hist_off, nwg, range_bits, (uint32_t*)nullptr, (const uint32_t*)w.slice_off, w.idx);
-        ZK_CHECK_LAUNCH(ctx);
-        return ZK_OK;
-    };
     if (stage) { int rc = stage(stage_user, 0); if (rc) return rc; }
-    if (sort_ahead) {
-        // whatever the staging callback made the context's stream wait for (the upload of column 0) the sort stream must see too
-        ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, mains[0]));
-        ZK_HIP(ctx, hipStreamWaitEvent(sort_st, ctx->ev_pipe, 0));
-        PK_TRY_MSM(enqueue_sort(0, 0, sort_st));
-        ZK_HIP(ctx, hipEventRecord(ctx->ev_sorted[0], sort_st));
-    }
     size_t staged = stage ? 1 : count;            // columns [0, staged) have been handed to the staging callback
     size_t stepno = 0;                            // groups / columns enqueued so far: rotates bucket buffers, side streams, pipelines
     for (size_t it = 0; it < count; ++stepno) {
-        const size_t grp = sort_ahead ? 1 : group_of(it);          // columns this step commits (a group of small-valued columns, or one column)
+        const size_t grp = group_of(it);          // columns this step commits (a group of small-valued columns, or one column)
         const int par = (int)(stepno % 3), pipe = (int)(stepno % (size_t)npipe);
-        const int slot = sort_ahead ? (int)(it & 1) : pipe;
         hipStream_t side = npipe == 2 ? ((stepno & 1) ? ctx->stream2b : ctx->stream2) : (par == 0 ? ctx->stream2 : par == 1 ? ctx->stream2b : ctx->stream2c);
         ctx->stream = mains[pipe];
         for (; staged < it + grp; ++staged) { int rc = stage(stage_user, staged); if (rc) return rc; }      // every column of the group is on its way before its sort is enqueued
+        // the step by kind: a GM group, a per-window group (cnt columns each), or one merged column; its sort workspace is the pipeline's copy
+        const bool nar = is_narrow(it), grouped = nar && gm;
+        const uint32_t cnt = (uint32_t)grp;
+        const uint32_t nbc = grouped ? cnt * SG * pn.B : nar ? cnt * (uint32_t)pn.W * pn.B : nb;
+        const size_t tasks = nar ? (size_t)nbc + std::max(((size_t)n * cnt * pn.W) / TASK_CAP, (size_t)TASK_TARGET) + 1 : max_tasks;
+        const SortWs w = carve_sort_ws(grouped ? dims_G : nar ? dims_N : dims_M, ws + (size_t)pipe * words);
+        uint32_t* wflag_it = reinterpret_cast<uint32_t*>(wsum_all + count) + it * MSM_WFLAGS;
+        // bucket buffer: buckets | partials of the reduction | task partials | (per-window path) the folded windows
         G1Xyzz29* buckets = (G1Xyzz29*)bkbuf[par];
-        if (sort_ahead) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_sorted[slot], 0));
-        else PK_TRY_MSM(enqueue_sort(it, slot, ctx->stream));
+        G1Xyzz29* partial = buckets + (nar ? nbN : nb);
+        G1Xyzz29* task_partial = partial + (grouped ? (size_t)red_blocks_N * NG * 4 : nar ? (size_t)red_blocks_N * NG : red_pts);
+        G1Xyzz29* folded = task_partial + max_tasks_N;
+        {
+            ZkProfScope ps(ctx, "msm_sort");
+            if (grouped) PK_TRY_MSM(sort_gm(ctx, ctx->stream, w, pn, d_scalar_ptrs + it, cnt, n_narrow, (uint64_t)tab_stride, range_bits_G, nwgG, bpcG, SG));
+            else if (nar) {
+                PK_TRY_MSM(sort_digits(ctx, ctx->stream, w, pn, d_scalar_ptrs + it, cnt, n_narrow, n_pad, nullptr, nullptr));
+                ZK_HIP(ctx, hipMemcpyAsync(wflag_it, w.wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            } else {
+                // hint 2: long runs of equal scalars (running products) put whole runs into one partition; four slice-workgroups per
+                // partition stream them faster than one
+                PK_TRY_MSM(sort_partitioned(ctx, ctx->stream, w, pl, d_scalar_ptrs[it], (uint64_t)n, (uint64_t)tab_stride, range_bits, nwg, staged_scatter, binsort && !(narrow && narrow[it] == 2), nullptr, nullptr));
+            }
+        }
         // reduce(step - 3) must be done with this bucket buffer -- but only the accumulation writes it: the sort of this MSM
         // runs while that reduction finishes
         if (stepno >= 3) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[par], 0));
-        if (is_narrow(it) && gm) {
-            // ---- GM: one bucket set per column, accumulated like a merged MSM (idx holds table indices); reduction and window sum per column
-            const uint32_t cnt = (uint32_t)grp, nbc = cnt * SG * pn.B;
-            const size_t tasks_c = (size_t)nbc + std::max(((size_t)n * cnt * pn.W) / TASK_CAP, (size_t)TASK_TARGET) + 1;
-            const WsG w = ws_gm(slot);
-            G1Xyzz29* partialN = buckets + nbN;
-            G1Xyzz29* task_partialN = partialN + (size_t)red_blocks_N * NG * 4;
-            {
-                ZkProfScope ps(ctx, "msm_buckets_narrow");
-                hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((tasks_c + 255) / 256)), dim3(256), 0, ctx->stream, d_table_n, (const uint32_t*)w.offsets, (const uint32_t*)w.idx,
-                                   (const uint32_t*)w.order, (const uint32_t*)w.toff, (const uint32_t*)w.nmulti, nbc, buckets, task_partialN, 0, (uint64_t)0, (const uint32_t*)nullptr, 0u, perm_G);
-            }
-            {
-                ZkProfScope ps(ctx, "msm_combine");
-                hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((tasks_c + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.toff, task_partialN);
-                hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nbc + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
-                                   (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partialN, buckets, perm_G);
-                hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
-                                   (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partialN, buckets, perm_G);
-                ZK_CHECK_LAUNCH(ctx);
-            }
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
-            ZK_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_p1[par], 0));
-            {
-                ZkProfScope ps(ctx, "msm_reduce_narrow", side);
-                // the SG sets of a column are SG "windows" of equal weight: reduced separately, their partials summed with the column's
-                hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(red_blocks_N, cnt * SG), dim3(RED_THREADS), 0, side, (const G1Xyzz29*)buckets, pn.B, partialN);
-                ZK_CHECK_LAUNCH(ctx);
-                hipLaunchKernelGGL(k_msm_window_sum, dim3(cnt), dim3(RED_THREADS), 0, side, (const G1Xyzz29*)partialN, red_blocks_N * SG, wsum_all + it);
-                ZK_CHECK_LAUNCH(ctx);
-            }
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], side));
-        } else if (is_narrow(it)) {
-            // ---- per-window path: bucket accumulation, fold of the occupied windows of every column of the group, one window reduced per column
-            const uint32_t cnt = (uint32_t)grp, wins = cnt * (uint32_t)pn.W, nbc = wins * pn.B;
-            const size_t tasks_c = (size_t)nbc + std::max(((size_t)n * wins) / TASK_CAP, (size_t)TASK_TARGET) + 1;
-            const WsN w = ws_narrow(slot);
-            G1Xyzz29* partialN = buckets + nbN;
-            G1Xyzz29* task_partialN = partialN + (size_t)red_blocks_N * NG;
-            G1Xyzz29* folded = task_partialN + max_tasks_N;
-            uint32_t* wflag_it = reinterpret_cast<uint32_t*>(wsum_all + count) + it * MSM_WFLAGS;
-            {
-                ZkProfScope ps(ctx, "msm_buckets_narrow");
-                hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((tasks_c + 255) / 256)), dim3(256), 0, ctx->stream, d_table_n, (const uint32_t*)w.offsets, (const uint32_t*)w.idx,
-                                   (const uint32_t*)w.order, (const uint32_t*)w.toff, (const uint32_t*)w.nmulti, nbc, buckets, task_partialN, pn.c - 1, (uint64_t)tab_stride, (const uint32_t*)wflag_it,
-                                   cnt > 1 ? (uint32_t)pn.W : 0u);
-            }
-            {
-                ZkProfScope ps(ctx, "msm_combine");
-                hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((tasks_c + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.toff, task_partialN);
-                hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nbc + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
-                                   (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partialN, buckets);
-                hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
-                                   (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partialN, buckets);
-                ZK_CHECK_LAUNCH(ctx);
-            }
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
-            ZK_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_p1[par], 0));
-            {
-                ZkProfScope ps(ctx, "msm_reduce_narrow", side);
-                hipLaunchKernelGGL(k_msm_fold_windows, dim3((pn.B + 63) / 64, cnt), dim3(256), 0, side, (const G1Xyzz29*)buckets, pn.B, pn.W, folded, (const uint32_t*)wflag_it);
-                hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(red_blocks_N, cnt), dim3(RED_THREADS), 0, side, (const G1Xyzz29*)folded, pn.B, partialN);
-                ZK_CHECK_LAUNCH(ctx);
-                hipLaunchKernelGGL(k_msm_window_sum, dim3(cnt), dim3(RED_THREADS), 0, side, (const G1Xyzz29*)partialN, red_blocks_N, wsum_all + it);
-                ZK_CHECK_LAUNCH(ctx);
-            }
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], side));
-        } else {
-            const WsM w = ws_merged(slot);
-            G1Xyzz29* partial = buckets + nb;
-            G1Xyzz29* task_partial = partial + red_pts;
-            {
-                ZkProfScope ps(ctx, "msm_buckets");
-                // idx already holds table indices: no window offset, no per-window skip (tab_stride = 0)
-                hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)((max_tasks + 255) / 256)), dim3(256), 0, ctx->stream, d_table, (const uint32_t*)w.offsets, (const uint32_t*)w.idx,
-                                   (const uint32_t*)w.order, (const uint32_t*)w.toff, (const uint32_t*)w.nmulti, nb, buckets, task_partial, 0, (uint64_t)0, (const uint32_t*)nullptr);
-            }
-            {
-                ZkProfScope ps(ctx, "msm_combine");
-                hipLaunchKernelGGL(k_msm_combine_wave, dim3(combine_grid((max_tasks + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.toff, task_partial);
-                hipLaunchKernelGGL(k_msm_combine_small, dim3(combine_grid((nb + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
-                                   (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partial, buckets);
-                hipLaunchKernelGGL(k_msm_combine, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)w.nmulti, (const uint32_t*)w.order,
-                                   (const uint32_t*)w.ntasks, (const uint32_t*)w.toff, (const G1Xyzz29*)task_partial, buckets);
-                ZK_CHECK_LAUNCH(ctx);
-            }
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
-            ZK_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_p1[par], 0));
-            {   // weighted bucket sum on a side stream: hides under the next MSMs
-                ZkProfScope ps(ctx, "msm_reduce", side);
-                if (it + 2 >= count) {
-                    // the caller waits for the reductions of the last two MSMs of a batch (and of a lone one): one launch with a
-                    // scalar multiplication per lane has the shorter dependent chain (about 60 additions against 150 over the
-                    // levels below), at twice the work
-                    const uint32_t rb = ((nb + RED_G_WIDE - 1) / RED_G_WIDE + RED_THREADS - 1) / RED_THREADS;      // <= nb / 2048 + 1 partials: fits red_pts
-                    hipLaunchKernelGGL((k_msm_reduce<RED_G_WIDE>), dim3(rb, 1), dim3(RED_THREADS), 0, side, (const G1Xyzz29*)buckets, nb, partial);
-                    hipLaunchKernelGGL(k_msm_window_sum, dim3(1), dim3(RED_THREADS), 0, side, (const G1Xyzz29*)partial, rb, wsum_all + it);
-                    ZK_CHECK_LAUNCH(ctx);
-                } else {
-                    PK_TRY_MSM(wsum_enqueue(ctx, side, buckets, nb, partial, wsum_all + it));
-                }
-            }
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], side));
+        // GM: one bucket set per column and set, accumulated like a merged MSM (idx holds table indices); per-window: the table window from the bucket
+        if (grouped) PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets_narrow", d_table_n, w, nbc, tasks, buckets, task_partial, 0, 0, nullptr, 0, perm_G));
+        else if (nar) PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets_narrow", d_table_n, w, nbc, tasks, buckets, task_partial, pn.c - 1, (uint64_t)tab_stride, wflag_it, cnt > 1 ? (uint32_t)pn.W : 0u, 0));
+        else PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets", d_table, w, nb, tasks, buckets, task_partial, 0, 0, nullptr, 0, 0));
+        ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
+        ZK_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_p1[par], 0));
+        {   // weighted bucket sum on a side stream: hides under the next MSMs
+            ZkProfScope ps(ctx, nar ? "msm_reduce_narrow" : "msm_reduce", side);
+            // GM: the SG sets of a column are SG "windows" of equal weight: reduced separately, their partials summed with the column's;
+            // per-window: the occupied windows of every column of the group are folded, one window reduced per column
+            if (grouped) PK_TRY_MSM(reduce_window(ctx, side, buckets, pn.B, 0, nullptr, nullptr, cnt, SG, false, partial, wsum_all + it, nullptr, nullptr, 0));
+            else if (nar) PK_TRY_MSM(reduce_window(ctx, side, buckets, pn.B, pn.W, folded, wflag_it, cnt, 1, false, partial, wsum_all + it, nullptr, nullptr, 0));
+            // the caller waits for the reductions of the last two MSMs of a batch (and of a lone one): one launch with a
+            // scalar multiplication per lane has the shorter dependent chain (about 60 additions against 150 over the
+            // levels of wsum_enqueue), at twice the work; its <= nb / 2048 + 1 partials fit red_pts
+            else if (it + 2 >= count) PK_TRY_MSM(reduce_window(ctx, side, buckets, nb, 0, nullptr, nullptr, 1, 1, false, partial, wsum_all + it, nullptr, nullptr, 0));
+            else PK_TRY_MSM(wsum_enqueue(ctx, side, buckets, nb, partial, wsum_all + it));
         }
-        if (it + grp < count) {
-            if (sort_ahead) {
-                // the next column: its staging (upload) is fenced into the sort stream, its sort goes into the other workspace copy,
-                // free once the accumulation + combination of MSM it - 1 (recorded as ev_p1 of that iteration) are through
-                ctx->stream = sort_st;
-                for (; staged < it + 2; ++staged) { int rc = stage(stage_user, staged); if (rc) return rc; }
-                if (it >= 1) ZK_HIP(ctx, hipStreamWaitEvent(sort_st, ctx->ev_p1[(it - 1) % 3], 0));
-                PK_TRY_MSM(enqueue_sort(it + 1, (int)((it + 1) & 1), sort_st));
-                ZK_HIP(ctx, hipEventRecord(ctx->ev_sorted[(it + 1) & 1], sort_st));
-            } else if (stage) {
-                // the columns of the NEXT step start crossing the link now, under this step's accumulation
-                ctx->stream = mains[(stepno + 1) % (size_t)npipe];
-                const size_t upto = it + grp + group_of(it + grp);
-                for (; staged < upto; ++staged) { int rc = stage(stage_user, staged); if (rc) return rc; }
-            }
+        ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], side));
+        if (stage && it + grp < count) {
+            // the columns of the NEXT step start crossing the link now, under this step's accumulation
+            ctx->stream = mains[(stepno + 1) % (size_t)npipe];
+            const size_t upto = it + grp + group_of(it + grp);
+            for (; staged < upto; ++staged) { int rc = stage(stage_user, staged); if (rc) return rc; }
         }
         it += grp;
     }
@@ -2162,22 +1969,19 @@ int msm_batch_merged(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, 
     ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[0], 0));
     if (stepno > 1) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[1], 0));
     if (stepno > 2) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[2], 0));
-    PK_TRY_MSM(enqueue_tails());
-    std::vector<G1Xyzz> hw(count), ht(tail_rows ? count : 0);
-    if (tail_rows) ZK_HIP(ctx, hipMemcpyAsync(ht.data(), tails_dev, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
-    ZK_HIP(ctx, hipMemcpyAsync(hw.data(), wsum_all, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
-    const auto t_enq = std::chrono::steady_clock::now();
-    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (getenv("ZK_MSM_TRACE")) {
-        const auto t_done = std::chrono::steady_clock::now();
-        fprintf(stderr, "[zk msm] batch of %zu x 2^%.0f: host enqueue %.3f ms, device drained %.3f ms later\n", count, log2((double)n),
-                std::chrono::duration<double, std::milli>(t_enq - t_batch0).count(), std::chrono::duration<double, std::milli>(t_done - t_enq).count());
+    return finish("");
+}
+// The sort workspace of a group of small-valued columns is sized for the worst case (every digit of all its columns non-zero:
+// 3 GiB per copy at 2^20 rows and sixteen columns): with memory short, groups of half the size are tried before the batch is
+// given up, down to single columns.
+int msm_batch_merged(zk_ctx* ctx, const MsmKnobs& kn, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_table, size_t tab_stride, const MsmPlan& pl,
+                     size_t n, G1Affine* h_out, MsmStageFn stage, void* stage_user, const G1Affine* d_table_n = nullptr, const MsmPlan* pl_n = nullptr, const uint8_t* narrow = nullptr) {
+    for (uint32_t cap = 0;;) {
+        uint32_t smaller_cap = 0;
+        const int rc = msm_batch_merged_capped(ctx, kn, d_scalar_ptrs, count, d_table, tab_stride, pl, n, h_out, stage, stage_user, d_table_n, pl_n, narrow, cap, &smaller_cap);
+        if (!smaller_cap) return rc;
+        cap = smaller_cap;
     }
-    for (size_t it = 0; it < count; ++it) {
-        if (tail_rows && narrow[it] == 1) host::msm_tail2(hw.data() + it, ht.data() + it, h_out + it);
-        else host::msm_tail(hw.data() + it, 1, pl.c, h_out + it);
-    }
-    return ZK_OK;
 }
 // Per-window table of an SRS basis (plan make_plan(2^k): c = k - 4 <= 16), for the columns that fill
 // few windows; built on first use like the merged one.
@@ -2188,8 +1992,7 @@ static int srs_window_table_narrow(zk_ctx* ctx, const zk_srs* srs, int basis, si
     const MsmPlan pl = make_plan(ns);
     *plan = pl;
     const size_t bytes = sizeof(G1Affine) * ns * pl.W;
-    const char* env = getenv("ZK_MSM_TABLE_GB");
-    const double cap_gb = env ? atof(env) : 32.0;
+    const double cap_gb = read_knobs().table_gb;
     if (n < 1024 || (double)bytes > cap_gb * (double)(1ull << 30)) return ZK_OK;
     if (!s->tabn[basis]) {
         const G1Affine* rp = nullptr;
@@ -2264,14 +2067,15 @@ int msm_batch_srs(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_
     rc = srs_window_table(ctx, srs, basis, n, &tab, &stride);
     if (rc) return rc;
     if (!tab) return msm_batch_tab(ctx, d_scalar_ptrs, count, b, brp, nullptr, 0, n, h_out, stage, stage_user);
+    const MsmKnobs kn = read_knobs();
     std::vector<uint8_t> forced;
-    if (const char* e = getenv("ZK_MSM_NARROW")) { forced.assign(count, (uint8_t)(atoi(e) != 0)); narrow = forced.data(); }
+    if (kn.narrow != KNOB_UNSET) { forced.assign(count, (uint8_t)(kn.narrow != 0)); narrow = forced.data(); }
     bool any = false;
     if (narrow) for (size_t i = 0; i < count; ++i) any |= narrow[i] == 1;
     const G1Affine* tabn = nullptr;
     MsmPlan pln{};
     if (any) { rc = srs_window_table_narrow(ctx, srs, basis, n, &tabn, &pln); if (rc) return rc; }
-    return msm_batch_merged(ctx, d_scalar_ptrs, count, tab, stride, make_plan_merged(srs->k), n, h_out, stage, stage_user, tabn, &pln, narrow);
+    return msm_batch_merged(ctx, kn, d_scalar_ptrs, count, tab, stride, make_plan_merged(srs->k, kn), n, h_out, stage, stage_user, tabn, &pln, narrow);
 }
 int msm_batch_rp(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_bases, const G1Affine* d_bases_rp, size_t n, G1Affine* h_out) {
     return msm_batch_tab(ctx, d_scalar_ptrs, count, d_bases, d_bases_rp, nullptr, 0, n, h_out);
@@ -2283,11 +2087,11 @@ int srs_window_table(zk_ctx* ctx, const zk_srs* srs, int basis, size_t n, const 
     *out = nullptr;
     *stride = 0;
     zk_srs* s = const_cast<zk_srs*>(srs);
-    const MsmPlan pl = make_plan_merged(s->k);
+    const MsmKnobs kn = read_knobs();
+    const MsmPlan pl = make_plan_merged(s->k, kn);
     const uint64_t ns = 1ull << s->k;
     const size_t bytes = sizeof(G1Affine) * ns * pl.W;
-    const char* env = getenv("ZK_MSM_TABLE_GB");
-    const double cap_gb = env ? atof(env) : 32.0;
+    const double cap_gb = kn.table_gb;
     if (n < 64 || (double)bytes > cap_gb * (double)(1ull << 30) || (uint64_t)pl.W * ns >= (1ull << 31)) return ZK_OK;
     // plan changed (measurement knobs): the top window's entries carry c - top_shift doublings, so a table is only valid for the
     // (c, top_shift) it was built for
@@ -2464,7 +2268,7 @@ extern "C" int zk_msm_g1_segments(zk_ctx* ctx, const void* d_scalars, const void
 // every canonical scalar, carry included, stays at or below 2^(c-1).
 extern "C" int zk_host_msm_plan(uint32_t k, int* window_bits, int* windows, int* top_shift) {
     if (!window_bits || !windows || !top_shift || k > 28) return ZK_ERR_INVALID_ARG;
-    const zk::MsmPlan m = zk::make_plan_merged(k);
+    const zk::MsmPlan m = zk::make_plan_merged(k, zk::read_knobs());
     *window_bits = m.c;
     *windows = m.W;
     *top_shift = m.top_shift;
@@ -2475,9 +2279,9 @@ extern "C" int zk_host_msm_plan(uint32_t k, int* window_bits, int* windows, int*
 extern "C" int zk_msm_plan(const zk_srs* srs, size_t n, int* window_bits, int* windows) {
     if (!srs || !window_bits || !windows) return ZK_ERR_INVALID_ARG;
     const uint64_t ns = 1ull << srs->k;
-    const zk::MsmPlan m = zk::make_plan_merged(srs->k);
-    const char* env = getenv("ZK_MSM_TABLE_GB");
-    const double cap_gb = env ? atof(env) : 32.0;
+    const zk::MsmKnobs kn = zk::read_knobs();
+    const zk::MsmPlan m = zk::make_plan_merged(srs->k, kn);
+    const double cap_gb = kn.table_gb;
     const bool merged = n >= 64 && (double)(sizeof(zk::G1Affine) * ns * m.W) <= cap_gb * (double)(1ull << 30) && (uint64_t)m.W * ns < (1ull << 31);
     const zk::MsmPlan pl = merged ? m : zk::make_plan(n);
     *window_bits = pl.c;
