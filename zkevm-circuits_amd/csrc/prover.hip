@@ -186,6 +186,56 @@ struct zk_proof {
 namespace {
 
 #define PK_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
+#define PK_ALLOC(ctx, buf, nbytes) do { if (!(buf).alloc(nbytes)) return (ctx)->fail(ZK_ERR_OOM, "prover: alloc failed"); } while (0)
+
+// puts the context's stream back, on every way out, in a scope that redirects it to the auxiliary stream
+struct StreamRestore {
+    zk_ctx* c; hipStream_t s;
+    explicit StreamRestore(zk_ctx* ctx) : c(ctx), s(ctx->stream) {}
+    ~StreamRestore() { c->stream = s; }
+};
+
+// Free device memory right now (the session pool's parked blocks are not in it: callers add zk_ctx::pool_bytes).  When the
+// runtime cannot tell: 0, and *ok = false for a caller that reacts to that in another way than by counting on nothing.
+size_t device_free_bytes(bool* ok = nullptr) {
+    size_t free_b = 0, total_b = 0;
+    const bool got = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    if (!got) { (void)hipGetLastError(); free_b = 0; }
+    if (ok) *ok = got;
+    return free_b;
+}
+
+// Degree class e of 0 .. E is evaluated on the cosets r that are multiples of 2^(E - e) (see the quotient stage).
+inline bool class_on_coset(uint32_t E, uint32_t e, uint32_t r) { return (r & ((1u << (E - e)) - 1u)) == 0; }
+// ... and, in a sharded session, by the rank the (class, coset) pair was dealt to: a table filled once, when the deal is made
+struct PairOwners {
+    uint32_t E = 0, rank = 0;
+    bool sharded = false;
+    std::vector<uint32_t> owner;              // [e << E | r]
+    size_t at(uint32_t e, uint32_t r) const { return ((size_t)e << E) | r; }
+    bool mine(uint32_t e, uint32_t r) const { return class_on_coset(E, e, r) && (!sharded || owner[at(e, r)] == rank); }
+};
+
+// (columns served, coset) of every coset r < R that serves a column, most columns first, then by index: the order in which
+// cosets of the advice columns are taken to be computed ahead (plan_advice_cosets, stage_late_advice_cosets)
+template <class Count>
+std::vector<std::pair<uint32_t, uint32_t>> cosets_by_columns_served(uint32_t R, Count served) {
+    std::vector<std::pair<uint32_t, uint32_t>> by_count;
+    for (uint32_t r = 0; r < R; ++r) {
+        const uint32_t cnt = served(r);
+        if (cnt) by_count.push_back({cnt, r});
+    }
+    std::sort(by_count.begin(), by_count.end(), [](const auto& a, const auto& b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
+    return by_count;
+}
+
+// sum_j ch^j * polys[j] over 2^k rows on the device: Horner from the last polynomial down (FOLD multiplies the accumulator by ch)
+int lincomb(zk_ctx* ctx, uint32_t k, const std::vector<const void*>& polys, const F4& ch, void* d_out) {
+    std::vector<uint32_t> words;
+    std::vector<const void*> cols;
+    for (size_t j = polys.size(); j-- > 0;) { words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_FOLD, 0u, 0u}); cols.push_back(polys[j]); }
+    return zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), cols.data(), (uint32_t)cols.size(), &ch, 1, k, k, 0, d_out);
+}
 
 int commit_lagrange(zk_ctx* ctx, const zk_srs* srs, const Fr* d_vals, size_t n, G1Affine* out) { return zk_commit(ctx, srs, 1, d_vals, n, out); }
 int commit_coeff(zk_ctx* ctx, const zk_srs* srs, const Fr* d_vals, size_t n, G1Affine* out) { return zk_commit(ctx, srs, 0, d_vals, n, out); }
@@ -193,7 +243,7 @@ int commit_coeff(zk_ctx* ctx, const zk_srs* srs, const Fr* d_vals, size_t n, G1A
 // Lagrange values -> coefficients (EvaluationDomain::lagrange_to_coeff)
 int to_coeff(zk_ctx* ctx, const zk_pk* pk, const DevBuf& lag, DevBuf* coeff) {
     const size_t n = (size_t)1 << pk->k;
-    if (!coeff->alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+    PK_ALLOC(ctx, *coeff, n * 32);
     const Fr omega_inv = fr_inv_host(fr_root_of_unity(pk->k)), ninv = fr_inv_host(fr_from_u64(1ull << pk->k));
     return ntt_run(ctx, coeff->fr(), pk->k, omega_inv, &ninv, nullptr, nullptr, lag.fr());
 }
@@ -393,6 +443,18 @@ void push_compressed(PB& b, const std::vector<Prog>& exprs) {
 }
 void push_perm_col(PB& b, const std::pair<uint32_t, uint32_t>& c) { b.col(c.first, c.second, 0); }
 
+// Results of `count` items that a sharded session deals round-robin (item i to rank i % world), `elem` bytes each.  `local`
+// holds this rank's results in its own order, share_size() of them with the unused tail zeroed; they are all-gathered, and
+// `out` receives all `count` in item order -- on every rank the same, so the transcripts stay identical.
+size_t share_size(const zk_proof* pr, size_t count) { return (count + pr->world - 1) / pr->world; }
+int share_gather(zk_ctx* ctx, const zk_proof* pr, const void* local, size_t count, size_t elem, void* out) {
+    const size_t per = share_size(pr, count);
+    std::vector<uint8_t> all(per * pr->world * elem);
+    if (per && pr->gather(pr->gather_user, local, per * elem, all.data())) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: all-gather callback failed");
+    for (size_t i = 0; i < count; ++i) memcpy((uint8_t*)out + i * elem, all.data() + ((i % pr->world) * per + i / pr->world) * elem, elem);
+    return ZK_OK;
+}
+
 // usable-row masks in Lagrange form
 // `count` commitments over one basis, split over the ranks of a sharded session: rank r commits
 // columns i = r, r + world, ... (pipelined batch) and the 64-byte points are all-gathered, so every
@@ -419,21 +481,95 @@ int sharded_commit(zk_ctx* ctx, const zk_proof* pr, const zk_srs* srs, int basis
         }
         return ZK_OK;
     }
-    const size_t per = (count + pr->world - 1) / pr->world;
     std::vector<const void*> mine;
     for (size_t i = pr->rank; i < count; i += pr->world) mine.push_back(ptrs[i]);
-    std::vector<G1Affine> local(per), all(per * pr->world);
-    memset((void*)local.data(), 0, sizeof(G1Affine) * per);
+    std::vector<G1Affine> local(share_size(pr, count));
+    memset((void*)local.data(), 0, sizeof(G1Affine) * local.size());
     PK_TRY(commit_batch_staged(ctx, srs, basis, mine.data(), mine.size(), n, local.data(), nullptr, nullptr, hint.data()));
-    if (per && pr->gather(pr->gather_user, local.data(), per * sizeof(G1Affine), all.data())) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: all-gather callback failed");
-    for (size_t i = 0; i < count; ++i) out[i] = all[(i % pr->world) * per + i / pr->world];
-    return ZK_OK;
+    return share_gather(ctx, pr, local.data(), count, sizeof(G1Affine), out);
 }
 
 int upload(zk_ctx* ctx, DevBuf* b, const void* h, size_t bytes) {
     if (!b->alloc(bytes)) return ctx->fail(ZK_ERR_OOM, "prover: alloc of %zu bytes failed", bytes);
     return zk_h2d(ctx, b->p, h, bytes);
 }
+
+
+// One all-gather of `bytes` per rank out of the device buffer d_send, by the first transport the session has:
+//   use_comm (a caller that may): the context's RCCL communicator, device to device into d_recv, stream-ordered -- no host
+//               copy, no synchronisation;
+//   the caller's device all-gather (zk_proof_set_device_gather), into d_recv: the stream is drained first, the callback
+//               completes on return;
+//   the host callback: d_send is downloaded into host.send (stage_send false: host.send goes out as it stands) and the
+//               ranks' blocks arrive in host.recv -- bringing them to the device is the caller's step.
+// *on_device says where the result lies.
+struct HostStaging { std::vector<uint8_t> send, recv; };
+int allgather_rows(zk_ctx* ctx, const zk_proof* pr, bool use_comm, const void* d_send, bool stage_send, size_t bytes, void* d_recv, HostStaging& host, bool* on_device) {
+    *on_device = use_comm || pr->gather_dev;
+    if (use_comm) return comm_allgather_dev(ctx, d_send, bytes, d_recv);
+    if (pr->gather_dev) {
+        PK_TRY(zk_ctx_sync(ctx));
+        if (pr->gather_dev(pr->gather_dev_user, d_send, bytes, d_recv)) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: device all-gather callback failed");
+        return ZK_OK;
+    }
+    host.send.resize(bytes); host.recv.resize((size_t)pr->world * bytes);
+    if (stage_send) PK_TRY(zk_d2h(ctx, host.send.data(), d_send, bytes));
+    if (pr->gather(pr->gather_user, host.send.data(), bytes, host.recv.data())) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: all-gather callback failed");
+    return ZK_OK;
+}
+
+struct Open { const Fr* poly; int32_t rot; F4 eval; };      // one opening: a polynomial (coefficients on the device), the rotation of x, the value there
+
+// ---- SHPLONK's host mathematics
+// construct_intermediate_sets: polynomials in order of first appearance with their point sets;
+// rotation sets in order of first appearance, each listing its polynomials; `super`: every point that is opened somewhere
+struct PolyQ { const Fr* poly; std::vector<int32_t> rots; std::vector<F4> evals; };
+struct RotSet { std::vector<int32_t> rots; std::vector<size_t> members; };
+void shplonk_intermediate_sets(const std::vector<Open>& queries, std::vector<PolyQ>& polys, std::vector<RotSet>& sets, std::vector<int32_t>& super) {
+    for (const Open& o : queries) {
+        auto it = std::find_if(polys.begin(), polys.end(), [&](const PolyQ& p) { return p.poly == o.poly; });
+        if (it == polys.end()) { polys.push_back({o.poly, {}, {}}); it = polys.end() - 1; }
+        if (std::find(it->rots.begin(), it->rots.end(), o.rot) == it->rots.end()) { it->rots.push_back(o.rot); it->evals.push_back(o.eval); }
+    }
+    for (size_t pi = 0; pi < polys.size(); ++pi) {
+        std::vector<int32_t> key = polys[pi].rots;
+        std::sort(key.begin(), key.end());
+        auto it = std::find_if(sets.begin(), sets.end(), [&](const RotSet& s_) { return s_.rots == key; });
+        if (it == sets.end()) { sets.push_back({key, {}}); it = sets.end() - 1; }
+        it->members.push_back(pi);
+        for (int32_t r_ : key) if (std::find(super.begin(), super.end(), r_) == super.end()) super.push_back(r_);
+    }
+}
+// r_ij(X): interpolation of polynomial j's evaluations over its set's points (degree < |S|), host side.  The Lagrange basis
+// of a set -- L_a(X) = prod_{b != a} (X - x_b) / (x_a - x_b), |S|^3 products -- is built ONCE per set; a member then costs
+// |S|^2.  (Per member it was 3.9 ms of the Keccak-shape proof: 48 columns opened at the same 14 points.)
+std::vector<std::vector<F4>> lagrange_basis(const std::vector<F4>& xs) {
+    const size_t m = xs.size();
+    std::vector<std::vector<F4>> basis(m);
+    for (size_t a = 0; a < m; ++a) {
+        std::vector<F4> num{host::fr_one()};       // prod_{b != a} (X - x_b)
+        F4 den = host::fr_one();
+        for (size_t b2 = 0; b2 < m; ++b2) {
+            if (b2 == a) continue;
+            std::vector<F4> nx(num.size() + 1, host::fr_zero());
+            for (size_t t = 0; t < num.size(); ++t) { nx[t + 1] = host::fr_add(nx[t + 1], num[t]); nx[t] = host::fr_sub(nx[t], host::fr_mul(num[t], xs[b2])); }
+            num.swap(nx);
+            den = host::fr_mul(den, host::fr_sub(xs[a], xs[b2]));
+        }
+        const F4 dinv = host::fr_inv(den);
+        for (F4& c : num) c = host::fr_mul(c, dinv);
+        basis[a] = std::move(num);
+    }
+    return basis;
+}
+std::vector<F4> interpolate(const std::vector<std::vector<F4>>& basis, const std::vector<F4>& ys) {
+    const size_t m = basis.size();
+    std::vector<F4> out(m, host::fr_zero());
+    for (size_t a = 0; a < m; ++a)
+        for (size_t t = 0; t < m; ++t) out[t] = host::fr_add(out[t], host::fr_mul(basis[a][t], ys[a]));
+    return out;
+}
+F4 eval_small(const std::vector<F4>& c, const F4& at) { F4 acc = host::fr_zero(); for (size_t t = c.size(); t-- > 0;) acc = host::fr_add(host::fr_mul(acc, at), c[t]); return acc; }
 
 }  // namespace
 
@@ -574,8 +710,7 @@ int zk_pk_create(zk_ctx* ctx, const zk_srs* srs, const void* h_blob, size_t blob
     // l0, l_last, l_active (built on the device: a delta at row 0, a delta at row u, ones below u) and the omega^i column
     {
         const Fr w = fr_root_of_unity(pk->k), one = Fr::one();
-        if (!pk->l0_lag.alloc(n * 32) || !pk->llast_lag.alloc(n * 32) || !pk->lactive_lag.alloc(n * 32) || !pk->omega_lag.alloc(n * 32))
-            return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+        PK_ALLOC(ctx, pk->l0_lag, n * 32); PK_ALLOC(ctx, pk->llast_lag, n * 32); PK_ALLOC(ctx, pk->lactive_lag, n * 32); PK_ALLOC(ctx, pk->omega_lag, n * 32);
         ZK_HIP(ctx, hipMemsetAsync(pk->l0_lag.p, 0, n * 32, ctx->stream));
         ZK_HIP(ctx, hipMemsetAsync(pk->llast_lag.p, 0, n * 32, ctx->stream));
         ZK_HIP(ctx, hipMemsetAsync(pk->lactive_lag.p, 0, n * 32, ctx->stream));
@@ -852,14 +987,13 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         zk_proof* pr = nullptr; std::vector<uint32_t> col; std::vector<size_t> pending; std::vector<Fr> g_of_r;
         int flush() {
             if (pending.empty()) return ZK_OK;
-            hipStream_t main_stream = ctx->stream;
+            StreamRestore back(ctx);
             ctx->stream = ctx->stream_aux;
-            struct Back { zk_ctx* c; hipStream_t s; ~Back() { c->stream = s; } } back{ctx, main_stream};
             const size_t n_ = (size_t)1 << pk->k;
             std::vector<Fr*> dsts;
             std::vector<const Fr*> srcs;
             for (size_t c_ : pending) {
-                if (!coeff[c_]->alloc(n_ * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+                PK_ALLOC(ctx, *coeff[c_], n_ * 32);
                 dsts.push_back(coeff[c_]->fr());
                 srcs.push_back(lag[c_]->fr());
             }
@@ -987,7 +1121,7 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
             static const size_t xg_knob = getenv("ZK_SHARD_EXCHANGE_GROUPS") ? (size_t)atol(getenv("ZK_SHARD_EXCHANGE_GROUPS")) : 16;
             const size_t groups_total = (total + sg.world - 1) / sg.world, XG = std::max<size_t>(1, std::min(xg_knob, groups_total));
             DevBuf gbuf, sbuf;
-            if (!gbuf.alloc((size_t)sg.world * XG * n * 32) || !sbuf.alloc(XG * n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+            PK_ALLOC(ctx, gbuf, (size_t)sg.world * XG * n * 32); PK_ALLOC(ctx, sbuf, XG * n * 32);
             // the last own column of the phase has not been transformed yet (the staging callback transforms column i - 1 when it uploads column i; the auxiliary
             // stream already waits for its upload): the exchange below may ship its coefficient form
             for (size_t c_ : sg.own) if (!sg.coeff[c_]->p) PK_TRY(to_coeff_aux(ctx, pk, *sg.lag[c_], sg.coeff[c_]));
@@ -1024,7 +1158,7 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
                         if (q_ == pr->rank || c_ >= total) continue;
                         const char* got = (const char*)gbuf.p + ((size_t)q_ * gcnt + g) * n * 32;
                         if (as_coeff(c_)) {
-                            if (!sg.coeff[c_]->alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+                            PK_ALLOC(ctx, *sg.coeff[c_], n * 32);
                             ZK_HIP(ctx, hipMemcpyAsync(sg.coeff[c_]->p, got, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
                             sg.lag[c_]->release();                   // nobody reads the Lagrange form of this column here
                             pr->lag_partial = true;
@@ -1687,7 +1821,7 @@ static int advice_coset_plan(zk_ctx* ctx, const zk_pk* pk, bool sharded, std::ve
     std::unordered_map<uint32_t, uint32_t> key_mask;
     for (uint32_t e = 0; e <= E; ++e) {
         uint32_t cosets = 0;
-        for (uint32_t r = 0; r < (1u << E); ++r) if ((r & ((1u << (E - e)) - 1u)) == 0) cosets |= 1u << r;
+        for (uint32_t r = 0; r < (1u << E); ++r) if (class_on_coset(E, e, r)) cosets |= 1u << r;
         for (uint32_t ref : qp->cls[e].refs) {
             const uint32_t t = ref >> 24;
             if (t == CT_ADVICE && (ref & 0xFFFFFFu) < pk->A) mask[ref & 0xFFFFFFu] |= cosets;
@@ -1745,8 +1879,9 @@ static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr) {
     const uint32_t E = pk->ext_k - pk->k, R = 1u << E;
     if (E > 5) return ZK_OK;
     const double col_bytes = (double)((size_t)1 << pk->k) * 32.0;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return ZK_OK; }
+    bool mem_known = false;
+    const size_t free_b = device_free_bytes(&mem_known);
+    if (!mem_known) return ZK_OK;            // nothing is computed ahead on a guess
     // columns' worth of buffers still to come, the advice columns' own coset buffers aside (counted below, per choice of cosets):
     // Lagrange + coefficient forms of the advice columns, of m / phi / Z with their temporaries, their coset buffers, h, slack
     // (a witness handed over in place brings its Lagrange forms along)
@@ -1761,13 +1896,7 @@ static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr) {
         if (key_need <= kcap) avail -= std::max(0.0, key_need - (double)pk->part_cache_bytes);
     }
     const double budget = std::min(cap, avail);
-    std::vector<std::pair<uint32_t, uint32_t>> by_count;          // (columns served, coset)
-    for (uint32_t r = 0; r < R; ++r) {
-        uint32_t cnt = 0;
-        for (uint32_t m_ : mask) cnt += m_ >> r & 1u;
-        if (cnt) by_count.push_back({cnt, r});
-    }
-    std::sort(by_count.begin(), by_count.end(), [](const auto& a, const auto& b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
+    const auto by_count = cosets_by_columns_served(R, [&](uint32_t r) { uint32_t cnt = 0; for (uint32_t m_ : mask) cnt += m_ >> r & 1u; return cnt; });
     uint32_t chosen = 0;
     double used = 0;
     for (const auto& cr : by_count) {
@@ -1956,250 +2085,280 @@ static int write_plan_summary(const std::shared_ptr<const QuotientPlan>& qp, uin
     return ZK_OK;
 }
 
-// Everything after the advice phases: lookups, permutation, quotient, evaluations, multi-open.
-// Consumes the session (it is freed whether or not the call succeeds).
-int zk_proof_finish(zk_ctx* ctx, zk_proof* pr_raw, void* h_proof, size_t proof_cap, size_t* proof_len) {
-    if (!ctx) return ZK_ERR_INVALID_ARG;
-    PoolScope pool_scope(ctx);
-    std::unique_ptr<zk_proof> pr(pr_raw);
-    ZK_REQUIRE(ctx, pr && h_proof && proof_len, "null pointer");
-    const zk_pk* pk = pr->pk;
-    if (pr->phase != pk->num_phases) return ctx->fail(ZK_ERR_INVALID_ARG, "only %u of %u advice phases were committed", pr->phase, pk->num_phases);
-    const zk_srs* srs = pk->srs;
-    const uint32_t k = pk->k, ext_k = pk->ext_k;
-    const size_t n = (size_t)1 << k, ne = (size_t)1 << ext_k;
-    host::XorShiftRng& rng = pr->rng;
-    host::Transcript& tr = pr->tr;
-    std::vector<DevBuf>&inst_lag = pr->inst_lag, &inst_coeff = pr->inst_coeff, &adv_lag = pr->adv_lag;
-    std::vector<DevBuf>& adv_coeff = pr->adv_coeff;     // computed during the advice phases, in the shadow of the uploads
-    const F4 one = host::fr_one();
-    StageTrace trace(ctx);
-    Env lag{pk, nullptr, &adv_lag, &inst_lag, nullptr, nullptr, nullptr, one, one, one, one, {}, pr->challenges};
-    lag.theta = tr.squeeze();
-    // ---- more cosets of the advice columns, ahead of the quotient: what the advice phases could not fit (or afford) is
-    // computed NOW on the auxiliary stream, beside the lookup / permutation / grand-sum stages below -- hash joins, scans,
-    // batch inversions and chains of small-valued commitments that leave most of the device idle.  Same plan, same budget
-    // rule as in the advice phase, with the memory that is free at this point; the quotient waits for the stream before its
-    // first coset.  OFF by default (ZK_ADVICE_COSET_LATE_GB=<GiB> turns it on): measured on the SuperCircuit shape with 48 GiB
-    // (tools/gpu_r3v.sh) the quotient's transform stage drops from 237 to 149 ms and the lookup stage beside which the transforms
-    // run grows from 46 to 118 ms -- 1.437 -> 1.424 s for 25 GiB of device memory: these stages are not idle enough to hide them.
-    bool late_cosets = false;
-    // whatever way this function is left, the auxiliary stream must be through with the session's buffers before they go back to the pool
-    struct AuxJoin { zk_ctx* c; bool* on; ~AuxJoin() { if (*on && c->stream_aux) (void)hipStreamSynchronize(c->stream_aux); } } aux_join{ctx, &late_cosets};
-    {
-        const bool sharded_ = pr->world > 1 && pr->gather;
-        const char* env = getenv("ZK_ADVICE_COSET_LATE_GB");
-        const double cap = (env ? atof(env) : 0.0) * (double)(1ull << 30);
-        const uint32_t E_ = ext_k - k, R_ = 1u << E_;
-        if (!sharded_ && cap > 0 && pk->A && E_ <= 5 && ctx->ensure_aux()) {
-            std::vector<uint32_t> mask;
-            size_t key_slots = 0;
-            PK_TRY(advice_coset_plan(ctx, pk, false, mask, &key_slots));
-            if (pr->adv_coset.empty()) { pr->adv_coset.resize(R_); for (auto& v : pr->adv_coset) v.resize(pk->A); }
-            const double col_bytes = (double)n * 32.0;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-            // still to come: m / phi / Z in Lagrange and coefficient form with their temporaries, their coset buffers, h, slack;
-            // the key's own cosets if its cache is still empty
-            double avail = (double)free_b + (double)ctx->pool_bytes - (4.0 * (2.0 * pk->L + pk->C) + (2.0 * pk->L + pk->C + pk->I + 8.0) + 2.0 * R_ + 32.0) * col_bytes - 24.0 * (double)(1ull << 30);
-            if (pk->part_cache_state < 0 || (pk->part_cache_state == 1 && pk->part_cache_bytes == 0)) avail -= (double)key_slots * col_bytes;
-            std::vector<std::pair<uint32_t, uint32_t>> by_count;          // (columns still to transform, coset)
-            for (uint32_t r = 0; r < R_; ++r) {
-                uint32_t cnt = 0;
-                for (uint32_t c = 0; c < pk->A; ++c) cnt += (mask[c] >> r & 1u) && !pr->adv_coset[r][c].p && adv_coeff[c].p;
-                if (cnt) by_count.push_back({cnt, r});
-            }
-            std::sort(by_count.begin(), by_count.end(), [](const auto& a, const auto& b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
-            double used = 0;
-            hipStream_t main_stream = ctx->stream;
-            struct Back { zk_ctx* c; hipStream_t s; ~Back() { c->stream = s; } } back{ctx, main_stream};
-            const Fr w_ext = fr_root_of_unity(ext_k);
-            for (const auto& cr : by_count) {
-                if (used + cr.first * col_bytes > std::min(cap, avail)) continue;          // a smaller coset further down may still fit
-                Fr g = fr_zeta();
-                for (uint32_t i = 0; i < cr.second; ++i) g = g * w_ext;
-                std::vector<const void*> csrc;
-                std::vector<void*> cdst;
-                bool ok = true;
-                for (uint32_t c = 0; c < pk->A && ok; ++c) {
-                    if (!(mask[c] >> cr.second & 1u) || pr->adv_coset[cr.second][c].p || !adv_coeff[c].p) continue;
-                    DevBuf& slot = pr->adv_coset[cr.second][c];
-                    if (!slot.alloc(n * 32)) { ok = false; break; }
-                    csrc.push_back(adv_coeff[c].p);
-                    cdst.push_back(slot.p);
-                }
-                if (!late_cosets) {          // first batch: the stream starts behind everything the main stream has enqueued (pooled blocks)
-                    ZK_HIP(ctx, hipEventRecord(ctx->ev_aux, main_stream));
-                    ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_aux, 0));
-                }
-                ctx->stream = ctx->stream_aux;
-                late_cosets = true;
-                if (!csrc.empty()) PK_TRY(zk_coeff_to_coset_batch(ctx, csrc.data(), k, &g, cdst.data(), csrc.size()));
-                ctx->stream = main_stream;
-                used += csrc.size() * col_bytes;
-                if (!ok) break;
-            }
-            if (late_cosets) {
-                ZK_HIP(ctx, hipEventRecord(ctx->ev_aux, ctx->stream_aux));
-                if (getenv("ZK_PROVER_TRACE")) fprintf(stderr, "[zk prover] advice cosets computed beside the lookup / permutation stages: %.1f GiB\n", used / (double)(1ull << 30));
-            }
-        }
-    }
-
-    // ---- lookups, round 1 (mv_lookup::prover::Argument::prepare): theta-compressed table and input tuples,
-    // multiplicities m over ALL input tuples of the argument.  Every lookup is enqueued back to back
-    // (compression programs, device hash join); one download of the status words, one pipelined batch
-    // of commits.  The unusable rows of m stay zero, as upstream leaves them.
-    std::vector<std::vector<DevBuf>> lk_f(pk->L);
-    std::vector<DevBuf> lk_t(pk->L), lk_m(pk->L), lk_phi(pk->L);
-    std::vector<uint8_t> same_table(pk->L, 0);            // lookup l reads the table of the lookup this rank worked on before it (lk_t lives at table_owner[l])
-    std::vector<uint32_t> table_owner(pk->L, 0);
+// ================================================================================================
+// The finishing pass: everything after the advice phases.  One function per stage of the protocol, called by zk_proof_finish
+// (at the end of this part) in transcript order.  `Finish` carries what more than one stage reads; a buffer that only one stage
+// uses is a local of that stage's function and goes back to the session pool where the function returns.
+struct Finish {
+    zk_ctx* ctx;
+    zk_proof* pr;
+    const zk_pk* pk;
+    const zk_srs* srs;
+    const uint32_t k, ext_k;
+    const size_t n;
+    Env lag;                                  // the Lagrange forms, and the challenges as they are squeezed
+    StageTrace trace;
+    const bool sharded;                       // one of several ranks
     // Sharded sessions (round 6): the lookup arguments are split over the ranks like their commitments -- rank r compresses the tuples, counts the multiplicities and forms the
     // running sum of arguments r, r + world, ... only; the Lagrange forms of m and phi (what the additive split's remainders, the coefficient forms and with them every later
     // stage read) are all-gathered device to device behind each of the two rounds.  The blinding rows are drawn for every argument on every rank (one RNG sequence).
     // ZK_SHARD_LOOKUPS=0: every rank works on every argument, as before.
-    const bool shard_args = pr->world > 1 && pr->gather && pk->L >= pr->world && !(getenv("ZK_SHARD_LOOKUPS") && atoi(getenv("ZK_SHARD_LOOKUPS")) == 0);
-    std::vector<uint32_t> act;                             // the arguments this rank works on, in order
-    for (uint32_t l = 0; l < pk->L; ++l) if (!shard_args || l % pr->world == pr->rank) act.push_back(l);
-    // all-gather of columns owned round-robin (column l by rank l % world): a rank's columns packed into one send buffer, several groups of `world` per exchange
-    auto exchange_owned = [&](std::vector<DevBuf>& cols) -> int {
-        const size_t total = cols.size(), W = pr->world, groups_total = (total + W - 1) / W;
-        static const size_t xg_knob = getenv("ZK_SHARD_EXCHANGE_GROUPS") ? (size_t)atol(getenv("ZK_SHARD_EXCHANGE_GROUPS")) : 16;
-        const size_t XG = std::max<size_t>(1, std::min(xg_knob, groups_total));
-        DevBuf gbuf, sbuf;
-        if (!gbuf.alloc(W * XG * n * 32) || !sbuf.alloc(XG * n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-        std::vector<uint8_t> hs, hr;
-        for (size_t grp0 = 0; grp0 < groups_total; grp0 += XG) {
-            const size_t gcnt = std::min(XG, groups_total - grp0);
-            for (size_t g = 0; g < gcnt; ++g) {
-                const size_t mine_c = (grp0 + g) * W + pr->rank;
-                if (mine_c < total) ZK_HIP(ctx, hipMemcpyAsync((char*)sbuf.p + g * n * 32, cols[mine_c].p, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-                else ZK_HIP(ctx, hipMemsetAsync((char*)sbuf.p + g * n * 32, 0, n * 32, ctx->stream));
-            }
-            if (pr->gather_dev) {
-                PK_TRY(zk_ctx_sync(ctx));
-                if (pr->gather_dev(pr->gather_dev_user, sbuf.p, gcnt * n * 32, gbuf.p)) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: device all-gather callback failed");
-            } else {
-                hs.resize(gcnt * n * 32); hr.resize(W * gcnt * n * 32);
-                PK_TRY(zk_d2h(ctx, hs.data(), sbuf.p, hs.size()));
-                if (pr->gather(pr->gather_user, hs.data(), hs.size(), hr.data())) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: all-gather callback failed");
-                PK_TRY(zk_h2d(ctx, gbuf.p, hr.data(), hr.size()));
-            }
-            for (size_t g = 0; g < gcnt; ++g)
-                for (uint32_t q_ = 0; q_ < W; ++q_) {
-                    const size_t c_ = (grp0 + g) * W + q_;
-                    if (q_ == pr->rank || c_ >= total) continue;
-                    ZK_HIP(ctx, hipMemcpyAsync(cols[c_].p, (char*)gbuf.p + ((size_t)q_ * gcnt + g) * n * 32, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-                }
-            PK_TRY(zk_ctx_sync(ctx));                      // gbuf / sbuf are reused by the next chunk (and freed at the end)
+    const bool shard_args;
+    std::vector<uint32_t> act;                // the arguments this rank works on, in order
+    bool late_cosets = false;                 // the auxiliary stream holds coset transforms of this session's advice columns
+    // lookups: compressed inputs and tables (until the grand sums have read them), m and phi in Lagrange form
+    std::vector<std::vector<DevBuf>> lk_f;
+    std::vector<DevBuf> lk_t, lk_m, lk_phi;
+    std::vector<uint8_t> same_table;          // lookup l reads the table of the lookup this rank worked on before it (lk_t lives at table_owner[l])
+    std::vector<uint32_t> table_owner;
+    std::vector<DevBuf> pz_lag;               // permutation products, Lagrange form
+    // coefficient forms of what the quotient reads and the proof opens
+    DevBuf random_coeff;
+    std::vector<DevBuf> pz_coeff, m_coeff, phi_coeff, rem_coeff;      // rem_coeff: the remainders of the additive split (CT_SPLIT_R)
+    DevBuf h;                                 // the quotient: d - 1 pieces of n coefficients
+    // the evaluation point, and the evaluations in the order the proof lists them (marks: where each group starts)
+    F4 x, w, w_inv;
+    std::vector<Open> evals, queries;         // queries: the multi-open's order
+    size_t e_fix = 0, e_random = 0, e_sigma = 0, e_lk = 0;
+    std::vector<size_t> e_pz;
+    DevBuf hcomb;                             // h(X) = sum_i x^(n i) h_i(X)
+    F4 h_eval;
+
+    Finish(zk_ctx* c, zk_proof* p)
+        : ctx(c), pr(p), pk(p->pk), srs(p->pk->srs), k(p->pk->k), ext_k(p->pk->ext_k), n((size_t)1 << p->pk->k),
+          lag{p->pk, nullptr, &p->adv_lag, &p->inst_lag, nullptr, nullptr, nullptr, host::fr_one(), host::fr_one(), host::fr_one(), host::fr_one(), {}, p->challenges},
+          trace(c), sharded(p->world > 1 && p->gather),
+          shard_args(sharded && pk->L >= p->world && !(getenv("ZK_SHARD_LOOKUPS") && atoi(getenv("ZK_SHARD_LOOKUPS")) == 0)),
+          lk_f(pk->L), lk_t(pk->L), lk_m(pk->L), lk_phi(pk->L), same_table(pk->L, 0), table_owner(pk->L, 0), pz_lag(pk->C),
+          pz_coeff(pk->C), m_coeff(pk->L), phi_coeff(pk->L), e_pz(pk->C) {
+        for (uint32_t l = 0; l < pk->L; ++l) if (!shard_args || l % pr->world == pr->rank) act.push_back(l);
+        const Fr t = fr_root_of_unity(k);
+        memcpy(w.l, &t, 32);
+        w_inv = host::fr_inv(w);
+    }
+    Finish(const Finish&) = delete;           // `lag` points into this object
+    Finish& operator=(const Finish&) = delete;
+
+    // rotations are points: x w^rot, rot mod n
+    F4 rotate(int32_t rot) const { F4 p = x; const F4 b = rot >= 0 ? w : w_inv; for (int32_t i = 0; i < (rot >= 0 ? rot : -rot); ++i) p = host::fr_mul(p, b); return p; }
+    int32_t norm_rot(int32_t rot) const { const int64_t nn = (int64_t)n; return (int32_t)((((int64_t)rot % nn) + nn) % nn); }
+    F4 point_of(int32_t nrot) const { const int64_t nn = (int64_t)n; return rotate(nrot > nn / 2 ? (int32_t)(nrot - nn) : nrot); }
+};
+
+// whatever way zk_proof_finish is left, the auxiliary stream must be through with the session's buffers before they go back to the pool
+struct AuxJoin { zk_ctx* c; const bool* on; ~AuxJoin() { if (*on && c->stream_aux) (void)hipStreamSynchronize(c->stream_aux); } };
+
+// ---- more cosets of the advice columns, ahead of the quotient: what the advice phases could not fit (or afford) is
+// computed NOW on the auxiliary stream, beside the lookup / permutation / grand-sum stages below -- hash joins, scans,
+// batch inversions and chains of small-valued commitments that leave most of the device idle.  Same plan as in the advice
+// phase (plan_advice_cosets), with the memory that is free at this point; the quotient waits for the stream before its
+// first coset.  OFF by default (ZK_ADVICE_COSET_LATE_GB=<GiB> turns it on): measured on the SuperCircuit shape with 48 GiB
+// (tools/gpu_r3v.sh) the quotient's transform stage drops from 237 to 149 ms and the lookup stage beside which the transforms
+// run grows from 46 to 118 ms -- 1.437 -> 1.424 s for 25 GiB of device memory: these stages are not idle enough to hide them.
+// The budget and the selection rule are NOT plan_advice_cosets': this one reserves 24 GiB and four columns per m / phi / Z
+// (there: 16 GiB and three) and skips a coset that does not fit to try a smaller one (there: stops at the first).  Nobody
+// recorded why they differ; each is kept as it was measured.
+static int stage_late_advice_cosets(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n;
+    const char* env = getenv("ZK_ADVICE_COSET_LATE_GB");
+    const double cap = (env ? atof(env) : 0.0) * (double)(1ull << 30);
+    const uint32_t E = f.ext_k - f.k, R = 1u << E;
+    if (f.sharded || !(cap > 0) || !pk->A || E > 5 || !ctx->ensure_aux()) return ZK_OK;
+    std::vector<uint32_t> mask;
+    size_t key_slots = 0;
+    PK_TRY(advice_coset_plan(ctx, pk, false, mask, &key_slots));
+    if (pr->adv_coset.empty()) { pr->adv_coset.resize(R); for (auto& v : pr->adv_coset) v.resize(pk->A); }
+    const double col_bytes = (double)n * 32.0;
+    const size_t free_b = device_free_bytes();          // unknown counts as none
+    // still to come: m / phi / Z in Lagrange and coefficient form with their temporaries, their coset buffers, h, slack;
+    // the key's own cosets if its cache is still empty
+    double avail = (double)free_b + (double)ctx->pool_bytes - (4.0 * (2.0 * pk->L + pk->C) + (2.0 * pk->L + pk->C + pk->I + 8.0) + 2.0 * R + 32.0) * col_bytes - 24.0 * (double)(1ull << 30);
+    if (pk->part_cache_state < 0 || (pk->part_cache_state == 1 && pk->part_cache_bytes == 0)) avail -= (double)key_slots * col_bytes;
+    auto todo = [&](uint32_t r, uint32_t c) { return (mask[c] >> r & 1u) && !pr->adv_coset[r][c].p && pr->adv_coeff[c].p; };      // still to transform
+    const auto by_count = cosets_by_columns_served(R, [&](uint32_t r) { uint32_t cnt = 0; for (uint32_t c = 0; c < pk->A; ++c) cnt += todo(r, c); return cnt; });
+    double used = 0;
+    StreamRestore back(ctx);
+    const hipStream_t main_stream = ctx->stream;
+    const Fr w_ext = fr_root_of_unity(f.ext_k);
+    for (const auto& cr : by_count) {
+        if (used + cr.first * col_bytes > std::min(cap, avail)) continue;          // a smaller coset further down may still fit
+        Fr g = fr_zeta();
+        for (uint32_t i = 0; i < cr.second; ++i) g = g * w_ext;
+        std::vector<const void*> csrc;
+        std::vector<void*> cdst;
+        bool ok = true;
+        for (uint32_t c = 0; c < pk->A && ok; ++c) {
+            if (!todo(cr.second, c)) continue;
+            DevBuf& slot = pr->adv_coset[cr.second][c];
+            if (!slot.alloc(n * 32)) { ok = false; break; }
+            csrc.push_back(pr->adv_coeff[c].p);
+            cdst.push_back(slot.p);
         }
-        return ZK_OK;
-    };
+        if (!f.late_cosets) {          // first batch: the stream starts behind everything the main stream has enqueued (pooled blocks)
+            ZK_HIP(ctx, hipEventRecord(ctx->ev_aux, main_stream));
+            ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_aux, 0));
+        }
+        ctx->stream = ctx->stream_aux;
+        f.late_cosets = true;
+        if (!csrc.empty()) PK_TRY(zk_coeff_to_coset_batch(ctx, csrc.data(), f.k, &g, cdst.data(), csrc.size()));
+        ctx->stream = main_stream;
+        used += csrc.size() * col_bytes;
+        if (!ok) break;
+    }
+    if (f.late_cosets) {
+        ZK_HIP(ctx, hipEventRecord(ctx->ev_aux, ctx->stream_aux));
+        if (getenv("ZK_PROVER_TRACE")) fprintf(stderr, "[zk prover] advice cosets computed beside the lookup / permutation stages: %.1f GiB\n", used / (double)(1ull << 30));
+    }
+    return ZK_OK;
+}
+
+// all-gather of columns owned round-robin (column l by rank l % world): a rank's columns packed into one send buffer, several groups of `world` per exchange
+static int exchange_owned(Finish& f, std::vector<DevBuf>& cols) {
+    zk_ctx* ctx = f.ctx; const zk_proof* pr = f.pr; const size_t n = f.n;
+    const size_t total = cols.size(), W = pr->world, groups_total = (total + W - 1) / W;
+    static const size_t xg_knob = getenv("ZK_SHARD_EXCHANGE_GROUPS") ? (size_t)atol(getenv("ZK_SHARD_EXCHANGE_GROUPS")) : 16;
+    const size_t XG = std::max<size_t>(1, std::min(xg_knob, groups_total));
+    DevBuf gbuf, sbuf;
+    PK_ALLOC(ctx, gbuf, W * XG * n * 32);
+    PK_ALLOC(ctx, sbuf, XG * n * 32);
+    HostStaging host;
+    for (size_t grp0 = 0; grp0 < groups_total; grp0 += XG) {
+        const size_t gcnt = std::min(XG, groups_total - grp0);
+        for (size_t g = 0; g < gcnt; ++g) {
+            const size_t mine_c = (grp0 + g) * W + pr->rank;
+            if (mine_c < total) ZK_HIP(ctx, hipMemcpyAsync((char*)sbuf.p + g * n * 32, cols[mine_c].p, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+            else ZK_HIP(ctx, hipMemsetAsync((char*)sbuf.p + g * n * 32, 0, n * 32, ctx->stream));
+        }
+        bool on_device = false;
+        PK_TRY(allgather_rows(ctx, pr, false, sbuf.p, true, gcnt * n * 32, gbuf.p, host, &on_device));
+        if (!on_device) PK_TRY(zk_h2d(ctx, gbuf.p, host.recv.data(), host.recv.size()));
+        for (size_t g = 0; g < gcnt; ++g)
+            for (uint32_t q_ = 0; q_ < W; ++q_) {
+                const size_t c_ = (grp0 + g) * W + q_;
+                if (q_ == pr->rank || c_ >= total) continue;
+                ZK_HIP(ctx, hipMemcpyAsync(cols[c_].p, (char*)gbuf.p + ((size_t)q_ * gcnt + g) * n * 32, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+            }
+        PK_TRY(zk_ctx_sync(ctx));                      // gbuf / sbuf are reused by the next chunk (and freed at the end)
+    }
+    return ZK_OK;
+}
+
+// ---- lookups, round 1 (mv_lookup::prover::Argument::prepare): theta-compressed table and input tuples,
+// multiplicities m over ALL input tuples of the argument.  Every lookup is enqueued back to back
+// (compression programs, device hash join); one download of the status words, one pipelined batch
+// of commits.  The unusable rows of m stay zero, as upstream leaves them.
+static int stage_lookup_multiplicities(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n; host::Transcript& tr = pr->tr;
     if (pk->L) {
         Prog prev_table;
         DevBuf status;
-        if (!status.alloc((size_t)pk->L * 4)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+        PK_ALLOC(ctx, status, (size_t)pk->L * 4);
         ZK_HIP(ctx, hipMemsetAsync(status.p, 0xFF, (size_t)pk->L * 4, ctx->stream));
         std::vector<const void*> mptrs(pk->L);
         for (uint32_t l = 0; l < pk->L; ++l) {            // every m exists on every rank (the ones of other ranks arrive below)
-            if (!lk_m[l].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            mptrs[l] = lk_m[l].p;
+            PK_ALLOC(ctx, f.lk_m[l], n * 32);
+            mptrs[l] = f.lk_m[l].p;
         }
         uint32_t prev_l = 0;
         bool have_prev = false;
-        for (const uint32_t l : act) {
+        for (const uint32_t l : f.act) {
             const auto& lk = pk->lookups[l];
             PB pt;
             push_compressed(pt, lk.tables); pt.fold(C_ONE);
             // consecutive arguments into the same table (chunk_lookups() splits a table's inputs over as many arguments as the
             // degree bound needs; the EVM circuit's 80-odd lookups go into a dozen tables): one compressed table, one hash
             static const bool share_tables = !(getenv("ZK_LOOKUP_SHARE") && atoi(getenv("ZK_LOOKUP_SHARE")) == 0);      // measurement knob
-            same_table[l] = share_tables && have_prev && pt.g.size() == prev_table.size() && memcmp(pt.g.data(), prev_table.data(), pt.g.size() * sizeof(Instr)) == 0;
-            table_owner[l] = same_table[l] ? table_owner[prev_l] : l;
+            f.same_table[l] = share_tables && have_prev && pt.g.size() == prev_table.size() && memcmp(pt.g.data(), prev_table.data(), pt.g.size() * sizeof(Instr)) == 0;
+            f.table_owner[l] = f.same_table[l] ? f.table_owner[prev_l] : l;
             prev_table = pt.g;
             prev_l = l; have_prev = true;
-            if (!same_table[l]) {
-                if (!lk_t[l].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                PK_TRY(run_program(ctx, lag, pt.g, lk_t[l].p));
+            if (!f.same_table[l]) {
+                PK_ALLOC(ctx, f.lk_t[l], n * 32);
+                PK_TRY(run_program(ctx, f.lag, pt.g, f.lk_t[l].p));
             }
-            lk_f[l].resize(lk.inputs.size());
+            f.lk_f[l].resize(lk.inputs.size());
             std::vector<const Fr*> fptrs;
             for (size_t a = 0; a < lk.inputs.size(); ++a) {
                 PB pf;
                 push_compressed(pf, lk.inputs[a]); pf.fold(C_ONE);
-                if (!lk_f[l][a].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                PK_TRY(run_program(ctx, lag, pf.g, lk_f[l][a].p));
-                fptrs.push_back(lk_f[l][a].fr());
+                PK_ALLOC(ctx, f.lk_f[l][a], n * 32);
+                PK_TRY(run_program(ctx, f.lag, pf.g, f.lk_f[l][a].p));
+                fptrs.push_back(f.lk_f[l][a].fr());
             }
-            PK_TRY(lookup_multiplicities_enqueue(ctx, fptrs.data(), fptrs.size(), lk_t[table_owner[l]].fr(), pk->u, lk_m[l].fr(), n, (uint32_t*)status.p + l, same_table[l]));
+            PK_TRY(lookup_multiplicities_enqueue(ctx, fptrs.data(), fptrs.size(), f.lk_t[f.table_owner[l]].fr(), pk->u, f.lk_m[l].fr(), n, (uint32_t*)status.p + l, f.same_table[l]));
         }
         std::vector<uint32_t> st(pk->L);
         PK_TRY(zk_d2h(ctx, st.data(), status.p, (size_t)pk->L * 4));
         for (uint32_t l = 0; l < pk->L; ++l)
             if (st[l] != 0xFFFFFFFFu) return ctx->fail(ZK_ERR_INVALID_ARG, "lookup %u: input at row %u is not in the table (witness does not satisfy the circuit)", l, st[l]);
-        trace.mark("  lookup: m (all lookups)");
+        f.trace.mark("  lookup: m (all lookups)");
         std::vector<G1Affine> coms(pk->L);
-        PK_TRY(sharded_commit(ctx, pr.get(), srs, 1, mptrs.data(), pk->L, n, coms.data(), 1));      // multiplicities are small counts
+        PK_TRY(sharded_commit(ctx, pr, f.srs, 1, mptrs.data(), pk->L, n, coms.data(), 1));      // multiplicities are small counts
         for (const G1Affine& com : coms) tr.write_point(com);
-        if (shard_args) PK_TRY(exchange_owned(lk_m));
+        if (f.shard_args) PK_TRY(exchange_owned(f, f.lk_m));
     }
-    trace.mark("lookup m");
-    lag.lk_m = &lk_m;
-    lag.beta = tr.squeeze();
-    lag.gamma = tr.squeeze();
-    {   // beta * delta^j for the permutation numerators;  delta = 7^(2^28)
-        F4 delta = host::fr_pow(host::fr_from_u64(7), 1ull << 28), cur = lag.beta;
-        for (uint32_t j = 0; j < pk->P; ++j) { lag.beta_delta.push_back(cur); cur = host::fr_mul(cur, delta); }
-    }
+    f.trace.mark("lookup m");
+    f.lag.lk_m = &f.lk_m;
+    return ZK_OK;
+}
 
-    // ---- permutation grand products
-    std::vector<DevBuf> pz_lag(pk->C);
-    {
-        // All chunks are enqueued back to back (ratios -> unscaled running products); the chunks are
-        // chained afterwards with one small download: Z_c = Z_c^raw * prod_{c' < c} Z_c'^raw(omega^u).
-        DevBuf num, den, tails_d;
-        if (!num.alloc(n * 32) || !den.alloc(n * 32) || !tails_d.alloc((size_t)pk->C * 32 + 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-        for (uint32_t c = 0; c < pk->C; ++c) {
-            PB pn, pd;
-            const uint32_t j0 = c * pk->chunk, j1 = std::min(pk->P, j0 + pk->chunk);
-            for (uint32_t j = j0; j < j1; ++j) {
-                push_perm_col(pn, pk->perm_cols[j]); pn.col(CT_SPECIAL, SP_X).mulc(C_DELTA0 + j).op(Q_ADD).addc(C_GAMMA);
-                if (j > j0) pn.op(Q_MUL);
-                push_perm_col(pd, pk->perm_cols[j]); pd.col(CT_SIGMA, j).mulc(C_BETA).op(Q_ADD).addc(C_GAMMA);
-                if (j > j0) pd.op(Q_MUL);
-            }
-            pn.fold(C_ONE); pd.fold(C_ONE);
-            PK_TRY(run_program(ctx, lag, pn.g, num.p));
-            PK_TRY(run_program(ctx, lag, pd.g, den.p));
-            PK_TRY(zk_fr_batch_invert(ctx, den.p, n));
-            PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_MUL, num.p, den.p, num.p, n));
-            if (!pz_lag[c].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            PK_TRY(zk_fr_prefix_product(ctx, num.p, pz_lag[c].p, n));      // z[0] = 1, z[i+1] = z[i] * ratio[i]
-            ZK_HIP(ctx, hipMemcpyAsync((char*)tails_d.p + (size_t)c * 32, (char*)pz_lag[c].p + (size_t)pk->u * 32, 32, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        std::vector<F4> tails(pk->C);
-        if (pk->C) PK_TRY(zk_d2h(ctx, tails.data(), tails_d.p, (size_t)pk->C * 32));
-        trace.mark("  perm: running products");
-        std::vector<F4> blind((size_t)pk->C * pk->bf);
-        std::vector<const void*> zptrs(pk->C);
-        F4 start = one;
-        for (uint32_t c = 0; c < pk->C; ++c) {
-            if (c) PK_TRY(zk_fr_scale(ctx, pz_lag[c].p, &start, n));       // Z_c(1) = Z_{c-1}(omega^u)
-            start = host::fr_mul(start, tails[c]);
-            for (uint32_t r_ = 0; r_ < pk->bf; ++r_) blind[(size_t)c * pk->bf + r_] = rng.next_fr();
-            ZK_HIP(ctx, hipMemcpyAsync((char*)pz_lag[c].p + (n - pk->bf) * 32, blind.data() + (size_t)c * pk->bf, (size_t)pk->bf * 32, hipMemcpyHostToDevice, ctx->stream));
-            zptrs[c] = pz_lag[c].p;
-        }
-        trace.mark("  perm: chain + blind");
-        std::vector<G1Affine> coms(pk->C);
-        PK_TRY(sharded_commit(ctx, pr.get(), srs, 1, zptrs.data(), pk->C, n, coms.data(), 2));      // running products stay constant over every stretch of rows without copies
-        trace.mark("  perm: commits");
-        for (const G1Affine& com : coms) tr.write_point(com);
-        if (pk->C && !host::fr_eq(start, one)) return ctx->fail(ZK_ERR_INVALID_ARG, "permutation argument does not close: copy constraints are not satisfied by the witness");
+// ---- permutation grand products
+// All chunks are enqueued back to back (ratios -> unscaled running products); the chunks are
+// chained afterwards with one small download: Z_c = Z_c^raw * prod_{c' < c} Z_c'^raw(omega^u).
+static int stage_permutation_products(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n; host::XorShiftRng& rng = pr->rng; host::Transcript& tr = pr->tr;
+    const F4 one = host::fr_one();
+    {   // beta * delta^j for the permutation numerators (here and on the quotient's cosets);  delta = 7^(2^28)
+        F4 delta = host::fr_pow(host::fr_from_u64(7), 1ull << 28), cur = f.lag.beta;
+        for (uint32_t j = 0; j < pk->P; ++j) { f.lag.beta_delta.push_back(cur); cur = host::fr_mul(cur, delta); }
     }
-    trace.mark("permutation Z");
-    // ---- lookups, round 2 (Prepared::commit_grand_sum): phi[0] = 0, phi[i+1] = phi[i] + sum_a 1/(f_a[i]+beta) - m[i]/(t[i]+beta),
-    // the last bf rows random; enqueued back to back with one closing check and one commit batch
+    DevBuf num, den, tails_d;
+    PK_ALLOC(ctx, num, n * 32); PK_ALLOC(ctx, den, n * 32); PK_ALLOC(ctx, tails_d, (size_t)pk->C * 32 + 32);
+    for (uint32_t c = 0; c < pk->C; ++c) {
+        PB pn, pd;
+        const uint32_t j0 = c * pk->chunk, j1 = std::min(pk->P, j0 + pk->chunk);
+        for (uint32_t j = j0; j < j1; ++j) {
+            push_perm_col(pn, pk->perm_cols[j]); pn.col(CT_SPECIAL, SP_X).mulc(C_DELTA0 + j).op(Q_ADD).addc(C_GAMMA);
+            if (j > j0) pn.op(Q_MUL);
+            push_perm_col(pd, pk->perm_cols[j]); pd.col(CT_SIGMA, j).mulc(C_BETA).op(Q_ADD).addc(C_GAMMA);
+            if (j > j0) pd.op(Q_MUL);
+        }
+        pn.fold(C_ONE); pd.fold(C_ONE);
+        PK_TRY(run_program(ctx, f.lag, pn.g, num.p));
+        PK_TRY(run_program(ctx, f.lag, pd.g, den.p));
+        PK_TRY(zk_fr_batch_invert(ctx, den.p, n));
+        PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_MUL, num.p, den.p, num.p, n));
+        PK_ALLOC(ctx, f.pz_lag[c], n * 32);
+        PK_TRY(zk_fr_prefix_product(ctx, num.p, f.pz_lag[c].p, n));      // z[0] = 1, z[i+1] = z[i] * ratio[i]
+        ZK_HIP(ctx, hipMemcpyAsync((char*)tails_d.p + (size_t)c * 32, (char*)f.pz_lag[c].p + (size_t)pk->u * 32, 32, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    std::vector<F4> tails(pk->C);
+    if (pk->C) PK_TRY(zk_d2h(ctx, tails.data(), tails_d.p, (size_t)pk->C * 32));
+    f.trace.mark("  perm: running products");
+    std::vector<F4> blind((size_t)pk->C * pk->bf);
+    std::vector<const void*> zptrs(pk->C);
+    F4 start = one;
+    for (uint32_t c = 0; c < pk->C; ++c) {
+        if (c) PK_TRY(zk_fr_scale(ctx, f.pz_lag[c].p, &start, n));       // Z_c(1) = Z_{c-1}(omega^u)
+        start = host::fr_mul(start, tails[c]);
+        for (uint32_t r_ = 0; r_ < pk->bf; ++r_) blind[(size_t)c * pk->bf + r_] = rng.next_fr();
+        ZK_HIP(ctx, hipMemcpyAsync((char*)f.pz_lag[c].p + (n - pk->bf) * 32, blind.data() + (size_t)c * pk->bf, (size_t)pk->bf * 32, hipMemcpyHostToDevice, ctx->stream));
+        zptrs[c] = f.pz_lag[c].p;
+    }
+    f.trace.mark("  perm: chain + blind");
+    std::vector<G1Affine> coms(pk->C);
+    PK_TRY(sharded_commit(ctx, pr, f.srs, 1, zptrs.data(), pk->C, n, coms.data(), 2));      // running products stay constant over every stretch of rows without copies
+    f.trace.mark("  perm: commits");
+    for (const G1Affine& com : coms) tr.write_point(com);
+    if (pk->C && !host::fr_eq(start, one)) return ctx->fail(ZK_ERR_INVALID_ARG, "permutation argument does not close: copy constraints are not satisfied by the witness");
+    f.trace.mark("permutation Z");
+    return ZK_OK;
+}
+
+// ---- lookups, round 2 (Prepared::commit_grand_sum): phi[0] = 0, phi[i+1] = phi[i] + sum_a 1/(f_a[i]+beta) - m[i]/(t[i]+beta),
+// the last bf rows random; enqueued back to back with one closing check and one commit batch
+static int stage_lookup_grand_sums(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n; host::XorShiftRng& rng = pr->rng; host::Transcript& tr = pr->tr;
     if (pk->L) {
         // ONE batch inversion for all arguments of the proof: every (t + beta) and (f_a + beta) column is written into one buffer --
         // slot list below; an argument that reads the table of the one before it has no table slot of its own --, inverted by a
@@ -2209,67 +2368,66 @@ int zk_proof_finish(zk_ctx* ctx, zk_proof* pr_raw, void* h_proof, size_t proof_c
         // memory the arguments are processed in several such batches.
         std::vector<size_t> slot0(pk->L), tslot(pk->L), nslots(pk->L);
         DevBuf g, closing_d;
-        if (!g.alloc(n * 32) || !closing_d.alloc((size_t)pk->L * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+        PK_ALLOC(ctx, g, n * 32); PK_ALLOC(ctx, closing_d, (size_t)pk->L * 32);
         std::vector<F4> blind((size_t)pk->L * pk->bf);
         for (size_t q = 0; q < blind.size(); ++q) blind[q] = rng.next_fr();            // argument by argument, row by row: the order they were always drawn in, on every rank
         std::vector<const void*> pptrs(pk->L);
         for (uint32_t l = 0; l < pk->L; ++l) {            // every phi exists on every rank (the ones of other ranks arrive below)
-            if (!lk_phi[l].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            pptrs[l] = lk_phi[l].p;
+            PK_ALLOC(ctx, f.lk_phi[l], n * 32);
+            pptrs[l] = f.lk_phi[l].p;
         }
         ZK_HIP(ctx, hipMemsetAsync(closing_d.p, 0, (size_t)pk->L * 32, ctx->stream));
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+        const size_t free_b = device_free_bytes();          // unknown counts as none: batches of four slots
         const size_t max_slots = std::max<size_t>(4, (free_b + ctx->pool_bytes) / 4 / (n * 32));
-        const size_t NA = act.size();
+        const size_t NA = f.act.size();
         for (size_t j0 = 0; j0 < NA;) {
             // arguments act[j0 .. j1) share one inversion; an argument is never separated from the owner of its table
             size_t slots = 0;
             size_t j1 = j0;
             while (j1 < NA) {
-                const uint32_t l1 = act[j1];
-                const size_t need = lk_f[l1].size() + (same_table[l1] && j1 > j0 ? 0 : 1);
-                if (j1 > j0 && slots + need > max_slots && !same_table[l1]) break;
+                const uint32_t l1 = f.act[j1];
+                const size_t need = f.lk_f[l1].size() + (f.same_table[l1] && j1 > j0 ? 0 : 1);
+                if (j1 > j0 && slots + need > max_slots && !f.same_table[l1]) break;
                 slot0[l1] = slots;
-                tslot[l1] = (same_table[l1] && j1 > j0) ? tslot[act[j1 - 1]] : slots;
+                tslot[l1] = (f.same_table[l1] && j1 > j0) ? tslot[f.act[j1 - 1]] : slots;
                 nslots[l1] = need;
                 slots += need;
                 ++j1;
             }
             DevBuf inv;
-            if (!inv.alloc(slots * n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
+            PK_ALLOC(ctx, inv, slots * n * 32);
             {   // t + beta and every f_a + beta of the batch, into their slots: ONE kind of launch for all of them (fr_add_const_many; each used to be a program of its own)
                 std::vector<const void*> asrc;
                 std::vector<void*> adst;
                 for (size_t j = j0; j < j1; ++j) {
-                    const uint32_t l = act[j];
-                    const size_t N = lk_f[l].size();
+                    const uint32_t l = f.act[j];
+                    const size_t N = f.lk_f[l].size();
                     const bool own_t = tslot[l] == slot0[l];
                     for (size_t a = own_t ? 0 : 1; a <= N; ++a) {
                         const size_t slot = a == 0 ? tslot[l] : slot0[l] + (own_t ? a : a - 1);
-                        asrc.push_back(a == 0 ? lk_t[table_owner[l]].p : lk_f[l][a - 1].p);
+                        asrc.push_back(a == 0 ? f.lk_t[f.table_owner[l]].p : f.lk_f[l][a - 1].p);
                         adst.push_back((char*)inv.p + slot * n * 32);
                     }
                 }
-                PK_TRY(fr_add_const_many(ctx, asrc.data(), adst.data(), asrc.size(), &lag.beta, n));
+                PK_TRY(fr_add_const_many(ctx, asrc.data(), adst.data(), asrc.size(), &f.lag.beta, n));
             }
             PK_TRY(zk_fr_batch_invert(ctx, inv.p, slots * n));
             for (size_t j = j0; j < j1; ++j) {
-                const uint32_t l = act[j];
-                DevBuf& phi = lk_phi[l];
-                const size_t N = lk_f[l].size();
+                const uint32_t l = f.act[j];
+                DevBuf& phi = f.lk_phi[l];
+                const size_t N = f.lk_f[l].size();
                 const bool own_t = tslot[l] == slot0[l];
                 const char* inv_t = (const char*)inv.p + tslot[l] * n * 32;
                 const char* inv_f = (const char*)inv.p + (slot0[l] + (own_t ? 1 : 0)) * n * 32;
                 // g = sum_a inv_f_a - m * inv_t
-                PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_MUL, lk_m[l].p, inv_t, g.p, n));
+                PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_MUL, f.lk_m[l].p, inv_t, g.p, n));
                 PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_SUB, inv_f, g.p, g.p, n));
                 for (size_t a = 1; a < N; ++a) PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_ADD, g.p, inv_f + a * n * 32, g.p, n));
                 PK_TRY(zk_fr_prefix_sum(ctx, g.p, phi.p, n));                       // phi[0] = 0, phi[i+1] = phi[i] + g[i]
                 ZK_HIP(ctx, hipMemcpyAsync((char*)closing_d.p + (size_t)l * 32, (char*)phi.p + (size_t)pk->u * 32, 32, hipMemcpyDeviceToDevice, ctx->stream));
                 ZK_HIP(ctx, hipMemcpyAsync((char*)phi.p + (n - pk->bf) * 32, blind.data() + (size_t)l * pk->bf, (size_t)pk->bf * 32, hipMemcpyHostToDevice, ctx->stream));
-                lk_f[l].clear();                                                    // f, t are not needed again (the quotient recomputes them on its cosets)
-                if (j + 1 == NA || !same_table[act[j + 1]]) lk_t[table_owner[l]].release();      // the table's last reader
+                f.lk_f[l].clear();                                                    // f, t are not needed again (the quotient recomputes them on its cosets)
+                if (j + 1 == NA || !f.same_table[f.act[j + 1]]) f.lk_t[f.table_owner[l]].release();      // the table's last reader
             }
             j0 = j1;
         }
@@ -2277,698 +2435,716 @@ int zk_proof_finish(zk_ctx* ctx, zk_proof* pr_raw, void* h_proof, size_t proof_c
         PK_TRY(zk_d2h(ctx, closing.data(), closing_d.p, (size_t)pk->L * 32));
         for (uint32_t l = 0; l < pk->L; ++l)
             if (!host::fr_is_zero(closing[l])) return ctx->fail(ZK_ERR_INVALID_ARG, "lookup %u: grand sum does not close", l);
-        trace.mark("  lookup: phi (all lookups)");
+        f.trace.mark("  lookup: phi (all lookups)");
         std::vector<G1Affine> coms(pk->L);
-        PK_TRY(sharded_commit(ctx, pr.get(), srs, 1, pptrs.data(), pk->L, n, coms.data(), 3));      // running sums: mostly equal increments (runs.hip)
+        PK_TRY(sharded_commit(ctx, pr, f.srs, 1, pptrs.data(), pk->L, n, coms.data(), 3));      // running sums: mostly equal increments (runs.hip)
         for (const G1Affine& com : coms) tr.write_point(com);
-        if (shard_args) PK_TRY(exchange_owned(lk_phi));
+        if (f.shard_args) PK_TRY(exchange_owned(f, f.lk_phi));
     }
-    trace.mark("lookup phi");
-    // ---- vanishing argument: the "random" polynomial.  In the reference's own proof it is the CONSTANT 1: the commitment in
-    // [REF aggregator/data/batch-task.json: chunk_proofs[0]] is g[0] = (1, 2) and its evaluation is 1 (tests/test_reference_chunk_proof.py)
-    // -- Scroll's halo2 fork commits no blinding polynomial; upstream PSE halo2 draws n uniform coefficients.  The verifier accepts
-    // either (it only opens the commitment); ZK_VANISHING_ONE (default) does what the reference's prover did, ZK_VANISHING_UNIFORM
-    // what upstream does.
-    DevBuf random_coeff;
-    {
-        if (!random_coeff.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-        G1Affine com;
-        if (pr->vanishing_random == ZK_VANISHING_ONE) {
-            ZK_HIP(ctx, hipMemsetAsync(random_coeff.p, 0, n * 32, ctx->stream));
-            ZK_HIP(ctx, hipMemcpyAsync(random_coeff.p, &one, 32, hipMemcpyHostToDevice, ctx->stream));
-            PK_TRY(zk_d2h(ctx, &com, srs->g, sizeof com));                    // commit(1) = g[0]
-        } else {
-            // n uniform coefficients: ChaCha20 in counter mode on the device, keyed from the session RNG
-            uint32_t key[8];
-            for (uint32_t& w_ : key) w_ = rng.next_u32();
-            PK_TRY(zk_fr_random(ctx, (const uint8_t*)key, 0, 0, random_coeff.p, n));
-            PK_TRY(commit_coeff(ctx, srs, random_coeff.fr(), n, &com));
-        }
-        tr.write_point(com);
-    }
-    trace.mark("random poly");
-    lag.y = tr.squeeze();
+    f.trace.mark("lookup phi");
+    return ZK_OK;
+}
 
-    // ---- coefficient forms of everything the quotient reads and the proof opens
-    std::vector<DevBuf> pz_coeff(pk->C), m_coeff(pk->L), phi_coeff(pk->L);
-    {   // one batch: several columns share a launch (ntt_run_many)
-        std::vector<Fr*> dsts;
-        std::vector<const Fr*> srcs;
-        auto want = [&](const DevBuf& lagv, DevBuf* co) -> int {
-            if (!co->alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            dsts.push_back(co->fr());
-            srcs.push_back(lagv.fr());
-            return ZK_OK;
-        };
-        for (uint32_t i = 0; i < pk->A; ++i) if (!adv_coeff[i].p) PK_TRY(want(adv_lag[i], &adv_coeff[i]));
-        for (uint32_t c = 0; c < pk->C; ++c) PK_TRY(want(pz_lag[c], &pz_coeff[c]));
-        for (uint32_t l = 0; l < pk->L; ++l) { PK_TRY(want(lk_m[l], &m_coeff[l])); PK_TRY(want(lk_phi[l], &phi_coeff[l])); }
-        const Fr omega_inv = fr_inv_host(fr_root_of_unity(pk->k)), ninv = fr_inv_host(fr_from_u64(1ull << pk->k));
-        PK_TRY(ntt_run_many(ctx, dsts.data(), srcs.data(), dsts.size(), pk->k, omega_inv, &ninv, nullptr, nullptr, false));
+// ---- vanishing argument: the "random" polynomial.  In the reference's own proof it is the CONSTANT 1: the commitment in
+// [REF aggregator/data/batch-task.json: chunk_proofs[0]] is g[0] = (1, 2) and its evaluation is 1 (tests/test_reference_chunk_proof.py)
+// -- Scroll's halo2 fork commits no blinding polynomial; upstream PSE halo2 draws n uniform coefficients.  The verifier accepts
+// either (it only opens the commitment); ZK_VANISHING_ONE (default) does what the reference's prover did, ZK_VANISHING_UNIFORM
+// what upstream does.
+static int stage_vanishing_random(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const size_t n = f.n; host::XorShiftRng& rng = pr->rng; host::Transcript& tr = pr->tr;
+    const F4 one = host::fr_one();
+    PK_ALLOC(ctx, f.random_coeff, n * 32);
+    G1Affine com;
+    if (pr->vanishing_random == ZK_VANISHING_ONE) {
+        ZK_HIP(ctx, hipMemsetAsync(f.random_coeff.p, 0, n * 32, ctx->stream));
+        ZK_HIP(ctx, hipMemcpyAsync(f.random_coeff.p, &one, 32, hipMemcpyHostToDevice, ctx->stream));
+        PK_TRY(zk_d2h(ctx, &com, f.srs->g, sizeof com));                    // commit(1) = g[0]
+    } else {
+        // n uniform coefficients: ChaCha20 in counter mode on the device, keyed from the session RNG
+        uint32_t key[8];
+        for (uint32_t& w_ : key) w_ = rng.next_u32();
+        PK_TRY(zk_fr_random(ctx, (const uint8_t*)key, 0, 0, f.random_coeff.p, n));
+        PK_TRY(commit_coeff(ctx, f.srs, f.random_coeff.fr(), n, &com));
     }
-    trace.mark("coefficient forms");
-    // ---- the quotient's constraints in halo2's order: gates, permutation, lookups (folded with y below)
-    const int32_t rot_last = -(int32_t)(pk->bf + 1);
-    // The extended domain is evaluated one coset at a time (g_r = zeta * omega_ext^r, r < 2^(ext_k-k)):
-    // every column the program reads is taken to that coset with a size-n transform of its
-    // coefficients, the program runs over n rows (rotations are index shifts inside a coset), and
-    // the result, divided by the vanishing polynomial -- a constant g_r^n - 1 on a coset of H --
-    // lands at stride 2^(ext_k-k) in the extended buffer.  Live memory is one n-row block per
-    // column instead of 2^(ext_k-k) of them: what lets 10^3-column circuits fit.
-    //
-    // Degree classes.  h = (sum_i y^(K-1-i) g_i) / (X^n - 1) is linear in the constraints, and a constraint of
-    // degree g only needs (g - 1) n evaluation points, i.e. the cosets r that are multiples of
-    // 2^(E - e), e = ceil(log2(g - 1)), E = ext_k - k: the extended domain of size 2^(k+e) is the union of
-    // exactly those cosets.  The constraints are therefore grouped by e; class e is evaluated on its 2^e
-    // cosets only, brought to coefficient form over its own (smaller) extended domain and added to h.  A
-    // column that occurs only in low-degree constraints needs 2^e coset transforms instead of 2^E, and the
-    // low-degree part of the program runs over 2^e n rows instead of 2^E n.  The polynomial h -- and with
-    // it every proof byte -- is the same as when everything is evaluated on the full extended domain
-    // (what halo2's evaluate_h does); how much is saved depends on the circuit's degree profile.
-    // The plan (which class evaluates what, each class's program) is a function of the key: made once, make_quotient_plan.
-    std::shared_ptr<const QuotientPlan> qplan;
+    tr.write_point(com);
+    f.trace.mark("random poly");
+    return ZK_OK;
+}
+
+// ---- coefficient forms of everything the quotient reads and the proof opens
+static int stage_coefficient_forms(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n;
+    // one batch: several columns share a launch (ntt_run_many)
+    std::vector<Fr*> dsts;
+    std::vector<const Fr*> srcs;
+    auto want = [&](const DevBuf& lagv, DevBuf* co) -> int {
+        PK_ALLOC(ctx, *co, n * 32);
+        dsts.push_back(co->fr());
+        srcs.push_back(lagv.fr());
+        return ZK_OK;
+    };
+    for (uint32_t i = 0; i < pk->A; ++i) if (!pr->adv_coeff[i].p) PK_TRY(want(pr->adv_lag[i], &pr->adv_coeff[i]));
+    for (uint32_t c = 0; c < pk->C; ++c) PK_TRY(want(f.pz_lag[c], &f.pz_coeff[c]));
+    for (uint32_t l = 0; l < pk->L; ++l) { PK_TRY(want(f.lk_m[l], &f.m_coeff[l])); PK_TRY(want(f.lk_phi[l], &f.phi_coeff[l])); }
+    const Fr omega_inv = fr_inv_host(fr_root_of_unity(pk->k)), ninv = fr_inv_host(fr_from_u64(1ull << pk->k));
+    PK_TRY(ntt_run_many(ctx, dsts.data(), srcs.data(), dsts.size(), pk->k, omega_inv, &ninv, nullptr, nullptr, false));
+    f.trace.mark("coefficient forms");
+    return ZK_OK;
+}
+
+// ---- the quotient.  Its constraints come in halo2's order: gates, permutation, lookups (folded with y).
+// The extended domain is evaluated one coset at a time (g_r = zeta * omega_ext^r, r < 2^(ext_k-k)):
+// every column the program reads is taken to that coset with a size-n transform of its
+// coefficients, the program runs over n rows (rotations are index shifts inside a coset), and
+// the result, divided by the vanishing polynomial -- a constant g_r^n - 1 on a coset of H --
+// lands at stride 2^(ext_k-k) in the extended buffer.  Live memory is one n-row block per
+// column instead of 2^(ext_k-k) of them: what lets 10^3-column circuits fit.
+//
+// Degree classes.  h = (sum_i y^(K-1-i) g_i) / (X^n - 1) is linear in the constraints, and a constraint of
+// degree g only needs (g - 1) n evaluation points, i.e. the cosets r that are multiples of
+// 2^(E - e), e = ceil(log2(g - 1)), E = ext_k - k: the extended domain of size 2^(k+e) is the union of
+// exactly those cosets.  The constraints are therefore grouped by e; class e is evaluated on its 2^e
+// cosets only, brought to coefficient form over its own (smaller) extended domain and added to h.  A
+// column that occurs only in low-degree constraints needs 2^e coset transforms instead of 2^E, and the
+// low-degree part of the program runs over 2^e n rows instead of 2^E n.  The polynomial h -- and with
+// it every proof byte -- is the same as when everything is evaluated on the full extended domain
+// (what halo2's evaluate_h does); how much is saved depends on the circuit's degree profile.
+// The plan (which class evaluates what, each class's program) is a function of the key: made once, make_quotient_plan.
+struct Quotient {
+    std::shared_ptr<const QuotientPlan> plan;
+    uint32_t E = 0, K = 0, nparts = 0;
+    std::vector<DevBuf> h;                    // class e over its own extended domain, 2^(k+e) rows (the top class's is the quotient itself)
+    const QPlanClass& cls(uint32_t e) const { return plan->cls[e]; }
+    bool reads(uint32_t e, uint32_t ref) const { return std::find(cls(e).refs.begin(), cls(e).refs.end(), ref) != cls(e).refs.end(); }
+};
+// What lives as long as the pass over the cosets (and the exchange of its results) does.
+// Sharded session: the unit of work is a (class, coset) pair -- class e on coset r costs the transforms of the columns
+// that class reads plus its program -- and the pairs are dealt to the ranks longest first (every rank computes the same
+// deal).  A rank keeps the finished, already divided n-row results of its pairs; afterwards they are all-gathered round
+// by round (round t = every rank's t-th pair) and interleaved into the classes' buffers on every rank.
+struct QPair { uint32_t e, r; double cost; };
+struct CosetWork { uint32_t r = 0; Fr g; std::vector<uint32_t> active; std::unordered_map<uint32_t, const void*> part_of; };      // one coset: the classes this rank runs there, where each column's coset lies
+struct CosetPass {
+    bool cache_on = false;                    // the key's own columns are read from (and put into) the key's coset cache
+    std::vector<DevBuf> part_buf;             // one coset buffer per column that is transformed here: allocated on first use
+    DevBuf hpart;                             // one class program's values on one coset
+    Env part;                                 // `lag` with the columns of the current coset
+    std::vector<std::vector<QPair>> deal;     // per rank, in the order of evaluation (by coset, then class)
+    PairOwners owners;
+    std::vector<std::pair<uint32_t, Fr>> cosets;      // the cosets this rank works on, with g_r
+    std::vector<DevBuf> mine;                 // this rank's finished pairs, in the order of its deal
+    DevBuf rtmp, gbuf;                        // the exchange: one received block (host transport), world of them (device transports)
+    HostStaging host;
+};
+static bool key_column(uint32_t ref) { const uint32_t t = ref >> 24; return t == CT_FIXED || t == CT_SIGMA || t == CT_SPECIAL; }
+
+// the plan, the powers of y, the remainders of the split constraints, one buffer per class
+static int quotient_prepare(Finish& f, Quotient& q) {
+    zk_ctx* ctx = f.ctx; const zk_pk* pk = f.pk; const size_t n = f.n;
     {
         std::string err;
-        const int rc_plan = quotient_plan(pk, &qplan, &err);
+        const int rc_plan = quotient_plan(pk, &q.plan, &err);
         if (rc_plan) return ctx->fail(rc_plan, "%s", err.c_str());
     }
-    const uint32_t E = ext_k - k, K = qplan->K;
-    const bool sharded = pr->world > 1 && pr->gather;
-    struct QClass { const Prog& prog; const std::vector<uint32_t>& refs; uint32_t last; bool used; DevBuf h; };
-    std::vector<QClass> qc;
-    qc.reserve(E + 1);
-    for (uint32_t e = 0; e <= E; ++e) qc.push_back(QClass{qplan->cls[e].prog, qplan->cls[e].refs, qplan->cls[e].last, qplan->cls[e].used, DevBuf()});
-    struct Remainder { DevBuf coeff; };
-    std::vector<Remainder> rems(qplan->rems.size());
-    lag.ypow.resize(K + 1);
-    lag.ypow[0] = host::fr_one();
-    for (uint32_t g_ = 1; g_ <= K; ++g_) lag.ypow[g_] = host::fr_mul(lag.ypow[g_ - 1], lag.y);
-    if (!rems.empty()) {
-        Env lag_r = lag;                       // the remainders read the Lagrange forms of Z, m and phi as well
-        lag_r.perm_z = &pz_lag;
-        lag_r.lk_m = &lk_m;
-        lag_r.lk_phi = &lk_phi;
+    q.E = f.ext_k - f.k; q.K = q.plan->K; q.nparts = 1u << q.E;
+    const uint32_t E = q.E, K = q.K;
+    q.h.resize(E + 1);
+    f.rem_coeff.resize(q.plan->rems.size());
+    f.lag.ypow.resize(K + 1);
+    f.lag.ypow[0] = host::fr_one();
+    for (uint32_t g_ = 1; g_ <= K; ++g_) f.lag.ypow[g_] = host::fr_mul(f.lag.ypow[g_ - 1], f.lag.y);
+    if (!f.rem_coeff.empty()) {
+        Env lag_r = f.lag;                     // the remainders read the Lagrange forms of Z, m and phi as well
+        lag_r.perm_z = &f.pz_lag;
+        lag_r.lk_m = &f.lk_m;
+        lag_r.lk_phi = &f.lk_phi;
         std::vector<Fr*> dsts;
-        for (size_t j = 0; j < rems.size(); ++j) {
-            const QPlanRem& rp = qplan->rems[j];
-            if (!rems[j].coeff.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            PK_TRY(run_program(ctx, lag_r, rp.prog, rems[j].coeff.p));                  // the parts on H, folded with y
-            const F4 yp = host::fr_pow(lag.y, K - 1 - rp.last);                         // ... and weighted like the constraints they belong to
-            PK_TRY(zk_fr_scale(ctx, rems[j].coeff.p, &yp, n));
-            dsts.push_back(rems[j].coeff.fr());
+        for (size_t j = 0; j < f.rem_coeff.size(); ++j) {
+            const QPlanRem& rp = q.plan->rems[j];
+            PK_ALLOC(ctx, f.rem_coeff[j], n * 32);
+            PK_TRY(run_program(ctx, lag_r, rp.prog, f.rem_coeff[j].p));                 // the parts on H, folded with y
+            const F4 yp = host::fr_pow(f.lag.y, K - 1 - rp.last);                       // ... and weighted like the constraints they belong to
+            PK_TRY(zk_fr_scale(ctx, f.rem_coeff[j].p, &yp, n));
+            dsts.push_back(f.rem_coeff[j].fr());
         }
         const Fr omega_inv = fr_inv_host(fr_root_of_unity(pk->k)), ninv = fr_inv_host(fr_from_u64(1ull << pk->k));
         PK_TRY(ntt_run_many(ctx, dsts.data(), nullptr, dsts.size(), pk->k, omega_inv, &ninv, nullptr, nullptr, false));
-        trace.mark("  quotient: remainders of the split constraints");
+        f.trace.mark("  quotient: remainders of the split constraints");
     }
-    const std::vector<uint32_t>& refs = qplan->refs;          // every column any class reads
     for (uint32_t e = 0; e <= E; ++e)
-        if (qc[e].used || e == E) {
-            if (!qc[e].h.alloc(((size_t)n << e) * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            if (!qc[e].used) ZK_HIP(ctx, hipMemsetAsync(qc[e].h.p, 0, ((size_t)n << e) * 32, ctx->stream));
+        if (q.cls(e).used || e == E) {
+            PK_ALLOC(ctx, q.h[e], ((size_t)n << e) * 32);
+            if (!q.cls(e).used) ZK_HIP(ctx, hipMemsetAsync(q.h[e].p, 0, ((size_t)n << e) * 32, ctx->stream));
         }
-    DevBuf& h = qc[E].h;
-    {
-        const uint32_t nparts = 1u << E;
-        auto of_key = [](uint32_t ref) { const uint32_t t = ref >> 24; return t == CT_FIXED || t == CT_SIGMA || t == CT_SPECIAL; };
-        if (pk->part_cache_state < 0) {       // decide once: do the key's own cosets fit the budget?
-            size_t key_slots = 0;             // (column of the key, coset) pairs some class reads: what the cache will hold
-            for (uint32_t ref : refs) {
-                if (!of_key(ref)) continue;
-                for (uint32_t r = 0; r < nparts; ++r) {
-                    bool read = false;
-                    for (uint32_t e = 0; e <= E && !read; ++e)
-                        read = qc[e].used && (r & ((1u << (E - e)) - 1u)) == 0 && std::find(qc[e].refs.begin(), qc[e].refs.end(), ref) != qc[e].refs.end();
-                    key_slots += read;
-                }
-            }
-            // The budget is shared by every key alive on this context (a Prover keeps the chunk, compression and aggregation
-            // keys resident together): the cap (ZK_PK_COSET_CACHE_GB, default 96) or a third of the device, whichever is
-            // smaller, less what other keys already hold -- and it must fit what the device has free right now, counting
-            // the session pool's parked blocks as free (pool_trim gives them back).
-            const char* env = getenv("ZK_PK_COSET_CACHE_GB");
-            double budget = (env ? atof(env) : 96.0) * (double)(1ull << 30);
-            budget = std::min(budget, (double)ctx->prop.totalGlobalMem / 3.0) - (double)ctx->coset_cache_bytes;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-            const double need = (double)key_slots * n * 32.0;
-            const double session = (double)refs.size() * n * 32.0 + (double)((size_t)n << E) * 32.0 * 2.0;       // this proof's own coset buffers and h
-            pk->part_cache_state = (need <= budget && need + session <= (double)free_b + (double)ctx->pool_bytes) ? 1 : 0;
-            if (pk->part_cache_state) pk->part_cache.resize(nparts);
-        }
-        const bool cache_on = pk->part_cache_state >= 1;
-        std::vector<DevBuf> part_buf(refs.size());       // one coset buffer per column that is transformed here: allocated on first use
-        auto pre_coset = [&](uint32_t ref, uint32_t r) -> const void* {      // an advice column's coset r computed during the advice phases, if any
-            if ((ref >> 24) != CT_ADVICE || r >= pr->adv_coset.size()) return nullptr;
-            const uint32_t c_ = ref & 0xFFFFFFu;
-            return c_ < pr->adv_coset[r].size() ? pr->adv_coset[r][c_].p : nullptr;
-        };
-        DevBuf hpart;
-        if (!hpart.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-        if (late_cosets) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux, 0));          // the cosets computed beside the earlier stages are complete
-        Env part = lag;
-        const Fr w_n = fr_root_of_unity(k), w_ext = fr_root_of_unity(ext_k);
-        Fr g = fr_zeta();
-        // Sharded session: the unit of work is a (class, coset) pair -- class e on coset r costs the transforms of the columns
-        // that class reads plus its program -- and the pairs are dealt to the ranks longest first (every rank computes the same
-        // deal).  A rank keeps the finished, already divided n-row results of its pairs; afterwards they are all-gathered round
-        // by round (round t = every rank's t-th pair) and interleaved into the classes' buffers on every rank.
-        const Fr one_fr = Fr::one();
-        std::vector<uint8_t> send, recv;
-        DevBuf rtmp, gbuf;
-        struct Pair { uint32_t e, r; double cost; };
-        std::vector<std::vector<Pair>> deal(sharded ? pr->world : 1);       // per rank, in the order of evaluation (by coset, then class)
-        std::vector<DevBuf> mine;                                           // this rank's finished pairs, in that order
-        auto owner = [&](uint32_t e, uint32_t r) -> uint32_t {
-            for (uint32_t q_ = 0; q_ < deal.size(); ++q_) for (const Pair& pp_ : deal[q_]) if (pp_.e == e && pp_.r == r) return q_;
-            return 0;
-        };
-        if (sharded) {
-            send.assign(n * 32, 0);
-            recv.resize((size_t)pr->world * n * 32);
-            if (!rtmp.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            std::vector<Pair> all;
-            for (uint32_t e = 0; e <= E; ++e)
-                if (qc[e].used)
-                    for (uint32_t r = 0; r < nparts; r += 1u << (E - e)) all.push_back({e, r, (double)qc[e].refs.size() + (double)qc[e].prog.size() / 64.0});
-            std::stable_sort(all.begin(), all.end(), [](const Pair& a, const Pair& b) { return a.cost > b.cost; });
-            std::vector<double> load(pr->world, 0.0);
-            for (const Pair& pp_ : all) {
-                uint32_t best = 0;
-                for (uint32_t q_ = 1; q_ < pr->world; ++q_) if (load[q_] < load[best]) best = q_;
-                load[best] += pp_.cost;
-                deal[best].push_back(pp_);
-            }
-            for (auto& d_ : deal) std::sort(d_.begin(), d_.end(), [](const Pair& a, const Pair& b) { return a.r != b.r ? a.r < b.r : a.e < b.e; });
-        }
-        // The cosets this rank works on, each with the classes active there (sharded: those of them this rank was dealt).
-        struct CosetWork { uint32_t r = 0; Fr g; std::vector<uint32_t> active; std::unordered_map<uint32_t, const void*> part_of; };
-        std::vector<std::pair<uint32_t, Fr>> rs;
-        for (uint32_t r_ = 0; r_ < nparts; ++r_) {
-            bool any = false;
-            for (uint32_t e = 0; e <= E && !any; ++e) any = qc[e].used && (r_ & ((1u << (E - e)) - 1u)) == 0 && (!sharded || owner(e, r_) == pr->rank);
-            if (any) rs.push_back({r_, g});
-            g = g * w_ext;
-        }
-        // ZK_QUOTIENT_OVERLAP=1 (round 6, measured and left OFF): the transforms of coset j + 1 run on the auxiliary stream WHILE the class
-        // programs of coset j run on the main one (into a second set of coset buffers: for an unsharded proof the odd cosets, which only
-        // the top class reads).  Both kernels are bound by vector issue; what each leaves to barriers / operand loads the other did not
-        // fill: EVM-style headline 2.393 s against 2.405 s, plain shape 0.989 against 0.979 (alternating A/B, profiles/r06_experiments.md).
-        const char* ov_env = getenv("ZK_QUOTIENT_OVERLAP");
-        const bool overlap = ov_env && atoi(ov_env) == 1 && rs.size() > 1 && ctx->ensure_aux();
-        std::vector<DevBuf> part_buf2(overlap ? refs.size() : 0);
-        struct EventPair { hipEvent_t e[2] = {nullptr, nullptr}; ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev_t;
-        if (overlap) for (hipEvent_t& x : ev_t.e) ZK_HIP(ctx, hipEventCreateWithFlags(&x, hipEventDisableTiming));
-        CosetWork work[2];
-        // the columns the active classes read on coset w.r: taken from where they already are (computed ahead, the key's cache) or
-        // transformed into `bufs` on the CURRENT stream of the context
-        auto transform = [&](CosetWork& w, std::vector<DevBuf>& bufs) -> int {
-            const uint32_t r_ = w.r;
-            w.active.clear();
-            for (uint32_t e = 0; e <= E; ++e)
-                if (qc[e].used && (r_ & ((1u << (E - e)) - 1u)) == 0 && (!sharded || owner(e, r_) == pr->rank)) w.active.push_back(e);
-            w.part_of.clear();
-            std::vector<const void*> bat_src;                 // the coset transforms of this round go out as one batch
-            std::vector<void*> bat_dst;
-            std::vector<std::pair<uint32_t, DevBuf>> fresh_slots;      // cache slots being filled: published only once they hold their coset
-            for (size_t i = 0; i < refs.size(); ++i) {
-                bool needed = false;
-                for (uint32_t e : w.active) needed |= std::find(qc[e].refs.begin(), qc[e].refs.end(), refs[i]) != qc[e].refs.end();
-                if (!needed) continue;
-                if (const void* pre = pre_coset(refs[i], r_)) { w.part_of[refs[i]] = pre; continue; }
-                if (!(cache_on && of_key(refs[i])) && !bufs[i].p && !bufs[i].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                void* dst = bufs[i].p;
-                DevBuf fresh;                             // a cache slot being filled: published only once it holds the coset
-                const bool cached = cache_on && of_key(refs[i]);
-                if (cached) {
-                    auto it = pk->part_cache[r_].find(refs[i]);
-                    if (it != pk->part_cache[r_].end()) { w.part_of[refs[i]] = it->second.p; continue; }   // computed by an earlier proof
-                    // a slot lives as long as the key, not the session's pool.  When the device has no room for it: give the
-                    // pool's parked blocks back and retry; if that fails too, freeze the cache (existing slots stay in use) and
-                    // compute this coset into a session buffer like any witness column's -- the proof goes on, uncached.
-                    const char* env_fail = getenv("ZK_PK_COSET_CACHE_FAIL_AFTER");        // test knob: the device "runs out" after this many slots
-                    const bool inject = env_fail && pk->part_cache_bytes / (n * 32) + fresh_slots.size() >= (size_t)atoll(env_fail);
-                    bool got = pk->part_cache_state == 1 && !inject && fresh.alloc_unpooled(n * 32);
-                    if (!got && pk->part_cache_state == 1) {
-                        (void)hipGetLastError();
-                        ctx->pool_trim();
-                        got = !inject && fresh.alloc_unpooled(n * 32);
-                        if (!got) { (void)hipGetLastError(); pk->part_cache_state = 2; }
-                    }
-                    if (got) dst = fresh.p;
-                    else {
-                        if (!bufs[i].p && !bufs[i].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                        dst = bufs[i].p;
-                    }
-                }
-                w.part_of[refs[i]] = dst;
-                if (refs[i] == colref(CT_SPECIAL, SP_X)) PK_TRY(zk_fr_powers(ctx, &w_n, &w.g, dst, n));   // X on the coset: g * omega^i
-                else {
-                    const Fr* cf = (refs[i] >> 24) == CT_SPLIT_R ? ((refs[i] & 0xFFFFFFu) < rems.size() ? rems[refs[i] & 0xFFFFFFu].coeff.fr() : nullptr)
-                                                                 : coeff_of(pk, refs[i], adv_coeff, inst_coeff, pz_coeff, m_coeff, phi_coeff);
-                    if (!cf) return ctx->fail(ZK_ERR_INVALID_ARG, "prover: unresolved column reference 0x%08x", refs[i]);
-                    bat_src.push_back(cf);
-                    bat_dst.push_back(dst);
-                }
-                if (cached && fresh.p) fresh_slots.emplace_back(refs[i], std::move(fresh));
-            }
-            PK_TRY(zk_coeff_to_coset_batch(ctx, bat_src.data(), k, &w.g, bat_dst.data(), bat_src.size()));
-            for (auto& fs : fresh_slots) {
-                pk->part_cache_bytes += n * 32;
-                ctx->coset_cache_bytes += n * 32;
-                pk->part_cache[r_][fs.first] = std::move(fs.second);
-            }
-            return ZK_OK;
-        };
-        auto programs = [&](CosetWork& w) -> int {
-            const uint32_t r_ = w.r;
-            part.part = &w.part_of;
-            Fr gn = w.g;
-            for (uint32_t i = 0; i < k; ++i) gn = sqr(gn);
-            const Fr vinv = fr_inv_host(gn - Fr::one());
-            for (uint32_t e : w.active) {
-                ctx->prof_tag = "quotient_coset";
-                const int rc_q = run_program(ctx, part, qc[e].prog, hpart.p);
-                ctx->prof_tag = nullptr;
-                PK_TRY(rc_q);
-                // class e lags (K - 1 - last) positions behind the end of the constraint list: its sum still takes y^(K-1-last)
-                const F4 yp = host::fr_pow(lag.y, K - 1 - qc[e].last);
-                Fr scale;
-                memcpy((void*)&scale, yp.l, 32);
-                scale = scale * vinv;
-                if (sharded) {                 // peers receive the finished values: keep them until the exchange
-                    PK_TRY(zk_fr_scale(ctx, hpart.p, &scale, n));
-                    DevBuf keep;
-                    if (!keep.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                    ZK_HIP(ctx, hipMemcpyAsync(keep.p, hpart.p, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-                    mine.push_back(std::move(keep));
-                }
-                PK_TRY(zk_fr_scatter_scaled(ctx, hpart.p, n, sharded ? &one_fr : &scale, qc[e].h.p, (size_t)1 << e, r_ >> (E - e)));
-            }
-            return ZK_OK;
-        };
-        for (size_t j = 0; j < rs.size(); ++j) {
-            CosetWork& cur = work[j & 1];
-            if (j == 0) {
-                cur.r = rs[0].first; cur.g = rs[0].second;
-                PK_TRY(transform(cur, part_buf));
-                trace.mark("  quotient: cosets of the columns");
-            }
-            if (overlap && j + 1 < rs.size()) {
-                // the auxiliary stream starts behind everything the main stream holds so far -- the programs of coset j - 1, which read the
-                // buffer set the transforms below write; pooled blocks handed out now were last used there as well
-                CosetWork& nxt = work[(j + 1) & 1];
-                nxt.r = rs[j + 1].first; nxt.g = rs[j + 1].second;
-                ZK_HIP(ctx, hipEventRecord(ctx->ev_aux, ctx->stream));
-                ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->ev_aux, 0));
-                hipStream_t main_stream = ctx->stream;
-                ctx->stream = ctx->stream_aux;
-                const int rc_t = transform(nxt, ((j + 1) & 1) ? part_buf2 : part_buf);
-                hipError_t e_rec = rc_t ? hipSuccess : hipEventRecord(ev_t.e[(j + 1) & 1], ctx->stream_aux);
-                ctx->stream = main_stream;
-                PK_TRY(rc_t);
-                ZK_HIP(ctx, e_rec);
-            }
-            if (overlap && j > 0) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev_t.e[j & 1], 0));
-            PK_TRY(programs(cur));
-            trace.mark("  quotient: program");
-            if (!overlap && j + 1 < rs.size()) {
-                CosetWork& nxt = work[(j + 1) & 1];
-                nxt.r = rs[j + 1].first; nxt.g = rs[j + 1].second;
-                PK_TRY(transform(nxt, part_buf));
-                trace.mark("  quotient: cosets of the columns");
-            }
-        }
-        if (sharded) {
-            if (mine.size() != deal[pr->rank].size()) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: %zu pairs evaluated, %zu dealt", mine.size(), deal[pr->rank].size());
-            size_t rounds = 0;
-            for (const auto& d_ : deal) rounds = std::max(rounds, d_.size());
-            for (size_t t = 0; t < rounds; ++t) {
-                const void* mine_t = t < mine.size() ? mine[t].p : hpart.p;           // a rank without a t-th pair sends filler nobody reads
-                const char* got = nullptr;
-                if (pr->use_comm) {
-                    // in-library RCCL: the finished pairs go device to device, stream-ordered (no host copy, no synchronisation)
-                    if (!gbuf.p && !gbuf.alloc((size_t)pr->world * n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                    PK_TRY(comm_allgather_dev(ctx, mine_t, n * 32, gbuf.p));
-                    got = (const char*)gbuf.p;
-                } else if (pr->gather_dev) {
-                    // a caller-supplied device all-gather (zk_proof_set_device_gather): device to device as well; the callback completes on return
-                    if (!gbuf.p && !gbuf.alloc((size_t)pr->world * n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                    PK_TRY(zk_ctx_sync(ctx));
-                    if (pr->gather_dev(pr->gather_dev_user, mine_t, n * 32, gbuf.p)) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: device all-gather callback failed");
-                    got = (const char*)gbuf.p;
-                } else {
-                    if (t < mine.size()) PK_TRY(zk_d2h(ctx, send.data(), mine_t, n * 32));
-                    if (pr->gather(pr->gather_user, send.data(), n * 32, recv.data())) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: all-gather callback failed");
-                }
-                for (uint32_t q_ = 0; q_ < pr->world; ++q_) {
-                    if (q_ == pr->rank || t >= deal[q_].size()) continue;
-                    const Pair& pp_ = deal[q_][t];
-                    const void* src = got ? (const void*)(got + (size_t)q_ * n * 32) : nullptr;
-                    if (!src) { PK_TRY(zk_h2d(ctx, rtmp.p, recv.data() + (size_t)q_ * n * 32, n * 32)); src = rtmp.p; }
-                    PK_TRY(zk_fr_scatter_scaled(ctx, src, n, &one_fr, qc[pp_.e].h.p, (size_t)1 << pp_.e, pp_.r >> (E - pp_.e)));
-                }
-            }
-        }
-    }
-    // every class back to coefficients over its own extended domain; the smaller ones are added into h
-    for (uint32_t e = 0; e < E; ++e) {
-        if (!qc[e].used) continue;
-        PK_TRY(zk_extended_to_coeff(ctx, qc[e].h.p, k + e));
-    }
-    PK_TRY(zk_extended_to_coeff(ctx, h.p, ext_k));
-    for (uint32_t e = 0; e < E; ++e) {
-        if (!qc[e].used) continue;
-        PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_ADD, h.p, qc[e].h.p, h.p, n << e));
-        qc[e].h.release();
-    }
-    trace.mark("quotient eval + ifft");
-    const uint32_t pieces = pk->d - 1;
-    {
-        std::vector<const void*> hptrs(pieces);
-        for (uint32_t i = 0; i < pieces; ++i) hptrs[i] = h.fr() + (size_t)i * n;
-        std::vector<G1Affine> coms(pieces);
-        PK_TRY(sharded_commit(ctx, pr.get(), srs, 0, hptrs.data(), pieces, n, coms.data()));
-        for (const G1Affine& com : coms) tr.write_point(com);
-    }
+    return ZK_OK;
+}
 
-    trace.mark("h commits");
-    const F4 x = tr.squeeze();
-    // ---- evaluations, written in halo2's order: advice queries, fixed queries, the random polynomial,
-    // the permutation's sigma polynomials, per permutation set Z(x), Z(wx) (and Z(w^last x) for all but
-    // the last set), per lookup phi(x), phi(wx), m(x)
-    const F4 w = [&] { Fr t = fr_root_of_unity(k); F4 r; memcpy(r.l, &t, 32); return r; }();
-    const F4 w_inv = host::fr_inv(w);
-    auto rotate = [&](int32_t rot) { F4 p = x; const F4 b = rot >= 0 ? w : w_inv; for (int32_t i = 0; i < (rot >= 0 ? rot : -rot); ++i) p = host::fr_mul(p, b); return p; };
-    const int64_t nn = (int64_t)n;
-    auto norm_rot = [&](int32_t rot) { return (int32_t)((((int64_t)rot % nn) + nn) % nn); };    // rotations are points: x w^rot, rot mod n
-    struct Open { const Fr* poly; int32_t rot; F4 eval; };
-    std::vector<Open> evals;
-    auto eval_at = [&](const Fr* coeffs, int32_t rot, F4* out) -> int { const F4 pt = rotate(rot); return zk_poly_eval(ctx, coeffs, n, &pt, out); };
-    for (const Query& qy : pk->adv_q) evals.push_back({adv_coeff[qy.idx].fr(), qy.rot, host::fr_zero()});
-    const size_t e_fix = evals.size();
-    for (const Query& qy : pk->fix_q) evals.push_back({pk->fixed_coeff[qy.idx].fr(), qy.rot, host::fr_zero()});
-    const size_t e_random = evals.size();
-    evals.push_back({random_coeff.fr(), 0, host::fr_zero()});
-    const size_t e_sigma = evals.size();
-    for (uint32_t j = 0; j < pk->P; ++j) evals.push_back({pk->sigma_coeff[j].fr(), 0, host::fr_zero()});
-    std::vector<size_t> e_pz(pk->C);
-    for (uint32_t c = 0; c < pk->C; ++c) {
-        e_pz[c] = evals.size();
-        for (int32_t rot : {0, 1}) evals.push_back({pz_coeff[c].fr(), rot, host::fr_zero()});
-        if (c + 1 < pk->C) evals.push_back({pz_coeff[c].fr(), rot_last, host::fr_zero()});
-    }
-    const size_t e_lk = evals.size();
-    for (uint32_t l = 0; l < pk->L; ++l) {
-        for (int32_t rot : {0, 1}) evals.push_back({phi_coeff[l].fr(), rot, host::fr_zero()});
-        evals.push_back({m_coeff[l].fr(), 0, host::fr_zero()});
-    }
-    {   // every (polynomial, point) pair in one pass: one table per distinct point, one Horner launch, one download
-        std::vector<int32_t> distinct;
-        std::vector<F4> points;
-        std::vector<uint32_t> pidx(evals.size());
-        std::vector<const void*> ptrs(evals.size());
-        for (size_t i = 0; i < evals.size(); ++i) {
-            const int32_t nr = norm_rot(evals[i].rot);
-            size_t at = std::find(distinct.begin(), distinct.end(), nr) - distinct.begin();
-            if (at == distinct.size()) { distinct.push_back(nr); points.push_back(rotate(evals[i].rot)); }
-            pidx[i] = (uint32_t)at;
-            ptrs[i] = evals[i].poly;
+// decided once per key: do the key's own cosets fit the budget?
+static void quotient_decide_key_cache(Finish& f, const Quotient& q) {
+    zk_ctx* ctx = f.ctx; const zk_pk* pk = f.pk; const size_t n = f.n;
+    const std::vector<uint32_t>& refs = q.plan->refs;
+    size_t key_slots = 0;             // (column of the key, coset) pairs some class reads: what the cache will hold
+    for (uint32_t ref : refs) {
+        if (!key_column(ref)) continue;
+        for (uint32_t r = 0; r < q.nparts; ++r) {
+            bool read = false;
+            for (uint32_t e = 0; e <= q.E && !read; ++e) read = q.cls(e).used && class_on_coset(q.E, e, r) && q.reads(e, ref);
+            key_slots += read;
         }
-        std::vector<F4> vals(evals.size());
-        if (sharded) {
-            // sharded session: pair i is evaluated by rank i mod world; the 32-byte values are all-gathered (every rank holds every
-            // coefficient form, so which rank evaluates what is free to choose)
-            const size_t per = (evals.size() + pr->world - 1) / pr->world;
-            std::vector<const void*> my_ptrs;
-            std::vector<uint32_t> my_pidx;
-            for (size_t i = pr->rank; i < evals.size(); i += pr->world) { my_ptrs.push_back(ptrs[i]); my_pidx.push_back(pidx[i]); }
-            std::vector<F4> local(per, host::fr_zero()), all(per * pr->world);
-            if (!my_ptrs.empty()) PK_TRY(zk_poly_eval_pairs(ctx, my_ptrs.data(), my_pidx.data(), my_ptrs.size(), points.data(), points.size(), n, local.data()));
-            if (pr->gather(pr->gather_user, local.data(), per * sizeof(F4), all.data())) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: all-gather callback failed");
-            for (size_t i = 0; i < evals.size(); ++i) vals[i] = all[(i % pr->world) * per + i / pr->world];
-        } else
-            PK_TRY(zk_poly_eval_pairs(ctx, ptrs.data(), pidx.data(), evals.size(), points.data(), points.size(), n, vals.data()));
-        for (size_t i = 0; i < evals.size(); ++i) evals[i].eval = vals[i];
-        for (const Open& o : evals) tr.write_scalar(o.eval);
     }
-    trace.mark("evaluations");
-    // h(X) = sum_i x^(n i) h_i(X): opened at x, the verifier derives its expected value itself
-    DevBuf hcomb;
-    F4 h_eval;
+    // The budget is shared by every key alive on this context (a Prover keeps the chunk, compression and aggregation
+    // keys resident together): the cap (ZK_PK_COSET_CACHE_GB, default 96) or a third of the device, whichever is
+    // smaller, less what other keys already hold -- and it must fit what the device has free right now, counting
+    // the session pool's parked blocks as free (pool_trim gives them back).
+    const char* env = getenv("ZK_PK_COSET_CACHE_GB");
+    double budget = (env ? atof(env) : 96.0) * (double)(1ull << 30);
+    budget = std::min(budget, (double)ctx->prop.totalGlobalMem / 3.0) - (double)ctx->coset_cache_bytes;
+    const size_t free_b = device_free_bytes();          // unknown counts as none
+    const double need = (double)key_slots * n * 32.0;
+    const double session = (double)refs.size() * n * 32.0 + (double)((size_t)n << q.E) * 32.0 * 2.0;       // this proof's own coset buffers and h
+    pk->part_cache_state = (need <= budget && need + session <= (double)free_b + (double)ctx->pool_bytes) ? 1 : 0;
+    if (pk->part_cache_state) pk->part_cache.resize(q.nparts);
+}
+
+// the (class, coset) pairs dealt to the ranks, who owns which, and the cosets this rank works on
+static int quotient_deal_pairs(Finish& f, const Quotient& q, CosetPass& cp) {
+    zk_ctx* ctx = f.ctx; const zk_proof* pr = f.pr;
+    const uint32_t E = q.E;
+    cp.deal.resize(f.sharded ? pr->world : 1);
+    cp.owners = PairOwners{E, pr->rank, f.sharded, std::vector<uint32_t>((size_t)(E + 1) << E, 0u)};
+    if (f.sharded) {
+        PK_ALLOC(ctx, cp.rtmp, f.n * 32);
+        std::vector<QPair> all;
+        for (uint32_t e = 0; e <= E; ++e)
+            if (q.cls(e).used)
+                for (uint32_t r = 0; r < q.nparts; r += 1u << (E - e)) all.push_back({e, r, (double)q.cls(e).refs.size() + (double)q.cls(e).prog.size() / 64.0});
+        std::stable_sort(all.begin(), all.end(), [](const QPair& a, const QPair& b) { return a.cost > b.cost; });
+        std::vector<double> load(pr->world, 0.0);
+        for (const QPair& pp_ : all) {
+            uint32_t best = 0;
+            for (uint32_t q_ = 1; q_ < pr->world; ++q_) if (load[q_] < load[best]) best = q_;
+            load[best] += pp_.cost;
+            cp.deal[best].push_back(pp_);
+            cp.owners.owner[cp.owners.at(pp_.e, pp_.r)] = best;
+        }
+        for (auto& d_ : cp.deal) std::sort(d_.begin(), d_.end(), [](const QPair& a, const QPair& b) { return a.r != b.r ? a.r < b.r : a.e < b.e; });
+    }
+    const Fr w_ext = fr_root_of_unity(f.ext_k);
+    Fr g = fr_zeta();
+    for (uint32_t r_ = 0; r_ < q.nparts; ++r_) {
+        bool any = false;
+        for (uint32_t e = 0; e <= E && !any; ++e) any = q.cls(e).used && cp.owners.mine(e, r_);
+        if (any) cp.cosets.push_back({r_, g});
+        g = g * w_ext;
+    }
+    return ZK_OK;
+}
+
+// the columns the active classes read on coset w.r: taken from where they already are (computed ahead, the key's cache) or
+// transformed into the pass's coset buffers
+static int quotient_transform(Finish& f, const Quotient& q, CosetPass& cp, CosetWork& w) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n;
+    const std::vector<uint32_t>& refs = q.plan->refs;
+    std::vector<DevBuf>& bufs = cp.part_buf;
+    const bool cache_on = cp.cache_on;
+    const uint32_t k = f.k;
+    const Fr w_n = fr_root_of_unity(k);
+    auto pre_coset = [&](uint32_t ref, uint32_t r) -> const void* {      // an advice column's coset r computed during the advice phases, if any
+        if ((ref >> 24) != CT_ADVICE || r >= pr->adv_coset.size()) return nullptr;
+        const uint32_t c_ = ref & 0xFFFFFFu;
+        return c_ < pr->adv_coset[r].size() ? pr->adv_coset[r][c_].p : nullptr;
+    };
+    const uint32_t r_ = w.r;
+    w.active.clear();
+    for (uint32_t e = 0; e <= q.E; ++e)
+        if (q.cls(e).used && cp.owners.mine(e, r_)) w.active.push_back(e);
+    w.part_of.clear();
+    std::vector<const void*> bat_src;                 // the coset transforms of this round go out as one batch
+    std::vector<void*> bat_dst;
+    std::vector<std::pair<uint32_t, DevBuf>> fresh_slots;      // cache slots being filled: published only once they hold their coset
+    for (size_t i = 0; i < refs.size(); ++i) {
+        bool needed = false;
+        for (uint32_t e : w.active) needed |= q.reads(e, refs[i]);
+        if (!needed) continue;
+        if (const void* pre = pre_coset(refs[i], r_)) { w.part_of[refs[i]] = pre; continue; }
+        if (!(cache_on && key_column(refs[i])) && !bufs[i].p) PK_ALLOC(ctx, bufs[i], n * 32);
+        void* dst = bufs[i].p;
+        DevBuf fresh;                             // a cache slot being filled: published only once it holds the coset
+        const bool cached = cache_on && key_column(refs[i]);
+        if (cached) {
+            auto it = pk->part_cache[r_].find(refs[i]);
+            if (it != pk->part_cache[r_].end()) { w.part_of[refs[i]] = it->second.p; continue; }   // computed by an earlier proof
+            // a slot lives as long as the key, not the session's pool.  When the device has no room for it: give the
+            // pool's parked blocks back and retry; if that fails too, freeze the cache (existing slots stay in use) and
+            // compute this coset into a session buffer like any witness column's -- the proof goes on, uncached.
+            const char* env_fail = getenv("ZK_PK_COSET_CACHE_FAIL_AFTER");        // test knob: the device "runs out" after this many slots
+            const bool inject = env_fail && pk->part_cache_bytes / (n * 32) + fresh_slots.size() >= (size_t)atoll(env_fail);
+            bool got = pk->part_cache_state == 1 && !inject && fresh.alloc_unpooled(n * 32);
+            if (!got && pk->part_cache_state == 1) {
+                (void)hipGetLastError();
+                ctx->pool_trim();
+                got = !inject && fresh.alloc_unpooled(n * 32);
+                if (!got) { (void)hipGetLastError(); pk->part_cache_state = 2; }
+            }
+            if (got) dst = fresh.p;
+            else {
+                if (!bufs[i].p) PK_ALLOC(ctx, bufs[i], n * 32);
+                dst = bufs[i].p;
+            }
+        }
+        w.part_of[refs[i]] = dst;
+        if (refs[i] == colref(CT_SPECIAL, SP_X)) PK_TRY(zk_fr_powers(ctx, &w_n, &w.g, dst, n));   // X on the coset: g * omega^i
+        else {
+            const Fr* cf = (refs[i] >> 24) == CT_SPLIT_R ? ((refs[i] & 0xFFFFFFu) < f.rem_coeff.size() ? f.rem_coeff[refs[i] & 0xFFFFFFu].fr() : nullptr)
+                                                         : coeff_of(pk, refs[i], pr->adv_coeff, pr->inst_coeff, f.pz_coeff, f.m_coeff, f.phi_coeff);
+            if (!cf) return ctx->fail(ZK_ERR_INVALID_ARG, "prover: unresolved column reference 0x%08x", refs[i]);
+            bat_src.push_back(cf);
+            bat_dst.push_back(dst);
+        }
+        if (cached && fresh.p) fresh_slots.emplace_back(refs[i], std::move(fresh));
+    }
+    PK_TRY(zk_coeff_to_coset_batch(ctx, bat_src.data(), k, &w.g, bat_dst.data(), bat_src.size()));
+    for (auto& fs : fresh_slots) {
+        pk->part_cache_bytes += n * 32;
+        ctx->coset_cache_bytes += n * 32;
+        pk->part_cache[r_][fs.first] = std::move(fs.second);
+    }
+    return ZK_OK;
+}
+
+// the programs of the classes active on coset w.r, divided by the vanishing polynomial, into the classes' buffers
+static int quotient_programs(Finish& f, Quotient& q, CosetPass& cp, CosetWork& w) {
+    zk_ctx* ctx = f.ctx; const size_t n = f.n;
+    const uint32_t k = f.k, E = q.E, K = q.K;
+    const bool sharded = f.sharded;
+    const Fr one_fr = Fr::one();
+    DevBuf& hpart = cp.hpart;
+    Env& part = cp.part;
+    std::vector<DevBuf>& mine = cp.mine;
+    const uint32_t r_ = w.r;
+    part.part = &w.part_of;
+    Fr gn = w.g;
+    for (uint32_t i = 0; i < k; ++i) gn = sqr(gn);
+    const Fr vinv = fr_inv_host(gn - Fr::one());
+    for (uint32_t e : w.active) {
+        ctx->prof_tag = "quotient_coset";
+        const int rc_q = run_program(ctx, part, q.cls(e).prog, hpart.p);
+        ctx->prof_tag = nullptr;
+        PK_TRY(rc_q);
+        // class e lags (K - 1 - last) positions behind the end of the constraint list: its sum still takes y^(K-1-last)
+        const F4 yp = host::fr_pow(f.lag.y, K - 1 - q.cls(e).last);
+        Fr scale;
+        memcpy((void*)&scale, yp.l, 32);
+        scale = scale * vinv;
+        if (sharded) {                 // peers receive the finished values: keep them until the exchange
+            PK_TRY(zk_fr_scale(ctx, hpart.p, &scale, n));
+            DevBuf keep;
+            PK_ALLOC(ctx, keep, n * 32);
+            ZK_HIP(ctx, hipMemcpyAsync(keep.p, hpart.p, n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+            mine.push_back(std::move(keep));
+        }
+        PK_TRY(zk_fr_scatter_scaled(ctx, hpart.p, n, sharded ? &one_fr : &scale, q.h[e].p, (size_t)1 << e, r_ >> (E - e)));
+    }
+    return ZK_OK;
+}
+
+// sharded session: the finished pairs of every rank into the classes' buffers of every rank
+static int quotient_exchange_pairs(Finish& f, Quotient& q, CosetPass& cp) {
+    zk_ctx* ctx = f.ctx; const zk_proof* pr = f.pr; const size_t n = f.n;
+    const Fr one_fr = Fr::one();
+    if (cp.mine.size() != cp.deal[pr->rank].size()) return ctx->fail(ZK_ERR_INVALID_ARG, "sharded session: %zu pairs evaluated, %zu dealt", cp.mine.size(), cp.deal[pr->rank].size());
+    size_t rounds = 0;
+    for (const auto& d_ : cp.deal) rounds = std::max(rounds, d_.size());
+    for (size_t t = 0; t < rounds; ++t) {
+        const void* mine_t = t < cp.mine.size() ? cp.mine[t].p : cp.hpart.p;           // a rank without a t-th pair sends filler nobody reads
+        // in-library RCCL: the finished pairs go device to device, stream-ordered (no host copy, no synchronisation); a caller-supplied
+        // device all-gather (zk_proof_set_device_gather): device to device as well, the callback completes on return; else through the host
+        if ((pr->use_comm || pr->gather_dev) && !cp.gbuf.p) PK_ALLOC(ctx, cp.gbuf, (size_t)pr->world * n * 32);
+        bool on_device = false;
+        PK_TRY(allgather_rows(ctx, pr, pr->use_comm, mine_t, t < cp.mine.size(), n * 32, cp.gbuf.p, cp.host, &on_device));
+        for (uint32_t q_ = 0; q_ < pr->world; ++q_) {
+            if (q_ == pr->rank || t >= cp.deal[q_].size()) continue;
+            const QPair& pp_ = cp.deal[q_][t];
+            const void* src = on_device ? (const void*)((const char*)cp.gbuf.p + (size_t)q_ * n * 32) : nullptr;
+            if (!src) { PK_TRY(zk_h2d(ctx, cp.rtmp.p, cp.host.recv.data() + (size_t)q_ * n * 32, n * 32)); src = cp.rtmp.p; }
+            PK_TRY(zk_fr_scatter_scaled(ctx, src, n, &one_fr, q.h[pp_.e].p, (size_t)1 << pp_.e, pp_.r >> (q.E - pp_.e)));
+        }
+    }
+    return ZK_OK;
+}
+
+// every class back to coefficients over its own extended domain; the smaller ones are added into h
+static int quotient_to_coeff(Finish& f, Quotient& q) {
+    zk_ctx* ctx = f.ctx;
+    const uint32_t E = q.E;
+    DevBuf& h = q.h[E];
+    for (uint32_t e = 0; e < E; ++e) {
+        if (!q.cls(e).used) continue;
+        PK_TRY(zk_extended_to_coeff(ctx, q.h[e].p, f.k + e));
+    }
+    PK_TRY(zk_extended_to_coeff(ctx, h.p, f.ext_k));
+    for (uint32_t e = 0; e < E; ++e) {
+        if (!q.cls(e).used) continue;
+        PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_ADD, h.p, q.h[e].p, h.p, f.n << e));
+        q.h[e].release();
+    }
+    f.h = std::move(h);
+    return ZK_OK;
+}
+
+static int stage_quotient(Finish& f) {
+    zk_ctx* ctx = f.ctx;
+    Quotient q;
+    PK_TRY(quotient_prepare(f, q));
     {
-        if (!hcomb.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-        F4 xn = x;
-        for (uint32_t i = 0; i < k; ++i) xn = host::fr_mul(xn, xn);
-        std::vector<uint32_t> words;
-        std::vector<const void*> cols;
-        for (uint32_t i = pieces; i-- > 0;) { words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_FOLD, 0u, 0u}); cols.push_back(h.fr() + (size_t)i * n); }
-        PK_TRY(zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), cols.data(), (uint32_t)cols.size(), &xn, 1, k, k, 0, hcomb.p));
-        PK_TRY(eval_at(hcomb.fr(), 0, &h_eval));
+        CosetPass cp;                         // its buffers go back to the pool before the classes are transformed back
+        if (f.pk->part_cache_state < 0) quotient_decide_key_cache(f, q);
+        cp.cache_on = f.pk->part_cache_state >= 1;
+        cp.part_buf.resize(q.plan->refs.size());
+        PK_ALLOC(ctx, cp.hpart, f.n * 32);
+        if (f.late_cosets) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux, 0));          // the cosets computed beside the earlier stages are complete
+        cp.part = f.lag;
+        PK_TRY(quotient_deal_pairs(f, q, cp));
+        CosetWork work;
+        for (const auto& rg : cp.cosets) {
+            work.r = rg.first; work.g = rg.second;
+            PK_TRY(quotient_transform(f, q, cp, work));
+            f.trace.mark("  quotient: cosets of the columns");
+            PK_TRY(quotient_programs(f, q, cp, work));
+            f.trace.mark("  quotient: program");
+        }
+        if (f.sharded) PK_TRY(quotient_exchange_pairs(f, q, cp));
     }
-    trace.mark("h recombination");
-    // ---- the multi-open's queries in halo2's order (plonk::prover::create_proof): advice, permutation
-    // products (x and wx per set, then w^last x for all but the last set in REVERSE set order), lookups,
-    // fixed, permutation sigma, then h and the random polynomial
-    std::vector<Open> queries;
+    PK_TRY(quotient_to_coeff(f, q));
+    f.trace.mark("quotient eval + ifft");
+    return ZK_OK;
+}
+
+static int stage_h_commits(Finish& f) {
+    zk_ctx* ctx = f.ctx; const size_t n = f.n;
+    const uint32_t pieces = f.pk->d - 1;
+    std::vector<const void*> hptrs(pieces);
+    for (uint32_t i = 0; i < pieces; ++i) hptrs[i] = f.h.fr() + (size_t)i * n;
+    std::vector<G1Affine> coms(pieces);
+    PK_TRY(sharded_commit(ctx, f.pr, f.srs, 0, hptrs.data(), pieces, n, coms.data()));
+    for (const G1Affine& com : coms) f.pr->tr.write_point(com);
+    f.trace.mark("h commits");
+    return ZK_OK;
+}
+
+// ---- evaluations, written in halo2's order: advice queries, fixed queries, the random polynomial,
+// the permutation's sigma polynomials, per permutation set Z(x), Z(wx) (and Z(w^last x) for all but
+// the last set), per lookup phi(x), phi(wx), m(x)
+static int stage_evaluations(Finish& f) {
+    zk_ctx* ctx = f.ctx; zk_proof* pr = f.pr; const zk_pk* pk = f.pk; const size_t n = f.n;
+    const int32_t rot_last = -(int32_t)(pk->bf + 1);
+    std::vector<Open>& evals = f.evals;
+    for (const Query& qy : pk->adv_q) evals.push_back({pr->adv_coeff[qy.idx].fr(), qy.rot, host::fr_zero()});
+    f.e_fix = evals.size();
+    for (const Query& qy : pk->fix_q) evals.push_back({pk->fixed_coeff[qy.idx].fr(), qy.rot, host::fr_zero()});
+    f.e_random = evals.size();
+    evals.push_back({f.random_coeff.fr(), 0, host::fr_zero()});
+    f.e_sigma = evals.size();
+    for (uint32_t j = 0; j < pk->P; ++j) evals.push_back({pk->sigma_coeff[j].fr(), 0, host::fr_zero()});
+    for (uint32_t c = 0; c < pk->C; ++c) {
+        f.e_pz[c] = evals.size();
+        for (int32_t rot : {0, 1}) evals.push_back({f.pz_coeff[c].fr(), rot, host::fr_zero()});
+        if (c + 1 < pk->C) evals.push_back({f.pz_coeff[c].fr(), rot_last, host::fr_zero()});
+    }
+    f.e_lk = evals.size();
+    for (uint32_t l = 0; l < pk->L; ++l) {
+        for (int32_t rot : {0, 1}) evals.push_back({f.phi_coeff[l].fr(), rot, host::fr_zero()});
+        evals.push_back({f.m_coeff[l].fr(), 0, host::fr_zero()});
+    }
+    // every (polynomial, point) pair in one pass: one table per distinct point, one Horner launch, one download
+    std::vector<int32_t> distinct;
+    std::vector<F4> points;
+    std::vector<uint32_t> pidx(evals.size());
+    std::vector<const void*> ptrs(evals.size());
+    for (size_t i = 0; i < evals.size(); ++i) {
+        const int32_t nr = f.norm_rot(evals[i].rot);
+        size_t at = std::find(distinct.begin(), distinct.end(), nr) - distinct.begin();
+        if (at == distinct.size()) { distinct.push_back(nr); points.push_back(f.rotate(evals[i].rot)); }
+        pidx[i] = (uint32_t)at;
+        ptrs[i] = evals[i].poly;
+    }
+    std::vector<F4> vals(evals.size());
+    if (f.sharded) {
+        // sharded session: pair i is evaluated by rank i mod world; the 32-byte values are all-gathered (every rank holds every
+        // coefficient form, so which rank evaluates what is free to choose)
+        std::vector<const void*> my_ptrs;
+        std::vector<uint32_t> my_pidx;
+        for (size_t i = pr->rank; i < evals.size(); i += pr->world) { my_ptrs.push_back(ptrs[i]); my_pidx.push_back(pidx[i]); }
+        std::vector<F4> local(share_size(pr, evals.size()), host::fr_zero());
+        if (!my_ptrs.empty()) PK_TRY(zk_poly_eval_pairs(ctx, my_ptrs.data(), my_pidx.data(), my_ptrs.size(), points.data(), points.size(), n, local.data()));
+        PK_TRY(share_gather(ctx, pr, local.data(), evals.size(), sizeof(F4), vals.data()));
+    } else
+        PK_TRY(zk_poly_eval_pairs(ctx, ptrs.data(), pidx.data(), evals.size(), points.data(), points.size(), n, vals.data()));
+    for (size_t i = 0; i < evals.size(); ++i) evals[i].eval = vals[i];
+    for (const Open& o : evals) pr->tr.write_scalar(o.eval);
+    f.trace.mark("evaluations");
+    return ZK_OK;
+}
+
+// h(X) = sum_i x^(n i) h_i(X): opened at x, the verifier derives its expected value itself
+static int stage_h_recombination(Finish& f) {
+    zk_ctx* ctx = f.ctx; const size_t n = f.n;
+    PK_ALLOC(ctx, f.hcomb, n * 32);
+    F4 xn = f.x;
+    for (uint32_t i = 0; i < f.k; ++i) xn = host::fr_mul(xn, xn);
+    std::vector<const void*> pieces(f.pk->d - 1);
+    for (size_t i = 0; i < pieces.size(); ++i) pieces[i] = f.h.fr() + i * n;
+    PK_TRY(lincomb(ctx, f.k, pieces, xn, f.hcomb.p));
+    PK_TRY(zk_poly_eval(ctx, f.hcomb.fr(), n, &f.x, &f.h_eval));
+    f.trace.mark("h recombination");
+    return ZK_OK;
+}
+
+// ---- the multi-open's queries in halo2's order (plonk::prover::create_proof): advice, permutation
+// products (x and wx per set, then w^last x for all but the last set in REVERSE set order), lookups,
+// fixed, permutation sigma, then h and the random polynomial
+static void stage_opening_queries(Finish& f) {
+    const zk_pk* pk = f.pk;
+    const std::vector<Open>& evals = f.evals;
+    std::vector<Open>& queries = f.queries;
+    const size_t e_fix = f.e_fix, e_random = f.e_random, e_sigma = f.e_sigma, e_lk = f.e_lk;
     for (size_t i = 0; i < e_fix; ++i) queries.push_back(evals[i]);
-    for (uint32_t c = 0; c < pk->C; ++c) { queries.push_back(evals[e_pz[c]]); queries.push_back(evals[e_pz[c] + 1]); }
-    for (uint32_t c = pk->C > 1 ? pk->C - 1 : 0; c-- > 0;) queries.push_back(evals[e_pz[c] + 2]);
+    for (uint32_t c = 0; c < pk->C; ++c) { queries.push_back(evals[f.e_pz[c]]); queries.push_back(evals[f.e_pz[c] + 1]); }
+    for (uint32_t c = pk->C > 1 ? pk->C - 1 : 0; c-- > 0;) queries.push_back(evals[f.e_pz[c] + 2]);
     for (size_t i = e_lk; i < evals.size(); ++i) queries.push_back(evals[i]);
     for (size_t i = e_fix; i < e_random; ++i) queries.push_back(evals[i]);
     for (size_t i = e_sigma; i < e_sigma + pk->P; ++i) queries.push_back(evals[i]);
-    queries.push_back({hcomb.fr(), 0, h_eval});
+    queries.push_back({f.hcomb.fr(), 0, f.h_eval});
     queries.push_back(evals[e_random]);
-    for (Open& o : queries) o.rot = norm_rot(o.rot);
-    auto point_of = [&](int32_t nrot) { return rotate(nrot > nn / 2 ? (int32_t)(nrot - nn) : nrot); };
-    // sum_j ch^j * polys[j] on the device: Horner from the last polynomial down (FOLD multiplies the accumulator by ch)
-    auto lincomb = [&](const std::vector<const void*>& polys, const F4& ch, void* d_out) -> int {
-        std::vector<uint32_t> words;
-        std::vector<const void*> cols;
-        for (size_t j = polys.size(); j-- > 0;) { words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_FOLD, 0u, 0u}); cols.push_back(polys[j]); }
-        return zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), cols.data(), (uint32_t)cols.size(), &ch, 1, k, k, 0, d_out);
-    };
-    DevBuf batch, wit;
-    if (!batch.alloc(n * 32) || !wit.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-    if (pr->multiopen == ZK_MULTIOPEN_SHPLONK) {
-        // ---- SHPLONK / BDFG21 (poly::kzg::multiopen::shplonk::ProverSHPLONK::create_proof): what
-        // the reference's call sites instantiate.  Two commitments whatever the number of polynomials and points.
-        const F4 y = tr.squeeze();
-        // construct_intermediate_sets: polynomials in order of first appearance with their point sets;
-        // rotation sets in order of first appearance, each listing its polynomials
-        struct PolyQ { const Fr* poly; std::vector<int32_t> rots; std::vector<F4> evals; };
-        std::vector<PolyQ> polys;
-        for (const Open& o : queries) {
-            auto it = std::find_if(polys.begin(), polys.end(), [&](const PolyQ& p) { return p.poly == o.poly; });
-            if (it == polys.end()) { polys.push_back({o.poly, {}, {}}); it = polys.end() - 1; }
-            if (std::find(it->rots.begin(), it->rots.end(), o.rot) == it->rots.end()) { it->rots.push_back(o.rot); it->evals.push_back(o.eval); }
+    for (Open& o : queries) o.rot = f.norm_rot(o.rot);
+}
+
+// Division of N_i (degree < n, vanishing on S; coefficients in `num`) by Z_S(X) = prod (X - z), in place.  Few points: one
+// synthetic division per point.  Many (a column opened at 14 rotations: 14 dependent scans, 1.7 ms of the Keccak-shape proof
+// at k = 18): Q_i = N_i / Z_S is fixed by its values on a coset g H of the domain -- transform, divide point by point by
+// Z_S(g w^j) (one batch inversion), transform back: the cost no longer depends on |S|.
+struct CosetDivision { DevBuf x, ginv, den; };      // g w^j and g^-i (made once per proof, by the first set that needs them), Z_S(g w^j)
+static int shplonk_divide_by_zs(Finish& f, CosetDivision& cd, const std::vector<F4>& zs, DevBuf& num, DevBuf& tmp) {
+    zk_ctx* ctx = f.ctx; const size_t n = f.n; const uint32_t k = f.k;
+    const F4 coset_g = host::fr_from_u64(7), one = host::fr_one();
+    bool by_coset = zs.size() >= 4 && n >= 4 * zs.size();
+    if (by_coset) {
+        // no point of S may lie on the coset (z = x w^rot for a random x: z^n = g^n has probability n / r)
+        F4 gn = coset_g;
+        for (uint32_t i = 0; i < k; ++i) gn = host::fr_mul(gn, gn);
+        for (const F4& z : zs) { F4 zn = z; for (uint32_t i = 0; i < k; ++i) zn = host::fr_mul(zn, zn); if (host::fr_eq(zn, gn)) by_coset = false; }
+    }
+    if (!by_coset) {
+        size_t len = n;
+        for (const F4& z : zs) {
+            PK_TRY(zk_kate_division(ctx, num.p, len, &z, tmp.p));
+            --len;
+            PK_TRY(zk_d2d(ctx, num.p, tmp.p, len * 32));
+            ZK_HIP(ctx, hipMemsetAsync((char*)num.p + len * 32, 0, (n - len) * 32, ctx->stream));
         }
-        struct Set { std::vector<int32_t> rots; std::vector<size_t> members; };
-        std::vector<Set> sets;
-        std::vector<int32_t> super;                  // every point that is opened somewhere
-        for (size_t pi = 0; pi < polys.size(); ++pi) {
-            std::vector<int32_t> key = polys[pi].rots;
-            std::sort(key.begin(), key.end());
-            auto it = std::find_if(sets.begin(), sets.end(), [&](const Set& s_) { return s_.rots == key; });
-            if (it == sets.end()) { sets.push_back({key, {}}); it = sets.end() - 1; }
-            it->members.push_back(pi);
-            for (int32_t r_ : key) if (std::find(super.begin(), super.end(), r_) == super.end()) super.push_back(r_);
-        }
-        const F4 v = tr.squeeze();
-        // r_ij(X): interpolation of polynomial j's evaluations over its set's points (degree < |S|), host side.  The Lagrange basis
-        // of a set -- L_a(X) = prod_{b != a} (X - x_b) / (x_a - x_b), |S|^3 products -- is built ONCE per set; a member then costs
-        // |S|^2.  (Per member it was 3.9 ms of the Keccak-shape proof: 48 columns opened at the same 14 points.)
-        auto lagrange_basis = [&](const std::vector<F4>& xs) {
-            const size_t m = xs.size();
-            std::vector<std::vector<F4>> basis(m);
-            for (size_t a = 0; a < m; ++a) {
-                std::vector<F4> num{host::fr_one()};       // prod_{b != a} (X - x_b)
-                F4 den = host::fr_one();
-                for (size_t b2 = 0; b2 < m; ++b2) {
-                    if (b2 == a) continue;
-                    std::vector<F4> nx(num.size() + 1, host::fr_zero());
-                    for (size_t t = 0; t < num.size(); ++t) { nx[t + 1] = host::fr_add(nx[t + 1], num[t]); nx[t] = host::fr_sub(nx[t], host::fr_mul(num[t], xs[b2])); }
-                    num.swap(nx);
-                    den = host::fr_mul(den, host::fr_sub(xs[a], xs[b2]));
-                }
-                const F4 dinv = host::fr_inv(den);
-                for (F4& c : num) c = host::fr_mul(c, dinv);
-                basis[a] = std::move(num);
-            }
-            return basis;
-        };
-        auto interpolate = [&](const std::vector<std::vector<F4>>& basis, const std::vector<F4>& ys) {
-            const size_t m = basis.size();
-            std::vector<F4> out(m, host::fr_zero());
-            for (size_t a = 0; a < m; ++a)
-                for (size_t t = 0; t < m; ++t) out[t] = host::fr_add(out[t], host::fr_mul(basis[a][t], ys[a]));
-            return out;
-        };
-        auto eval_small = [&](const std::vector<F4>& c, const F4& at) { F4 acc = host::fr_zero(); for (size_t t = c.size(); t-- > 0;) acc = host::fr_add(host::fr_mul(acc, at), c[t]); return acc; };
-        std::vector<DevBuf> qfull(sets.size()), hset(sets.size());
-        DevBuf coset_x, coset_ginv, coset_den;                 // division of large rotation sets on a coset of the domain (below)
-        const F4 coset_g = host::fr_from_u64(7);
-        std::vector<std::vector<F4>> Rset(sets.size());       // R_i(X) = sum_j y^j r_ij(X)
-        DevBuf tmp;
-        if (!tmp.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-        for (size_t si = 0; si < sets.size(); ++si) {
-            const Set& st = sets[si];
-            std::vector<F4> zs;
-            for (int32_t r_ : st.rots) zs.push_back(point_of(r_));
-            // N_i(X) = sum_j y^j (P_ij(X) - r_ij(X)):  Qfull_i = sum_j y^j P_ij on the device, R_i on the host
-            std::vector<const void*> members;
-            const std::vector<std::vector<F4>> basis = lagrange_basis(zs);
-            std::vector<F4> R(st.rots.size(), host::fr_zero());
-            F4 ypow = host::fr_one();
-            for (size_t pi : st.members) {
-                members.push_back(polys[pi].poly);
-                std::vector<F4> ys(st.rots.size());
-                for (size_t a = 0; a < st.rots.size(); ++a) {
-                    const size_t where = std::find(polys[pi].rots.begin(), polys[pi].rots.end(), st.rots[a]) - polys[pi].rots.begin();
-                    ys[a] = polys[pi].evals[where];
-                }
-                const std::vector<F4> rj = interpolate(basis, ys);
-                for (size_t t = 0; t < R.size(); ++t) R[t] = host::fr_add(R[t], host::fr_mul(ypow, rj[t]));
-                ypow = host::fr_mul(ypow, y);
-            }
-            Rset[si] = R;
-            if (!qfull[si].alloc(n * 32) || !hset[si].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-            trace.mark("  shplonk: interpolation (host)");
-            PK_TRY(lincomb(members, y, qfull[si].p));
-            trace.mark("  shplonk: set combination");
-            // Q_i = N_i / prod (X - z): subtract R_i from the low coefficients, divide point by point
-            PK_TRY(zk_d2d(ctx, hset[si].p, qfull[si].p, n * 32));
-            std::vector<F4> low(R.size());
-            PK_TRY(zk_d2h(ctx, low.data(), hset[si].p, R.size() * 32));
-            for (size_t t = 0; t < R.size(); ++t) low[t] = host::fr_sub(low[t], R[t]);
-            PK_TRY(zk_h2d(ctx, hset[si].p, low.data(), R.size() * 32));
-            // Division by Z_S(X) = prod (X - z).  Few points: one synthetic division per point.  Many (a column opened at 14
-            // rotations: 14 dependent scans, 1.7 ms of the Keccak-shape proof at k = 18): N_i has degree < n and vanishes on S,
-            // so Q_i = N_i / Z_S is fixed by its values on a coset g H of the domain -- transform, divide point by point by
-            // Z_S(g w^j) (one batch inversion), transform back: the cost no longer depends on |S|.
-            bool by_coset = zs.size() >= 4 && n >= 4 * zs.size();
-            if (by_coset) {
-                // no point of S may lie on the coset (z = x w^rot for a random x: z^n = g^n has probability n / r)
-                F4 gn = coset_g;
-                for (uint32_t i = 0; i < k; ++i) gn = host::fr_mul(gn, gn);
-                for (const F4& z : zs) { F4 zn = z; for (uint32_t i = 0; i < k; ++i) zn = host::fr_mul(zn, zn); if (host::fr_eq(zn, gn)) by_coset = false; }
-            }
-            if (by_coset) {
-                if (!coset_x.p) {        // g w^j and g^-i, once per proof
-                    if (!coset_x.alloc(n * 32) || !coset_ginv.alloc(n * 32) || !coset_den.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc failed");
-                    const F4 ginv = host::fr_inv(coset_g), one = host::fr_one();
-                    PK_TRY(zk_fr_powers(ctx, &w, &coset_g, coset_x.p, n));
-                    PK_TRY(zk_fr_powers(ctx, &ginv, &one, coset_ginv.p, n));
-                }
-                std::vector<uint32_t> words;
-                std::vector<F4> cs;
-                for (size_t t = 0; t < zs.size(); ++t) {
-                    words.insert(words.end(), {Q_PUSH_COL, 0u, 0u, Q_ADD_CONST, (uint32_t)t, 0u});
-                    if (t) words.insert(words.end(), {Q_MUL, 0u, 0u});
-                    cs.push_back(host::fr_sub(host::fr_zero(), zs[t]));
-                }
-                words.insert(words.end(), {Q_FOLD, (uint32_t)zs.size(), 0u});
-                cs.push_back(host::fr_one());
-                const void* xcol[1] = {coset_x.p};
-                PK_TRY(zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), xcol, 1, cs.data(), (uint32_t)cs.size(), k, k, 0, coset_den.p));     // Z_S(g w^j)
-                PK_TRY(zk_fr_batch_invert(ctx, coset_den.p, n));
-                PK_TRY(zk_coeff_to_coset(ctx, hset[si].p, k, &coset_g, tmp.p));                                                                          // N_i(g w^j)
-                const uint32_t mulw[] = {Q_PUSH_COL, 0u, 0u, Q_PUSH_COL, 1u, 0u, Q_MUL, 0u, 0u, Q_FOLD, 0u, 0u};
-                const F4 one = host::fr_one();
-                const void* c2[2] = {tmp.p, coset_den.p};
-                PK_TRY(zk_quotient_eval(ctx, mulw, 4, c2, 2, &one, 1, k, k, 0, hset[si].p));                                                              // Q_i(g w^j)
-                PK_TRY(zk_ntt(ctx, hset[si].p, k, 1));                                                                                                  // q_i g^i
-                const void* c3[2] = {hset[si].p, coset_ginv.p};
-                PK_TRY(zk_quotient_eval(ctx, mulw, 4, c3, 2, &one, 1, k, k, 0, tmp.p));
-                PK_TRY(zk_d2d(ctx, hset[si].p, tmp.p, n * 32));
-            } else {
-                size_t len = n;
-                for (const F4& z : zs) {
-                    PK_TRY(zk_kate_division(ctx, hset[si].p, len, &z, tmp.p));
-                    --len;
-                    PK_TRY(zk_d2d(ctx, hset[si].p, tmp.p, len * 32));
-                    ZK_HIP(ctx, hipMemsetAsync((char*)hset[si].p + len * 32, 0, (n - len) * 32, ctx->stream));
-                }
-            }
-            trace.mark("  shplonk: set division");
-        }
-        // h = sum_i v^i Q_i; commit
-        {
-            std::vector<const void*> qs;
-            for (size_t si = 0; si < sets.size(); ++si) qs.push_back(hset[si].p);
-            PK_TRY(lincomb(qs, v, batch.p));
-            G1Affine com;
-            PK_TRY(commit_coeff(ctx, srs, batch.fr(), n, &com));
-            tr.write_point(com);
-        }
-        trace.mark("  shplonk: h");
-        const F4 u = tr.squeeze();
-        // L(X) = sum_i v^i Z_{T \ S_i}(u) (Qfull_i(X) - R_i(u)) - Z_T(u) h(X);  the proof's second point commits to
-        // L(X) / (X - u), normalised by 1 / Z_{T \ S_0}(u) (the verifier scales the first set's term to one)
-        std::vector<F4> coef(sets.size() + 1);
-        F4 zT = host::fr_one(), constant = host::fr_zero(), vpow = host::fr_one(), z0_inv = host::fr_one();
-        for (int32_t r_ : super) zT = host::fr_mul(zT, host::fr_sub(u, point_of(r_)));
-        for (size_t si = 0; si < sets.size(); ++si) {
-            F4 zdiff = host::fr_one();
-            for (int32_t r_ : super) if (std::find(sets[si].rots.begin(), sets[si].rots.end(), r_) == sets[si].rots.end()) zdiff = host::fr_mul(zdiff, host::fr_sub(u, point_of(r_)));
-            if (si == 0) z0_inv = host::fr_inv(zdiff);
-            coef[si] = host::fr_mul(host::fr_mul(vpow, zdiff), z0_inv);
-            constant = host::fr_add(constant, host::fr_mul(coef[si], eval_small(Rset[si], u)));
-            vpow = host::fr_mul(vpow, v);
-        }
-        coef[sets.size()] = host::fr_mul(zT, z0_inv);
-        {
-            std::vector<uint32_t> words;
-            std::vector<const void*> cols;
-            for (size_t si = 0; si < sets.size(); ++si) {
-                words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_MUL_CONST, (uint32_t)si, 0u});
-                if (si) words.insert(words.end(), {Q_ADD, 0u, 0u});
-                cols.push_back(qfull[si].p);
-            }
-            words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_MUL_CONST, (uint32_t)sets.size(), 0u, Q_SUB, 0u, 0u});
-            cols.push_back(batch.p);
-            coef.push_back(host::fr_one());
-            words.insert(words.end(), {Q_FOLD, (uint32_t)sets.size() + 1, 0u});
-            PK_TRY(zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), cols.data(), (uint32_t)cols.size(), coef.data(), (uint32_t)coef.size(), k, k, 0, tmp.p));
-            F4 c0;
-            PK_TRY(zk_d2h(ctx, &c0, tmp.p, 32));
-            c0 = host::fr_sub(c0, constant);
-            PK_TRY(zk_h2d(ctx, tmp.p, &c0, 32));
-            PK_TRY(zk_kate_division(ctx, tmp.p, n, &u, wit.p));
-            G1Affine com;
-            PK_TRY(commit_coeff(ctx, srs, wit.fr(), n - 1, &com));
-            tr.write_point(com);
-        }
-        PK_TRY(zk_ctx_sync(ctx));
-        trace.mark("multiopen (shplonk)");
-        if (tr.err) return ctx->fail(ZK_ERR_INVALID_ARG, "transcript failed with status %d (external callback, or the identity point in a Poseidon / EVM transcript)", tr.err);
-        *proof_len = tr.proof.size();
-        if (tr.proof.size() > proof_cap) return ctx->fail(ZK_ERR_INVALID_ARG, "proof buffer too small: need %zu bytes", tr.proof.size());
-        memcpy(h_proof, tr.proof.data(), tr.proof.size());
         return ZK_OK;
     }
-    // ---- GWC multi-open (poly::kzg::multiopen::gwc::ProverGWC::create_proof): one witness per distinct
-    // point in order of first appearance, the point's polynomials combined with ascending powers of v
+    if (!cd.x.p) {
+        PK_ALLOC(ctx, cd.x, n * 32);
+        PK_ALLOC(ctx, cd.ginv, n * 32);
+        PK_ALLOC(ctx, cd.den, n * 32);
+        const F4 ginv = host::fr_inv(coset_g);
+        PK_TRY(zk_fr_powers(ctx, &f.w, &coset_g, cd.x.p, n));
+        PK_TRY(zk_fr_powers(ctx, &ginv, &one, cd.ginv.p, n));
+    }
+    std::vector<uint32_t> words;
+    std::vector<F4> cs;
+    for (size_t t = 0; t < zs.size(); ++t) {
+        words.insert(words.end(), {Q_PUSH_COL, 0u, 0u, Q_ADD_CONST, (uint32_t)t, 0u});
+        if (t) words.insert(words.end(), {Q_MUL, 0u, 0u});
+        cs.push_back(host::fr_sub(host::fr_zero(), zs[t]));
+    }
+    words.insert(words.end(), {Q_FOLD, (uint32_t)zs.size(), 0u});
+    cs.push_back(host::fr_one());
+    const void* xcol[1] = {cd.x.p};
+    PK_TRY(zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), xcol, 1, cs.data(), (uint32_t)cs.size(), k, k, 0, cd.den.p));     // Z_S(g w^j)
+    PK_TRY(zk_fr_batch_invert(ctx, cd.den.p, n));
+    PK_TRY(zk_coeff_to_coset(ctx, num.p, k, &coset_g, tmp.p));                                                                            // N_i(g w^j)
+    const uint32_t mulw[] = {Q_PUSH_COL, 0u, 0u, Q_PUSH_COL, 1u, 0u, Q_MUL, 0u, 0u, Q_FOLD, 0u, 0u};
+    const void* c2[2] = {tmp.p, cd.den.p};
+    PK_TRY(zk_quotient_eval(ctx, mulw, 4, c2, 2, &one, 1, k, k, 0, num.p));                                                                // Q_i(g w^j)
+    PK_TRY(zk_ntt(ctx, num.p, k, 1));                                                                                                    // q_i g^i
+    const void* c3[2] = {num.p, cd.ginv.p};
+    PK_TRY(zk_quotient_eval(ctx, mulw, 4, c3, 2, &one, 1, k, k, 0, tmp.p));
+    return zk_d2d(ctx, num.p, tmp.p, n * 32);
+}
+
+// ---- SHPLONK / BDFG21 (poly::kzg::multiopen::shplonk::ProverSHPLONK::create_proof): what
+// the reference's call sites instantiate.  Two commitments whatever the number of polynomials and points.
+static int multiopen_shplonk(Finish& f) {
+    zk_ctx* ctx = f.ctx; const size_t n = f.n; const uint32_t k = f.k; host::Transcript& tr = f.pr->tr;
+    DevBuf batch, wit;
+    PK_ALLOC(ctx, batch, n * 32);
+    PK_ALLOC(ctx, wit, n * 32);
+    const F4 y = tr.squeeze();
+    std::vector<PolyQ> polys;
+    std::vector<RotSet> sets;
+    std::vector<int32_t> super;                  // every point that is opened somewhere
+    shplonk_intermediate_sets(f.queries, polys, sets, super);
+    const F4 v = tr.squeeze();
+    std::vector<DevBuf> qfull(sets.size()), hset(sets.size());
+    CosetDivision coset_div;
+    std::vector<std::vector<F4>> Rset(sets.size());       // R_i(X) = sum_j y^j r_ij(X)
+    DevBuf tmp;
+    PK_ALLOC(ctx, tmp, n * 32);
+    for (size_t si = 0; si < sets.size(); ++si) {
+        const RotSet& st = sets[si];
+        std::vector<F4> zs;
+        for (int32_t r_ : st.rots) zs.push_back(f.point_of(r_));
+        // N_i(X) = sum_j y^j (P_ij(X) - r_ij(X)):  Qfull_i = sum_j y^j P_ij on the device, R_i on the host
+        std::vector<const void*> members;
+        const std::vector<std::vector<F4>> basis = lagrange_basis(zs);
+        std::vector<F4> R(st.rots.size(), host::fr_zero());
+        F4 ypow = host::fr_one();
+        for (size_t pi : st.members) {
+            members.push_back(polys[pi].poly);
+            std::vector<F4> ys(st.rots.size());
+            for (size_t a = 0; a < st.rots.size(); ++a) {
+                const size_t where = std::find(polys[pi].rots.begin(), polys[pi].rots.end(), st.rots[a]) - polys[pi].rots.begin();
+                ys[a] = polys[pi].evals[where];
+            }
+            const std::vector<F4> rj = interpolate(basis, ys);
+            for (size_t t = 0; t < R.size(); ++t) R[t] = host::fr_add(R[t], host::fr_mul(ypow, rj[t]));
+            ypow = host::fr_mul(ypow, y);
+        }
+        Rset[si] = R;
+        PK_ALLOC(ctx, qfull[si], n * 32);
+        PK_ALLOC(ctx, hset[si], n * 32);
+        f.trace.mark("  shplonk: interpolation (host)");
+        PK_TRY(lincomb(ctx, k, members, y, qfull[si].p));
+        f.trace.mark("  shplonk: set combination");
+        // Q_i = N_i / prod (X - z): subtract R_i from the low coefficients, divide point by point
+        PK_TRY(zk_d2d(ctx, hset[si].p, qfull[si].p, n * 32));
+        std::vector<F4> low(R.size());
+        PK_TRY(zk_d2h(ctx, low.data(), hset[si].p, R.size() * 32));
+        for (size_t t = 0; t < R.size(); ++t) low[t] = host::fr_sub(low[t], R[t]);
+        PK_TRY(zk_h2d(ctx, hset[si].p, low.data(), R.size() * 32));
+        PK_TRY(shplonk_divide_by_zs(f, coset_div, zs, hset[si], tmp));
+        f.trace.mark("  shplonk: set division");
+    }
+    // h = sum_i v^i Q_i; commit
+    {
+        std::vector<const void*> qs;
+        for (size_t si = 0; si < sets.size(); ++si) qs.push_back(hset[si].p);
+        PK_TRY(lincomb(ctx, k, qs, v, batch.p));
+        G1Affine com;
+        PK_TRY(commit_coeff(ctx, f.srs, batch.fr(), n, &com));
+        tr.write_point(com);
+    }
+    f.trace.mark("  shplonk: h");
+    const F4 u = tr.squeeze();
+    // L(X) = sum_i v^i Z_{T \ S_i}(u) (Qfull_i(X) - R_i(u)) - Z_T(u) h(X);  the proof's second point commits to
+    // L(X) / (X - u), normalised by 1 / Z_{T \ S_0}(u) (the verifier scales the first set's term to one)
+    std::vector<F4> coef(sets.size() + 1);
+    F4 zT = host::fr_one(), constant = host::fr_zero(), vpow = host::fr_one(), z0_inv = host::fr_one();
+    for (int32_t r_ : super) zT = host::fr_mul(zT, host::fr_sub(u, f.point_of(r_)));
+    for (size_t si = 0; si < sets.size(); ++si) {
+        F4 zdiff = host::fr_one();
+        for (int32_t r_ : super) if (std::find(sets[si].rots.begin(), sets[si].rots.end(), r_) == sets[si].rots.end()) zdiff = host::fr_mul(zdiff, host::fr_sub(u, f.point_of(r_)));
+        if (si == 0) z0_inv = host::fr_inv(zdiff);
+        coef[si] = host::fr_mul(host::fr_mul(vpow, zdiff), z0_inv);
+        constant = host::fr_add(constant, host::fr_mul(coef[si], eval_small(Rset[si], u)));
+        vpow = host::fr_mul(vpow, v);
+    }
+    coef[sets.size()] = host::fr_mul(zT, z0_inv);
+    {
+        std::vector<uint32_t> words;
+        std::vector<const void*> cols;
+        for (size_t si = 0; si < sets.size(); ++si) {
+            words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_MUL_CONST, (uint32_t)si, 0u});
+            if (si) words.insert(words.end(), {Q_ADD, 0u, 0u});
+            cols.push_back(qfull[si].p);
+        }
+        words.insert(words.end(), {Q_PUSH_COL, (uint32_t)cols.size(), 0u, Q_MUL_CONST, (uint32_t)sets.size(), 0u, Q_SUB, 0u, 0u});
+        cols.push_back(batch.p);
+        coef.push_back(host::fr_one());
+        words.insert(words.end(), {Q_FOLD, (uint32_t)sets.size() + 1, 0u});
+        PK_TRY(zk_quotient_eval(ctx, words.data(), (uint32_t)(words.size() / 3), cols.data(), (uint32_t)cols.size(), coef.data(), (uint32_t)coef.size(), k, k, 0, tmp.p));
+        F4 c0;
+        PK_TRY(zk_d2h(ctx, &c0, tmp.p, 32));
+        c0 = host::fr_sub(c0, constant);
+        PK_TRY(zk_h2d(ctx, tmp.p, &c0, 32));
+        PK_TRY(zk_kate_division(ctx, tmp.p, n, &u, wit.p));
+        G1Affine com;
+        PK_TRY(commit_coeff(ctx, f.srs, wit.fr(), n - 1, &com));
+        tr.write_point(com);
+    }
+    PK_TRY(zk_ctx_sync(ctx));
+    f.trace.mark("multiopen (shplonk)");
+    return ZK_OK;
+}
+
+// ---- GWC multi-open (poly::kzg::multiopen::gwc::ProverGWC::create_proof): one witness per distinct
+// point in order of first appearance, the point's polynomials combined with ascending powers of v
+static int multiopen_gwc(Finish& f) {
+    zk_ctx* ctx = f.ctx; const size_t n = f.n; host::Transcript& tr = f.pr->tr;
+    const std::vector<Open>& queries = f.queries;
+    DevBuf batch, wit;
+    PK_ALLOC(ctx, batch, n * 32);
+    PK_ALLOC(ctx, wit, n * 32);
     const F4 v = tr.squeeze();
     std::vector<int32_t> rots;
     for (const Open& o : queries) if (std::find(rots.begin(), rots.end(), o.rot) == rots.end()) rots.push_back(o.rot);
     for (int32_t rot : rots) {
         std::vector<const void*> members;
         for (const Open& o : queries) if (o.rot == rot) members.push_back(o.poly);
-        PK_TRY(lincomb(members, v, batch.p));
-        const F4 z = point_of(rot);
+        PK_TRY(lincomb(ctx, f.k, members, v, batch.p));
+        const F4 z = f.point_of(rot);
         PK_TRY(zk_kate_division(ctx, batch.p, n, &z, wit.p));
         G1Affine com;
-        PK_TRY(commit_coeff(ctx, srs, wit.fr(), n - 1, &com));
+        PK_TRY(commit_coeff(ctx, f.srs, wit.fr(), n - 1, &com));
         tr.write_point(com);
     }
     PK_TRY(zk_ctx_sync(ctx));
-    trace.mark("multiopen");
+    f.trace.mark("multiopen");
+    return ZK_OK;
+}
+
+// the finished transcript into the caller's buffer
+static int write_proof_out(zk_ctx* ctx, const host::Transcript& tr, void* h_proof, size_t proof_cap, size_t* proof_len) {
     if (tr.err) return ctx->fail(ZK_ERR_INVALID_ARG, "transcript failed with status %d (external callback, or the identity point in a Poseidon / EVM transcript)", tr.err);
     *proof_len = tr.proof.size();
     if (tr.proof.size() > proof_cap) return ctx->fail(ZK_ERR_INVALID_ARG, "proof buffer too small: need %zu bytes", tr.proof.size());
     memcpy(h_proof, tr.proof.data(), tr.proof.size());
     return ZK_OK;
+}
+
+// Everything after the advice phases: lookups, permutation, quotient, evaluations, multi-open -- the stages above, with the
+// transcript's challenges squeezed between them.  Consumes the session (it is freed whether or not the call succeeds).
+int zk_proof_finish(zk_ctx* ctx, zk_proof* pr_raw, void* h_proof, size_t proof_cap, size_t* proof_len) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    PoolScope pool_scope(ctx);
+    std::unique_ptr<zk_proof> pr(pr_raw);
+    ZK_REQUIRE(ctx, pr && h_proof && proof_len, "null pointer");
+    if (pr->phase != pr->pk->num_phases) return ctx->fail(ZK_ERR_INVALID_ARG, "only %u of %u advice phases were committed", pr->phase, pr->pk->num_phases);
+    host::Transcript& tr = pr->tr;
+    Finish f(ctx, pr.get());
+    // Declared after `pr` and `f`, so destroyed first: the auxiliary stream is joined before any buffer of the session (the
+    // stages' in `f`, the advice columns and their cosets in `pr`) goes back to the pool, on every return path.
+    AuxJoin aux_join{ctx, &f.late_cosets};
+    f.lag.theta = tr.squeeze();
+    PK_TRY(stage_late_advice_cosets(f));
+    PK_TRY(stage_lookup_multiplicities(f));
+    f.lag.beta = tr.squeeze();
+    f.lag.gamma = tr.squeeze();
+    PK_TRY(stage_permutation_products(f));
+    PK_TRY(stage_lookup_grand_sums(f));
+    PK_TRY(stage_vanishing_random(f));
+    f.lag.y = tr.squeeze();
+    PK_TRY(stage_coefficient_forms(f));
+    PK_TRY(stage_quotient(f));
+    PK_TRY(stage_h_commits(f));
+    f.x = tr.squeeze();
+    PK_TRY(stage_evaluations(f));
+    PK_TRY(stage_h_recombination(f));
+    stage_opening_queries(f);
+    PK_TRY(pr->multiopen == ZK_MULTIOPEN_SHPLONK ? multiopen_shplonk(f) : multiopen_gwc(f));
+    return write_proof_out(ctx, tr, h_proof, proof_cap, proof_len);
 }
 
 // ---- host-only transcript objects and hashes (no context, no device) -----------------------------
