@@ -83,7 +83,13 @@ int zk_timer_stop_ms(zk_ctx* ctx, float* ms);   /* synchronises on the stop even
  * ...) is bracketed by an event pair; zk_prof_get drains the stream and returns the accumulated
  * device milliseconds and launch count for one name.  on = 2 records only the groups of the roofline
  * kernels ("msm_buckets", "ntt_*", "quotient*"): every event pair costs a little stream time, and a
- * throughput measurement should carry as few as it needs.                                        */
+ * throughput measurement should carry as few as it needs.
+ * The structure-reading commitment paths (csrc/runs.hip) book, at on = 1 only: "runs_prefix_table"
+ * (one per build of a basis's prefix-sum table), "runs_collect" (each run-end sweep, the count-only
+ * one included), "runs_direct" (run ends summed by double-and-add), "runs_ends_msm" (the bucket
+ * method over one column's run ends), "diff_fixed_table" (one per build of the fixed-point table),
+ * "diff_mode" (each sampling of the common increment), "diff_sparse" (difference images plus
+ * c times the fixed point, one per chunk of columns).                                            */
 int zk_prof_enable(zk_ctx* ctx, int on);
 int zk_prof_reset(zk_ctx* ctx);
 int zk_prof_get(zk_ctx* ctx, const char* name, double* total_ms, uint64_t* count);

@@ -99,18 +99,21 @@ static int srs_prefix_table(zk_ctx* ctx, const zk_srs* srs, int basis, const G1A
     G1Affine* tab = nullptr;
     if (hipMalloc(&tab, sizeof(G1Affine) * n) != hipSuccess) { (void)hipGetLastError(); ctx->pool_put(t1, (n1 + n2) * sizeof(G1Xyzz29)); return ZK_OK; }
     auto grid = [](uint64_t items) { return dim3((unsigned)((items + 255) / 256)); };
-    hipLaunchKernelGGL(k_pfx_totals_affine, grid(n1), dim3(256), 0, ctx->stream, rp, n, t1);
-    hipLaunchKernelGGL(k_pfx_totals_xyzz, grid(n2), dim3(256), 0, ctx->stream, (const G1Xyzz29*)t1, n1, t2);
-    hipLaunchKernelGGL(k_pfx_serial_exclusive, dim3(1), dim3(64), 0, ctx->stream, t2, n2);
-    hipLaunchKernelGGL(k_pfx_down, grid(n2), dim3(256), 0, ctx->stream, t1, n1, (const G1Xyzz29*)t2);
-    hipLaunchKernelGGL(k_pfx_finish, grid(n1), dim3(256), 0, ctx->stream, rp, n, (const G1Xyzz29*)t1, tab);
     // -(P_0 + ... + P_{n-2}): what a column committed through its first differences owes for the constant part of its increments
     G1Affine* negtot = nullptr;
     if (hipMalloc(&negtot, sizeof(G1Affine)) != hipSuccess) { (void)hipGetLastError(); negtot = nullptr; }
-    if (negtot) {
-        hipLaunchKernelGGL(k_pfx_totals_affine, grid(n1), dim3(256), 0, ctx->stream, (const G1Affine*)tab, n - 1, t1);
-        hipLaunchKernelGGL(k_pfx_totals_xyzz, grid(n2), dim3(256), 0, ctx->stream, (const G1Xyzz29*)t1, (n - 1 + PFX_SEG - 1) / PFX_SEG, t2);
-        hipLaunchKernelGGL(k_pfx_neg_total, dim3(1), dim3(64), 0, ctx->stream, (const G1Xyzz29*)t2, ((n - 1 + PFX_SEG - 1) / PFX_SEG + PFX_SEG - 1) / PFX_SEG, negtot);
+    {
+        ZkProfScope prof(ctx, "runs_prefix_table");
+        hipLaunchKernelGGL(k_pfx_totals_affine, grid(n1), dim3(256), 0, ctx->stream, rp, n, t1);
+        hipLaunchKernelGGL(k_pfx_totals_xyzz, grid(n2), dim3(256), 0, ctx->stream, (const G1Xyzz29*)t1, n1, t2);
+        hipLaunchKernelGGL(k_pfx_serial_exclusive, dim3(1), dim3(64), 0, ctx->stream, t2, n2);
+        hipLaunchKernelGGL(k_pfx_down, grid(n2), dim3(256), 0, ctx->stream, t1, n1, (const G1Xyzz29*)t2);
+        hipLaunchKernelGGL(k_pfx_finish, grid(n1), dim3(256), 0, ctx->stream, rp, n, (const G1Xyzz29*)t1, tab);
+        if (negtot) {
+            hipLaunchKernelGGL(k_pfx_totals_affine, grid(n1), dim3(256), 0, ctx->stream, (const G1Affine*)tab, n - 1, t1);
+            hipLaunchKernelGGL(k_pfx_totals_xyzz, grid(n2), dim3(256), 0, ctx->stream, (const G1Xyzz29*)t1, (n - 1 + PFX_SEG - 1) / PFX_SEG, t2);
+            hipLaunchKernelGGL(k_pfx_neg_total, dim3(1), dim3(64), 0, ctx->stream, (const G1Xyzz29*)t2, ((n - 1 + PFX_SEG - 1) / PFX_SEG + PFX_SEG - 1) / PFX_SEG, negtot);
+        }
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -240,7 +243,10 @@ static int srs_fixed_table(zk_ctx* ctx, const zk_srs* srs, int basis, const G1Af
     if (!s->pfx_negtot[basis]) return ZK_OK;
     G1Affine* tab = nullptr;
     if (hipMalloc(&tab, sizeof(G1Affine) * FIXED_WINDOWS * FIXED_DIGITS) != hipSuccess) { (void)hipGetLastError(); return ZK_OK; }
-    hipLaunchKernelGGL(k_fixed_table, dim3(FIXED_WINDOWS), dim3(FIXED_DIGITS), 0, ctx->stream, (const G1Affine*)s->pfx_negtot[basis], tab);
+    {
+        ZkProfScope prof(ctx, "diff_fixed_table");
+        hipLaunchKernelGGL(k_fixed_table, dim3(FIXED_WINDOWS), dim3(FIXED_DIGITS), 0, ctx->stream, (const G1Affine*)s->pfx_negtot[basis], tab);
+    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { (void)hipFree(tab); return ctx->fail(ZK_ERR_HIP, "fixed-base table: %s", hipGetErrorString(e)); }
@@ -273,6 +279,7 @@ int msm_runs_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
             uint32_t h_counts[RUN_COLS];
             hipError_t e = hipMemsetAsync(d_counts, 0, 256, ctx->stream);
             if (e == hipSuccess) {
+                ZkProfScope prof(ctx, "runs_collect");
                 hipLaunchKernelGGL(k_runs_collect, dim3((unsigned)((n + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->stream, rcols, (uint64_t)n, (const G1Affine*)nullptr, (Fr*)nullptr, (G1Affine*)nullptr, cap, d_counts);
                 e = hipGetLastError();
             }
@@ -302,7 +309,10 @@ int msm_runs_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
         for (size_t j = 0; j < cnt; ++j) rcols.p[j] = d_scalar_ptrs[sel[first + j]];
         hipError_t e = hipMemsetAsync(d_counts, 0, 256, ctx->stream);
         if (e != hipSuccess) return release(ctx->fail(ZK_ERR_HIP, "run collection: %s", hipGetErrorString(e)));
-        hipLaunchKernelGGL(k_runs_collect, dim3((unsigned)((n + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->stream, rcols, (uint64_t)n, pfx, d_scal, d_base, cap, d_counts);
+        {
+            ZkProfScope prof(ctx, "runs_collect");
+            hipLaunchKernelGGL(k_runs_collect, dim3((unsigned)((n + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->stream, rcols, (uint64_t)n, pfx, d_scal, d_base, cap, d_counts);
+        }
         uint32_t h_counts[RUN_COLS];
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(h_counts, d_counts, cnt * 4, hipMemcpyDeviceToHost, ctx->stream);
@@ -319,8 +329,11 @@ int msm_runs_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
             if (pb) {
                 G1Xyzz29* d_part = (G1Xyzz29*)pb;
                 G1Xyzz* d_res = (G1Xyzz*)(pb + (size_t)cnt * blocks * sizeof(G1Xyzz29));
-                hipLaunchKernelGGL(k_runs_mul, dim3(blocks, (unsigned)cnt), dim3(256), 0, ctx->stream, (const Fr*)d_scal, (const G1Affine*)d_base, cap, (const uint32_t*)d_counts, d_part);
-                hipLaunchKernelGGL(k_runs_sum, dim3((unsigned)cnt), dim3(64), 0, ctx->stream, (const G1Xyzz29*)d_part, blocks, d_res);
+                {
+                    ZkProfScope prof(ctx, "runs_direct");
+                    hipLaunchKernelGGL(k_runs_mul, dim3(blocks, (unsigned)cnt), dim3(256), 0, ctx->stream, (const Fr*)d_scal, (const G1Affine*)d_base, cap, (const uint32_t*)d_counts, d_part);
+                    hipLaunchKernelGGL(k_runs_sum, dim3((unsigned)cnt), dim3(64), 0, ctx->stream, (const G1Xyzz29*)d_part, blocks, d_res);
+                }
                 std::vector<G1Xyzz> hres(cnt);
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), d_res, cnt * sizeof(G1Xyzz), hipMemcpyDeviceToHost, ctx->stream);
@@ -340,7 +353,10 @@ int msm_runs_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
             if (h_counts[j] == 0) { memset(h_out + col, 0, sizeof(G1Affine)); done[col] = 1; continue; }      // the zero column
             const Fr* sp = d_scal + j * cap;
             const G1Affine* bp = d_base + j * cap;
-            rc = msm_batch_tab(ctx, &sp, 1, bp, bp, nullptr, 0, h_counts[j], h_out + col);
+            {
+                ZkProfScope prof(ctx, "runs_ends_msm");
+                rc = msm_batch_tab(ctx, &sp, 1, bp, bp, nullptr, 0, h_counts[j], h_out + col);
+            }
             if (rc) return release(rc);
             done[col] = 1;
         }
@@ -417,7 +433,10 @@ int msm_diff_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
             RunCols rcols{};
             for (size_t j = 0; j < cnt; ++j) rcols.p[j] = d_scalar_ptrs[sel[first + j]];
             uint32_t h_votes[RUN_COLS];
-            hipLaunchKernelGGL(k_diff_mode, dim3((unsigned)cnt), dim3(DIFF_SAMPLES), 0, ctx->stream, rcols, (uint64_t)n, d_c0, d_votes);
+            {
+                ZkProfScope prof(ctx, "diff_mode");
+                hipLaunchKernelGGL(k_diff_mode, dim3((unsigned)cnt), dim3(DIFF_SAMPLES), 0, ctx->stream, rcols, (uint64_t)n, d_c0, d_votes);
+            }
             hipError_t e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(h_votes, d_votes, cnt * 4, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -449,11 +468,17 @@ int msm_diff_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
         uint32_t* d_votes = (uint32_t*)(d_res + CHUNK);
         RunCols rcols{};
         for (size_t j = 0; j < cnt; ++j) rcols.p[j] = d_scalar_ptrs[sel[first + j]];
-        hipLaunchKernelGGL(k_diff_mode, dim3((unsigned)cnt), dim3(DIFF_SAMPLES), 0, ctx->stream, rcols, (uint64_t)n, d_c, d_votes);
-        hipLaunchKernelGGL(k_diff_sparse, dim3((unsigned)((n + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->stream, rcols, (uint64_t)n, (const Fr*)d_c, d_s);
-        // c * (-(P_0 + ... + P_{n-2})) for every column of the chunk, out of the point's fixed-base table; the results are fetched
-        // after the batch below has drained the stream (no synchronisation of their own)
-        hipLaunchKernelGGL(k_fixed_mul, dim3((unsigned)cnt), dim3(64), 0, ctx->stream, (const Fr*)d_c, fixed_tab, d_res);
+        {
+            ZkProfScope prof(ctx, "diff_mode");
+            hipLaunchKernelGGL(k_diff_mode, dim3((unsigned)cnt), dim3(DIFF_SAMPLES), 0, ctx->stream, rcols, (uint64_t)n, d_c, d_votes);
+        }
+        {
+            ZkProfScope prof(ctx, "diff_sparse");
+            hipLaunchKernelGGL(k_diff_sparse, dim3((unsigned)((n + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->stream, rcols, (uint64_t)n, (const Fr*)d_c, d_s);
+            // c * (-(P_0 + ... + P_{n-2})) for every column of the chunk, out of the point's fixed-base table; the results are fetched
+            // after the batch below has drained the stream (no synchronisation of their own)
+            hipLaunchKernelGGL(k_fixed_mul, dim3((unsigned)cnt), dim3(64), 0, ctx->stream, (const Fr*)d_c, fixed_tab, d_res);
+        }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return release(ctx->fail(ZK_ERR_HIP, "difference commitments: %s", hipGetErrorString(e)));
         // the mostly-zero images over the prefix basis, judged and committed like any batch of columns
