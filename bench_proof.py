@@ -759,6 +759,13 @@ def build_shape(ctx, k: int, A: int, F: int, P: int, L: int, d: int, distinct: i
                 data_m[t][i][pick] = limbs
     zero_col = np.zeros((n, 4), dtype=np.uint64)
     adv_m = [data_m[(col // 3) % D][col % 3] if col < 3 * groups else zero_col for col in range(A)]
+    # the same witness as the integers it was made from (--typed), for the columns that hold nothing else: "small" cells only, no
+    # column that a phase computes from a challenge, no step column of the EVM block (those are converted further down)
+    zero_ints = np.zeros(n, dtype=np.uint64)
+    c.advice_ints = [None] * A
+    if dist == "small":
+        for col in range(A - 2 if phases else A):
+            c.advice_ints[col] = data[(col // 3) % D, col % 3] if col < 3 * groups else (None if evm and col < 3 * groups + n_step else zero_ints)
     f_usable = f_tc = zero_col
     if evm:
         step_cols, usable = evm_witness(evm_spec, n, u, seed + 2)
@@ -865,8 +872,14 @@ class PhaseDriver:
                 b_.free()
 
 
+def narrowest_cells(ints: np.ndarray) -> np.ndarray:
+    """a column of integers below 2^64 in the narrowest cell type that holds every value (ProofSession.advice_phase_typed)"""
+    top = int(ints.max()) if ints.size else 0
+    return ints.astype(next(dt for bits, dt in ((8, np.uint8), (16, np.uint16), (32, np.uint32), (64, np.uint64)) if top < 1 << bits))
+
+
 def proof_bench(ctx, k, circ, blob, adv_m, inst_m, inst, shplonk=True, repeat=3, verify=True, pinned=False, t_build=0.0,
-                session_hook=None, barrier=None, report=True, world=1, transcript_kind=None, profiled_extra=False, resident=False):
+                session_hook=None, barrier=None, report=True, world=1, transcript_kind=None, profiled_extra=False, resident=False, typed=False):
     """keygen_pk + `repeat` proving sessions of one circuit; returns the result record (None on
     ranks that do not report).  Verified afterwards by the oracle's pairing verifier.
     resident: the witness columns are uploaded BEFORE the sessions (one device buffer per column) and handed over as device
@@ -876,11 +889,18 @@ def proof_bench(ctx, k, circ, blob, adv_m, inst_m, inst, shplonk=True, repeat=3,
     npub = [int(np.flatnonzero(np.asarray(a).reshape(-1, 4).any(axis=1))[-1]) + 1 if np.asarray(a).any() else 0 for a in inst_m]
     inst = [list(col[:m]) for col, m in zip(inst, npub)]
     inst_m = [np.ascontiguousarray(a[:m]) for a, m in zip(inst_m, npub)]
+    if typed:           # every column the generator knows as integers goes over in its narrowest cell type; the others stay Montgomery
+        ints = getattr(circ, "advice_ints", None) or [None] * len(adv_m)
+        narrow = {}
+        for v in ints:
+            if v is not None and id(v) not in narrow:
+                narrow[id(v)] = narrowest_cells(v)
+        adv_m = [a if v is None else narrow[id(v)] for a, v in zip(adv_m, ints)]
     if pinned:          # what a host integration would do: witness columns in page-locked memory
         pin = {}
         for a in adv_m:
             if id(a) not in pin:
-                pin[id(a)] = ctx.host_alloc(a.shape)
+                pin[id(a)] = ctx.host_alloc(a.shape, a.dtype)
                 pin[id(a)][:] = a
         adv_m = [pin[id(a)] for a in adv_m]
     S = 0x5EC2E7
@@ -913,6 +933,8 @@ def proof_bench(ctx, k, circ, blob, adv_m, inst_m, inst, shplonk=True, repeat=3,
         keep = session_hook(sess) if session_hook else None
         if resident:
             sess.advice_phase_dev({i: c for i, c in enumerate(adv_dev)}, in_place=True)
+        elif typed:
+            sess.advice_phase_typed({i: c for i, c in enumerate(adv_m)})
         else:
             sess.advice_phase({i: c for i, c in enumerate(adv_m)})
         proof = sess.finish()
@@ -938,7 +960,14 @@ def proof_bench(ctx, k, circ, blob, adv_m, inst_m, inst, shplonk=True, repeat=3,
                             multiopen="shplonk" if shplonk else "gwc", transcript=kinds[transcript_kind]))
     pk.destroy(); srs.destroy()
     d = circ.degree()
-    return {
+    extra = {}
+    if typed:           # what crosses PCIe per proof: the usable rows of every column at its cell width, plus the blinding rows
+        cell = [z.binding.typed_cell_width(a) for a in adv_m]
+        extra = {"typed_columns_by_cell_bytes": {str(w): cell.count(w) for w in sorted(set(cell))},
+                 "witness_upload_bytes": sum(circ.u * w + (circ.n - circ.u) * 32 for w in cell), "witness_upload_bytes_as_fr": len(cell) * circ.n * 32}
+        if profiled_extra:
+            extra["fr_from_uint_ms"] = round(ctx.prof_get("fr_from_uint")[0], 3)
+    return {**extra,
         "metric": "synthetic-shape full proof wall-clock (s), 1x MI355X",
         "value": round(min(times), 4), "unit": "s", "higher_is_better": False,
         "k": k, "advice": circ.A, "fixed": circ.F, "instance": circ.I, "permutation_columns": len(circ.perm_cols),
@@ -963,6 +992,8 @@ def main():
     ap.add_argument("--host-upload", action="store_true", help="sharded runs: every rank uploads every advice column (no device all-gather)")
     ap.add_argument("--rccl", action="store_true", help="sharded runs: exchange through the library's own RCCL communicator (zk_comm_init) instead of torch.distributed callbacks")
     ap.add_argument("--pinned", action="store_true", help="advice columns in page-locked host memory (zk_host_alloc)")
+    ap.add_argument("--typed", action="store_true", help="with --pinned: advice columns whose generated values are all below 2^64 go over as integers of "
+                    "their narrowest cell width (zk_proof_advice_phase_typed) instead of 32-byte Montgomery elements")
     ap.add_argument("--cpu-baseline", action="store_true", help="time the C oracle's MSM / NTT at 2^k on the host and scale by the prover's counts")
     ap.add_argument("--keccak", action="store_true", help="Keccak-circuit stand-in (SURVEY 8d config 3): 59 unusable rows, 13-rotation gates, degree 9")
     ap.add_argument("--shape", default="", help="A,F,P,L,d: circuit with this many advice / fixed / permutation columns, lookups and "
@@ -1010,7 +1041,8 @@ def main():
     elif world > 1:    # device all-gather of the advice columns unless --host-upload asks every rank to upload everything
         hook = (lambda sess: shard.shard_session(sess)) if args.host_upload else (lambda sess: shard.shard_session_device(sess))
     out = proof_bench(ctx, args.k, circ, blob, adv_m, inst_m, inst, shplonk=args.shplonk, repeat=args.repeat, verify=not args.no_verify, pinned=args.pinned,
-                      t_build=t_build, session_hook=hook, barrier=barrier or (dist.barrier if world > 1 else None), report=(rank == 0), world=world)
+                      t_build=t_build, session_hook=hook, barrier=barrier or (dist.barrier if world > 1 else None), report=(rank == 0), world=world,
+                      **({"typed": True, "profiled_extra": True} if args.typed and args.pinned else {}))
     if world > 1 and rank != 0:
         if dist is not None:
             dist.destroy_process_group()

@@ -9,6 +9,10 @@
 //     <dir>/instance.bin   I columns of 2^k x 32 B
 //     <dir>/repr.bin       vk.transcript_repr, 32 B (optional: without it the key keeps the library's stand-in)
 //     <dir>/seed.bin       16 B XorShift seed of the blinding RNG (optional: zeros)
+//     <dir>/widths.bin     A bytes, the cell width of each advice column (optional: every column 32).  Column c of advice.bin then
+//                          holds 2^k cells of widths[c] bytes: 1, 2, 4, 8, 16 = little-endian unsigned integers, 32 = Montgomery
+//                          limbs (ProofSession::advice_phase_typed).  The stand-alone MockProver pass takes field elements only and
+//                          is left to the session's own row checks.
 //   writes <dir>/proof_cpp.bin and prints what it did.  Exit status 0 only if MockProver's row checks pass and a proof came out.
 //
 // Build: g++ -std=c++17 -I include examples/prove_from_files.cpp -o prove_from_files -L zkevm-circuits_amd/lib -lzkmi355 -Wl,-rpath,$PWD/zkevm-circuits_amd/lib
@@ -53,14 +57,21 @@ int main(int argc, char** argv) {
         ctx.check(zk_pk_shape(ctx.raw(), pk.raw(), shape));
         const size_t n = size_t(1) << shape[0], A = shape[4], I = shape[5], usable = n - shape[11] - 1;
         const std::vector<uint8_t> advice = slurp(dir + "/advice.bin"), instance = slurp(dir + "/instance.bin", I != 0);
-        if (advice.size() != A * n * 32 || instance.size() != I * n * 32) throw std::runtime_error("advice.bin / instance.bin do not hold A / I columns of 2^k field elements");
+        std::vector<uint8_t> widths = slurp(dir + "/widths.bin", false);
+        const bool typed = !widths.empty();
+        if (typed && widths.size() != A) throw std::runtime_error("widths.bin does not hold one byte per advice column");
+        if (!typed) widths.assign(A, 32);
         std::vector<const void*> adv_ptrs, inst_ptrs;
-        for (size_t c = 0; c < A; ++c) adv_ptrs.push_back(advice.data() + c * n * 32);
+        size_t adv_bytes = 0;
+        for (size_t c = 0; c < A; ++c) { adv_ptrs.push_back(advice.data() + adv_bytes); adv_bytes += n * widths[c]; }
+        if (advice.size() != adv_bytes || instance.size() != I * n * 32) throw std::runtime_error("advice.bin / instance.bin do not hold A / I columns of 2^k cells");
         for (size_t c = 0; c < I; ++c) inst_ptrs.push_back(instance.data() + c * n * 32);
-        // MockProver::run(..).assert_satisfied_par() first, as the reference's tests do before they prove
-        const std::vector<zk_mock_failure> failures = mock_verify(ctx, pk, adv_ptrs, inst_ptrs);
-        for (const zk_mock_failure& f : failures) std::printf("mock: kind %u index %u sub %u row %u\n", f.kind, f.index, f.sub, f.row);
-        if (!failures.empty()) return 1;
+        if (!typed) {
+            // MockProver::run(..).assert_satisfied_par() first, as the reference's tests do before they prove
+            const std::vector<zk_mock_failure> failures = mock_verify(ctx, pk, adv_ptrs, inst_ptrs);
+            for (const zk_mock_failure& f : failures) std::printf("mock: kind %u index %u sub %u row %u\n", f.kind, f.index, f.sub, f.row);
+            if (!failures.empty()) return 1;
+        }
         std::array<uint8_t, 16> seed{};
         const std::vector<uint8_t> seed_file = slurp(dir + "/seed.bin", false);
         if (seed_file.size() == 16) std::memcpy(seed.data(), seed_file.data(), 16);
@@ -71,8 +82,13 @@ int main(int argc, char** argv) {
         ProofSession session(ctx, pk, inst, seed, shplonk);
         std::vector<uint32_t> all(A);
         for (uint32_t c = 0; c < A; ++c) all[c] = c;
-        (void)session.advice_phase(all, adv_ptrs);
-        if (!session.mock_verify().empty()) throw std::runtime_error("the session's own row checks disagree with the stand-alone ones");
+        if (typed) (void)session.advice_phase_typed(all, adv_ptrs, widths);
+        else (void)session.advice_phase(all, adv_ptrs);
+        const std::vector<zk_mock_failure> in_session = session.mock_verify();
+        if (typed) {
+            for (const zk_mock_failure& f : in_session) std::printf("mock: kind %u index %u sub %u row %u\n", f.kind, f.index, f.sub, f.row);
+            if (!in_session.empty()) return 1;
+        } else if (!in_session.empty()) throw std::runtime_error("the session's own row checks disagree with the stand-alone ones");
         const std::vector<uint8_t> proof = session.finish();
         std::ofstream(dir + "/proof_cpp.bin", std::ios::binary).write((const char*)proof.data(), (std::streamsize)proof.size());
         std::printf("k = %u, %zu advice / %zu instance columns, mock checks passed, %s proof of %zu bytes written\n", shape[0], A, I, shplonk ? "SHPLONK" : "GWC", proof.size());

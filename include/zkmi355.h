@@ -110,6 +110,13 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */
 int zk_fr_scale(zk_ctx* ctx, void* d_a, const void* h_s, size_t n);
+/* d_out[i] = Montgomery Fr of the unsigned little-endian integer d_packed[i] (width_bytes = 1, 2, 4, 8 or 16), i < n.
+ * d_packed: n * width_bytes bytes, aligned to width_bytes.  d_out: n * 32 B, must not overlap d_packed.
+ * Asynchronous on the context's stream like zk_fr_scale.  Any other width, or a misaligned pointer: ZK_ERR_INVALID_ARG.
+ * Booked under the zk_prof name "fr_from_uint" with n * (width_bytes + 32) algorithmic bytes per launch.
+ * A witness whose packed cells are already on the device (produced by another kernel) becomes an advice column by this call
+ * followed by zk_proof_advice_phase_dev; host columns of packed cells go to zk_proof_advice_phase_typed. */
+int zk_fr_from_uint(zk_ctx* ctx, const void* d_packed, uint32_t width_bytes, size_t n, void* d_out);
 /* ff::BatchInvert semantics (zeros stay zero), in place -- SURVEY 8a K12 */
 int zk_fr_batch_invert(zk_ctx* ctx, void* d_a, size_t n);
 
@@ -600,6 +607,17 @@ int zk_proof_advice_phase(zk_ctx* ctx, zk_proof* proof, const uint32_t* col_inde
 #define ZK_ADVICE_DEV_IN_PLACE 1u
 int zk_proof_advice_phase_dev(zk_ctx* ctx, zk_proof* proof, const uint32_t* col_index, const void* const* d_cols, uint32_t ncols, uint32_t flags,
                               void* h_challenges, uint32_t* num_challenges);
+/* zk_proof_advice_phase for host columns given as typed cells: h_cols[j] holds n cells of widths[j] bytes each
+ * (1, 2, 4, 8, 16: unsigned little-endian integers; 32: Montgomery Fr exactly as zk_proof_advice_phase takes it).
+ * Same transcript, same proof bytes as passing the same values as Fr.  As there, the last blinding_factors + 1 rows are
+ * the session's: whatever the caller put in them is neither uploaded nor read.
+ * A column narrower than 32 crosses PCIe as usable_rows * width bytes and is expanded to Montgomery form on the device; one
+ * call may mix widths.  Columns of 8 bytes or fewer take the small-value commitment path (zk_commit_batch_hint's hint 1)
+ * without being sampled.  Any other width or a null `widths`: ZK_ERR_INVALID_ARG, nothing is uploaded and the phase can be
+ * called again.  In a sharded session (world > 1): ZK_ERR_UNSUPPORTED.  There is no typed device-resident phase: packed cells
+ * already on the device go through zk_fr_from_uint and zk_proof_advice_phase_dev.                                          */
+int zk_proof_advice_phase_typed(zk_ctx* ctx, zk_proof* proof, const uint32_t* col_index, const void* const* h_cols, const uint8_t* widths,
+                                uint32_t ncols, void* h_challenges, uint32_t* num_challenges);
 /* consumes the session (freed on success and on failure)                                         */
 int zk_proof_finish(zk_ctx* ctx, zk_proof* proof, void* h_proof, size_t proof_cap, size_t* proof_len);
 void zk_proof_abort(zk_ctx* ctx, zk_proof* proof);

@@ -108,6 +108,13 @@ inline std::vector<Fr> kate_division(const Context& c, const std::vector<Fr>& a,
     return out;
 }
 
+// d_out[i] = Fr::from(d_packed[i]) for n little-endian unsigned cells of cell_bytes = 1, 2, 4, 8 or 16 bytes each, device to device
+// (zk_fr_from_uint; asynchronous on the context's stream).  With ProofSession::advice_phase_dev: a witness whose cells another
+// kernel left on the device as integers.
+inline void fr_from_uint(const Context& c, const void* d_packed, uint32_t cell_bytes, size_t n, void* d_out) {
+    c.check(zk_fr_from_uint(c.raw(), d_packed, cell_bytes, n, d_out));
+}
+
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {
    public:
@@ -263,6 +270,18 @@ class ProofSession {
         std::vector<Fr> ch(num_challenges_ ? num_challenges_ : 1);
         uint32_t cnt = (uint32_t)ch.size();
         c_.check(zk_proof_advice_phase_dev(c_.raw(), s_, column_index.data(), device_columns.data(), (uint32_t)column_index.size(), in_place ? ZK_ADVICE_DEV_IN_PLACE : 0u, ch.data(), &cnt));
+        ch.resize(cnt);
+        return ch;
+    }
+    // the same for host columns held as the integers they are (zk_proof_advice_phase_typed): cell_bytes[j] = 1, 2, 4, 8 or 16 for n
+    // little-endian unsigned cells of that size, 32 for Montgomery Fr.  Narrow columns cross PCIe at their own width and are expanded on
+    // the device; same challenges, same proof.  Not for sharded sessions.  Packed cells that are already on the device: fr_from_uint
+    // below, then advice_phase_dev.
+    std::vector<Fr> advice_phase_typed(const std::vector<uint32_t>& column_index, const std::vector<const void*>& columns, const std::vector<uint8_t>& cell_bytes) {
+        if (cell_bytes.size() != column_index.size() || columns.size() != column_index.size()) throw Error(ZK_ERR_INVALID_ARG, "advice_phase_typed: one column and one cell width per column index");
+        std::vector<Fr> ch(num_challenges_ ? num_challenges_ : 1);
+        uint32_t cnt = (uint32_t)ch.size();
+        c_.check(zk_proof_advice_phase_typed(c_.raw(), s_, column_index.data(), columns.data(), cell_bytes.data(), (uint32_t)column_index.size(), ch.data(), &cnt));
         ch.resize(cnt);
         return ch;
     }

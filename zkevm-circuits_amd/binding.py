@@ -72,6 +72,17 @@ def _host_ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def typed_cell_width(a: np.ndarray) -> int:
+    """bytes per cell of a typed witness column (zk_proof_advice_phase_typed, zk_fr_from_uint): 1, 2, 4, 8 for a one-dimensional
+    uint8 / uint16 / uint32 / uint64 array, 16 for (n, 2) uint64 (low word first), 32 for (n, 4) uint64 (Montgomery Fr)"""
+    a = np.asarray(a)
+    if a.ndim == 1 and a.dtype in (np.uint8, np.uint16, np.uint32, np.uint64):
+        return a.dtype.itemsize
+    if a.ndim == 2 and a.dtype == np.uint64 and a.shape[1] in (2, 4):
+        return 8 * a.shape[1]
+    raise ZkError(f"not a typed witness column: dtype {a.dtype}, shape {a.shape} (uint8/16/32/64 of shape (n,), or uint64 of shape (n, 2) or (n, 4))")
+
+
 class DeviceBuffer:
     """Owning handle of a device allocation made through the C ABI."""
 
@@ -399,6 +410,24 @@ class ProofSession:
         self.ctx._ck(lib().zk_proof_advice_phase(self.ctx.h, self.h, ci, pc, ctypes.c_uint32(len(idx)), _host_ptr(out), ctypes.byref(cnt)))
         return out[:cnt.value].copy()
 
+    def advice_phase_typed(self, columns: dict) -> np.ndarray:
+        """advice_phase for columns held as the integers they are: {advice column index: array of n cells}, the cell width taken
+        from the array (typed_cell_width): uint8 / uint16 / uint32 / uint64 of shape (n,), (n, 2) uint64 for 128-bit cells (low
+        word first), (n, 4) uint64 for Montgomery Fr as advice_phase takes it.  Narrow columns cross PCIe at their own width and
+        are expanded on the device; same challenges, same proof bytes.  Not available in a sharded session."""
+        idx = sorted(columns)
+        cols = [np.ascontiguousarray(columns[i]) for i in idx]
+        wd = (ctypes.c_uint8 * max(len(idx), 1))(*[typed_cell_width(c) for c in cols])
+        ci = (ctypes.c_uint32 * max(len(idx), 1))(*idx)
+        pc = (ctypes.c_void_p * max(len(idx), 1))(*[c.ctypes.data for c in cols])
+        cap = getattr(self, "_challenge_cap", None)
+        if cap is None:
+            cap = self._challenge_cap = max(1, self.pk.shape()["challenges"])
+        out = np.zeros((cap, 4), dtype=np.uint64)
+        cnt = ctypes.c_uint32(cap)
+        self.ctx._ck(lib().zk_proof_advice_phase_typed(self.ctx.h, self.h, ci, pc, wd, ctypes.c_uint32(len(idx)), _host_ptr(out), ctypes.byref(cnt)))
+        return out[:cnt.value].copy()
+
     def advice_phase_dev(self, columns: dict, in_place: bool = False) -> np.ndarray:
         """{advice column index: DeviceBuffer (n x 32 B, Montgomery)}: the phase's witness columns resident on the device.
         in_place: the session works in these buffers (it overwrites their blinding rows) until finish() / abort() returns.
@@ -526,6 +555,10 @@ class Context:
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))
+
+    def fr_from_uint(self, packed: DeviceBuffer, width_bytes: int, n: int, out: DeviceBuffer, offset_bytes: int = 0):
+        """out[i] = Montgomery Fr of the unsigned little-endian integer of width_bytes (1, 2, 4, 8, 16) at packed + offset_bytes + i * width_bytes"""
+        self._ck(lib().zk_fr_from_uint(self.h, ctypes.c_void_p(packed.ptr + offset_bytes), ctypes.c_uint32(width_bytes), ctypes.c_size_t(n), ctypes.c_void_p(out.ptr)))
 
     def fr_batch_invert(self, a: DeviceBuffer, n: int):
         self._ck(lib().zk_fr_batch_invert(self.h, ctypes.c_void_p(a.ptr), ctypes.c_size_t(n)))

@@ -914,9 +914,23 @@ int zk_proof_begin_instances(zk_ctx* ctx, const zk_pk* pk, const void* const* h_
 // challenges) on entry; on return it holds how many the phase produced.
 static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr);
 static int advice_lagrange_readers(zk_ctx* ctx, const zk_pk* pk, std::vector<uint8_t>* need);
-static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, uint32_t ncols, void* h_challenges, uint32_t* num_challenges, bool dev_src, bool in_place);
+static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, uint32_t ncols, void* h_challenges, uint32_t* num_challenges, bool dev_src, bool in_place,
+                             const uint8_t* widths = nullptr /* host columns as typed cells: bytes per cell of h_cols[j], 32 = Montgomery Fr */);
 int zk_proof_advice_phase(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, uint32_t ncols, void* h_challenges, uint32_t* num_challenges) {
     return advice_phase_impl(ctx, pr, col_index, h_cols, ncols, h_challenges, num_challenges, false, false);
+}
+// The same phase for host columns given as typed cells (widths[j] bytes per cell of h_cols[j]: 1, 2, 4, 8, 16 = unsigned little-endian
+// integers, 32 = Montgomery Fr): a narrow column crosses PCIe as usable_rows x width bytes and becomes the Montgomery column on the
+// device (k_fr_from_uint, on the copy stream right behind its upload).  Same transcript, same bytes.
+int zk_proof_advice_phase_typed(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, const uint8_t* widths, uint32_t ncols, void* h_challenges, uint32_t* num_challenges) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    ZK_REQUIRE(ctx, pr && widths, "null pointer");
+    for (uint32_t j = 0; j < ncols; ++j) {
+        const uint8_t w = widths[j];
+        if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16 && w != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "column %u: cell width %u (must be 1, 2, 4, 8, 16 or 32 bytes)", j, (unsigned)w);
+    }
+    if (pr->world > 1) return ctx->fail(ZK_ERR_UNSUPPORTED, "typed witness columns in a sharded session (world %u) are not supported: pass Montgomery columns to zk_proof_advice_phase", pr->world);
+    return advice_phase_impl(ctx, pr, col_index, h_cols, ncols, h_challenges, num_challenges, false, false, widths);
 }
 // The same phase for witness columns that are RESIDENT ON THE DEVICE (n x 32 B each, Montgomery, device pointers): a witness
 // generated on the GPU, or one uploaded ahead of the proof.  Judged small / dense on the device.  Same transcript, same bytes as the
@@ -932,7 +946,8 @@ int zk_proof_advice_phase_dev(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_ind
     ZK_REQUIRE(ctx, (flags & ~(uint32_t)ZK_ADVICE_DEV_IN_PLACE) == 0, "unknown flag");
     return advice_phase_impl(ctx, pr, col_index, d_cols, ncols, h_challenges, num_challenges, true, (flags & ZK_ADVICE_DEV_IN_PLACE) != 0);
 }
-static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, uint32_t ncols, void* h_challenges, uint32_t* num_challenges, bool dev_src, bool in_place) {
+static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, uint32_t ncols, void* h_challenges, uint32_t* num_challenges, bool dev_src, bool in_place,
+                             const uint8_t* widths) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
     PoolScope pool_scope(ctx);
     ZK_REQUIRE(ctx, pr && (ncols == 0 || (col_index && h_cols)), "null pointer");
@@ -949,12 +964,13 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
     // the phase's columns in ascending column order, j % world == rank); the others arrive over the fabric and may be passed as NULL.
     const bool owner_only = dev_src && pr->world > 1 && pr->gather && pr->gather_dev;
     std::vector<const void*> by_col(pk->A, nullptr);
-    std::vector<uint8_t> seen(pk->A, 0);
+    std::vector<uint8_t> seen(pk->A, 0), width_of(pk->A, 32);
     for (uint32_t j = 0; j < ncols; ++j) {
         const uint32_t c = col_index[j];
         if (c >= pk->A || pk->adv_phase[c] != pr->phase || seen[c] || (!h_cols[j] && !owner_only)) return ctx->fail(ZK_ERR_INVALID_ARG, "advice column %u does not belong to phase %u (or is repeated)", c, pr->phase);
         by_col[c] = h_cols[j];
         seen[c] = 1;
+        if (widths) width_of[c] = widths[j];
     }
     if (owner_only) {
         uint32_t pos = 0;
@@ -978,6 +994,8 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
     struct Stage {
         zk_ctx* ctx; size_t body, tail;
         std::vector<const void*> src; std::vector<void*> dst; std::vector<F4> blind_v; const F4* blind = nullptr;
+        std::vector<uint8_t> width;                                      // bytes per cell of src[c]: below 32, the column is uploaded packed and expanded on the device
+        void* packed = nullptr;                                          // staging of ONE packed column: upload and expansion share the in-order copy stream, so the next upload cannot overtake the expansion
         uint32_t world = 1;
         hipMemcpyKind kind = hipMemcpyHostToDevice;                       // device-resident witness: device to device
         std::vector<size_t> own;                                         // device-gather mode: only these columns are uploaded by this rank
@@ -1027,11 +1045,19 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         if (in_place && by_col[c] && (!owner_only || sg.dst.size() % pr->world == pr->rank)) pr->adv_lag[c].borrow(const_cast<void*>(by_col[c]));
         else if (!pr->adv_lag[c].alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc of %zu bytes failed", n * 32);
         sg.src.push_back(by_col[c]);
+        sg.width.push_back(width_of[c]);
         sg.dst.push_back(pr->adv_lag[c].p);
         sg.lag.push_back(&pr->adv_lag[c]);
         sg.coeff.push_back(&pr->adv_coeff[c]);
         sg.col.push_back(c);
         for (uint32_t r = 0; r <= pk->bf; ++r) sg.blind_v.push_back(pr->rng.next_fr());
+    }
+    DevBuf packed_buf;                            // back in the pool when the phase returns: by then the main stream has waited for the last expansion
+    size_t widest_packed = 0;
+    for (uint8_t w : sg.width) if (w < 32) widest_packed = std::max<size_t>(widest_packed, w);
+    if (widest_packed) {
+        PK_ALLOC(ctx, packed_buf, (size_t)pk->u * widest_packed);
+        sg.packed = packed_buf.p;
     }
     PinnedBuf blind_pinned;
     if (!blind_pinned.alloc(sg.blind_v.size() * sizeof(F4))) return ctx->fail(ZK_ERR_OOM, "prover: pinned staging allocation failed");
@@ -1076,7 +1102,10 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         static const bool skip_upload = getenv("ZK_DEBUG_SKIP_UPLOAD") != nullptr;       // measurement only (the proof is garbage): is the phase bound by PCIe or by the device?
         for (size_t c_ = it * s_->world; c_ < std::min((it + 1) * (size_t)s_->world, s_->dst.size()); ++c_) {
             if (skip_upload) continue;
-            if (s_->dst[c_] != s_->src[c_]) ZK_HIP(s_->ctx, hipMemcpyAsync(s_->dst[c_], s_->src[c_], s_->body, s_->kind, s_->ctx->stream_copy));      // in place: only the blinding rows move
+            if (s_->width[c_] < 32) {                                     // typed cells: body / 32 rows of width bytes, expanded behind the upload
+                ZK_HIP(s_->ctx, hipMemcpyAsync(s_->packed, s_->src[c_], s_->body / 32 * s_->width[c_], hipMemcpyHostToDevice, s_->ctx->stream_copy));
+                PK_TRY(fr_from_uint_run(s_->ctx, s_->ctx->stream_copy, s_->packed, s_->width[c_], s_->body / 32, (Fr*)s_->dst[c_]));
+            } else if (s_->dst[c_] != s_->src[c_]) ZK_HIP(s_->ctx, hipMemcpyAsync(s_->dst[c_], s_->src[c_], s_->body, s_->kind, s_->ctx->stream_copy));      // in place: only the blinding rows move
             ZK_HIP(s_->ctx, hipMemcpyAsync((char*)s_->dst[c_] + s_->body, s_->blind + c_ * (s_->tail / 32), s_->tail, hipMemcpyHostToDevice, s_->ctx->stream_copy));
         }
         PK_TRY(copy_stream_fence(s_->ctx));
@@ -1092,7 +1121,22 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         PK_TRY(sample_narrow_dev(ctx, own_src.data(), own_src.size(), n, own_narrow.data()));
         for (size_t j = 0; j < own_src.size(); ++j) narrow[pr->rank + j * pr->world] = own_narrow[j];
     } else if (dev_src) PK_TRY(sample_narrow_dev(ctx, sg.src.data(), sg.src.size(), n, narrow.data()));
-    else sample_narrow(sg.src.data(), sg.src.size(), n, narrow.data());       // witness columns of (mostly) small values take the per-window MSM path
+    else if (!widths) sample_narrow(sg.src.data(), sg.src.size(), n, narrow.data());       // witness columns of (mostly) small values take the per-window MSM path
+    else {
+        // typed cells: 8 bytes or fewer are below 2^64 by construction; 16-byte cells are sampled as the integers they are (same rule: at
+        // most a quarter of the samples at 2^64 or above), Montgomery columns as ever
+        std::vector<const void*> fr_only(sg.src.size(), nullptr);
+        for (size_t c_ = 0; c_ < sg.src.size(); ++c_) if (sg.width[c_] == 32) fr_only[c_] = sg.src[c_];
+        sample_narrow(fr_only.data(), fr_only.size(), n, narrow.data());
+        const size_t samples = std::min<size_t>(pk->u, 1024), step = pk->u / (samples ? samples : 1);
+        for (size_t c_ = 0; c_ < sg.src.size(); ++c_) {
+            if (sg.width[c_] <= 8) narrow[c_] = 1;
+            if (sg.width[c_] != 16) continue;
+            size_t large = 0;
+            for (size_t i = 0; i < samples; ++i) large += ((const uint64_t*)sg.src[c_])[2 * (i * step) + 1] != 0;
+            narrow[c_] = large <= samples / 4;
+        }
+    }
     trace.mark("  advice: columns sampled");
     // ... and their blinding rows (the last blinding_factors + 1, field-sized) are committed apart, so that they do not occupy every window
     struct TailGuard { zk_ctx* c; ~TailGuard() { c->msm_blinded_tail = 0; } } tail_guard{ctx};

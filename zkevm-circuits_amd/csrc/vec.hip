@@ -416,6 +416,97 @@ int fr_add_const_many(zk_ctx* ctx, const void* const* d_src, void* const* d_dst,
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
+
+// ---- typed narrow cells: out[i] = Montgomery Fr of the W-byte little-endian unsigned integer in[i] ------------------------------
+// One mul29 per cell: the integer (at most five non-zero limbs) times the plain constant 2^517 = 2^256 * 2^261 leaves x * 2^256.
+// Memory shape: a wave owns FU_CELLS * 64 consecutive cells and writes them in FU_CELLS sweeps, lane L the cell sweep * 64 + L, so
+// every sweep stores 64 consecutive elements (the two 16-byte transactions per lane of the rest of this file).  The loads of all
+// sweeps are issued before the first product.  W >= 4: a lane loads its own cell (4 / 8 / 16 B per lane, consecutive lanes on
+// consecutive cells).  W < 4: a byte or a halfword per lane would spend a whole load instruction on 64 or 128 bytes, so lane L loads
+// the FU_CELLS consecutive cells FU_CELLS * L .. as ONE dword (W = 1) or dwordx2 (W = 2) and the sweeps fetch their cell from the
+// owning lane with a shuffle.  That load needs 4 / 8-byte alignment while the caller guarantees W: the launch passes the pointer
+// rounded down and `head`, the number of cells of the first packed word that lie in front of the data.  Cells are addressed by their
+// virtual index v = i + head; a packed word that is not wholly inside [head, head + n) -- only the first and the last can be --
+// is put together from loads of its valid cells alone, so nothing outside the caller's n * W bytes is read.
+constexpr int FU_CELLS = 4;
+template <int W>
+__global__ void __launch_bounds__(256) k_fr_from_uint(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, Fr* __restrict__ out, Fr c517_plain) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t v0 = wave * (FU_CELLS * 64), end = head + n;         // virtual cells [v0, v0 + 256) of this wave; valid: head <= v < end
+    uint32_t x[FU_CELLS][4];
+#pragma unroll
+    for (int j = 0; j < FU_CELLS; ++j) x[j][0] = x[j][1] = x[j][2] = x[j][3] = 0;
+    if constexpr (W < 4) {
+        static_assert(FU_CELLS == 4, "a packed word holds four cells");
+        const uint64_t q = v0 + (uint64_t)FU_CELLS * lane;              // first virtual cell of this lane's packed word
+        uint32_t lo = 0, hi = 0;                                        // cell t of the word: bits [8 W t, 8 W (t + 1)) of hi:lo
+        if (q >= head && q + FU_CELLS <= end) {
+            if constexpr (W == 1) lo = *reinterpret_cast<const uint32_t*>(src + q);
+            else { const uint2 p = *reinterpret_cast<const uint2*>(src + q * 2); lo = p.x; hi = p.y; }
+        } else {
+#pragma unroll
+            for (int t = 0; t < FU_CELLS; ++t) {
+                if (q + t < head || q + t >= end) continue;
+                if constexpr (W == 1) lo |= (uint32_t)src[q + t] << (8 * t);
+                else {
+                    const uint32_t c = *reinterpret_cast<const uint16_t*>(src + (q + t) * 2);
+                    if (t < 2) lo |= c << (16 * t); else hi |= c << (16 * (t - 2));
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < FU_CELLS; ++j) {                            // cell j * 64 + lane of the wave sits in lane (j * 64 + lane) / 4, position lane % 4
+            const int owner = j * (64 / FU_CELLS) + (int)(lane >> 2);
+            const uint32_t t = lane & 3u;
+            if constexpr (W == 1) x[j][0] = (__shfl(lo, owner) >> (8 * t)) & 0xffu;
+            else {
+                const uint32_t a = __shfl(lo, owner), b = __shfl(hi, owner);
+                x[j][0] = ((t & 2u ? b : a) >> (16 * (t & 1u))) & 0xffffu;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < FU_CELLS; ++j) {
+            const uint64_t v = v0 + (uint64_t)j * 64 + lane;
+            if (v >= end) continue;                                     // head == 0 here
+            if constexpr (W == 4) x[j][0] = *reinterpret_cast<const uint32_t*>(src + v * 4);
+            else if constexpr (W == 8) { const uint2 p = *reinterpret_cast<const uint2*>(src + v * 8); x[j][0] = p.x; x[j][1] = p.y; }
+            else { const uint4 p = *reinterpret_cast<const uint4*>(src + v * 16); x[j][0] = p.x; x[j][1] = p.y; x[j][2] = p.z; x[j][3] = p.w; }
+        }
+    }
+    const Fr29 c517 = unpack29<Fr29P>(c517_plain);
+#pragma unroll
+    for (int j = 0; j < FU_CELLS; ++j) {
+        const uint64_t v = v0 + (uint64_t)j * 64 + lane;
+        if (v < head || v >= end) continue;
+        const Fr cell{{x[j][0], x[j][1], x[j][2], x[j][3], 0, 0, 0, 0}};
+        stg(out + (v - head), pack29_lt2p(mul29(unpack29<Fr29P>(cell), c517)));
+    }
+}
+int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint32_t width, uint64_t n, Fr* d_out) {
+    if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16) return ctx->fail(ZK_ERR_INVALID_ARG, "cell width %u: must be 1, 2, 4, 8 or 16 bytes", width);
+    if ((uintptr_t)d_packed % width) return ctx->fail(ZK_ERR_INVALID_ARG, "packed cells of %u bytes at an address that is no multiple of %u", width, width);
+    if (!n) return ZK_OK;
+    static const Fr c517 = [] { Fr c = Fr::one(); for (int i = 0; i < 517 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^517 mod r (Fr::one() holds 2^256)
+    const uint32_t load_bytes = width < 4 ? width * FU_CELLS : width;
+    const uint32_t head = (uint32_t)((uintptr_t)d_packed % load_bytes) / width;
+    const uint8_t* base = (const uint8_t*)d_packed - (size_t)head * width;
+    const uint64_t per_block = (uint64_t)FU_CELLS * 256, blocks = (head + n + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many cells for one launch");
+    ZkProfScope prof(ctx, "fr_from_uint", stream);
+    prof.bytes = n * (width + 32ull);
+    const dim3 g((unsigned)blocks), t(256);
+    switch (width) {
+        case 1: hipLaunchKernelGGL(k_fr_from_uint<1>, g, t, 0, stream, base, head, n, d_out, c517); break;
+        case 2: hipLaunchKernelGGL(k_fr_from_uint<2>, g, t, 0, stream, base, head, n, d_out, c517); break;
+        case 4: hipLaunchKernelGGL(k_fr_from_uint<4>, g, t, 0, stream, base, head, n, d_out, c517); break;
+        case 8: hipLaunchKernelGGL(k_fr_from_uint<8>, g, t, 0, stream, base, head, n, d_out, c517); break;
+        default: hipLaunchKernelGGL(k_fr_from_uint<16>, g, t, 0, stream, base, head, n, d_out, c517); break;
+    }
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
 }  // namespace zk
 
 using namespace zk;
@@ -435,6 +526,14 @@ int zk_fr_scale(zk_ctx* ctx, void* d_a, const void* h_s, size_t n) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
     ZK_REQUIRE(ctx, d_a && h_s, "null pointer");
     return fr_scale_run(ctx, (Fr*)d_a, *(const Fr*)h_s, n);
+}
+
+int zk_fr_from_uint(zk_ctx* ctx, const void* d_packed, uint32_t width_bytes, size_t n, void* d_out) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    ZK_REQUIRE(ctx, (d_packed && d_out) || !n, "null pointer");
+    const uintptr_t a = (uintptr_t)d_packed, o = (uintptr_t)d_out;
+    ZK_REQUIRE(ctx, width_bytes > 16 || a + n * width_bytes <= o || o + n * sizeof(Fr) <= a, "the output overlaps the packed cells");
+    return fr_from_uint_run(ctx, ctx->stream, d_packed, width_bytes, n, (Fr*)d_out);
 }
 
 int zk_fr_batch_invert(zk_ctx* ctx, void* d_a, size_t n) {
