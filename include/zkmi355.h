@@ -117,6 +117,12 @@ int zk_fr_scale(zk_ctx* ctx, void* d_a, const void* h_s, size_t n);
  * A witness whose packed cells are already on the device (produced by another kernel) becomes an advice column by this call
  * followed by zk_proof_advice_phase_dev; host columns of packed cells go to zk_proof_advice_phase_typed. */
 int zk_fr_from_uint(zk_ctx* ctx, const void* d_packed, uint32_t width_bytes, size_t n, void* d_out);
+/* zk_fr_from_uint for several columns at once: count columns of n cells each; widths[j] in {1,2,4,8,16}; d_packed[j] aligned to
+ * widths[j]; d_out[j] n x 32 B Montgomery Fr.  Asynchronous on the context's stream like zk_fr_from_uint; 16 columns per launch (a
+ * workgroup works on one column, so one call may mix widths).  Outputs must not overlap each other or any input; several columns may
+ * read the same packed cells.  Any other width, a misaligned or NULL pointer: ZK_ERR_INVALID_ARG and nothing is written.
+ * count = 0: ZK_OK.  Booked under the zk_prof name "fr_from_uint_batch", per launch, with the sum of n * (widths[j] + 32) bytes. */
+int zk_fr_from_uint_batch(zk_ctx* ctx, const void* const* d_packed, const uint8_t* widths, size_t count, size_t n, void* const* d_out);
 /* ff::BatchInvert semantics (zeros stay zero), in place -- SURVEY 8a K12 */
 int zk_fr_batch_invert(zk_ctx* ctx, void* d_a, size_t n);
 
@@ -614,10 +620,23 @@ int zk_proof_advice_phase_dev(zk_ctx* ctx, zk_proof* proof, const uint32_t* col_
  * A column narrower than 32 crosses PCIe as usable_rows * width bytes and is expanded to Montgomery form on the device; one
  * call may mix widths.  Columns of 8 bytes or fewer take the small-value commitment path (zk_commit_batch_hint's hint 1)
  * without being sampled.  Any other width or a null `widths`: ZK_ERR_INVALID_ARG, nothing is uploaded and the phase can be
- * called again.  In a sharded session (world > 1): ZK_ERR_UNSUPPORTED.  There is no typed device-resident phase: packed cells
- * already on the device go through zk_fr_from_uint and zk_proof_advice_phase_dev.                                          */
+ * called again.  In a sharded session (world > 1): ZK_ERR_UNSUPPORTED.  Packed cells that are already on the device go to
+ * zk_proof_advice_phase_typed_dev.                                                                                          */
 int zk_proof_advice_phase_typed(zk_ctx* ctx, zk_proof* proof, const uint32_t* col_index, const void* const* h_cols, const uint8_t* widths,
                                 uint32_t ncols, void* h_challenges, uint32_t* num_challenges);
+/* zk_proof_advice_phase_typed for cells that are RESIDENT ON THE DEVICE (a witness kernel's output): d_cols[j] is a device pointer
+ * aligned to widths[j] (8 for width 32).  widths[j] = 1, 2, 4, 8, 16: at least usable_rows (n - blinding_factors - 1) little-endian
+ * unsigned cells of that width, and only those are read; widths[j] = 32: an n x 32 B Montgomery column, copied as
+ * zk_proof_advice_phase_dev with flags = 0 copies it.  The rows from usable_rows on are the session's blinding values.
+ * Narrow columns are expanded straight into the session's own buffers, 16 columns per launch, on the stream that orders the
+ * commitments behind an upload: no n x 32 B copy on the caller's side, no staging buffer, no host synchronisation per column.
+ * Columns of 8 bytes or fewer take the small-value commitment path without being sampled; 16- and 32-byte columns are judged on
+ * the device.  The buffers are only read (several columns may name the same one) and not after the call returns.
+ * Same transcript, same challenges, same proof bytes as zk_proof_advice_phase on the same values.
+ * A bad width, a NULL or misaligned pointer, a column of another phase: ZK_ERR_INVALID_ARG, and the phase can be called again.
+ * In a sharded session (world > 1): ZK_ERR_UNSUPPORTED, before any work.                                                        */
+int zk_proof_advice_phase_typed_dev(zk_ctx* ctx, zk_proof* proof, const uint32_t* col_index, const void* const* d_cols, const uint8_t* widths,
+                                    uint32_t ncols, void* h_challenges, uint32_t* num_challenges);
 /* consumes the session (freed on success and on failure)                                         */
 int zk_proof_finish(zk_ctx* ctx, zk_proof* proof, void* h_proof, size_t proof_cap, size_t* proof_len);
 void zk_proof_abort(zk_ctx* ctx, zk_proof* proof);

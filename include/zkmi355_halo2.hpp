@@ -114,6 +114,12 @@ inline std::vector<Fr> kate_division(const Context& c, const std::vector<Fr>& a,
 inline void fr_from_uint(const Context& c, const void* d_packed, uint32_t cell_bytes, size_t n, void* d_out) {
     c.check(zk_fr_from_uint(c.raw(), d_packed, cell_bytes, n, d_out));
 }
+// the same for several columns of n cells each, sixteen per launch (zk_fr_from_uint_batch): cell_bytes[j] per column, one call may
+// mix widths; outputs overlap neither each other nor any input
+inline void fr_from_uint_batch(const Context& c, const std::vector<const void*>& d_packed, const std::vector<uint8_t>& cell_bytes, size_t n, const std::vector<void*>& d_out) {
+    if (cell_bytes.size() != d_packed.size() || d_out.size() != d_packed.size()) throw Error(ZK_ERR_INVALID_ARG, "fr_from_uint_batch: one cell width and one output per column");
+    c.check(zk_fr_from_uint_batch(c.raw(), d_packed.data(), cell_bytes.data(), d_packed.size(), n, d_out.data()));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {
@@ -275,13 +281,24 @@ class ProofSession {
     }
     // the same for host columns held as the integers they are (zk_proof_advice_phase_typed): cell_bytes[j] = 1, 2, 4, 8 or 16 for n
     // little-endian unsigned cells of that size, 32 for Montgomery Fr.  Narrow columns cross PCIe at their own width and are expanded on
-    // the device; same challenges, same proof.  Not for sharded sessions.  Packed cells that are already on the device: fr_from_uint
-    // below, then advice_phase_dev.
+    // the device; same challenges, same proof.  Not for sharded sessions.  Packed cells that are already on the device:
+    // advice_phase_typed_dev.
     std::vector<Fr> advice_phase_typed(const std::vector<uint32_t>& column_index, const std::vector<const void*>& columns, const std::vector<uint8_t>& cell_bytes) {
         if (cell_bytes.size() != column_index.size() || columns.size() != column_index.size()) throw Error(ZK_ERR_INVALID_ARG, "advice_phase_typed: one column and one cell width per column index");
         std::vector<Fr> ch(num_challenges_ ? num_challenges_ : 1);
         uint32_t cnt = (uint32_t)ch.size();
         c_.check(zk_proof_advice_phase_typed(c_.raw(), s_, column_index.data(), columns.data(), cell_bytes.data(), (uint32_t)column_index.size(), ch.data(), &cnt));
+        ch.resize(cnt);
+        return ch;
+    }
+    // the same for cells resident on the device (zk_proof_advice_phase_typed_dev; a witness kernel's output): device pointers to at
+    // least usable_rows packed cells (cell_bytes[j] = 1, 2, 4, 8, 16) or to an n x 32 B Montgomery column (32).  Expanded straight into
+    // the session's buffers, sixteen columns per launch; the caller's buffers are only read, and not after the call returns.
+    std::vector<Fr> advice_phase_typed_dev(const std::vector<uint32_t>& column_index, const std::vector<const void*>& device_columns, const std::vector<uint8_t>& cell_bytes) {
+        if (cell_bytes.size() != column_index.size() || device_columns.size() != column_index.size()) throw Error(ZK_ERR_INVALID_ARG, "advice_phase_typed_dev: one column and one cell width per column index");
+        std::vector<Fr> ch(num_challenges_ ? num_challenges_ : 1);
+        uint32_t cnt = (uint32_t)ch.size();
+        c_.check(zk_proof_advice_phase_typed_dev(c_.raw(), s_, column_index.data(), device_columns.data(), cell_bytes.data(), (uint32_t)column_index.size(), ch.data(), &cnt));
         ch.resize(cnt);
         return ch;
     }

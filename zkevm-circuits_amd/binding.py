@@ -64,6 +64,11 @@ def lib():
         _lib.zk_transcript_proof.restype = ctypes.c_size_t
         _lib.zk_vk_destroy.restype = None
         _lib.zk_vk_destroy.argtypes = [ctypes.c_void_p]
+        vpp, u8p, u32p = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+        _lib.zk_fr_from_uint_batch.restype = ctypes.c_int
+        _lib.zk_fr_from_uint_batch.argtypes = [ctypes.c_void_p, vpp, u8p, ctypes.c_size_t, ctypes.c_size_t, vpp]
+        _lib.zk_proof_advice_phase_typed_dev.restype = ctypes.c_int
+        _lib.zk_proof_advice_phase_typed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u32p, vpp, u8p, ctypes.c_uint32, ctypes.c_void_p, u32p]
     return _lib
 
 
@@ -444,6 +449,24 @@ class ProofSession:
         self.ctx._ck(lib().zk_proof_advice_phase_dev(self.ctx.h, self.h, ci, ptrs, ctypes.c_uint32(len(idx)), ctypes.c_uint32(1 if in_place else 0), _host_ptr(out), ctypes.byref(cnt)))
         return out[:cnt.value].copy()
 
+    def advice_phase_typed_dev(self, columns: dict) -> np.ndarray:
+        """advice_phase_typed for cells resident on the device: {advice column index: (device pointer or DeviceBuffer, cell width)}.
+        Width 1, 2, 4, 8, 16: at least usable_rows packed little-endian unsigned cells; 32: an n x 32 B Montgomery column.  The
+        buffers are only read, and not after the call returns; several columns may share one.  Narrow columns are expanded straight
+        into the session's buffers, sixteen per launch; same challenges, same proof bytes.  Not available in a sharded session."""
+        idx = sorted(columns)
+        ptr_of = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        ci = (ctypes.c_uint32 * max(len(idx), 1))(*idx)
+        pc = (ctypes.c_void_p * max(len(idx), 1))(*[ptr_of(columns[i][0]) for i in idx])
+        wd = (ctypes.c_uint8 * max(len(idx), 1))(*[columns[i][1] for i in idx])
+        cap = getattr(self, "_challenge_cap", None)
+        if cap is None:
+            cap = self._challenge_cap = max(1, self.pk.shape()["challenges"])
+        out = np.zeros((cap, 4), dtype=np.uint64)
+        cnt = ctypes.c_uint32(cap)
+        self.ctx._ck(lib().zk_proof_advice_phase_typed_dev(self.ctx.h, self.h, ci, pc, wd, len(idx), _host_ptr(out), ctypes.byref(cnt)))
+        return out[:cnt.value].copy()
+
     def mock_verify(self, gate_rows: Optional[Sequence[int]] = None, lookup_rows: Optional[Sequence[int]] = None, cap: int = 4096):
         """zk_proof_mock_verify: MockProver's row checks over the columns this session holds, with the challenges its transcript
         produced; after the last advice phase, before finish().  Returns (records, total) like Context.mock_verify."""
@@ -559,6 +582,17 @@ class Context:
     def fr_from_uint(self, packed: DeviceBuffer, width_bytes: int, n: int, out: DeviceBuffer, offset_bytes: int = 0):
         """out[i] = Montgomery Fr of the unsigned little-endian integer of width_bytes (1, 2, 4, 8, 16) at packed + offset_bytes + i * width_bytes"""
         self._ck(lib().zk_fr_from_uint(self.h, ctypes.c_void_p(packed.ptr + offset_bytes), ctypes.c_uint32(width_bytes), ctypes.c_size_t(n), ctypes.c_void_p(out.ptr)))
+
+    def fr_from_uint_batch(self, ptrs: Sequence[int], widths: Sequence[int], n: int, outs: Sequence[int]):
+        """fr_from_uint for len(ptrs) columns of n cells each, sixteen columns per launch: ptrs[j] / outs[j] are device pointers (or
+        DeviceBuffers) of the packed cells of widths[j] bytes and of the n x 32 B output; one call may mix widths"""
+        ptr_of = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        assert len(ptrs) == len(widths) == len(outs)
+        cnt = len(ptrs)
+        pp = (ctypes.c_void_p * max(cnt, 1))(*[ptr_of(p) for p in ptrs])
+        po = (ctypes.c_void_p * max(cnt, 1))(*[ptr_of(p) for p in outs])
+        wd = (ctypes.c_uint8 * max(cnt, 1))(*widths)
+        self._ck(lib().zk_fr_from_uint_batch(self.h, pp, wd, cnt, n, po))
 
     def fr_batch_invert(self, a: DeviceBuffer, n: int):
         self._ck(lib().zk_fr_batch_invert(self.h, ctypes.c_void_p(a.ptr), ctypes.c_size_t(n)))

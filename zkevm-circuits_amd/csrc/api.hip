@@ -550,6 +550,48 @@ int sample_narrow_dev(zk_ctx* ctx, const void* const* d_cols, size_t count, size
     for (size_t c = 0; c < count; ++c) narrow[c] = large[c] <= samples * NARROW_MAX_LARGE_NUM / NARROW_MAX_LARGE_DEN ? 1 : 0;
     return ZK_OK;
 }
+// ... and for typed columns resident on the device (widths[c] bytes per cell): 8 bytes or fewer are below 2^64 by construction and
+// are not read; a column of 16-byte cells is judged by the high words of up to 4096 of its `rows` packed cells (one workgroup per
+// column, one launch and one download for all of them); Montgomery columns go through sample_narrow_dev.
+__global__ void __launch_bounds__(256) k_sample_large_u128(const uint64_t* const* __restrict__ cols, uint64_t rows, uint32_t* __restrict__ large) {
+    const uint64_t* col = cols[blockIdx.x];
+    const uint64_t samples = rows < 4096 ? rows : 4096, step = rows / (samples ? samples : 1);
+    uint32_t cnt = 0;
+    for (uint64_t i = threadIdx.x; i < samples; i += 256) cnt += col[2 * (i * step + (i * 7 + blockIdx.x) % (step ? step : 1)) + 1] != 0;
+    __shared__ uint32_t tot;
+    if (threadIdx.x == 0) tot = 0;
+    __syncthreads();
+    atomicAdd(&tot, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0) large[blockIdx.x] = tot;
+}
+int sample_narrow_dev_typed(zk_ctx* ctx, const void* const* d_cols, const uint8_t* widths, size_t count, size_t n, size_t rows, uint8_t* narrow) {
+    std::vector<const void*> fr_cols, u128_cols;
+    std::vector<size_t> fr_at, u128_at;
+    for (size_t c = 0; c < count; ++c) {
+        if (widths[c] <= 8) narrow[c] = 1;
+        else if (widths[c] == 16) { u128_cols.push_back(d_cols[c]); u128_at.push_back(c); }
+        else { fr_cols.push_back(d_cols[c]); fr_at.push_back(c); }
+    }
+    std::vector<uint8_t> fr_narrow(fr_cols.size());
+    if (int rc = sample_narrow_dev(ctx, fr_cols.data(), fr_cols.size(), n, fr_narrow.data())) return rc;
+    for (size_t j = 0; j < fr_at.size(); ++j) narrow[fr_at[j]] = fr_narrow[j];
+    if (u128_cols.empty()) return ZK_OK;
+    if (!rows) { for (size_t c : u128_at) narrow[c] = 1; return ZK_OK; }
+    const size_t cnt = u128_cols.size();
+    char* scratch = (char*)ctx->get_scratch(SC_TMP, cnt * 12);
+    if (!scratch) return ctx->fail(ZK_ERR_OOM, "column classification: scratch allocation failed");
+    ZK_HIP(ctx, hipMemcpyAsync(scratch, u128_cols.data(), cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t* d_large = (uint32_t*)(scratch + cnt * 8);
+    hipLaunchKernelGGL(k_sample_large_u128, dim3((unsigned)cnt), dim3(256), 0, ctx->stream, (const uint64_t* const*)scratch, (uint64_t)rows, d_large);
+    ZK_CHECK_LAUNCH(ctx);
+    std::vector<uint32_t> large(cnt);
+    ZK_HIP(ctx, hipMemcpyAsync(large.data(), d_large, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t samples = rows < 4096 ? rows : 4096;
+    for (size_t j = 0; j < cnt; ++j) narrow[u128_at[j]] = large[j] <= samples * NARROW_MAX_LARGE_NUM / NARROW_MAX_LARGE_DEN ? 1 : 0;
+    return ZK_OK;
+}
 int commit_batch_staged(zk_ctx* ctx, const zk_srs* srs, int basis, const void* const* d_scalar_ptrs, size_t count, size_t n, void* h_out_affine, MsmStageFn stage, void* stage_user, const uint8_t* narrow) {
     if (count == 0) return ZK_OK;            // an empty batch (a circuit without permutation columns or lookups) commits nothing
     ZK_REQUIRE(ctx, srs && h_out_affine && d_scalar_ptrs, "null pointer");

@@ -252,6 +252,7 @@ int msm_diff_try(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_s
 int commit_batch_staged(zk_ctx* ctx, const zk_srs* srs, int basis, const void* const* d_scalar_ptrs, size_t count, size_t n, void* h_out_affine, MsmStageFn stage, void* stage_user, const uint8_t* narrow = nullptr);
 void sample_narrow(const void* const* h_cols, size_t count, size_t n, uint8_t* narrow);   // host sampling of Montgomery-form columns: 1 = at most a quarter of the sampled values are >= 2^64
 int sample_narrow_dev(zk_ctx* ctx, const void* const* d_cols, size_t count, size_t n, uint8_t* narrow);   // the same for columns resident on the device
+int sample_narrow_dev_typed(zk_ctx* ctx, const void* const* d_cols, const uint8_t* widths, size_t count, size_t n, size_t rows, uint8_t* narrow);   // typed columns on the device: <= 8 bytes small by construction, 16 judged over `rows` packed cells, 32 as sample_narrow_dev
 int lookup_multiplicities_enqueue(zk_ctx* ctx, const Fr* const* d_inputs, size_t num_inputs, const Fr* d_table, size_t usable_rows, Fr* d_m, size_t n, uint32_t* d_status, bool reuse_hash = false);   // lookup.hip, no sync
 // row checks of zk_mock_verify (lookup.hip; enqueued on the context's stream, no sync)
 struct MockFail { uint32_t kind, index, sub, row; };          // == zk_mock_failure
@@ -263,6 +264,7 @@ int mock_perm_enqueue(zk_ctx* ctx, const Fr* const* d_sigma, const Fr* const* d_
                       uint32_t kind, MockFail* d_out, uint32_t cap, uint32_t* d_counter);
 int fr_add_const_many(zk_ctx* ctx, const void* const* d_src, void* const* d_dst, size_t count, const void* h_k, size_t n);   // vec.hip: dst[c] = src[c] + k, any number of columns, no upload / sync
 int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint32_t width, uint64_t n, Fr* d_out);   // vec.hip: zk_fr_from_uint on any stream of the context (validates width and alignment)
+int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_packed, const uint8_t* widths, size_t count, uint64_t n, Fr* const* d_out);   // vec.hip: count columns of n cells each, sixteen per launch (validates every width and alignment before the first launch)
 int g_to_lagrange(zk_ctx* ctx, const G1Affine* d_g, uint32_t k, G1Affine* d_out);   // ecntt.hip: inverse FFT over G1
 bool comm_ready(const zk_ctx* ctx);                                                              // comm.hip: in-library RCCL collectives
 int comm_allgather_dev(zk_ctx* ctx, const void* d_send, size_t bytes, void* d_recv);             // stream-ordered, no host sync

@@ -946,6 +946,21 @@ int zk_proof_advice_phase_dev(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_ind
     ZK_REQUIRE(ctx, (flags & ~(uint32_t)ZK_ADVICE_DEV_IN_PLACE) == 0, "unknown flag");
     return advice_phase_impl(ctx, pr, col_index, d_cols, ncols, h_challenges, num_challenges, true, (flags & ZK_ADVICE_DEV_IN_PLACE) != 0);
 }
+// The typed phase for cells RESIDENT ON THE DEVICE (d_cols[j]: at least usable_rows packed cells of widths[j] bytes, or an n x 32 B
+// Montgomery column): a witness kernel's bytes, flags, counters and 128-bit halves become the session's Lagrange columns without a
+// caller-side n x 32 B copy -- sixteen narrow columns per k_fr_from_uint_batch launch, written straight into the session's buffers on
+// the copy stream.  The caller's buffers are only read, and not after the call returns.  Same transcript, same bytes.
+int zk_proof_advice_phase_typed_dev(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* d_cols, const uint8_t* widths, uint32_t ncols, void* h_challenges, uint32_t* num_challenges) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    ZK_REQUIRE(ctx, pr && widths, "null pointer");
+    for (uint32_t j = 0; j < ncols; ++j) {
+        const uint8_t w = widths[j];
+        if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16 && w != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "column %u: cell width %u (must be 1, 2, 4, 8, 16 or 32 bytes)", j, (unsigned)w);
+        if (d_cols && (uintptr_t)d_cols[j] % (w < 32 ? w : 8)) return ctx->fail(ZK_ERR_INVALID_ARG, "column %u: cells of %u bytes at a misaligned address", j, (unsigned)w);
+    }
+    if (pr->world > 1) return ctx->fail(ZK_ERR_UNSUPPORTED, "typed witness columns in a sharded session (world %u) are not supported: pass Montgomery columns to zk_proof_advice_phase_dev", pr->world);
+    return advice_phase_impl(ctx, pr, col_index, d_cols, ncols, h_challenges, num_challenges, true, false, widths);
+}
 static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_index, const void* const* h_cols, uint32_t ncols, void* h_challenges, uint32_t* num_challenges, bool dev_src, bool in_place,
                              const uint8_t* widths) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
@@ -996,6 +1011,7 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         std::vector<const void*> src; std::vector<void*> dst; std::vector<F4> blind_v; const F4* blind = nullptr;
         std::vector<uint8_t> width;                                      // bytes per cell of src[c]: below 32, the column is uploaded packed and expanded on the device
         void* packed = nullptr;                                          // staging of ONE packed column: upload and expansion share the in-order copy stream, so the next upload cannot overtake the expansion
+        bool grouped = false; size_t expanded = 0;                       // typed cells resident on the device: columns [0, expanded) are on the copy stream, a group of FU_GROUP per staging call that runs out of them
         uint32_t world = 1;
         hipMemcpyKind kind = hipMemcpyHostToDevice;                       // device-resident witness: device to device
         std::vector<size_t> own;                                         // device-gather mode: only these columns are uploaded by this rank
@@ -1040,6 +1056,7 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
     sg.pk = pk;
     sg.pr = pr;
     sg.kind = dev_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    sg.grouped = dev_src && widths;
     for (uint32_t c = 0; c < pk->A; ++c) {        // column-index order = transcript order
         if (!seen[c]) continue;
         if (in_place && by_col[c] && (!owner_only || sg.dst.size() % pr->world == pr->rank)) pr->adv_lag[c].borrow(const_cast<void*>(by_col[c]));
@@ -1055,7 +1072,7 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
     DevBuf packed_buf;                            // back in the pool when the phase returns: by then the main stream has waited for the last expansion
     size_t widest_packed = 0;
     for (uint8_t w : sg.width) if (w < 32) widest_packed = std::max<size_t>(widest_packed, w);
-    if (widest_packed) {
+    if (widest_packed && !sg.grouped) {        // cells already on the device are expanded from where they are
         PK_ALLOC(ctx, packed_buf, (size_t)pk->u * widest_packed);
         sg.packed = packed_buf.p;
     }
@@ -1102,6 +1119,24 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         static const bool skip_upload = getenv("ZK_DEBUG_SKIP_UPLOAD") != nullptr;       // measurement only (the proof is garbage): is the phase bound by PCIe or by the device?
         for (size_t c_ = it * s_->world; c_ < std::min((it + 1) * (size_t)s_->world, s_->dst.size()); ++c_) {
             if (skip_upload) continue;
+            if (s_->grouped) {
+                // the narrow columns of sixteen consecutive columns in one launch, from the caller's cells into the session's buffers; the
+                // Montgomery columns among them are copied, and every column gets its blinding rows.  The calls for the other fifteen only fence.
+                if (c_ < s_->expanded) continue;
+                constexpr size_t FU_GROUP = 16;
+                const size_t g1 = std::min(c_ + FU_GROUP, s_->dst.size());
+                const void* gsrc[FU_GROUP]; Fr* gdst[FU_GROUP]; uint8_t gw[FU_GROUP];
+                size_t cnt = 0;
+                for (size_t g = c_; g < g1; ++g) {
+                    if (s_->width[g] < 32) { gsrc[cnt] = s_->src[g]; gdst[cnt] = (Fr*)s_->dst[g]; gw[cnt] = s_->width[g]; ++cnt; }
+                    else ZK_HIP(s_->ctx, hipMemcpyAsync(s_->dst[g], s_->src[g], s_->body, s_->kind, s_->ctx->stream_copy));
+                }
+                PK_TRY(fr_from_uint_batch_run(s_->ctx, s_->ctx->stream_copy, gsrc, gw, cnt, s_->body / 32, gdst));
+                for (size_t g = c_; g < g1; ++g)
+                    ZK_HIP(s_->ctx, hipMemcpyAsync((char*)s_->dst[g] + s_->body, s_->blind + g * (s_->tail / 32), s_->tail, hipMemcpyHostToDevice, s_->ctx->stream_copy));
+                s_->expanded = g1;
+                continue;
+            }
             if (s_->width[c_] < 32) {                                     // typed cells: body / 32 rows of width bytes, expanded behind the upload
                 ZK_HIP(s_->ctx, hipMemcpyAsync(s_->packed, s_->src[c_], s_->body / 32 * s_->width[c_], hipMemcpyHostToDevice, s_->ctx->stream_copy));
                 PK_TRY(fr_from_uint_run(s_->ctx, s_->ctx->stream_copy, s_->packed, s_->width[c_], s_->body / 32, (Fr*)s_->dst[c_]));
@@ -1120,7 +1155,8 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
         std::vector<uint8_t> own_narrow(own_src.size());
         PK_TRY(sample_narrow_dev(ctx, own_src.data(), own_src.size(), n, own_narrow.data()));
         for (size_t j = 0; j < own_src.size(); ++j) narrow[pr->rank + j * pr->world] = own_narrow[j];
-    } else if (dev_src) PK_TRY(sample_narrow_dev(ctx, sg.src.data(), sg.src.size(), n, narrow.data()));
+    } else if (dev_src && widths) PK_TRY(sample_narrow_dev_typed(ctx, sg.src.data(), sg.width.data(), sg.src.size(), n, pk->u, narrow.data()));
+    else if (dev_src) PK_TRY(sample_narrow_dev(ctx, sg.src.data(), sg.src.size(), n, narrow.data()));
     else if (!widths) sample_narrow(sg.src.data(), sg.src.size(), n, narrow.data());       // witness columns of (mostly) small values take the per-window MSM path
     else {
         // typed cells: 8 bytes or fewer are below 2^64 by construction; 16-byte cells are sampled as the integers they are (same rule: at

@@ -430,9 +430,8 @@ int fr_add_const_many(zk_ctx* ctx, const void* const* d_src, void* const* d_dst,
 // is put together from loads of its valid cells alone, so nothing outside the caller's n * W bytes is read.
 constexpr int FU_CELLS = 4;
 template <int W>
-__global__ void __launch_bounds__(256) k_fr_from_uint(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, Fr* __restrict__ out, Fr c517_plain) {
+__device__ __forceinline__ void fr_from_uint_wave(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, Fr* __restrict__ out, const Fr& c517_plain, uint64_t wave) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t v0 = wave * (FU_CELLS * 64), end = head + n;         // virtual cells [v0, v0 + 256) of this wave; valid: head <= v < end
     uint32_t x[FU_CELLS][4];
 #pragma unroll
@@ -484,11 +483,41 @@ __global__ void __launch_bounds__(256) k_fr_from_uint(const uint8_t* __restrict_
         stg(out + (v - head), pack29_lt2p(mul29(unpack29<Fr29P>(cell), c517)));
     }
 }
+template <int W>
+__global__ void __launch_bounds__(256) k_fr_from_uint(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, Fr* __restrict__ out, Fr c517_plain) {
+    fr_from_uint_wave<W>(src, head, n, out, c517_plain, ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+}
+// The same for up to FU_BATCH columns of n cells each in ONE launch: blockIdx.y is the column, so a workgroup never straddles two
+// columns and its cell width is uniform -- it selects the code path without divergence.  The table travels as a kernel argument (no
+// upload, no host synchronisation).  Every column has its own `head` (its pointer is aligned to its cell width only), taken from the
+// address here; the grid is sized for the longest column and a wave past its column's end does nothing.
+constexpr int FU_BATCH = 16;
+struct FuColumn { const void* src; Fr* dst; uint32_t width; };
+struct FuBatch { FuColumn col[FU_BATCH]; };
+__global__ void __launch_bounds__(256) k_fr_from_uint_batch(FuBatch b, uint64_t n, Fr c517_plain) {
+    const FuColumn col = b.col[blockIdx.y];
+    const uint32_t load_bytes = col.width < 4 ? col.width * FU_CELLS : col.width;
+    const uint32_t head = (uint32_t)((uintptr_t)col.src % load_bytes) / col.width;
+    const uint8_t* base = (const uint8_t*)col.src - (size_t)head * col.width;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave * (FU_CELLS * 64) >= head + n) return;                     // whole waves only: the shuffles stay inside a wave
+    switch (col.width) {
+        case 1: fr_from_uint_wave<1>(base, head, n, col.dst, c517_plain, wave); break;
+        case 2: fr_from_uint_wave<2>(base, head, n, col.dst, c517_plain, wave); break;
+        case 4: fr_from_uint_wave<4>(base, head, n, col.dst, c517_plain, wave); break;
+        case 8: fr_from_uint_wave<8>(base, head, n, col.dst, c517_plain, wave); break;
+        default: fr_from_uint_wave<16>(base, head, n, col.dst, c517_plain, wave); break;
+    }
+}
+static const Fr& fr_c517() {
+    static const Fr c517 = [] { Fr c = Fr::one(); for (int i = 0; i < 517 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^517 mod r (Fr::one() holds 2^256)
+    return c517;
+}
 int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint32_t width, uint64_t n, Fr* d_out) {
     if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16) return ctx->fail(ZK_ERR_INVALID_ARG, "cell width %u: must be 1, 2, 4, 8 or 16 bytes", width);
     if ((uintptr_t)d_packed % width) return ctx->fail(ZK_ERR_INVALID_ARG, "packed cells of %u bytes at an address that is no multiple of %u", width, width);
     if (!n) return ZK_OK;
-    static const Fr c517 = [] { Fr c = Fr::one(); for (int i = 0; i < 517 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^517 mod r (Fr::one() holds 2^256)
+    const Fr& c517 = fr_c517();
     const uint32_t load_bytes = width < 4 ? width * FU_CELLS : width;
     const uint32_t head = (uint32_t)((uintptr_t)d_packed % load_bytes) / width;
     const uint8_t* base = (const uint8_t*)d_packed - (size_t)head * width;
@@ -503,6 +532,29 @@ int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint
         case 4: hipLaunchKernelGGL(k_fr_from_uint<4>, g, t, 0, stream, base, head, n, d_out, c517); break;
         case 8: hipLaunchKernelGGL(k_fr_from_uint<8>, g, t, 0, stream, base, head, n, d_out, c517); break;
         default: hipLaunchKernelGGL(k_fr_from_uint<16>, g, t, 0, stream, base, head, n, d_out, c517); break;
+    }
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// count columns, FU_BATCH per launch; everything is validated before the first launch, so a refused call has written nothing
+int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_packed, const uint8_t* widths, size_t count, uint64_t n, Fr* const* d_out) {
+    for (size_t c = 0; c < count; ++c) {
+        const uint32_t width = widths[c];
+        if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16) return ctx->fail(ZK_ERR_INVALID_ARG, "column %zu: cell width %u: must be 1, 2, 4, 8 or 16 bytes", c, width);
+        if ((uintptr_t)d_packed[c] % width) return ctx->fail(ZK_ERR_INVALID_ARG, "column %zu: packed cells of %u bytes at an address that is no multiple of %u", c, width, width);
+    }
+    if (!n || !count) return ZK_OK;
+    const uint64_t per_block = (uint64_t)FU_CELLS * 256, blocks = (FU_CELLS - 1 + n + per_block - 1) / per_block;      // a column's head is below FU_CELLS cells
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many cells for one launch");
+    for (size_t c0 = 0; c0 < count; c0 += FU_BATCH) {
+        const size_t cnt = std::min<size_t>(FU_BATCH, count - c0);
+        FuBatch b;
+        ZkProfScope prof(ctx, "fr_from_uint_batch", stream);
+        for (size_t c = 0; c < FU_BATCH; ++c) {
+            if (c < cnt) { b.col[c] = {d_packed[c0 + c], d_out[c0 + c], widths[c0 + c]}; prof.bytes += n * (widths[c0 + c] + 32ull); }
+            else b.col[c] = {nullptr, nullptr, 0};
+        }
+        hipLaunchKernelGGL(k_fr_from_uint_batch, dim3((unsigned)blocks, (unsigned)cnt), dim3(256), 0, stream, b, n, fr_c517());
     }
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
@@ -534,6 +586,29 @@ int zk_fr_from_uint(zk_ctx* ctx, const void* d_packed, uint32_t width_bytes, siz
     const uintptr_t a = (uintptr_t)d_packed, o = (uintptr_t)d_out;
     ZK_REQUIRE(ctx, width_bytes > 16 || a + n * width_bytes <= o || o + n * sizeof(Fr) <= a, "the output overlaps the packed cells");
     return fr_from_uint_run(ctx, ctx->stream, d_packed, width_bytes, n, (Fr*)d_out);
+}
+
+int zk_fr_from_uint_batch(zk_ctx* ctx, const void* const* d_packed, const uint8_t* widths, size_t count, size_t n, void* const* d_out) {
+    if (!ctx) return ZK_ERR_INVALID_ARG;
+    if (!count) return ZK_OK;
+    ZK_REQUIRE(ctx, d_packed && widths && d_out, "null pointer");
+    // an output may touch neither another output nor any input (inputs may coincide): one sweep over the buffers in address order
+    struct Span { uintptr_t lo, hi; bool out; };
+    std::vector<Span> spans;
+    for (size_t c = 0; c < count; ++c) {
+        ZK_REQUIRE(ctx, (d_packed[c] && d_out[c]) || !n, "null column pointer");
+        if (widths[c] > 16) continue;                                   // refused below, with the other widths
+        spans.push_back({(uintptr_t)d_packed[c], (uintptr_t)d_packed[c] + n * widths[c], false});
+        spans.push_back({(uintptr_t)d_out[c], (uintptr_t)d_out[c] + n * sizeof(Fr), true});
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& x, const Span& y) { return x.lo < y.lo; });
+    uintptr_t end_any = 0, end_out = 0;
+    for (const Span& s : spans) {
+        ZK_REQUIRE(ctx, s.lo >= (s.out ? end_any : end_out) || !n, "an output overlaps another output or packed cells");
+        end_any = std::max(end_any, s.hi);
+        if (s.out) end_out = std::max(end_out, s.hi);
+    }
+    return fr_from_uint_batch_run(ctx, ctx->stream, d_packed, widths, count, n, (Fr* const*)d_out);
 }
 
 int zk_fr_batch_invert(zk_ctx* ctx, void* d_a, size_t n) {
