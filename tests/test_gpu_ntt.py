@@ -207,3 +207,44 @@ def test_fixed_structure_passes_equal_the_generic_kernels(ctx, cref, k):
     assert np.array_equal(default[0][0], cref.best_fft(cols[0], bn254.omega_for_k(k), k))
     for c, v in zip(cols, default[1]):
         assert np.array_equal(c, v)
+
+
+@pytest.mark.parametrize("k", [11, 12, 14, 21])
+def test_passes_without_inter_pass_tables_equal_the_tabulated_ones(zk, ctx, cref, k):
+    """csrc/ntt.hip: a domain without inter-pass twiddle tables (above 2^24, or no memory for them; ZK_NTT_OUT_TABLE=0 builds
+    one at any size) takes the run-time kernels with two-level twiddles in the strided passes and the output scale in the last
+    pass, nothing folded.  A context of its own, so that no cached domain is reused: forward, inverse and fused-coset transforms
+    of three columns in one batch, bit for bit as on the default context, and the oracle on the first column.
+    k = 11 (digits 6, 5): a radix-2 first step in the last pass; 12 (6, 6): two generic passes; 14 (7, 7): the smallest size
+    with compile-time instances, which must not be taken; 21 (7, 7, 7): three passes, a non-zero twiddle shift in the first."""
+    import os
+    n = 1 << k
+    cols = [cref.rand_fr_stream(8800 + 17 * k + i, n) for i in range(3)]
+    g = cref.fr_const(0x7AB1E + k)
+
+    def run(c):
+        bufs = [c.to_device(col) for col in cols]
+        outs = [c.alloc(n * 32) for _ in cols]
+        c.ntt_batch(bufs, k)
+        fwd = [b.download((n, 4)) for b in bufs]
+        c.ntt_batch(bufs, k, inverse=True)
+        inv = [b.download((n, 4)) for b in bufs]
+        c.coeff_to_coset_batch(bufs, k, g, outs)
+        cos = [o.download((n, 4)) for o in outs]
+        for b_ in bufs + outs:
+            b_.free()
+        return fwd, inv, cos
+    default = run(ctx)
+    os.environ["ZK_NTT_OUT_TABLE"] = "0"
+    own = zk.Context(0)
+    try:
+        tableless = run(own)
+    finally:
+        os.environ.pop("ZK_NTT_OUT_TABLE")
+        own.close()
+    for a_, b_ in zip(default, tableless):
+        for x_, y_ in zip(a_, b_):
+            assert np.array_equal(x_, y_)
+    assert np.array_equal(tableless[0][0], cref.best_fft(cols[0], bn254.omega_for_k(k), k))
+    for c_, v in zip(cols, tableless[1]):
+        assert np.array_equal(c_, v)

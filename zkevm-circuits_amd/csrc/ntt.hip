@@ -15,6 +15,9 @@
 // Butterflies use the carry-free 29-bit Montgomery product with twiddles held in R' = 2^261 form,
 // so data stays in halo2curves' R = 2^256 form with no conversion; sums are kept lazily reduced
 // and only the value written back to HBM is brought to the canonical representative.
+#include <climits>
+#include <type_traits>
+
 #include "ctx.hpp"
 #include "ff29.hip.hpp"
 
@@ -195,207 +198,133 @@ __device__ __forceinline__ void dit_first_step(Fr29 (&e)[4], const Tw29* __restr
     }
 }
 
+// ------------------------------------------------------------------ the steps of a pass, written once per pass kind
+// A pass is a sequence of DIT steps with a workgroup barrier between them: radix 4, with one radix-2 step in front when the digit
+// size is odd.  The body of a step is templated on what shapes its instruction stream: the radix, whether it is the first step
+// (operands from global memory) or the last (results to global memory), and the optional operands.  The digit size and the step
+// index are ordinary arguments.  Each pass kind has two kinds of kernel around the same body:
+//   k_ntt_pass_f<LOG_NP, HAS_PRE> / k_ntt_last_f<LOG_NP>   recurse over the steps at compile time and hand the body constants:
+//       straight-line code per step, every option decided (Opt OPT_NO / OPT_YES);
+//   k_ntt_pass / k_ntt_last   loop over the steps at run time and select among the instantiations of the body; the options
+//       are OPT_RUNTIME, a uniform branch on a kernel argument.  They serve every shape without an instance: single-pass sizes,
+//       digits of 2^6 and less, domains without an inter-pass table, and everything under ZK_NTT_FIXED=0.
+// All operands of a step (the 2^R elements, their coset shifts, the inter-pass twiddles of the outputs) are requested before the
+// first of them is used: the first step waits for global memory once, not once per element and table.
+// Same arithmetic in the same order whatever the instantiation: the kernels of a pass kind are bit-identical.
+enum Opt { OPT_NO, OPT_YES, OPT_RUNTIME };
+template <Opt O>
+__device__ __forceinline__ bool opt_on(bool at_run_time) { return O == OPT_YES || (O == OPT_RUNTIME && at_run_time); }
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Bool = std::integral_constant<bool, V>;
+
 // ------------------------------------------------------------------------------ non-last pass
 // Tile = [n_p digits][T columns], element (d, c) lives at base + d*m + c with
 // base = hi_idx * (n_p*m) + blk*T.  DIT: the first step reads its operands straight from global
 // memory (digit bit-reversed), the steps in between go through LDS, the last step multiplies by
 // the inter-pass twiddle omega^((j'' * i_p) << tw_shift), j'' = blk*T + c, and writes to global
-// memory: no staging copy on either side.  Steps are radix-4 (radix-2 first when log_np is odd).
+// memory: no staging copy on either side.
 // LDS invariant: limbs 0..7 < 2^29 (normalised), value < 2^261.
-__global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_pass(NttIo io, const Tw29* __restrict__ tw, const Fr* __restrict__ lo,
-           const Fr* __restrict__ hi, int h, int log_np, int log_t, int log_m, int tw_shift, const Fr* __restrict__ pre,
-           const Fr* __restrict__ out_tw, uint32_t ncols, int xcd_cols) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    // One-dimensional grid over (tile, column).  The per-element tables (inter-pass twiddles, coset shifts: 32 B per element of the
-    // TILE, the same for every column) are read by every column's workgroup of a tile: those workgroups are numbered so that they
-    // are consecutive workgroups of ONE XCD (workgroups go to the eight XCDs round-robin, each XCD has its own L2) -- the table
-    // lines are fetched from HBM once per tile instead of once per (tile, column).
-    uint32_t tile_id, col;
-    if (xcd_cols) { const uint32_t slot = blockIdx.x >> 3; col = slot % ncols; tile_id = (slot / ncols) * 8u + (blockIdx.x & 7u); }
-    else { col = blockIdx.x % ncols; tile_id = blockIdx.x / ncols; }
-    const Fr* __restrict__ src = io.src[col];
-    Fr* __restrict__ dst = io.dst[col];
-    const int tile = 1 << (log_np + log_t);
-    Lds29 L{smem, tile};
-    const int T = 1 << log_t;
-    const uint64_t m = 1ull << log_m;
-    const uint32_t tiles_per_hi = (uint32_t)(m >> log_t);
-    const uint32_t hi_idx = tile_id / tiles_per_hi, blk = tile_id % tiles_per_hi;
-    const uint64_t base = ((uint64_t)hi_idx << (log_np + log_m)) + ((uint64_t)blk << log_t);
-
-    for (int s = 0; s < log_np;) {
-        const int r = ((log_np - s) & 1) ? 1 : 2;
-        const bool first = s == 0, last = s + r == log_np;
-        const int hgt = 1 << s, items = tile >> r;
-        for (int it = threadIdx.x; it < items; it += blockDim.x) {
-            const int c = it & (T - 1), b = it >> log_t;      // c fastest: T-element contiguous runs in global memory
-            const int j = b & (hgt - 1);
-            const int lo_d = ((b >> s) << (s + r)) | j;
-            Fr29 e[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k >= (1 << r)) break;
-                const int dl = lo_d + k * hgt;
-                if (first) {
-                    const uint64_t gi = base + (uint64_t)bitrev(dl, log_np) * m + c;
-                    e[k] = unpack29<Fr29P>(ldg(src + gi));
-                    if (pre) e[k] = mul29(e[k], unpack29<Fr29P>(ldg(pre + gi)));     // coset shift a[i] * g^i fused into the load (table in R' form)
-                } else {
-                    e[k] = L.load((dl << log_t) | c);
-                }
-            }
-            if (first) { if (r == 2) dit_first_step<2>(e, tw, log_np); else dit_first_step<1>(e, tw, log_np); }
-            else if (r == 2) dit_step<2>(e, tw, log_np, s, j);
-            else dit_step<1>(e, tw, log_np, s, j);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k >= (1 << r)) break;
-                const int dl = lo_d + k * hgt;
-                if (last) {
-                    const uint32_t jpp = (blk << log_t) + c;
-                    const uint64_t go = base + (uint64_t)dl * m + c;
-                    // inter-pass twiddle: one load from the per-domain table in output order (one product),
-                    // or two table entries and two products when the table was not built
-                    const Fr29 v = mul29(e[k], out_tw ? unpack29<Fr29P>(ldg(out_tw + go)) : two_level29(lo, hi, h, (jpp * (uint32_t)dl) << tw_shift));
-                    stg(dst + go, pack29_raw(v));           // an intermediate: below 2p, not canonical (the next pass does not need it to be)
-                } else {
-                    L.store((dl << log_t) | c, e[k]);
-                }
-            }
-        }
-        s += r;
-        if (s < log_np) __syncthreads();
-    }
-}
-
-static bool ntt_xcd_remap() { static const bool on = getenv("ZK_NTT_XCD") && atoi(getenv("ZK_NTT_XCD")) == 1; return on; }      // measurement knob, off: neutral at every size (profiles/r03_ntt_xcd.md)
-__host__ __device__ __forceinline__ int ntt_row_pad(int log_np) { return log_np >= 8 ? 8 : 0; }     // <= 16 rows per tile then: at most 128 extra elements
-// ----------------------------------------------------------------------------------- last pass
-// Rows of n_P contiguous elements; tile = T rows i1 = blk*T + c (row stride = midN * n_P) at a
-// fixed middle digit `mid`.  LDS layout [c][d].  Same step structure as the other passes: the
-// first step reads the bit-reversed digits of its rows from global memory (32-byte sectors of a
-// 32 KiB row, all consumed by this workgroup in the same sweep), the last step writes
-// output index = i1 + n1 * (mid + midN * i_P) with c fastest (T consecutive outputs).  Every
-// output is multiplied by `fin` (1 or the inverse-transform scale, R' form), which also brings
-// the lazy sums back below 2p.
-__global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_last(NttIo io, const Tw29* __restrict__ tw, int log_np, int log_t,
-           int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    const Fr* __restrict__ src = io.src[blockIdx.y];
-    Fr* __restrict__ dst = io.dst[blockIdx.y];
-    const int tile = 1 << (log_np + log_t);
-    const int T = 1 << log_t;
-    // rows are padded by 8 words: the last step reads with c fastest (coalesced output), and with a row
-    // stride that is a multiple of the 32 banks the T rows of a wave would collide on every bank
-    const int row = (1 << log_np) + ntt_row_pad(log_np);
-    Lds29 L{smem, T * row};
-    // Workgroups go to the eight XCDs round-robin and each XCD has its own L2.  A tile of T rows writes T * 32-byte runs
-    // (64 B at T = 2), i.e. HALF of every 128-byte line it touches; the other half belongs to the tile next to it.  With the
-    // plain numbering those two tiles run on different XCDs and each L2 writes its half back on its own (masked partial
-    // writes); renumbered so that neighbouring tiles are consecutive workgroups of ONE XCD, the halves meet in that L2.
-    uint32_t bx = blockIdx.x;
-    if (xcd_remap) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
-    const uint32_t mid = bx & ((1u << log_mid) - 1), blk = bx >> log_mid;
-    const Fr29 fin29 = unpack29<Fr29P>(fin);
-
-    for (int s = 0; s < log_np;) {
-        const int r = ((log_np - s) & 1) ? 1 : 2;
-        const bool first = s == 0, last = s + r == log_np;
-        const int hgt = 1 << s, items = tile >> r;
-        for (int it = threadIdx.x; it < items; it += blockDim.x) {
-            int c, b;
-            if (last) { c = it & (T - 1); b = it >> log_t; }                              // c fastest: coalesced output
-            else { b = it & ((1 << (log_np - r)) - 1); c = it >> (log_np - r); }          // d fastest: conflict-free LDS
-            const int j = b & (hgt - 1);
-            const int lo_d = ((b >> s) << (s + r)) | j;
-            const uint64_t i1 = ((uint64_t)blk << log_t) + c;
-            Fr29 e[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k >= (1 << r)) break;
-                const int dl = lo_d + k * hgt;
-                if (first) {
-                    const uint64_t gi = (((i1 << log_mid) + mid) << log_np) + bitrev(dl, log_np);
-                    e[k] = unpack29<Fr29P>(ldg(src + gi));
-                    if (pre) e[k] = mul29(e[k], unpack29<Fr29P>(ldg(pre + gi)));     // only when this is the only pass
-                } else {
-                    e[k] = L.load(c * row + dl);
-                }
-            }
-            if (first) { if (r == 2) dit_first_step<2>(e, tw, log_np); else dit_first_step<1>(e, tw, log_np); }
-            else if (r == 2) dit_step<2>(e, tw, log_np, s, j);
-            else dit_step<1>(e, tw, log_np, s, j);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (k >= (1 << r)) break;
-                const int dl = lo_d + k * hgt;
-                if (last) {
-                    const uint64_t o = i1 + (((uint64_t)mid + ((uint64_t)dl << log_mid)) << log_n1);
-                    stg(dst + o, fin_folded ? reduce_lazy29(e[k]) : pack29_lt2p(mul29(e[k], fin29)));
-                } else {
-                    L.store(c * row + dl, e[k]);
-                }
-            }
-        }
-        s += r;
-        if (s < log_np) __syncthreads();
-    }
-}
-
-
-// ------------------------------------------------------------------ the two passes with their step structure fixed at compile time
-// k_ntt_pass / k_ntt_last above take the digit size at run time: which step is the first, which the last, whether a step is radix 2
-// or 4, whether element k of it exists -- all of it is decided by branches around every element, and the compiler neither moves a load
-// across a branch nor joins the loads of different elements: the first step waited for global memory once per element and table
-// (eight dependent round trips to HBM per thread on a coset transform), the last step once per inter-pass twiddle.  The same passes
-// with LOG_NP as a template parameter are straight-line code per step: all operands of a step (the 2^R elements, their coset shifts,
-// the twiddles of the butterflies, the inter-pass twiddles of the outputs) are requested before the first of them is used.
-// Same arithmetic in the same order: results are bit-identical to the generic kernels (which remain for every other shape; ZK_NTT_FIXED=0
-// selects them everywhere).
-template <int LOG_NP, int S, bool HAS_PRE>
-__device__ __forceinline__ void ntt_pass_steps(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw,
-                                               const Fr* __restrict__ pre, const Fr* __restrict__ out_tw, const int log_t, const uint64_t m, const uint64_t base) {
-    constexpr int R = ((LOG_NP - S) & 1) ? 1 : 2, NE = 1 << R, hgt = 1 << S;
-    constexpr bool FIRST = S == 0, LAST = S + R == LOG_NP;
-    const int T = 1 << log_t, items = (1 << (LOG_NP + log_t)) >> R;
+// PRE: the coset shift a[i] * g^i is fused into the load (table `pre`, R' form).  TABLE: the inter-pass twiddle is one load from
+// the per-domain table in output order (one product); without it, two entries of the two-level table and two products.
+// A strided pass only exists for log_n >= 11, so its digit is 2^5 at least and no step is the first and the last at once.
+template <int R, bool FIRST, bool LAST, Opt PRE, Opt TABLE>
+__device__ __forceinline__ void ntt_pass_step(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw, const Fr* __restrict__ pre,
+                                              const Fr* __restrict__ out_tw, const Fr* __restrict__ lo, const Fr* __restrict__ hi, const int h, const int tw_shift,
+                                              const int log_np, const int s, const int log_t, const uint64_t m, const uint64_t base, const uint32_t blk) {
+    static_assert(!(FIRST && LAST) && (R == 2 || FIRST), "a strided pass has two steps at least, and only its first can be radix 2");
+    constexpr int NE = 1 << R;
+    const int hgt = 1 << s, T = 1 << log_t, items = (1 << (log_np + log_t)) >> R;
+    const bool has_pre = opt_on<PRE>(pre != nullptr), has_table = opt_on<TABLE>(out_tw != nullptr);
     for (int it = threadIdx.x; it < items; it += blockDim.x) {
         const int c = it & (T - 1), b = it >> log_t;      // c fastest: T-element contiguous runs in global memory
         const int j = b & (hgt - 1);
-        const int lo_d = ((b >> S) << (S + R)) | j;
+        const int lo_d = ((b >> s) << (s + R)) | j;
         Fr otw[NE];
-        if (LAST) {
+        if (LAST && has_table) {
 #pragma unroll
             for (int k = 0; k < NE; ++k) otw[k] = ldg(out_tw + base + (uint64_t)(lo_d + k * hgt) * m + c);
         }
         Fr29 e[4];
         if (FIRST) {
             Fr raw[NE], praw[NE];
+            uint64_t gi[NE];
 #pragma unroll
             for (int k = 0; k < NE; ++k) {
-                const uint64_t gi = base + (uint64_t)bitrev(lo_d + k * hgt, LOG_NP) * m + c;
-                raw[k] = ldg(src + gi);
-                if (HAS_PRE) praw[k] = ldg(pre + gi);
+                gi[k] = base + (uint64_t)bitrev(lo_d + k * hgt, log_np) * m + c;
+                raw[k] = ldg(src + gi[k]);
+                if (PRE == OPT_YES) praw[k] = ldg(pre + gi[k]);
             }
 #pragma unroll
             for (int k = 0; k < NE; ++k) {
                 e[k] = unpack29<Fr29P>(raw[k]);
-                if (HAS_PRE) e[k] = mul29(e[k], unpack29<Fr29P>(praw[k]));     // coset shift a[i] * g^i (table in R' form)
+                if (has_pre) e[k] = mul29(e[k], unpack29<Fr29P>(PRE == OPT_YES ? praw[k] : ldg(pre + gi[k])));      // decided at run time: loaded behind the branch
             }
-            dit_first_step<R>(e, tw, LOG_NP);
+            dit_first_step<R>(e, tw, log_np);
         } else {
 #pragma unroll
             for (int k = 0; k < NE; ++k) e[k] = L.load(((lo_d + k * hgt) << log_t) | c);
-            dit_step<R>(e, tw, LOG_NP, S, j);
+            dit_step<R>(e, tw, log_np, s, j);
         }
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
             const int dl = lo_d + k * hgt;
-            if (LAST) stg(dst + base + (uint64_t)dl * m + c, pack29_raw(mul29(e[k], unpack29<Fr29P>(otw[k]))));      // an intermediate (the next pass reads it): any representative below 2p will do, no conditional subtraction
-            else L.store((dl << log_t) | c, e[k]);
+            if (LAST) {
+                const Fr29 w = has_table ? unpack29<Fr29P>(otw[k]) : two_level29(lo, hi, h, ((((uint32_t)blk << log_t) + c) * (uint32_t)dl) << tw_shift);
+                stg(dst + base + (uint64_t)dl * m + c, pack29_raw(mul29(e[k], w)));      // an intermediate (the next pass reads it): any representative below 2p will do, no conditional subtraction
+            } else {
+                L.store((dl << log_t) | c, e[k]);
+            }
         }
     }
+}
+
+// One-dimensional grid over (tile, column).  The per-element tables (inter-pass twiddles, coset shifts: 32 B per element of the
+// TILE, the same for every column) are read by every column's workgroup of a tile: those workgroups are numbered so that they
+// are consecutive workgroups of ONE XCD (workgroups go to the eight XCDs round-robin, each XCD has its own L2) -- the table
+// lines are fetched from HBM once per tile instead of once per (tile, column).  One more level (log_grp > 0): a tile of T < 4
+// columns reads and writes runs shorter than a 128-byte line, and the 2^log_grp = 4 / T tiles that share those lines are consecutive
+// workgroups of ONE XCD as well (same L2: the line is fetched once and its parts are written back together), ahead of the columns
+// of the launch.
+struct PassTile { uint32_t col, blk; uint64_t base; };
+__device__ __forceinline__ PassTile pass_tile(int log_np, int log_t, int log_m, uint32_t ncols, int xcd_cols, int log_grp) {
+    uint32_t tile_id, col;
+    if (xcd_cols) {
+        const uint32_t slot = blockIdx.x >> 3, sub = slot & ((1u << log_grp) - 1u), s2 = slot >> log_grp;
+        col = s2 % ncols;
+        tile_id = ((((s2 / ncols) << 3) + (blockIdx.x & 7u)) << log_grp) + sub;
+    } else { col = blockIdx.x % ncols; tile_id = blockIdx.x / ncols; }
+    const uint32_t tiles_per_hi = (uint32_t)((1ull << log_m) >> log_t);
+    const uint32_t hi_idx = tile_id / tiles_per_hi, blk = tile_id % tiles_per_hi;
+    return PassTile{col, blk, ((uint64_t)hi_idx << (log_np + log_m)) + ((uint64_t)blk << log_t)};
+}
+
+// every strided-pass kernel takes the same arguments (one launch site, launch_pass); an instance leaves unused what its options rule out
+__global__ void __launch_bounds__(NTT_THREADS)
+k_ntt_pass(NttIo io, const Tw29* __restrict__ tw, const Fr* __restrict__ lo, const Fr* __restrict__ hi, int h, int log_np, int log_t, int log_m, int tw_shift,
+           const Fr* __restrict__ pre, const Fr* __restrict__ out_tw, uint32_t ncols, int xcd_cols, int log_grp) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const PassTile t = pass_tile(log_np, log_t, log_m, ncols, xcd_cols, log_grp);
+    const Lds29 L{smem, 1 << (log_np + log_t)};
+    const Fr* __restrict__ src = io.src[t.col];
+    Fr* __restrict__ dst = io.dst[t.col];
+    for (int s = 0; s < log_np;) {
+        const int r = ((log_np - s) & 1) ? 1 : 2;      // radix 2 only in front of an odd digit
+        auto step = [&](auto R, auto FIRST, auto LAST) {
+            ntt_pass_step<decltype(R)::value, decltype(FIRST)::value, decltype(LAST)::value, OPT_RUNTIME, OPT_RUNTIME>(L, src, dst, tw, pre, out_tw, lo, hi, h, tw_shift, log_np, s, log_t, 1ull << log_m, t.base, t.blk);
+        };
+        if (s == 0) { if (r == 1) step(Int<1>{}, Bool<true>{}, Bool<false>{}); else step(Int<2>{}, Bool<true>{}, Bool<false>{}); }
+        else if (s + r == log_np) step(Int<2>{}, Bool<false>{}, Bool<true>{});
+        else step(Int<2>{}, Bool<false>{}, Bool<false>{});
+        s += r;
+        if (s < log_np) __syncthreads();
+    }
+}
+template <int LOG_NP, int S, bool HAS_PRE>
+__device__ __forceinline__ void ntt_pass_steps(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw,
+                                               const Fr* __restrict__ pre, const Fr* __restrict__ out_tw, const int log_t, const uint64_t m, const uint64_t base) {
+    constexpr int R = ((LOG_NP - S) & 1) ? 1 : 2;
+    constexpr bool LAST = S + R == LOG_NP;
+    ntt_pass_step<R, S == 0, LAST, HAS_PRE ? OPT_YES : OPT_NO, OPT_YES>(L, src, dst, tw, pre, out_tw, nullptr, nullptr, 0, 0, LOG_NP, S, log_t, m, base, 0u);
     if constexpr (!LAST) {
         __syncthreads();
         ntt_pass_steps<LOG_NP, S + R, HAS_PRE>(L, src, dst, tw, pre, out_tw, log_t, m, base);
@@ -403,58 +332,109 @@ __device__ __forceinline__ void ntt_pass_steps(const Lds29& L, const Fr* __restr
 }
 template <int LOG_NP, bool HAS_PRE>
 __global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_pass_f(NttIo io, const Tw29* __restrict__ tw, int log_t, int log_m, const Fr* __restrict__ pre, const Fr* __restrict__ out_tw, uint32_t ncols, int xcd_cols, int log_grp) {
+k_ntt_pass_f(NttIo io, const Tw29* __restrict__ tw, const Fr* __restrict__ lo, const Fr* __restrict__ hi, int h, int /* LOG_NP */, int log_t, int log_m, int tw_shift,
+             const Fr* __restrict__ pre, const Fr* __restrict__ out_tw, uint32_t ncols, int xcd_cols, int log_grp) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    // (tile, column) numbering as in k_ntt_pass, with one more level: a tile of T < 4 columns reads and writes runs shorter than a
-    // 128-byte line, and the 2^log_grp = 4 / T tiles that share those lines are consecutive workgroups of ONE XCD as well (same L2:
-    // the line is fetched once and its parts are written back together), ahead of the columns of the launch
-    uint32_t tile_id, col;
-    if (xcd_cols) {
-        const uint32_t slot = blockIdx.x >> 3, sub = slot & ((1u << log_grp) - 1u), s2 = slot >> log_grp;
-        col = s2 % ncols;
-        tile_id = ((((s2 / ncols) << 3) + (blockIdx.x & 7u)) << log_grp) + sub;
-    } else { col = blockIdx.x % ncols; tile_id = blockIdx.x / ncols; }
-    Lds29 L{smem, 1 << (LOG_NP + log_t)};
-    const uint64_t m = 1ull << log_m;
-    const uint32_t tiles_per_hi = (uint32_t)(m >> log_t);
-    const uint32_t hi_idx = tile_id / tiles_per_hi, blk = tile_id % tiles_per_hi;
-    const uint64_t base = ((uint64_t)hi_idx << (LOG_NP + log_m)) + ((uint64_t)blk << log_t);
-    ntt_pass_steps<LOG_NP, 0, HAS_PRE>(L, io.src[col], io.dst[col], tw, pre, out_tw, log_t, m, base);
+    const PassTile t = pass_tile(LOG_NP, log_t, log_m, ncols, xcd_cols, log_grp);
+    ntt_pass_steps<LOG_NP, 0, HAS_PRE>(Lds29{smem, 1 << (LOG_NP + log_t)}, io.src[t.col], io.dst[t.col], tw, pre, out_tw, log_t, 1ull << log_m, t.base);
 }
 
-template <int LOG_NP, int S>
-__device__ __forceinline__ void ntt_last_steps(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw,
-                                               const int log_t, const int row, const uint32_t blk, const uint32_t mid, const int log_mid, const int log_n1) {
-    constexpr int R = ((LOG_NP - S) & 1) ? 1 : 2, NE = 1 << R, hgt = 1 << S;
-    constexpr bool FIRST = S == 0, LAST = S + R == LOG_NP;
-    const int T = 1 << log_t, items = (1 << (LOG_NP + log_t)) >> R;
+__host__ __device__ __forceinline__ int ntt_row_pad(int log_np) { return log_np >= 8 ? 8 : 0; }     // <= 16 rows per tile then: at most 128 extra elements
+// ----------------------------------------------------------------------------------- last pass
+// Rows of n_P contiguous elements; tile = T rows i1 = blk*T + c (row stride = midN * n_P) at a
+// fixed middle digit `mid`.  LDS layout [c][d].  Same step structure as the other passes: the
+// first step reads the bit-reversed digits of its rows from global memory (32-byte sectors of a
+// 32 KiB row, all consumed by this workgroup in the same sweep), the last step writes
+// output index = i1 + n1 * (mid + midN * i_P) with c fastest (T consecutive outputs).
+// Rows are padded by 8 words (`row`): the last step reads with c fastest (coalesced output), and with a row
+// stride that is a multiple of the 32 banks the T rows of a wave would collide on every bank.
+// PRE: the coset shift, only when this is the only pass.  FOLDED: the output scale rode on the last inter-pass twiddle and the
+// outputs are only reduced; otherwise every output is multiplied by `fin` (1 or the inverse-transform scale, R' form), which
+// also brings the lazy sums back below 2p.  A digit of 2 or 4 (log_n = 1, 2) is one step, first and last at once.
+template <int R, bool FIRST, bool LAST, Opt PRE, Opt FOLDED>
+__device__ __forceinline__ void ntt_last_step(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw, const Fr* __restrict__ pre,
+                                              const Fr29& fin29, const bool fin_folded, const int log_np, const int s, const int log_t, const int row,
+                                              const uint32_t blk, const uint32_t mid, const int log_mid, const int log_n1) {
+    static_assert(R == 2 || FIRST, "only the first step of a pass can be radix 2");
+    constexpr int NE = 1 << R;
+    const int hgt = 1 << s, T = 1 << log_t, items = (1 << (log_np + log_t)) >> R;
+    const bool has_pre = opt_on<PRE>(pre != nullptr), folded = opt_on<FOLDED>(fin_folded);
     for (int it = threadIdx.x; it < items; it += blockDim.x) {
         int c, b;
         if (LAST) { c = it & (T - 1); b = it >> log_t; }                              // c fastest: coalesced output
-        else { b = it & ((1 << (LOG_NP - R)) - 1); c = it >> (LOG_NP - R); }          // d fastest: conflict-free LDS
+        else { b = it & ((1 << (log_np - R)) - 1); c = it >> (log_np - R); }          // d fastest: conflict-free LDS
         const int j = b & (hgt - 1);
-        const int lo_d = ((b >> S) << (S + R)) | j;
+        const int lo_d = ((b >> s) << (s + R)) | j;
         const uint64_t i1 = ((uint64_t)blk << log_t) + c;
         Fr29 e[4];
         if (FIRST) {
-            Fr raw[NE];
+            Fr raw[NE], praw[NE];
+            uint64_t gi[NE];
 #pragma unroll
-            for (int k = 0; k < NE; ++k) raw[k] = ldg(src + ((((i1 << log_mid) + mid) << LOG_NP) + bitrev(lo_d + k * hgt, LOG_NP)));
+            for (int k = 0; k < NE; ++k) {
+                gi[k] = (((i1 << log_mid) + mid) << log_np) + bitrev(lo_d + k * hgt, log_np);
+                raw[k] = ldg(src + gi[k]);
+                if (PRE == OPT_YES) praw[k] = ldg(pre + gi[k]);
+            }
 #pragma unroll
-            for (int k = 0; k < NE; ++k) e[k] = unpack29<Fr29P>(raw[k]);
-            dit_first_step<R>(e, tw, LOG_NP);
+            for (int k = 0; k < NE; ++k) {
+                e[k] = unpack29<Fr29P>(raw[k]);
+                if (has_pre) e[k] = mul29(e[k], unpack29<Fr29P>(PRE == OPT_YES ? praw[k] : ldg(pre + gi[k])));      // decided at run time: loaded behind the branch
+            }
+            dit_first_step<R>(e, tw, log_np);
         } else {
 #pragma unroll
             for (int k = 0; k < NE; ++k) e[k] = L.load(c * row + lo_d + k * hgt);
-            dit_step<R>(e, tw, LOG_NP, S, j);
+            dit_step<R>(e, tw, log_np, s, j);
         }
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
             const int dl = lo_d + k * hgt;
-            if (LAST) stg(dst + (i1 + (((uint64_t)mid + ((uint64_t)dl << log_mid)) << log_n1)), reduce_lazy29(e[k]));      // the output scale rode on the last inter-pass twiddle
+            if (LAST) stg(dst + (i1 + (((uint64_t)mid + ((uint64_t)dl << log_mid)) << log_n1)), folded ? reduce_lazy29(e[k]) : pack29_lt2p(mul29(e[k], fin29)));
             else L.store(c * row + dl, e[k]);
         }
     }
+}
+
+// Workgroups go to the eight XCDs round-robin and each XCD has its own L2.  A tile of T rows writes T * 32-byte runs
+// (64 B at T = 2), i.e. HALF of every 128-byte line it touches; the other half belongs to the tile next to it.  With the
+// plain numbering those two tiles run on different XCDs and each L2 writes its half back on its own (masked partial
+// writes); renumbered so that neighbouring tiles are consecutive workgroups of ONE XCD, the halves meet in that L2.
+__device__ __forceinline__ uint32_t last_tile(int xcd_remap) {
+    return xcd_remap ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+}
+
+// blockIdx.y = column; the same arguments for every last-pass kernel, as for the strided pass
+__global__ void __launch_bounds__(NTT_THREADS)
+k_ntt_last(NttIo io, const Tw29* __restrict__ tw, int log_np, int log_t, int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const Fr* __restrict__ src = io.src[blockIdx.y];
+    Fr* __restrict__ dst = io.dst[blockIdx.y];
+    const int row = (1 << log_np) + ntt_row_pad(log_np);
+    const Lds29 L{smem, row << log_t};
+    const uint32_t bx = last_tile(xcd_remap), mid = bx & ((1u << log_mid) - 1), blk = bx >> log_mid;
+    const Fr29 fin29 = unpack29<Fr29P>(fin);
+    for (int s = 0; s < log_np;) {
+        const int r = ((log_np - s) & 1) ? 1 : 2;
+        const bool last = s + r == log_np;
+        auto step = [&](auto R, auto FIRST, auto LAST) {
+            ntt_last_step<decltype(R)::value, decltype(FIRST)::value, decltype(LAST)::value, OPT_RUNTIME, OPT_RUNTIME>(L, src, dst, tw, pre, fin29, fin_folded != 0, log_np, s, log_t, row, blk, mid, log_mid, log_n1);
+        };
+        if (s == 0 && last) { if (r == 1) step(Int<1>{}, Bool<true>{}, Bool<true>{}); else step(Int<2>{}, Bool<true>{}, Bool<true>{}); }
+        else if (s == 0) { if (r == 1) step(Int<1>{}, Bool<true>{}, Bool<false>{}); else step(Int<2>{}, Bool<true>{}, Bool<false>{}); }
+        else if (last) step(Int<2>{}, Bool<false>{}, Bool<true>{});
+        else step(Int<2>{}, Bool<false>{}, Bool<false>{});
+        s += r;
+        if (s < log_np) __syncthreads();
+    }
+}
+// the instances exist for digits of 2^7 and more: at least two steps, no coset shift (not the only pass), the scale folded
+template <int LOG_NP, int S>
+__device__ __forceinline__ void ntt_last_steps(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw,
+                                               const int log_t, const int row, const uint32_t blk, const uint32_t mid, const int log_mid, const int log_n1) {
+    constexpr int R = ((LOG_NP - S) & 1) ? 1 : 2;
+    constexpr bool LAST = S + R == LOG_NP;
+    ntt_last_step<R, S == 0, LAST, OPT_NO, OPT_YES>(L, src, dst, tw, nullptr, Fr29{}, true, LOG_NP, S, log_t, row, blk, mid, log_mid, log_n1);
     if constexpr (!LAST) {
         __syncthreads();
         ntt_last_steps<LOG_NP, S + R>(L, src, dst, tw, log_t, row, blk, mid, log_mid, log_n1);
@@ -462,14 +442,11 @@ __device__ __forceinline__ void ntt_last_steps(const Lds29& L, const Fr* __restr
 }
 template <int LOG_NP>
 __global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_last_f(NttIo io, const Tw29* __restrict__ tw, int log_t, int log_n1, int log_mid, int xcd_remap) {
+k_ntt_last_f(NttIo io, const Tw29* __restrict__ tw, int /* LOG_NP */, int log_t, int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int row = (1 << LOG_NP) + ntt_row_pad(LOG_NP);
-    Lds29 L{smem, (1 << log_t) * row};
-    uint32_t bx = blockIdx.x;
-    if (xcd_remap) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
-    const uint32_t mid = bx & ((1u << log_mid) - 1), blk = bx >> log_mid;
-    ntt_last_steps<LOG_NP, 0>(L, io.src[blockIdx.y], io.dst[blockIdx.y], tw, log_t, row, blk, mid, log_mid, log_n1);
+    const uint32_t bx = last_tile(xcd_remap), mid = bx & ((1u << log_mid) - 1), blk = bx >> log_mid;
+    ntt_last_steps<LOG_NP, 0>(Lds29{smem, row << log_t}, io.src[blockIdx.y], io.dst[blockIdx.y], tw, log_t, row, blk, mid, log_mid, log_n1);
 }
 
 __global__ void k_scale(Fr* a, Fr s, uint64_t n) {
@@ -506,7 +483,31 @@ static uint64_t domain_key(uint32_t log_n, const Fr& omega, const Fr* scale) {
     return hsh;
 }
 
-static int get_domain(zk_ctx* ctx, uint32_t log_n, const Fr& omega, const Fr* scale, std::shared_ptr<NttDomain>* out) {
+// Measurement knobs (environment variables): read once at the top of a call (ntt_run_many) into this struct, never kept between
+// calls -- tests flip them inside one process.  KNOB_UNSET: not set; the range of a knob is checked where it is applied.
+constexpr int KNOB_UNSET = INT_MIN;
+struct NttKnobs {
+    bool fixed;                          // ZK_NTT_FIXED (0: the run-time kernels everywhere)
+    bool out_table;                      // ZK_NTT_OUT_TABLE (0: a domain built under it gets no inter-pass twiddle tables, as above 2^24; a cached domain stays as it is)
+    int batch;                           // ZK_NTT_BATCH: columns per launch, 1 .. NTT_BATCH
+    int pass_logtile, last_logtile;      // ZK_NTT_PASS_LOGTILE, ZK_NTT_LAST_LOGTILE: 10 .. 12
+    bool xcd_last;                       // ZK_NTT_XCD (1: last_tile's renumbering; off: neutral at every size, profiles/r03_ntt_xcd.md)
+    bool xcd_cols;                       // ZK_NTT_XCD_COLS (0: plain numbering of the strided passes' workgroups)
+};
+static NttKnobs read_ntt_knobs() {
+    auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : KNOB_UNSET; };
+    NttKnobs k;
+    k.fixed = num("ZK_NTT_FIXED") != 0;
+    k.out_table = num("ZK_NTT_OUT_TABLE") != 0;
+    k.batch = num("ZK_NTT_BATCH");
+    k.pass_logtile = num("ZK_NTT_PASS_LOGTILE");
+    k.last_logtile = num("ZK_NTT_LAST_LOGTILE");
+    k.xcd_last = num("ZK_NTT_XCD") == 1;
+    k.xcd_cols = num("ZK_NTT_XCD_COLS") != 0;
+    return k;
+}
+
+static int get_domain(zk_ctx* ctx, const NttKnobs& kn, uint32_t log_n, const Fr& omega, const Fr* scale, std::shared_ptr<NttDomain>* out) {
     const uint64_t key = domain_key(log_n, omega, scale);
     auto it = ctx->domains.find(key);
     if (it != ctx->domains.end()) { *out = it->second; return ZK_OK; }
@@ -549,7 +550,7 @@ static int get_domain(zk_ctx* ctx, uint32_t log_n, const Fr& omega, const Fr* sc
         d->pass[p].tw = d->d_tw29[p];
     }
     // full inter-pass twiddle tables (n x 32 B per non-last pass) while the domain is not huge
-    if (P > 1 && log_n <= 24) {
+    if (P > 1 && log_n <= 24 && kn.out_table) {
         const uint64_t n = 1ull << log_n;
         for (int p = 0; p + 1 < P; ++p) {
             if (hipMalloc(&d->d_out_tw[p], sizeof(Fr) * n) != hipSuccess) { (void)hipGetLastError(); d->d_out_tw[p] = nullptr; break; }
@@ -567,151 +568,209 @@ static int get_domain(zk_ctx* ctx, uint32_t log_n, const Fr& omega, const Fr* sc
     return ZK_OK;
 }
 
-static int set_lds_attr(zk_ctx* ctx) {
-    if (ctx->ntt_attr_set) return ZK_OK;
-    ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_pass, hipFuncAttributeMaxDynamicSharedMemorySize, NTT_TILE * NTT_LDS_BYTES_PER_ELT));
-    ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_last, hipFuncAttributeMaxDynamicSharedMemorySize, (NTT_TILE + 128) * NTT_LDS_BYTES_PER_ELT));
-    ctx->ntt_attr_set = true;
+// Cached power tables of a coset generator g, keyed by (log_n, g, kind); null when there is no memory for a new one.
+//   POW_TWO_LEVEL: g^e = tab[e & (2^h - 1)] * tab[2^h + (e >> h)], h = ceil(log_n / 2), R form (k_distribute_powers)
+//   POW_FULL:      tab[i] = g^i for every i < n, R' form: the first pass of a transform multiplies it in as it loads
+// The coset generators are a handful of constants (zeta, zeta^-1): the tables stay with the context.
+enum PowKind { POW_TWO_LEVEL, POW_FULL };
+static int get_pow_table(zk_ctx* ctx, uint32_t log_n, const Fr& g, PowKind kind, const Fr** out) {
+    *out = nullptr;
+    const uint64_t key = domain_key(log_n, g, nullptr) ^ (kind == POW_FULL ? 0xF0117ABull : 0xC05E7ull);
+    auto it = ctx->pow_tables.find(key);
+    if (it != ctx->pow_tables.end()) { *out = (const Fr*)it->second; return ZK_OK; }
+    const int h = (int)(log_n + 1) / 2;
+    const uint32_t nlo = kind == POW_FULL ? 1u << log_n : 1u << h, nhi = kind == POW_FULL ? 0u : 1u << (log_n - h);
+    Fr* tab = nullptr;
+    if (hipMalloc(&tab, sizeof(Fr) * ((size_t)nlo + nhi)) != hipSuccess) { (void)hipGetLastError(); return ZK_OK; }
+    int rc = build_powers(ctx, g, Fr::one(), tab, nlo, kind == POW_FULL ? 1 : 0);
+    if (!rc && nhi) {
+        Fr step = g;
+        for (int i = 0; i < h; ++i) step = sqr(step);
+        rc = build_powers(ctx, step, Fr::one(), tab + nlo, nhi, 0);
+    }
+    if (rc) { (void)hipFree(tab); return rc; }
+    ctx->pow_tables[key] = tab;
+    *out = tab;
+    return ZK_OK;
+}
+// a[i] *= g^i as a pass of its own (EvaluationDomain::distribute_powers_zeta generalised)
+static int run_distribute(zk_ctx* ctx, uint32_t log_n, const Fr& g, const Fr* from, Fr* to) {
+    const Fr* tab = nullptr;
+    int rc = get_pow_table(ctx, log_n, g, POW_TWO_LEVEL, &tab);
+    if (rc) return rc;
+    if (!tab) return ctx->fail(ZK_ERR_OOM, "coset table allocation failed");
+    const int h = (int)(log_n + 1) / 2;
+    const uint64_t n = 1ull << log_n;
+    hipLaunchKernelGGL(k_distribute_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, from, to, tab, tab + (1u << h), h, n);
+    ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
 
-
-// launchers of the fixed-structure passes: false = this digit size has no instance (the caller takes the generic kernel)
-template <int LOG_NP, bool HAS_PRE>
-static bool launch_pass_f(zk_ctx* ctx, unsigned grid, unsigned threads, size_t lds, const NttIo& io, const Tw29* tw, int log_t, int log_m, const Fr* pre, const Fr* out_tw, uint32_t ncols, int xcd_cols, int log_grp) {
-    const uint32_t bit = 1u << (2 * (LOG_NP - 7) + (HAS_PRE ? 1 : 0));          // the attribute is per device: remembered per context
-    if (!(ctx->ntt_fixed_attr & bit)) {
-        // a device that refuses the LDS size (not a gfx950, a lowered limit): this instance stays unused, the caller takes the generic kernel
-        if (hipFuncSetAttribute((const void*)k_ntt_pass_f<LOG_NP, HAS_PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, NTT_TILE * NTT_LDS_BYTES_PER_ELT) != hipSuccess) { (void)hipGetLastError(); return false; }
-        ctx->ntt_fixed_attr |= bit;
+// ---- launch plans: the geometry of one launch, decided on the host before anything is enqueued
+struct NttPlan {
+    int log_t, tile;          // T = 2^log_t runs (strided pass) or rows (last pass) per workgroup; tile = elements per workgroup
+    unsigned blocks;          // tiles per column
+    dim3 grid;                // strided pass: (blocks * nb); last pass: (blocks, nb)
+    unsigned threads;
+    size_t lds;
+    int xcd, log_grp;         // XCD-aware workgroup numbering (pass_tile / last_tile), and the tiles per 128-byte line that go with it
+    bool fixed;               // a compile-time instance serves this launch
+};
+static bool has_fixed_instance(int log_np) { return log_np >= 7 && log_np <= NTT_MAX_DIGIT; }      // 7, 8: the three-pass sizes (2^21 .. 2^24)
+static unsigned plan_threads(int tile, bool fixed) {
+    if (fixed) return (unsigned)std::max(64, std::min(1024, tile >> 2));      // one radix-4 item per thread and step
+    return tile >= 4096 ? 1024 : (tile >= 1024 ? 512 : (tile >= 256 ? 128 : 64));
+}
+static NttPlan plan_pass(const NttDomain& dom, int p, size_t nb, const NttKnobs& kn) {
+    const NttPass& ps = dom.pass[p];
+    NttPlan pl{};
+    // tile of the strided passes: 4096 elements (T = 4: 128-byte runs) when there are two passes; with three passes
+    // 2048 elements measured 8-10 % faster (two workgroups per CU: one loads while the other computes)
+    int log_tile = dom.npass == 3 ? 11 : 12;
+    if (kn.pass_logtile >= 10 && kn.pass_logtile <= 12) log_tile = kn.pass_logtile;
+    pl.log_t = std::min(std::max(log_tile - ps.log_np, 0), ps.log_m);
+    pl.tile = 1 << (ps.log_np + pl.log_t);
+    pl.blocks = (unsigned)((1ull << dom.log_n) >> (ps.log_np + pl.log_t));
+    pl.fixed = kn.fixed && ps.out_tw && has_fixed_instance(ps.log_np);
+    pl.grid = dim3(pl.blocks * (unsigned)nb);
+    pl.threads = plan_threads(pl.tile, pl.fixed);
+    pl.lds = (size_t)pl.tile * NTT_LDS_BYTES_PER_ELT;
+    const int log_grp = pl.log_t < 2 ? 2 - pl.log_t : 0;           // tiles per 128-byte line of a run
+    if (pl.fixed) {
+        pl.xcd = (kn.xcd_cols && pl.blocks % (8u << log_grp) == 0 && (nb > 1 || log_grp > 0)) ? 1 : 0;
+        pl.log_grp = pl.xcd ? log_grp : 0;
+    } else {
+        pl.xcd = (nb > 1 && pl.blocks % 8 == 0 && kn.xcd_cols) ? 1 : 0;
     }
-    hipLaunchKernelGGL((k_ntt_pass_f<LOG_NP, HAS_PRE>), dim3(grid), dim3(threads), lds, ctx->stream, io, tw, log_t, log_m, pre, out_tw, ncols, xcd_cols, log_grp);
-    return true;
+    return pl;
 }
-static bool ntt_fixed_on() { const char* e = getenv("ZK_NTT_FIXED"); return !(e && atoi(e) == 0); }      // measurement knob, read per call (tests flip it inside one process)
-static bool launch_pass_fixed(zk_ctx* ctx, int log_np, unsigned grid, unsigned threads, size_t lds, const NttIo& io, const Tw29* tw, int log_t, int log_m, const Fr* pre, const Fr* out_tw, uint32_t ncols, int xcd_cols, int log_grp) {
-    if (!ntt_fixed_on() || !out_tw) return false;
-#define ZK_PASS_CASE(N) case N: return pre ? launch_pass_f<N, true>(ctx, grid, threads, lds, io, tw, log_t, log_m, pre, out_tw, ncols, xcd_cols, log_grp) \
-                                           : launch_pass_f<N, false>(ctx, grid, threads, lds, io, tw, log_t, log_m, pre, out_tw, ncols, xcd_cols, log_grp);
-    switch (log_np) { ZK_PASS_CASE(7) ZK_PASS_CASE(8) ZK_PASS_CASE(9) ZK_PASS_CASE(10) ZK_PASS_CASE(11) default: return false; }      // 7, 8: the three-pass sizes (2^21 .. 2^24)
-#undef ZK_PASS_CASE
-}
-template <int LOG_NP>
-static bool launch_last_f(zk_ctx* ctx, dim3 grid, unsigned threads, size_t lds, const NttIo& io, const Tw29* tw, int log_t, int log_n1, int log_mid, int xcd_remap) {
-    const uint32_t bit = 1u << (24 + LOG_NP - 7);
-    if (!(ctx->ntt_fixed_attr & bit)) {
-        if (hipFuncSetAttribute((const void*)k_ntt_last_f<LOG_NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (NTT_TILE + 128) * NTT_LDS_BYTES_PER_ELT) != hipSuccess) { (void)hipGetLastError(); return false; }
-        ctx->ntt_fixed_attr |= bit;
-    }
-    hipLaunchKernelGGL((k_ntt_last_f<LOG_NP>), grid, dim3(threads), lds, ctx->stream, io, tw, log_t, log_n1, log_mid, xcd_remap);
-    return true;
-}
-static bool launch_last_fixed(zk_ctx* ctx, int log_np, dim3 grid, unsigned threads, size_t lds, const NttIo& io, const Tw29* tw, int log_t, int log_n1, int log_mid, int xcd_remap) {
-    if (!ntt_fixed_on()) return false;
-#define ZK_LAST_CASE(N) case N: return launch_last_f<N>(ctx, grid, threads, lds, io, tw, log_t, log_n1, log_mid, xcd_remap);
-    switch (log_np) { ZK_LAST_CASE(7) ZK_LAST_CASE(8) ZK_LAST_CASE(9) ZK_LAST_CASE(10) ZK_LAST_CASE(11) default: return false; }
-#undef ZK_LAST_CASE
+static NttPlan plan_last(const NttDomain& dom, size_t nb, const NttKnobs& kn) {
+    const int P = dom.npass;
+    const NttPass& ps = dom.pass[P - 1];
+    const int log_n1 = P == 1 ? 0 : dom.pass[0].log_np, log_mid = P == 3 ? dom.pass[1].log_np : 0;
+    NttPlan pl{};
+    // the last pass reads whole rows: a 2048-element tile (two rows of 2^10, 72 KiB of LDS) lets two workgroups share a CU
+    // and overlap their load / compute / store phases: -4 % at 2^20, -5 % at 2^22
+    int log_tile = 11;
+    if (kn.last_logtile >= 10 && kn.last_logtile <= 12) log_tile = kn.last_logtile;
+    pl.log_t = std::min(std::max(log_tile - ps.log_np, 0), log_n1);
+    pl.tile = 1 << (ps.log_np + pl.log_t);
+    pl.blocks = (unsigned)((1ull << dom.log_n) >> (ps.log_np + pl.log_t));
+    pl.fixed = kn.fixed && P > 1 && dom.fin_folded && has_fixed_instance(ps.log_np);      // the instances only reduce: the scale must have been folded
+    pl.grid = dim3(pl.blocks, (unsigned)nb);
+    pl.threads = plan_threads(pl.tile, pl.fixed);
+    pl.lds = (size_t)(pl.tile + (ntt_row_pad(ps.log_np) << pl.log_t)) * NTT_LDS_BYTES_PER_ELT;
+    pl.xcd = (log_mid == 0 && pl.blocks % 8 == 0 && pl.blocks >= 16 && kn.xcd_last) ? 1 : 0;
+    return pl;
 }
 
-static int pick_threads(int tile) { return tile >= 4096 ? 1024 : (tile >= 1024 ? 512 : (tile >= 256 ? 128 : 64)); }
+// hipFuncSetAttribute (dynamic LDS beyond 64 KiB) is per device: done once per kernel and context.  false: the device refuses the
+// size (not a gfx950, a lowered limit) -- an instance then stays unused and the launch takes the generic kernel.
+static bool pass_kernel_ready(zk_ctx* ctx, const void* kernel, size_t max_lds) {
+    auto it = ctx->ntt_fixed_attr.find(kernel);
+    if (it != ctx->ntt_fixed_attr.end()) return it->second;
+    const bool ok = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    return ctx->ntt_fixed_attr[kernel] = ok;
+}
+constexpr size_t NTT_PASS_MAX_LDS = (size_t)NTT_TILE * NTT_LDS_BYTES_PER_ELT, NTT_LAST_MAX_LDS = (size_t)(NTT_TILE + 128) * NTT_LDS_BYTES_PER_ELT;
+
+using PassKernel = decltype(&k_ntt_pass);
+using LastKernel = decltype(&k_ntt_last);
+static PassKernel pass_instance(int log_np, bool pre) {
+    switch (log_np) {
+        case 7: return pre ? k_ntt_pass_f<7, true> : k_ntt_pass_f<7, false>;
+        case 8: return pre ? k_ntt_pass_f<8, true> : k_ntt_pass_f<8, false>;
+        case 9: return pre ? k_ntt_pass_f<9, true> : k_ntt_pass_f<9, false>;
+        default: return pre ? k_ntt_pass_f<10, true> : k_ntt_pass_f<10, false>;
+    }
+}
+static LastKernel last_instance(int log_np) {
+    switch (log_np) {
+        case 7: return k_ntt_last_f<7>;
+        case 8: return k_ntt_last_f<8>;
+        case 9: return k_ntt_last_f<9>;
+        default: return k_ntt_last_f<10>;
+    }
+}
+// strided pass p of the domain; `pre`: the coset shift table of a first pass, or null
+static int launch_pass(zk_ctx* ctx, const NttDomain& dom, int p, size_t nb, const NttKnobs& kn, const NttIo& io, const Fr* pre) {
+    const NttPass& ps = dom.pass[p];
+    if (ps.log_np < 3) return ctx->fail(ZK_ERR_INVALID_ARG, "NTT: a strided pass over a digit of 2^%d", ps.log_np);      // its steps have no first-and-last instantiation
+    NttPlan pl = plan_pass(dom, p, nb, kn);
+    PassKernel kernel = pl.fixed ? pass_instance(ps.log_np, pre != nullptr) : k_ntt_pass;
+    if (pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_PASS_MAX_LDS)) {
+        NttKnobs generic = kn;
+        generic.fixed = false;
+        pl = plan_pass(dom, p, nb, generic);
+        kernel = k_ntt_pass;
+    }
+    if (!pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_PASS_MAX_LDS)) return ctx->fail(ZK_ERR_HIP, "NTT: the device refuses %zu bytes of LDS per workgroup", NTT_PASS_MAX_LDS);
+    ZkProfScope pscope(ctx, "ntt_pass");
+    pscope.bytes = (uint64_t)nb * (1ull << dom.log_n) * 64 / (uint64_t)dom.npass;      // a transform's algorithmic 64 B per element (read once, write once), spread over its P launches
+    hipLaunchKernelGGL(kernel, pl.grid, dim3(pl.threads), pl.lds, ctx->stream, io, ps.tw, (const Fr*)dom.d_lo, (const Fr*)dom.d_hi, dom.h, ps.log_np, pl.log_t, ps.log_m,
+                       (int)dom.log_n - ps.log_np - ps.log_m, pre, ps.out_tw, (uint32_t)nb, pl.xcd, pl.log_grp);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// `pre`: the coset shift table when this is the only pass, or null
+static int launch_last(zk_ctx* ctx, const NttDomain& dom, size_t nb, const NttKnobs& kn, const NttIo& io, const Fr* pre) {
+    const int P = dom.npass;
+    const NttPass& ps = dom.pass[P - 1];
+    NttPlan pl = plan_last(dom, nb, kn);
+    LastKernel kernel = pl.fixed ? last_instance(ps.log_np) : k_ntt_last;
+    if (pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_LAST_MAX_LDS)) {
+        NttKnobs generic = kn;
+        generic.fixed = false;
+        pl = plan_last(dom, nb, generic);
+        kernel = k_ntt_last;
+    }
+    if (!pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_LAST_MAX_LDS)) return ctx->fail(ZK_ERR_HIP, "NTT: the device refuses %zu bytes of LDS per workgroup", NTT_LAST_MAX_LDS);
+    ZkProfScope pscope(ctx, "ntt_last");
+    pscope.bytes = (uint64_t)nb * (1ull << dom.log_n) * 64 / (uint64_t)P;
+    hipLaunchKernelGGL(kernel, pl.grid, dim3(pl.threads), pl.lds, ctx->stream, io, ps.tw, ps.log_np, pl.log_t, P == 1 ? 0 : dom.pass[0].log_np, P == 3 ? dom.pass[1].log_np : 0,
+                       dom.final_mul, pre, dom.fin_folded ? 1 : 0, pl.xcd);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
 
 // Generic driver.  `scale` (nullable) multiplies every output; coset_pre (nullable): a[i] *= g^i
 // before the transform; coset_post (nullable): out[i] *= g^i after it.  d_src (nullable): the input
 // is read from d_src and d_data only receives the result (out of place, no extra copy).
-// `count` transforms over the same domain, in place (d_src == nullptr) or from d_src[i] to d_data[i]; launched
-// NTT_BATCH columns at a time.  coset_post and the unfused coset shift are per-column passes and only taken by the
-// single-column entry point.
-int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_t count, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, bool fuse_pre);
+// `count` transforms over the same domain, in place (d_srcs == nullptr) or from d_srcs[i] to d_datas[i]; launched
+// NTT_BATCH columns at a time.  The coset shifts that are passes of their own (coset_post, and coset_pre when it is not
+// fused into the first pass) are per column: those transforms go one column per launch group.
 int ntt_run(zk_ctx* ctx, Fr* d_data, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, const Fr* d_src, bool fuse_pre) {
     return ntt_run_many(ctx, &d_data, d_src ? &d_src : nullptr, 1, log_n, omega, scale, coset_pre, coset_post, fuse_pre);
 }
 int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_t count, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, bool fuse_pre) {
     if (count == 0) return ZK_OK;
-    if (count > 1 && (log_n == 0 || coset_post)) {          // rare shapes: one by one
+    const NttKnobs kn = read_ntt_knobs();
+    if (log_n == 0) {   // size-1 transforms: identity (times the scale)
         for (size_t i = 0; i < count; ++i) {
-            const Fr* one_src = d_srcs ? d_srcs[i] : nullptr;
-            int r = ntt_run_many(ctx, d_datas + i, one_src ? &one_src : nullptr, 1, log_n, omega, scale, coset_pre, coset_post, fuse_pre);
-            if (r) return r;
+            if (d_srcs && d_srcs[i] && d_srcs[i] != d_datas[i]) ZK_HIP(ctx, hipMemcpyAsync(d_datas[i], d_srcs[i], sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
+            if (scale) {
+                hipLaunchKernelGGL(k_scale, dim3(1), dim3(64), 0, ctx->stream, d_datas[i], *scale, (uint64_t)1);
+                ZK_CHECK_LAUNCH(ctx);
+            }
         }
         return ZK_OK;
     }
-    Fr* d_data = d_datas[0];
-    const Fr* d_src = d_srcs ? d_srcs[0] : nullptr;
-    if (log_n == 0) {   // size-1 transform: identity (times the scale)
-        if (d_src && d_src != d_data) ZK_HIP(ctx, hipMemcpyAsync(d_data, d_src, sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream));
-        if (scale) {
-            hipLaunchKernelGGL(k_scale, dim3(1), dim3(64), 0, ctx->stream, d_data, *scale, (uint64_t)1);
-            ZK_CHECK_LAUNCH(ctx);
-        }
-        return ZK_OK;
-    }
-    int rc = set_lds_attr(ctx);
-    if (rc) return rc;
     const uint64_t n = 1ull << log_n;
-
-    auto run_distribute = [&](const Fr& g, const Fr* from) -> int {
-        const int h = (int)(log_n + 1) / 2;
-        const uint32_t nlo = 1u << h, nhi = 1u << (log_n - h);
-        // the coset generators are a handful of constants (zeta, zeta^-1): keep their tables
-        const uint64_t key = domain_key(log_n, g, nullptr) ^ 0xC05E7ull;
-        Fr* tab = nullptr;
-        auto it = ctx->pow_tables.find(key);
-        if (it != ctx->pow_tables.end()) {
-            tab = (Fr*)it->second;
-        } else {
-            if (hipMalloc(&tab, sizeof(Fr) * ((size_t)nlo + nhi)) != hipSuccess) return ctx->fail(ZK_ERR_OOM, "coset table allocation failed");
-            int r = build_powers(ctx, g, Fr::one(), tab, nlo, 0);
-            if (r) return r;
-            Fr step = g;
-            for (int i = 0; i < h; ++i) step = sqr(step);
-            r = build_powers(ctx, step, Fr::one(), tab + nlo, nhi, 0);
-            if (r) return r;
-            ctx->pow_tables[key] = tab;
-        }
-        hipLaunchKernelGGL(k_distribute_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, from, d_data, tab, tab + nlo, h, n);
-        ZK_CHECK_LAUNCH(ctx);
-        return ZK_OK;
-    };
-    const Fr* cur = d_src ? d_src : d_data;
-    const Fr* pre_table = nullptr;       // full table g^i (R' form), multiplied in by the first pass as it loads
-    if (coset_pre && fuse_pre) {
-        const uint64_t key = domain_key(log_n, *coset_pre, nullptr) ^ 0xF0117ABull;
-        auto it = ctx->pow_tables.find(key);
-        if (it != ctx->pow_tables.end()) {
-            pre_table = (const Fr*)it->second;
-        } else {
-            Fr* tab = nullptr;
-            if (hipMalloc(&tab, sizeof(Fr) * n) != hipSuccess) { (void)hipGetLastError(); tab = nullptr; }    // no memory: separate pass below
-            if (tab) {
-                int r = build_powers(ctx, *coset_pre, Fr::one(), tab, (uint32_t)n, 1);
-                if (r) return r;
-                ctx->pow_tables[key] = tab;
-                pre_table = tab;
-            }
-        }
-    }
-    if (coset_pre && !pre_table) {
-        if (count > 1) {                                     // no memory for the shift table: the columns go one by one through the separate pass
-            for (size_t i = 0; i < count; ++i) {
-                const Fr* one_src = d_srcs ? d_srcs[i] : nullptr;
-                int r = ntt_run_many(ctx, d_datas + i, one_src ? &one_src : nullptr, 1, log_n, omega, scale, coset_pre, coset_post, fuse_pre);
-                if (r) return r;
-            }
-            return ZK_OK;
-        }
-        rc = run_distribute(*coset_pre, cur); if (rc) return rc; cur = d_data;
-    }
-
+    const Fr* pre_table = nullptr;       // full table g^i (R' form), multiplied in by the first pass as it loads; no memory for it: the separate pass
+    int rc = (coset_pre && fuse_pre) ? get_pow_table(ctx, log_n, *coset_pre, POW_FULL, &pre_table) : ZK_OK;
+    if (rc) return rc;
+    const bool pre_apart = coset_pre && !pre_table;
     std::shared_ptr<NttDomain> dom;
-    rc = get_domain(ctx, log_n, omega, scale, &dom);
+    rc = get_domain(ctx, kn, log_n, omega, scale, &dom);
     if (rc) return rc;
     const int P = dom->npass;
     // columns per launch: enough tiles to give every CU a few workgroups, bounded by the scratch it takes
     size_t per_launch = 1;
-    if (count > 1) {
+    if (count > 1 && !pre_apart && !coset_post) {
         const uint64_t tiles = std::max<uint64_t>(1, n >> 12);
         per_launch = (size_t)std::min<uint64_t>(NTT_BATCH, std::max<uint64_t>(1, 4096 / tiles));       // sixteen columns at 2^20: a launch's last round of workgroups and the 10-20 us between dependent launches are paid once per sixteen columns (headline proof, alternating A/B on one box: 1.006 s with four, 0.9855 with eight, 0.9793 with sixteen; alone the transform does not care: 94.8 / 94.6 us)
-        if (const char* e = getenv("ZK_NTT_BATCH")) { const int v = atoi(e); if (v >= 1 && v <= NTT_BATCH) per_launch = (size_t)v; }      // measurement knob
+        if (kn.batch >= 1 && kn.batch <= NTT_BATCH) per_launch = (size_t)kn.batch;
     }
     Fr* scratch = nullptr;
     if (P > 1) {
@@ -729,73 +788,25 @@ int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_
     }
     for (size_t first = 0; first < count; first += per_launch) {
         const size_t nb = std::min(per_launch, count - first);
-        NttIo io_in{}, io_mid{}, io_last{};
         // buffers: P=1: data->data (whole transform inside one workgroup, safe in place)
         //          P=2: data->scratch, scratch->data;   P=3: data->data, data->scratch, scratch->data
+        NttIo io{};                                            // .src = where the next pass reads
         for (size_t j = 0; j < nb; ++j) {
             Fr* dd = d_datas[first + j];
-            const Fr* ss = (count == 1) ? cur : (d_srcs && d_srcs[first + j] ? d_srcs[first + j] : dd);
-            io_in.src[j] = ss;
-            io_in.dst[j] = dd;
+            io.src[j] = d_srcs && d_srcs[first + j] ? d_srcs[first + j] : dd;
+            if (pre_apart) { rc = run_distribute(ctx, log_n, *coset_pre, io.src[j], dd); if (rc) return rc; io.src[j] = dd; }
         }
-        NttIo cur_io = io_in;                                  // .src = where the next pass reads
         for (int p = 0; p + 1 < P; ++p) {
-            const NttPass& ps = dom->pass[p];
-            // tile of the strided passes: 4096 elements (T = 4: 128-byte runs) when there are two passes; with three passes
-            // 2048 elements measured 8-10 % faster (two workgroups per CU: one loads while the other computes)
-            int log_tile_pass = P == 3 ? 11 : 12;
-            if (const char* e = getenv("ZK_NTT_PASS_LOGTILE")) { const int v = atoi(e); if (v >= 10 && v <= 12) log_tile_pass = v; }    // measurement knob
-            int log_t = log_tile_pass - ps.log_np;
-            if (log_t < 0) log_t = 0;
-            if (log_t > ps.log_m) log_t = ps.log_m;
-            const int tile = 1 << (ps.log_np + log_t);
-            NttIo io{};
-            for (size_t j = 0; j < nb; ++j) {
-                io.src[j] = cur_io.src[j];
-                io.dst[j] = (p == P - 2) ? scratch + j * n : d_datas[first + j];
-            }
-            const unsigned blocks = (unsigned)(n >> (ps.log_np + log_t));
-            const int tw_shift = (int)log_n - ps.log_np - ps.log_m;
-            ZkProfScope pscope(ctx, "ntt_pass");
-            pscope.bytes = (uint64_t)nb * n * 64 / (uint64_t)P;      // a transform's algorithmic 64 B per element (read once, write once), spread over its P launches
-            static const bool xcd_off = getenv("ZK_NTT_XCD_COLS") && atoi(getenv("ZK_NTT_XCD_COLS")) == 0;       // measurement knob
-            const int xcd_cols = (nb > 1 && blocks % 8 == 0 && !xcd_off) ? 1 : 0;
-            const int log_grp = log_t < 2 ? 2 - log_t : 0;           // tiles per 128-byte line of a run
-            const int xcd_fixed = (!xcd_off && blocks % (8u << log_grp) == 0 && (nb > 1 || log_grp > 0)) ? 1 : 0;
-            if (!launch_pass_fixed(ctx, ps.log_np, blocks * (unsigned)nb, (unsigned)std::max(64, std::min(1024, tile >> 2)) /* one radix-4 item per thread and step */, (size_t)tile * NTT_LDS_BYTES_PER_ELT, io, ps.tw, log_t, ps.log_m,
-                                   p == 0 ? pre_table : (const Fr*)nullptr, ps.out_tw, (uint32_t)nb, xcd_fixed, xcd_fixed ? log_grp : 0))
-                hipLaunchKernelGGL(k_ntt_pass, dim3(blocks * (unsigned)nb), dim3(pick_threads(tile)), (size_t)tile * NTT_LDS_BYTES_PER_ELT, ctx->stream, io, ps.tw,
-                                   dom->d_lo, dom->d_hi, dom->h, ps.log_np, log_t, ps.log_m, tw_shift, p == 0 ? pre_table : (const Fr*)nullptr, ps.out_tw,
-                                   (uint32_t)nb, xcd_cols);
-            ZK_CHECK_LAUNCH(ctx);
-            for (size_t j = 0; j < nb; ++j) cur_io.src[j] = io.dst[j];
+            for (size_t j = 0; j < nb; ++j) io.dst[j] = (p == P - 2) ? scratch + j * n : d_datas[first + j];
+            rc = launch_pass(ctx, *dom, p, nb, kn, io, p == 0 ? pre_table : nullptr);
+            if (rc) return rc;
+            for (size_t j = 0; j < nb; ++j) io.src[j] = io.dst[j];
         }
-        {
-            const NttPass& ps = dom->pass[P - 1];
-            const int log_n1 = P == 1 ? 0 : dom->pass[0].log_np;
-            const int log_mid = P == 3 ? dom->pass[1].log_np : 0;
-            // the last pass reads whole rows: a 2048-element tile (two rows of 2^10, 72 KiB of LDS) lets two workgroups share a CU
-            // and overlap their load / compute / store phases: -4 % at 2^20, -5 % at 2^22
-            int log_tile_last = 11;
-            if (const char* e = getenv("ZK_NTT_LAST_LOGTILE")) { const int v = atoi(e); if (v >= 10 && v <= 12) log_tile_last = v; }    // measurement knob
-            int log_t = log_tile_last - ps.log_np;
-            if (log_t < 0) log_t = 0;
-            if (log_t > log_n1) log_t = log_n1;
-            const int tile = 1 << (ps.log_np + log_t);
-            const unsigned blocks = (unsigned)(n >> (ps.log_np + log_t));
-            NttIo io{};
-            for (size_t j = 0; j < nb; ++j) { io.src[j] = cur_io.src[j]; io.dst[j] = d_datas[first + j]; }
-            ZkProfScope pscope(ctx, "ntt_last");
-            pscope.bytes = (uint64_t)nb * n * 64 / (uint64_t)P;
-            const int xcd_last = (log_mid == 0 && blocks % 8 == 0 && blocks >= 16 && ntt_xcd_remap()) ? 1 : 0;
-            const size_t lds_last = (size_t)(tile + (ntt_row_pad(ps.log_np) << log_t)) * NTT_LDS_BYTES_PER_ELT;
-            if (!(P > 1 && dom->fin_folded && launch_last_fixed(ctx, ps.log_np, dim3(blocks, (unsigned)nb), (unsigned)std::max(64, std::min(1024, tile >> 2)), lds_last, io, ps.tw, log_t, log_n1, log_mid, xcd_last)))
-                hipLaunchKernelGGL(k_ntt_last, dim3(blocks, (unsigned)nb), dim3(pick_threads(tile)), lds_last, ctx->stream, io, ps.tw,
-                                   ps.log_np, log_t, log_n1, log_mid, dom->final_mul, P == 1 ? pre_table : (const Fr*)nullptr, dom->fin_folded ? 1 : 0, xcd_last);
-            ZK_CHECK_LAUNCH(ctx);
-        }
+        for (size_t j = 0; j < nb; ++j) io.dst[j] = d_datas[first + j];
+        rc = launch_last(ctx, *dom, nb, kn, io, P == 1 ? pre_table : nullptr);
+        if (rc) return rc;
+        if (coset_post) for (size_t j = 0; j < nb; ++j) { rc = run_distribute(ctx, log_n, *coset_post, io.dst[j], io.dst[j]); if (rc) return rc; }
     }
-    if (coset_post) { rc = run_distribute(*coset_post, d_data); if (rc) return rc; }
     return ZK_OK;
 }
 
