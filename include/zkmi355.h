@@ -133,8 +133,29 @@ int zk_fr_batch_invert(zk_ctx* ctx, void* d_a, size_t n);
 int zk_ntt(zk_ctx* ctx, void* d_data, uint32_t log_n, int inverse);
 /* zk_ntt over `count` columns of the same size, in place, several columns per launch. */
 int zk_ntt_batch(zk_ctx* ctx, void* const* d_datas, size_t count, uint32_t log_n, int inverse);
-/* best_fft with an arbitrary primitive 2^log_n-th root (h_omega: one Fr), no scaling.            */
+/* best_fft with an arbitrary primitive 2^log_n-th root (h_omega: one Fr), no scaling.  The root is not checked.  For a root
+ * that is not primitive (omega^n = 1 but omega^(n/2) != -1) the result is best_fft's, bit for bit, and NOT the sum above:
+ * like best_fft's, the butterflies subtract where the sum multiplies by omega^(n/2), so
+ *   out[i] = sum_j (-1)^c a[j] omega^(i*j - c*n/2),   c = sum_s bit_s(i) * bit_(log_n-1-s)(j).
+ * Every distinct root gets a domain (twiddle tables) of its own in the context's cache.            */
 int zk_ntt_omega(zk_ctx* ctx, void* d_data, uint32_t log_n, const void* h_omega);
+/* Host only (no context, no device): the launches of one launch group of a transform of `columns` columns of 2^log_n elements
+ * (1 <= log_n <= 28), as zk_ntt_batch / zk_coeff_to_coset_batch / ... decide them under the ZK_NTT_* knobs in force at the call.
+ * tables: the domain has its inter-pass twiddle tables (a domain built under ZK_NTT_OUT_TABLE=0 has none; no domain above 2^24 or
+ * of a single pass has any, whatever is passed).  It states what the domain IS: ZK_NTT_OUT_TABLE, which only acts when a domain
+ * is built and leaves a cached one as it is, is deliberately not consulted -- pass tables = 0 for a domain built under it.  coset_pass: a coset shift runs as a pass of its own (zk_coeff_to_extended,
+ * zk_extended_to_coeff), which is per column.
+ * out_head[4]: columns per launch group, columns in the first group (what the records describe), passes, tables in effect.
+ * The records are those of a FULL group (the first); a call whose column count is no multiple of the group size ends with a
+ * smaller group, whose plans are those of a call with that many columns (17 columns in groups of 16: ask for 1 as well).
+ * out_records: ZK_NTT_PLAN_WORDS words per launch, in launch order -- kind (0 strided pass, 1 last pass), pass index, passes,
+ * log2 of the digit, log2 of the digit's stride, log2 of the runs / rows per workgroup, workgroups per column, grid x, grid y,
+ * threads, dynamic LDS bytes, 1 for a compile-time instance (0: the run-time kernel), XCD-aware numbering on, log2 of the tiles
+ * grouped per 128-byte line.  *out_launches: the number of launches; out_records may be NULL with cap_records (in records) = 0.
+ * Not in the plan, because only a device decides them: fewer columns per launch when scratch memory is short, tables that found
+ * no memory, and the run-time kernel taken when the device refuses an instance's LDS size.                                    */
+#define ZK_NTT_PLAN_WORDS 14
+int zk_host_ntt_plan(uint32_t log_n, size_t columns, int tables, int coset_pass, uint32_t* out_head, uint32_t* out_records, size_t cap_records, uint32_t* out_launches);
 /* ONE transform of size 2^log_n spread over `world` contexts, one per GPU (the
  * 4-step split with a single all-to-all).  On entry rank r holds the residue class
  * x[r + world * i], i < m = 2^log_n / world, in d_local; on return d_local[j1 * (m / world) + c]

@@ -259,6 +259,24 @@ def plan_summary(words) -> dict:
             "classes": [dict(zip(names, (int(v) for v in words[8 + 8 * e:16 + 8 * e]))) for e in range(E + 1)]}
 
 
+NTT_PLAN_FIELDS = ("kind", "pass", "passes", "log_np", "log_m", "log_t", "blocks", "grid_x", "grid_y", "threads", "lds", "fixed", "xcd", "log_grp")
+
+
+def host_ntt_plan(log_n: int, columns: int = 1, tables: bool = True, coset_pass: bool = False) -> dict:
+    """zk_host_ntt_plan (no device): the launches of one launch group of a transform under the ZK_NTT_* knobs in force;
+    kind is "strided" or "last", fixed / xcd are bools"""
+    head, recs, cnt = (ctypes.c_uint32 * 4)(), (ctypes.c_uint32 * (3 * len(NTT_PLAN_FIELDS)))(), ctypes.c_uint32()
+    rc = lib().zk_host_ntt_plan(ctypes.c_uint32(log_n), ctypes.c_size_t(columns), ctypes.c_int(1 if tables else 0), ctypes.c_int(1 if coset_pass else 0),
+                                head, recs, ctypes.c_size_t(3), ctypes.byref(cnt))
+    if rc != 0:
+        raise ZkError(f"zk_host_ntt_plan({log_n}, {columns}) failed with status {rc}")
+    w = len(NTT_PLAN_FIELDS)
+    launches = [dict(zip(NTT_PLAN_FIELDS, recs[i * w:(i + 1) * w])) for i in range(cnt.value)]
+    for r in launches:
+        r["kind"], r["fixed"], r["xcd"] = ("strided", "last")[r["kind"]], bool(r["fixed"]), bool(r["xcd"])
+    return {"per_launch": head[0], "columns": head[1], "passes": head[2], "tables": bool(head[3]), "launches": launches}
+
+
 TRANSCRIPT_BLAKE2B, TRANSCRIPT_POSEIDON, TRANSCRIPT_EVM = 0, 1, 2
 
 

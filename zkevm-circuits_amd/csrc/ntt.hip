@@ -507,22 +507,30 @@ static NttKnobs read_ntt_knobs() {
     return k;
 }
 
+// The digit split of a size: P <= 3 passes of at most 2^NTT_MAX_DIGIT points each (log_n, npass and every pass's log_np / log_m).
+static void split_digits(NttDomain& d, uint32_t log_n) {
+    d.log_n = log_n;
+    const int P = log_n <= NTT_MAX_DIGIT ? 1 : (log_n <= 2 * NTT_MAX_DIGIT ? 2 : 3);
+    d.npass = P;
+    int rem = (int)log_n;
+    for (int p = 0; p < P; ++p) {
+        int b = (rem + (P - p) - 1) / (P - p);   // ceil split, big digits first
+        d.pass[p].log_np = b;
+        rem -= b;
+        d.pass[p].log_m = rem;
+    }
+}
+// full inter-pass twiddle tables (n x 32 B per non-last pass) while the domain is not huge
+static bool tables_fit(uint32_t log_n, int npass) { return npass > 1 && log_n <= 24; }
+
 static int get_domain(zk_ctx* ctx, const NttKnobs& kn, uint32_t log_n, const Fr& omega, const Fr* scale, std::shared_ptr<NttDomain>* out) {
     const uint64_t key = domain_key(log_n, omega, scale);
     auto it = ctx->domains.find(key);
     if (it != ctx->domains.end()) { *out = it->second; return ZK_OK; }
     auto d = std::make_shared<NttDomain>();
-    d->log_n = log_n;
+    split_digits(*d, log_n);
     d->final_mul = to_rprime(scale ? *scale : Fr::one());
-    const int P = log_n <= NTT_MAX_DIGIT ? 1 : (log_n <= 2 * NTT_MAX_DIGIT ? 2 : 3);
-    d->npass = P;
-    int rem = (int)log_n;
-    for (int p = 0; p < P; ++p) {
-        int b = (rem + (P - p) - 1) / (P - p);   // ceil split, big digits first
-        d->pass[p].log_np = b;
-        rem -= b;
-        d->pass[p].log_m = rem;
-    }
+    const int P = d->npass;
     // two-level tables (only needed when P > 1)
     if (P > 1) {
         d->h = (int)(log_n + 1) / 2;
@@ -549,8 +557,7 @@ static int get_domain(zk_ctx* ctx, const NttKnobs& kn, uint32_t log_n, const Fr&
         ZK_CHECK_LAUNCH(ctx);
         d->pass[p].tw = d->d_tw29[p];
     }
-    // full inter-pass twiddle tables (n x 32 B per non-last pass) while the domain is not huge
-    if (P > 1 && log_n <= 24 && kn.out_table) {
+    if (tables_fit(log_n, P) && kn.out_table) {
         const uint64_t n = 1ull << log_n;
         for (int p = 0; p + 1 < P; ++p) {
             if (hipMalloc(&d->d_out_tw[p], sizeof(Fr) * n) != hipSuccess) { (void)hipGetLastError(); d->d_out_tw[p] = nullptr; break; }
@@ -621,7 +628,8 @@ static unsigned plan_threads(int tile, bool fixed) {
     if (fixed) return (unsigned)std::max(64, std::min(1024, tile >> 2));      // one radix-4 item per thread and step
     return tile >= 4096 ? 1024 : (tile >= 1024 ? 512 : (tile >= 256 ? 128 : 64));
 }
-static NttPlan plan_pass(const NttDomain& dom, int p, size_t nb, const NttKnobs& kn) {
+// `table`: the pass has its inter-pass twiddle table (NttPass::out_tw)
+static NttPlan plan_pass(const NttDomain& dom, int p, size_t nb, const NttKnobs& kn, bool table) {
     const NttPass& ps = dom.pass[p];
     NttPlan pl{};
     // tile of the strided passes: 4096 elements (T = 4: 128-byte runs) when there are two passes; with three passes
@@ -631,7 +639,7 @@ static NttPlan plan_pass(const NttDomain& dom, int p, size_t nb, const NttKnobs&
     pl.log_t = std::min(std::max(log_tile - ps.log_np, 0), ps.log_m);
     pl.tile = 1 << (ps.log_np + pl.log_t);
     pl.blocks = (unsigned)((1ull << dom.log_n) >> (ps.log_np + pl.log_t));
-    pl.fixed = kn.fixed && ps.out_tw && has_fixed_instance(ps.log_np);
+    pl.fixed = kn.fixed && table && has_fixed_instance(ps.log_np);
     pl.grid = dim3(pl.blocks * (unsigned)nb);
     pl.threads = plan_threads(pl.tile, pl.fixed);
     pl.lds = (size_t)pl.tile * NTT_LDS_BYTES_PER_ELT;
@@ -697,12 +705,12 @@ static LastKernel last_instance(int log_np) {
 static int launch_pass(zk_ctx* ctx, const NttDomain& dom, int p, size_t nb, const NttKnobs& kn, const NttIo& io, const Fr* pre) {
     const NttPass& ps = dom.pass[p];
     if (ps.log_np < 3) return ctx->fail(ZK_ERR_INVALID_ARG, "NTT: a strided pass over a digit of 2^%d", ps.log_np);      // its steps have no first-and-last instantiation
-    NttPlan pl = plan_pass(dom, p, nb, kn);
+    NttPlan pl = plan_pass(dom, p, nb, kn, ps.out_tw != nullptr);
     PassKernel kernel = pl.fixed ? pass_instance(ps.log_np, pre != nullptr) : k_ntt_pass;
     if (pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_PASS_MAX_LDS)) {
         NttKnobs generic = kn;
         generic.fixed = false;
-        pl = plan_pass(dom, p, nb, generic);
+        pl = plan_pass(dom, p, nb, generic, ps.out_tw != nullptr);
         kernel = k_ntt_pass;
     }
     if (!pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_PASS_MAX_LDS)) return ctx->fail(ZK_ERR_HIP, "NTT: the device refuses %zu bytes of LDS per workgroup", NTT_PASS_MAX_LDS);
@@ -732,6 +740,16 @@ static int launch_last(zk_ctx* ctx, const NttDomain& dom, size_t nb, const NttKn
                        dom.final_mul, pre, dom.fin_folded ? 1 : 0, pl.xcd);
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
+}
+
+// Columns per launch of a call over `count` columns: enough tiles to give every CU a few workgroups (ntt_run_many lowers it when the
+// scratch for that many columns cannot be had).  A coset shift that is a pass of its own is per column: one column per launch.
+static size_t columns_per_launch(uint32_t log_n, size_t count, bool coset_pass, const NttKnobs& kn) {
+    if (count <= 1 || coset_pass) return 1;
+    const uint64_t tiles = std::max<uint64_t>(1, (1ull << log_n) >> 12);
+    size_t per_launch = (size_t)std::min<uint64_t>(NTT_BATCH, std::max<uint64_t>(1, 4096 / tiles));       // sixteen columns at 2^20: a launch's last round of workgroups and the 10-20 us between dependent launches are paid once per sixteen columns (headline proof, alternating A/B on one box: 1.006 s with four, 0.9855 with eight, 0.9793 with sixteen; alone the transform does not care: 94.8 / 94.6 us)
+    if (kn.batch >= 1 && kn.batch <= NTT_BATCH) per_launch = (size_t)kn.batch;
+    return per_launch;
 }
 
 // Generic driver.  `scale` (nullable) multiplies every output; coset_pre (nullable): a[i] *= g^i
@@ -765,13 +783,7 @@ int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_
     rc = get_domain(ctx, kn, log_n, omega, scale, &dom);
     if (rc) return rc;
     const int P = dom->npass;
-    // columns per launch: enough tiles to give every CU a few workgroups, bounded by the scratch it takes
-    size_t per_launch = 1;
-    if (count > 1 && !pre_apart && !coset_post) {
-        const uint64_t tiles = std::max<uint64_t>(1, n >> 12);
-        per_launch = (size_t)std::min<uint64_t>(NTT_BATCH, std::max<uint64_t>(1, 4096 / tiles));       // sixteen columns at 2^20: a launch's last round of workgroups and the 10-20 us between dependent launches are paid once per sixteen columns (headline proof, alternating A/B on one box: 1.006 s with four, 0.9855 with eight, 0.9793 with sixteen; alone the transform does not care: 94.8 / 94.6 us)
-        if (kn.batch >= 1 && kn.batch <= NTT_BATCH) per_launch = (size_t)kn.batch;
-    }
+    size_t per_launch = columns_per_launch(log_n, count, pre_apart || coset_post, kn);       // fewer below when the scratch for them cannot be had
     Fr* scratch = nullptr;
     if (P > 1) {
         // transforms on the auxiliary stream run BESIDE transforms of the main stream (coset transforms ahead of the quotient,
@@ -847,6 +859,36 @@ __global__ void __launch_bounds__(256) k_ntt_cross(const Fr* __restrict__ recv, 
 }  // namespace zk
 
 using namespace zk;
+// Host only: the launch plans a transform of `columns` columns of 2^log_n elements follows under the knobs in force, out of the same
+// split_digits / columns_per_launch / plan_pass / plan_last as ntt_run_many and its launch sites.  What it leaves out is what only
+// a device decides: ntt_run_many's fewer columns per launch when the scratch for them cannot be had, a domain whose tables found no
+// memory, and the generic kernel a launch takes when the device refuses an instance its LDS size (the plan BEFORE that fallback).
+// The records describe the first launch group; the smaller group that ends a call of, say, 17 columns has the plans of a call with
+// that many columns.  `tables` states what the domain is: kn.out_table only acts when get_domain builds one and is not consulted.
+extern "C" int zk_host_ntt_plan(uint32_t log_n, size_t columns, int tables, int coset_pass, uint32_t* out_head, uint32_t* out_records, size_t cap_records, uint32_t* out_launches) {
+    if (!out_head || !out_launches || log_n < 1 || log_n > 28 || columns < 1 || (!out_records && cap_records)) return ZK_ERR_INVALID_ARG;
+    const NttKnobs kn = read_ntt_knobs();
+    NttDomain dom;
+    split_digits(dom, log_n);
+    const int P = dom.npass;
+    const bool table = tables && tables_fit(log_n, P);
+    dom.fin_folded = table;
+    const size_t per_launch = columns_per_launch(log_n, columns, coset_pass != 0, kn), nb = std::min(per_launch, columns);
+    out_head[0] = (uint32_t)per_launch;
+    out_head[1] = (uint32_t)nb;
+    out_head[2] = (uint32_t)P;
+    out_head[3] = table ? 1u : 0u;
+    *out_launches = (uint32_t)P;
+    if (cap_records < (size_t)P) return out_records ? ZK_ERR_INVALID_ARG : ZK_OK;
+    for (int p = 0; p < P; ++p) {
+        const bool last = p == P - 1;
+        const NttPlan pl = last ? plan_last(dom, nb, kn) : plan_pass(dom, p, nb, kn, table);
+        const uint32_t rec[ZK_NTT_PLAN_WORDS] = {last ? 1u : 0u, (uint32_t)p, (uint32_t)P, (uint32_t)dom.pass[p].log_np, (uint32_t)dom.pass[p].log_m, (uint32_t)pl.log_t, pl.blocks,
+                                                 pl.grid.x, pl.grid.y, pl.threads, (uint32_t)pl.lds, pl.fixed ? 1u : 0u, (uint32_t)pl.xcd, (uint32_t)pl.log_grp};
+        memcpy(out_records + (size_t)p * ZK_NTT_PLAN_WORDS, rec, sizeof rec);
+    }
+    return ZK_OK;
+}
 extern "C" int zk_ntt_sharded(zk_ctx* ctx, void* d_local, uint32_t log_n, int inverse, uint32_t rank, uint32_t world, zk_alltoall_fn exchange, void* user) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
     ZK_REQUIRE(ctx, d_local, "null pointer");
