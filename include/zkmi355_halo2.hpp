@@ -213,7 +213,8 @@ class ParamsKZG {
     std::vector<uint8_t> g2_, s_g2_;   // G2 generator and s * generator, file encoding
 };
 
-// plonk::keygen_pk result
+// plonk::keygen_pk result.  circuit_blob: a key blob of version 3 (fixed and sigma columns as Montgomery elements) or version 4
+// (typed fixed cells and halo2's Assembly::mapping; the sigma columns are built on the device) -- the same key either way
 class ProvingKey {
    public:
     ProvingKey(const Context& c, const ParamsKZG& params, const std::vector<uint8_t>& circuit_blob) : c_(c) {

@@ -1,4 +1,4 @@
-//! `ConstraintSystem` + keygen `Assembly`  ->  key blob v3 (layout: INTEGRATION.md §3; parsed by
+//! `ConstraintSystem` + keygen `Assembly`  ->  key blob v4 (layout: INTEGRATION.md §3; parsed by
 //! `zk_pk_create`, csrc/prover.hip).  The Python mirror of this file is
 //! `zkevm-circuits_amd/plonk.py::Circuit::{cs_blob, blob}`, which the tests use.
 //!
@@ -29,7 +29,7 @@ const CT_ADVICE: u32 = 1;
 const CT_INSTANCE: u32 = 2;
 const C_CHAL0: u32 = 0xFFFD_0000; // C_CHAL0 + i = halo2 `Challenge` i
 const BLOB_MAGIC: u32 = 0x4B50_5A4B;
-const BLOB_VERSION: u32 = 3;
+const BLOB_VERSION: u32 = 4; // typed fixed cells + `Assembly::mapping`: the device builds the sigma columns
 
 pub(super) struct Blob {
     pub bytes: Vec<u8>,
@@ -122,9 +122,22 @@ where
     }
 }
 
-/// `fixed` = the fixed columns after selector compression, `sigma` = the permutation columns in
-/// Lagrange form (`permutation::keygen::Assembly::build_pk(..).permutations`), both n values each.
-pub(super) fn key_blob(cs: &ConstraintSystem<Fr>, k: u32, fixed: &[Vec<Fr>], sigma: &[Vec<Fr>]) -> Vec<u8> {
+/// Narrowest cell width of a version 4 fixed column: 1, 2, 4, 8 or 16 bytes of little-endian unsigned integer when every
+/// cell's canonical value fits, else 32 (the column then goes as it lives in memory, Montgomery form).
+fn cell_width(col: &[Fr]) -> usize {
+    let mut used = 1;
+    for v in col {
+        let repr = v.to_repr(); // canonical, little-endian
+        let bytes = repr.as_ref();
+        let top = bytes.iter().rposition(|b| *b != 0).map_or(0, |i| i + 1);
+        used = used.max(top);
+    }
+    [1usize, 2, 4, 8, 16].into_iter().find(|w| used <= *w).unwrap_or(32)
+}
+
+/// `fixed` = the fixed columns after selector compression (n values each), `mapping` = `permutation::keygen::Assembly::mapping`
+/// as keygen left it: mapping[j][i] = (j', i'), the next cell in the cycle of cell i of permutation column j.
+pub(super) fn key_blob(cs: &ConstraintSystem<Fr>, k: u32, fixed: &[Vec<Fr>], mapping: &[Vec<(usize, usize)>]) -> Vec<u8> {
     let mut b = Blob { bytes: Vec::new(), consts: Vec::new() };
     // programs first (they fill the constant pool), serialised after the header
     let gates: Vec<Vec<[u32; 3]>> = cs
@@ -225,10 +238,27 @@ pub(super) fn key_blob(cs: &ConstraintSystem<Fr>, k: u32, fixed: &[Vec<Fr>], sig
         }
     }
     assert_eq!(fixed.len(), cs.num_fixed_columns());
-    assert_eq!(sigma.len(), perm.len());
-    for col in fixed.iter().chain(sigma.iter()) {
+    assert_eq!(mapping.len(), perm.len());
+    let widths: Vec<usize> = fixed.iter().map(|col| cell_width(col)).collect();
+    for w in &widths {
+        put_u32(out, *w as u32);
+    }
+    for (col, w) in fixed.iter().zip(&widths) {
         assert_eq!(col.len(), 1usize << k);
-        out.extend_from_slice(fr_slice_bytes(col));
+        if *w == 32 {
+            out.extend_from_slice(fr_slice_bytes(col));
+        } else {
+            for v in col {
+                out.extend_from_slice(&v.to_repr().as_ref()[..*w]);
+            }
+        }
+    }
+    for col in mapping {
+        assert_eq!(col.len(), 1usize << k);
+        for (j, i) in col {
+            put_u32(out, *j as u32);
+            put_u32(out, *i as u32);
+        }
     }
     let _ = <Fr as PrimeField>::NUM_BITS;
     std::mem::take(&mut b.bytes)

@@ -129,13 +129,12 @@ where
 fn register_key(params: &ParamsKZG<Bn256>, pk: &plonk::ProvingKey<G1Affine>) -> Result<(), Error> {
     let vk = pk.get_vk();
     let cs = vk.cs();
-    // Lagrange forms kept by upstream's ProvingKey: `fixed_values` (after selector compression) and
-    // `permutation.permutations` (sigma columns).  Both are private to `plonk` / `plonk::permutation` upstream: the fork
-    // needs `pub(crate)` on `ProvingKey::{fixed_values, permutation}` and on `permutation::ProvingKey::permutations`
-    // (shim/README.md, "visibility patch")
+    // The fixed values kept by upstream's ProvingKey (`fixed_values`, after selector compression) and keygen's
+    // `permutation::keygen::Assembly::mapping`, which the fork keeps in `permutation::ProvingKey::mapping` for this purpose: the
+    // device builds the sigma columns from it.  All of these are private upstream: the fork needs `pub(crate)` on
+    // `ProvingKey::{fixed_values, permutation}` and the `mapping` field (shim/README.md, "visibility patch")
     let fixed: Vec<Vec<Fr>> = pk.fixed_values.iter().map(|p| p.to_vec()).collect();
-    let sigma: Vec<Vec<Fr>> = pk.permutation.permutations.iter().map(|p| p.to_vec()).collect();
-    let blob = export::key_blob(cs, params.k(), &fixed, &sigma);
+    let blob = export::key_blob(cs, params.k(), &fixed, &pk.permutation.mapping);
     let mut g = gpu().lock().unwrap();
     let srs = g.srs(params)?;
     let mut dpk = std::ptr::null_mut();

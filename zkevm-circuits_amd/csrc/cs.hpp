@@ -67,6 +67,7 @@ inline int program_degree(const Prog& g, std::vector<int>* tmp_degree) {
 }
 
 struct ConstraintSystem {
+    uint32_t version = 3;               // of the blob it was read from: 3 (Montgomery columns follow) or 4 (typed fixed cells and the permutation mapping follow)
     uint32_t k = 0, bf = 0, d = 0, ext_k = 0, F = 0, A = 0, I = 0, P = 0, L = 0;
     uint32_t chunk = 0, C = 0, u = 0;   // permutation chunk size, #chunks, last usable row index
     std::vector<std::pair<uint32_t, uint32_t>> perm_cols;
@@ -82,7 +83,8 @@ struct ConstraintSystem {
 };
 
 // Reads the constraint-system part of a blob from `r` into `cs`, every count checked against what the blob can hold
-// (with_columns: the F + P columns of n rows must follow as well).  ZK_OK, or ZK_ERR_INVALID_ARG with *err set; `r` is left
+// (with_columns: the column data of that version must follow as well -- version 3: F + P columns of n Montgomery elements;
+// version 4: F cell widths, F payloads of at least one byte per cell, P x n mapping pairs).  ZK_OK, or ZK_ERR_INVALID_ARG with *err set; `r` is left
 // at the first byte after the constraint system.
 int parse_cs(Reader& r, ConstraintSystem* cs, size_t blob_len, bool with_columns, std::string* err);
 

@@ -265,6 +265,7 @@ int mock_perm_enqueue(zk_ctx* ctx, const Fr* const* d_sigma, const Fr* const* d_
 int fr_add_const_many(zk_ctx* ctx, const void* const* d_src, void* const* d_dst, size_t count, const void* h_k, size_t n);   // vec.hip: dst[c] = src[c] + k, any number of columns, no upload / sync
 int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint32_t width, uint64_t n, Fr* d_out);   // vec.hip: zk_fr_from_uint on any stream of the context (validates width and alignment)
 int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_packed, const uint8_t* widths, size_t count, uint64_t n, Fr* const* d_out);   // vec.hip: count columns of n cells each, sixteen per launch (validates every width and alignment before the first launch)
+int sigma_from_mapping_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_map, size_t count, uint64_t n, uint32_t P, const Fr* d_omega, const Fr* d_delta, uint32_t* d_bad, Fr* const* d_out);   // vec.hip: count sigma columns of n cells from halo2's permutation mapping, (u32 j', u32 i') per cell, sixteen per launch; a pair outside [0, P) x [0, n) stores zero and sets *d_bad
 int g_to_lagrange(zk_ctx* ctx, const G1Affine* d_g, uint32_t k, G1Affine* d_out);   // ecntt.hip: inverse FFT over G1
 bool comm_ready(const zk_ctx* ctx);                                                              // comm.hip: in-library RCCL collectives
 int comm_allgather_dev(zk_ctx* ctx, const void* d_send, size_t bytes, void* d_recv);             // stream-ordered, no host sync

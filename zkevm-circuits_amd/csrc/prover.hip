@@ -581,7 +581,8 @@ int zk::cs::parse_cs(Reader& r, ConstraintSystem* pk, size_t blob_len, bool with
     auto fail = [&](int code, const char* fmt, auto... args) { snprintf(msg, sizeof msg, fmt, args...); *err = msg; return code; };
     if (r.u32() != 0x4B505A4Bu) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad magic");
     const uint32_t version = r.u32();
-    if (version != 3u) return fail(ZK_ERR_INVALID_ARG, "pk blob: unsupported version %u (this library reads version 3)", version);
+    if (version != 3u && version != 4u) return fail(ZK_ERR_INVALID_ARG, "pk blob: unsupported version %u (this library reads versions 3 and 4)", version);
+    pk->version = version;
     pk->k = r.u32(); pk->bf = r.u32(); pk->d = r.u32(); pk->F = r.u32(); pk->A = r.u32(); pk->I = r.u32(); pk->P = r.u32(); pk->L = r.u32();
     const uint32_t ngates = r.u32(), nconsts = r.u32();
     // halo2: cs.degree() >= 3 (the permutation argument); the extended domain has at most 2^28 rows
@@ -590,7 +591,9 @@ int zk::cs::parse_cs(Reader& r, ConstraintSystem* pk, size_t blob_len, bool with
     if (pk->bf + 2 >= n) return fail(ZK_ERR_INVALID_ARG, "pk blob: too many blinding rows");
     // every count of the header is checked against what the blob can hold before anything is sized by it
     if ((size_t)pk->A * 4 > r.left || (size_t)pk->P * 8 > r.left || (size_t)nconsts * 32 > r.left || (size_t)ngates * 4 > r.left || (size_t)pk->L * 8 > r.left ||
-        (with_columns && ((size_t)pk->F + pk->P) > r.left / (n * 32)) || pk->A > 0xFFFFFFu || pk->F > 0xFFFFFFu || pk->I > 0xFFFFFFu)
+        (with_columns && version == 3u && ((size_t)pk->F + pk->P) > r.left / (n * 32)) ||
+        (with_columns && version == 4u && ((size_t)pk->F > r.left / (n + 4) || (size_t)pk->P > (r.left - (size_t)pk->F * (n + 4)) / (n * 8))) ||      // a width word and at least one byte per fixed cell, eight per mapping pair
+        pk->A > 0xFFFFFFu || pk->F > 0xFFFFFFu || pk->I > 0xFFFFFFu)
         return fail(ZK_ERR_INVALID_ARG, "pk blob: header counts exceed the blob (%zu bytes)", blob_len);
     pk->u = (uint32_t)n - pk->bf - 1;
     pk->chunk = pk->d - 2;
@@ -661,6 +664,127 @@ int zk::cs::parse_cs(Reader& r, ConstraintSystem* pk, size_t blob_len, bool with
     return ZK_OK;
 }
 
+namespace {
+
+// The column data of a version 4 key blob: F cell widths, the F fixed payloads (1-16-byte unsigned integers or
+// Montgomery elements), the permutation mapping.  Sixteen columns at a time cross the link on the copy stream into one staging
+// buffer and are expanded there, right behind their upload, into the key's Lagrange buffers -- fr_from_uint_batch_run for the
+// narrow fixed columns, k_sigma_from_mapping for the sigma columns (Montgomery fixed columns go straight to their buffer) --
+// while the commitments of the previous columns run: the staging callback of commit_batch_staged fences each group.  `tables`
+// receives the delta^j table and, behind it, the kernel's flag word; the caller reads the flag once the device is drained.
+constexpr size_t V4_GROUP = 16;                    // columns per expansion launch (FU_BATCH, SM_BATCH of vec.hip)
+int load_columns_v4(zk_ctx* ctx, zk_pk* pk, Reader& r, DevBuf* tables) {
+    const size_t n = (size_t)1 << pk->k, F = pk->F, P = pk->P;
+    struct Stage {
+        zk_ctx* ctx; size_t n, F, P;
+        std::vector<const uint8_t*> src; std::vector<uint8_t> width; std::vector<void*> dst;      // F fixed then P sigma columns
+        char* staging = nullptr; const Fr* omega = nullptr; const Fr* delta = nullptr; uint32_t* bad = nullptr;
+        size_t done = 0;                          // columns [0, done) are enqueued on the copy stream
+    } st{ctx, n, F, P, {}, {}, {}};
+    for (size_t i = 0; i < F; ++i) {
+        const uint32_t w = r.u32();
+        if (!r.ok) return ctx->fail(ZK_ERR_INVALID_ARG, "pk blob: truncated table of fixed cell widths");
+        if (w != 1 && w != 2 && w != 4 && w != 8 && w != 16 && w != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "pk blob: fixed column %zu has cell width %u (must be 1, 2, 4, 8, 16 or 32 bytes)", i, w);
+        st.width.push_back((uint8_t)w);
+    }
+    for (size_t i = 0; i < F; ++i) {
+        const uint8_t* b = r.bytes(n * st.width[i]);
+        if (!b) return ctx->fail(ZK_ERR_INVALID_ARG, "pk blob: truncated fixed column %zu (%zu cells of %u bytes)", i, n, (unsigned)st.width[i]);
+        st.src.push_back(b);
+    }
+    for (size_t j = 0; j < P; ++j) {
+        const uint8_t* b = r.bytes(n * 8);
+        if (!b) return ctx->fail(ZK_ERR_INVALID_ARG, "pk blob: truncated permutation mapping (column %zu of %zu)", j, P);
+        st.src.push_back(b);
+        st.width.push_back(8);
+    }
+    for (size_t i = 0; i < F + P; ++i) {
+        DevBuf& lag = i < F ? pk->fixed_lag[i] : pk->sigma_lag[i - F];
+        if (!lag.alloc(n * 32)) return ctx->fail(ZK_ERR_OOM, "prover: alloc of %zu bytes failed", n * 32);
+        st.dst.push_back(lag.p);
+    }
+    if (F + P == 0) return ZK_OK;
+    // the staging buffer holds the packed cells or the mapping slices of one group (payload offsets in the blob have no alignment: the
+    // uploads are byte copies, and every column starts on a 16-byte boundary here)
+    auto slot = [n](uint8_t w) { return (n * w + 15) / 16 * 16; };
+    size_t staging_bytes = 0;
+    for (size_t g0 = 0; g0 < F + P; g0 = g0 < F ? std::min(g0 + V4_GROUP, F) : g0 + V4_GROUP) {
+        size_t bytes = 0;
+        for (size_t g = g0; g < std::min(g0 + V4_GROUP, g0 < F ? F : F + P); ++g) if (g >= F || st.width[g] < 32) bytes += slot(st.width[g]);
+        staging_bytes = std::max(staging_bytes, bytes);
+    }
+    DevBuf staging;
+    if (staging_bytes) PK_ALLOC(ctx, staging, staging_bytes);
+    st.staging = (char*)staging.p;
+    if (P) {
+        PK_ALLOC(ctx, *tables, P * 32 + 32);
+        std::vector<F4> dp;
+        const F4 delta = host::fr_pow(host::fr_from_u64(7), 1ull << 28);          // as the permutation argument forms beta * delta^j
+        F4 cur = host::fr_one();
+        for (size_t j = 0; j < P; ++j) { dp.push_back(cur); cur = host::fr_mul(cur, delta); }
+        ZK_HIP(ctx, hipMemcpyAsync(tables->p, dp.data(), P * 32, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(ctx, hipMemsetAsync((char*)tables->p + P * 32, 0, 32, ctx->stream));
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));                            // `dp` goes out of scope
+        st.delta = (const Fr*)tables->p;
+        st.bad = (uint32_t*)((char*)tables->p + P * 32);
+        st.omega = pk->omega_lag.fr();
+    }
+    // hints for the MSM (speed only): cells of 8 bytes or fewer are below 2^64 by construction, wider ones are sampled on the host
+    // as the v3 path samples its columns (through an aligned copy of the samples); sigma columns are field-sized
+    std::vector<uint8_t> narrow(F + P, 0);
+    {
+        const size_t samples = std::min<size_t>(n, 1024), step = n / samples;
+        std::vector<std::vector<F4>> picked;
+        std::vector<const void*> picked_ptr;
+        std::vector<size_t> picked_at;
+        for (size_t i = 0; i < F; ++i) {
+            if (st.width[i] <= 8) narrow[i] = 1;
+            else if (st.width[i] == 16) {
+                size_t large = 0;
+                for (size_t s_ = 0; s_ < samples; ++s_) { uint64_t hi; memcpy(&hi, st.src[i] + (s_ * step) * 16 + 8, 8); large += hi != 0; }
+                narrow[i] = large <= samples / 4;
+            } else {
+                picked.emplace_back(samples);
+                for (size_t s_ = 0; s_ < samples; ++s_) memcpy(picked.back()[s_].l, st.src[i] + (s_ * step) * 32, 32);
+                picked_at.push_back(i);
+            }
+        }
+        for (const auto& v : picked) picked_ptr.push_back(v.data());
+        std::vector<uint8_t> picked_narrow(picked.size());
+        sample_narrow(picked_ptr.data(), picked.size(), samples, picked_narrow.data());
+        for (size_t t = 0; t < picked.size(); ++t) narrow[picked_at[t]] = picked_narrow[t];
+    }
+    PK_TRY(copy_stream_open(ctx));
+    auto stage = [](void* user, size_t it) -> int {
+        Stage* s_ = (Stage*)user;
+        if (it >= s_->done) {                     // first column of a group: the whole group is enqueued now, the calls for the others only fence
+            const size_t g0 = s_->done, g1 = std::min(g0 + V4_GROUP, g0 < s_->F ? s_->F : s_->F + s_->P);
+            const void* gsrc[V4_GROUP]; Fr* gdst[V4_GROUP]; uint8_t gw[V4_GROUP];
+            size_t cnt = 0, off = 0;
+            for (size_t g = g0; g < g1; ++g) {
+                if (g < s_->F && s_->width[g] == 32) { ZK_HIP(s_->ctx, hipMemcpyAsync(s_->dst[g], s_->src[g], s_->n * 32, hipMemcpyHostToDevice, s_->ctx->stream_copy)); continue; }
+                const size_t bytes = s_->n * s_->width[g];
+                ZK_HIP(s_->ctx, hipMemcpyAsync(s_->staging + off, s_->src[g], bytes, hipMemcpyHostToDevice, s_->ctx->stream_copy));
+                gsrc[cnt] = s_->staging + off; gdst[cnt] = (Fr*)s_->dst[g]; gw[cnt] = s_->width[g]; ++cnt;
+                off += (bytes + 15) / 16 * 16;
+            }
+            if (g0 < s_->F) PK_TRY(fr_from_uint_batch_run(s_->ctx, s_->ctx->stream_copy, gsrc, gw, cnt, s_->n, gdst));
+            else PK_TRY(sigma_from_mapping_run(s_->ctx, s_->ctx->stream_copy, gsrc, cnt, s_->n, (uint32_t)s_->P, s_->omega, s_->delta, s_->bad, gdst));
+            s_->done = g1;
+        }
+        return copy_stream_fence(s_->ctx);
+    };
+    std::vector<G1Affine> coms(F + P);
+    PK_TRY(commit_batch_staged(ctx, pk->srs, 1, (const void* const*)st.dst.data(), F + P, n, coms.data(), stage, &st, narrow.data()));
+    PK_TRY(zk_ctx_sync(ctx));                     // the staging buffer is released on return
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream_copy));
+    for (size_t i = 0; i < F; ++i) { pk->fixed_com[i] = coms[i]; PK_TRY(to_coeff(ctx, pk, pk->fixed_lag[i], &pk->fixed_coeff[i])); }
+    for (size_t i = 0; i < P; ++i) { pk->sigma_com[i] = coms[F + i]; PK_TRY(to_coeff(ctx, pk, pk->sigma_lag[i], &pk->sigma_coeff[i])); }
+    return ZK_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 void zk_pk_destroy(zk_ctx* ctx, zk_pk* pk) {
@@ -690,7 +814,16 @@ int zk_pk_create(zk_ctx* ctx, const zk_srs* srs, const void* h_blob, size_t blob
     pk->fixed_lag.resize(pk->F); pk->fixed_coeff.resize(pk->F);
     pk->sigma_lag.resize(pk->P); pk->sigma_coeff.resize(pk->P);
     pk->fixed_com.resize(pk->F); pk->sigma_com.resize(pk->P);
-    {   // keygen's commit_lagrange over every fixed and sigma column as ONE pipelined batch: column i + 1
+    auto omega_column = [&]() -> int {              // omega^i, row by row
+        const Fr w = fr_root_of_unity(pk->k), one = Fr::one();
+        return zk_fr_powers(ctx, &w, &one, pk->omega_lag.p, n);
+    };
+    DevBuf v4_tables;                               // version 4: delta^j table and the flag word of k_sigma_from_mapping (read below, once the device is drained)
+    if (pk->version == 4u) {                        // the omega^i column first: the sigma columns are products with its rows
+        PK_ALLOC(ctx, pk->omega_lag, n * 32);
+        PK_TRY(omega_column());
+        PK_TRY(load_columns_v4(ctx, pk.get(), r, &v4_tables));
+    } else {   // keygen's commit_lagrange over every fixed and sigma column as ONE pipelined batch: column i + 1
         // crosses PCIe on the copy stream while the MSM of column i runs; the coefficient forms follow
         std::vector<const void*> h_cols;
         std::vector<void*> d_cols;
@@ -709,8 +842,9 @@ int zk_pk_create(zk_ctx* ctx, const zk_srs* srs, const void* h_blob, size_t blob
     }
     // l0, l_last, l_active (built on the device: a delta at row 0, a delta at row u, ones below u) and the omega^i column
     {
-        const Fr w = fr_root_of_unity(pk->k), one = Fr::one();
-        PK_ALLOC(ctx, pk->l0_lag, n * 32); PK_ALLOC(ctx, pk->llast_lag, n * 32); PK_ALLOC(ctx, pk->lactive_lag, n * 32); PK_ALLOC(ctx, pk->omega_lag, n * 32);
+        const Fr one = Fr::one();
+        PK_ALLOC(ctx, pk->l0_lag, n * 32); PK_ALLOC(ctx, pk->llast_lag, n * 32); PK_ALLOC(ctx, pk->lactive_lag, n * 32);
+        if (pk->version != 4u) PK_ALLOC(ctx, pk->omega_lag, n * 32);
         ZK_HIP(ctx, hipMemsetAsync(pk->l0_lag.p, 0, n * 32, ctx->stream));
         ZK_HIP(ctx, hipMemsetAsync(pk->llast_lag.p, 0, n * 32, ctx->stream));
         ZK_HIP(ctx, hipMemsetAsync(pk->lactive_lag.p, 0, n * 32, ctx->stream));
@@ -720,8 +854,13 @@ int zk_pk_create(zk_ctx* ctx, const zk_srs* srs, const void* h_blob, size_t blob
         PK_TRY(to_coeff(ctx, pk.get(), pk->l0_lag, &pk->l0_coeff));
         PK_TRY(to_coeff(ctx, pk.get(), pk->llast_lag, &pk->llast_coeff));
         PK_TRY(to_coeff(ctx, pk.get(), pk->lactive_lag, &pk->lactive_coeff));
-        PK_TRY(zk_fr_powers(ctx, &w, &one, pk->omega_lag.p, n));
+        if (pk->version != 4u) PK_TRY(omega_column());
         PK_TRY(zk_ctx_sync(ctx));
+    }
+    if (pk->version == 4u && pk->P) {               // the device is drained: did a mapping pair name a column or a row that does not exist?
+        uint32_t bad = 0;
+        ZK_HIP(ctx, hipMemcpy(&bad, (const char*)v4_tables.p + (size_t)pk->P * 32, 4, hipMemcpyDeviceToHost));
+        if (bad) return ctx->fail(ZK_ERR_INVALID_ARG, "pk blob: a permutation mapping entry is out of range (column >= %u or row >= %zu)", pk->P, n);
     }
     // Default vk.transcript_repr: Blake2b-512 ("Halo2-Verify-Key") over the whole constraint-system
     // part of the blob and the compressed fixed / sigma commitments.  halo2's own value hashes the Debug
@@ -730,7 +869,10 @@ int zk_pk_create(zk_ctx* ctx, const zk_srs* srs, const void* h_blob, size_t blob
     {
         host::Blake2b hsh;
         hsh.init("Halo2-Verify-Key");
-        hsh.update(h_blob, cs_len);
+        const uint32_t as_v3 = 3u;                   // the version word is read as 3: one circuit, one stand-in value, whichever layout carried its columns
+        hsh.update(h_blob, 4);
+        hsh.update(&as_v3, 4);
+        hsh.update((const uint8_t*)h_blob + 8, cs_len - 8);
         for (const auto& c : pk->fixed_com) { uint8_t b[32]; host::g1_compress(c, b); hsh.update(b, 32); }
         for (const auto& c : pk->sigma_com) { uint8_t b[32]; host::g1_compress(c, b); hsh.update(b, 32); }
         uint8_t dg[64];

@@ -559,6 +559,45 @@ int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
+
+// ---- sigma columns from the permutation mapping: out[j][i] = delta^j' * omega^i' for mapping[j][i] = (j', i') ------------------------
+// halo2's permutation::keygen::Assembly::mapping names, for cell i of permutation column j, the next cell (j', i') of its cycle; the
+// sigma polynomial's value there is delta^j' * omega^i'.  Up to SM_BATCH columns per launch in the manner of k_fr_from_uint_batch:
+// blockIdx.y is the column, the pointers travel as a kernel argument.  A lane owns one cell: one dwordx2 load of the pair (consecutive
+// lanes on consecutive pairs), one 32-byte read of the key's omega^i column at row i' -- coalesced wherever the cell maps to itself,
+// which is most of a circuit, a gather elsewhere --, one read of the P-entry delta table (column-uniform outside copy cycles, cached),
+// one Montgomery product, one coalesced 32-byte store.  Both indices are bounded before anything is read through them: a pair outside
+// [0, P) x [0, n) stores zero and raises the flag word, which the host reads once the stream is drained.
+constexpr int SM_BATCH = 16;
+struct SmColumn { const uint2* map; Fr* dst; };
+struct SmBatch { SmColumn col[SM_BATCH]; };
+__global__ void __launch_bounds__(256) k_sigma_from_mapping(SmBatch b, uint64_t n, uint32_t P, const Fr* __restrict__ omega, const Fr* __restrict__ delta, uint32_t* __restrict__ bad) {
+    const SmColumn col = b.col[blockIdx.y];
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint2 next = col.map[i];                                      // (j', i')
+    Fr v{};
+    if (next.x < P && next.y < n) v = ldg(delta + next.x) * ldg(omega + next.y);
+    else atomicOr(bad, 1u);
+    stg(col.dst + i, v);
+}
+int sigma_from_mapping_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_map, size_t count, uint64_t n, uint32_t P, const Fr* d_omega, const Fr* d_delta, uint32_t* d_bad, Fr* const* d_out) {
+    for (size_t c = 0; c < count; ++c)
+        if ((uintptr_t)d_map[c] % 8) return ctx->fail(ZK_ERR_INVALID_ARG, "column %zu: mapping pairs at an address that is no multiple of 8", c);
+    if (!n || !count) return ZK_OK;
+    const uint64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many cells for one launch");
+    for (size_t c0 = 0; c0 < count; c0 += SM_BATCH) {
+        const size_t cnt = std::min<size_t>(SM_BATCH, count - c0);
+        SmBatch b;
+        ZkProfScope prof(ctx, "sigma_from_mapping", stream);
+        prof.bytes = cnt * n * (8 + 32 + 32ull);
+        for (size_t c = 0; c < SM_BATCH; ++c) b.col[c] = c < cnt ? SmColumn{(const uint2*)d_map[c0 + c], d_out[c0 + c]} : SmColumn{nullptr, nullptr};
+        hipLaunchKernelGGL(k_sigma_from_mapping, dim3((unsigned)blocks, (unsigned)cnt), dim3(256), 0, stream, b, n, P, d_omega, d_delta, d_bad);
+    }
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
 }  // namespace zk
 
 using namespace zk;

@@ -576,7 +576,7 @@ int decode_and_replay(zk_ctx* ctx, const zk_vk* vk, size_t count, const void* co
 
 extern "C" {
 
-// keygen_vk's product without the columns: the constraint system of a v3 key blob, the key's F fixed and P sigma commitments,
+// keygen_vk's product without the columns: the constraint system of a key blob (version 3 or 4: the same key), the key's F fixed and P sigma commitments,
 // vk.transcript_repr.  Host only.
 int zk_vk_create(const void* h_cs_blob, size_t len, const void* h_commitments, size_t num_commitments, const void* h_vk_repr_fr32, zk_vk** out) {
     if (!h_cs_blob || !h_vk_repr_fr32 || !out || (!h_commitments && num_commitments)) return ZK_ERR_INVALID_ARG;
@@ -585,7 +585,16 @@ int zk_vk_create(const void* h_cs_blob, size_t len, const void* h_commitments, s
     std::string err;
     if (int rc = parse_cs(r, vk.get(), len, false, &err)) return rc;
     // the constraint-system part alone, or the whole key blob (its F + P columns are not read); nothing else may follow
-    if (r.left && r.left != ((size_t)vk->F + vk->P) * ((size_t)32 << vk->k)) return ZK_ERR_INVALID_ARG;
+    if (r.left && vk->version == 3u && r.left != ((size_t)vk->F + vk->P) * ((size_t)32 << vk->k)) return ZK_ERR_INVALID_ARG;
+    if (r.left && vk->version == 4u) {           // F cell widths, F payloads of n cells, P x n mapping pairs
+        size_t want = (size_t)vk->P * ((size_t)8 << vk->k);
+        for (uint32_t i = 0; i < vk->F; ++i) {
+            const uint32_t w = r.u32();
+            if (!r.ok || (w != 1 && w != 2 && w != 4 && w != 8 && w != 16 && w != 32)) return ZK_ERR_INVALID_ARG;
+            want += (size_t)w << vk->k;
+        }
+        if (r.left != want) return ZK_ERR_INVALID_ARG;
+    }
     if (num_commitments != (size_t)vk->F + vk->P) return ZK_ERR_INVALID_ARG;
     const G1Affine* c = (const G1Affine*)h_commitments;
     for (size_t i = 0; i < num_commitments; ++i) {

@@ -526,9 +526,11 @@ class Circuit:
         dp = [pow(FR_DELTA, j, R_MOD) for j in range(P)]
         return [[dp[mapping[j][i][0]] * wp[mapping[j][i][1]] % R_MOD for i in range(n)] for j in range(P)]
 
-    def cs_blob(self, cse: bool = False) -> bytes:
+    def cs_blob(self, cse: bool = False, version: int = BLOB_VERSION) -> bytes:
         """The constraint-system part of the key blob (everything but the column data): what the
-        default `vk.transcript_repr` of zk_pk_create hashes together with the key's commitments."""
+        default `vk.transcript_repr` of zk_pk_create hashes together with the key's commitments.
+        Versions 3 and 4 differ in the version word alone."""
+        assert version in (3, 4), "key blobs are written as version 3 or 4"
         gates = self.compile_gates_cse() if cse else [self.compile(g) for g in self.gates]
         lookups = [([self.compile(e) for e in lk.table], [[self.compile(e) for e in i] for i in lk.inputs]) for lk in self.lookups]
 
@@ -538,7 +540,7 @@ class Circuit:
         def queries(q):
             return struct.pack("<I", len(q)) + b"".join(struct.pack("<Ii", c, r) for c, r in q)
 
-        out = [struct.pack("<12I", BLOB_MAGIC, BLOB_VERSION, self.k, self.bf, self.degree(), self.F, self.A, self.I,
+        out = [struct.pack("<12I", BLOB_MAGIC, version, self.k, self.bf, self.degree(), self.F, self.A, self.I,
                            len(self.perm_cols), len(self.lookups), len(gates), len(self.consts))]
         out.append(struct.pack("<I", len(self.challenge_phase)))
         out += [struct.pack("<I", p) for p in self.advice_phase]
@@ -554,12 +556,78 @@ class Circuit:
                 out += [prog(p) for p in ins]
         return b"".join(out)
 
-    def blob(self, cse: bool = False) -> bytes:
+    @staticmethod
+    def fixed_cell_width(col: Sequence[int]) -> int:
+        """The narrowest cell width of a version 4 blob that holds every cell of a fixed column (reduced mod r): 1, 2, 4, 8 or
+        16 bytes of little-endian unsigned integer, or 32 (Montgomery form) when a cell is 2^128 or above."""
+        top = max((v % R_MOD for v in col), default=0)
+        for w in (1, 2, 4, 8, 16):
+            if top < 1 << (8 * w):
+                return w
+        return 32
+
+    def blob(self, cse: bool = False, version: int = BLOB_VERSION) -> bytes:
         """Serialise for zk_pk_create (layout documented in INTEGRATION.md).  cse: share
-        sub-expressions between gates through the evaluator's intermediates (same proof bytes)."""
+        sub-expressions between gates through the evaluator's intermediates (same proof bytes).
+        version 3: every fixed and sigma column as n Montgomery elements.  version 4: every fixed column as n cells of its
+        narrowest width and the permutation as halo2's `Assembly::mapping`, (u32 j', u32 i') per cell -- the device builds the
+        sigma columns, no field product is made here."""
         assert self.fixed is not None, "a shape-only circuit has no fixed assignment to export"
+        if version == 4:
+            widths = [self.fixed_cell_width(col) for col in self.fixed]
+            out = [self.cs_blob(cse, 4), struct.pack(f"<{self.F}I", *widths)]
+            for w, col in zip(widths, self.fixed):
+                out.append(column_to_mont(col).tobytes() if w == 32 else b"".join((v % R_MOD).to_bytes(w, "little") for v in col))
+            mapping = self.permutation_mapping()
+            out += [np.array(col, dtype="<u4").reshape(self.n, 2).tobytes() for col in mapping]
+            return b"".join(out)
         sig = self.sigma_columns()
-        out = [self.cs_blob(cse)]
+        out = [self.cs_blob(cse, version)]
         out += [column_to_mont(col).tobytes() for col in self.fixed]
         out += [column_to_mont(col).tobytes() for col in sig]
         return b"".join(out)
+
+    @staticmethod
+    def cs_blob_len(blob: bytes) -> int:
+        """Length of the constraint-system part at the head of a key blob (either version)."""
+        u32 = lambda at: struct.unpack_from("<I", blob, at)[0]
+        magic, _version, _k, _bf, _d, _F, A, _I, P, L, ngates, nconsts = struct.unpack_from("<12I", blob, 0)
+        assert magic == BLOB_MAGIC, "not a key blob"
+        at = 48
+        at += 4 + 4 * A + 4 * u32(at)                      # challenge count, advice phases, challenge phases
+        for _ in range(3):                                 # advice, fixed, instance queries
+            at += 4 + 8 * u32(at)
+        at += 8 * P + 32 * nconsts
+
+        def prog(at):
+            return at + 4 + 12 * u32(at)
+        for _ in range(ngates):
+            at = prog(at)
+        for _ in range(L):
+            m, ninputs = struct.unpack_from("<II", blob, at)
+            at += 8
+            for _ in range(m * (1 + ninputs)):
+                at = prog(at)
+        return at
+
+    @classmethod
+    def blob_v4_parts(cls, blob: bytes):
+        """(widths, fixed payloads, mapping) of a version 4 key blob: the F cell widths, the F payloads as bytes (n cells of that
+        width each), and mapping[j][i] = (j', i') as `permutation_mapping()` returns it."""
+        magic, version, k, _bf, _d, F = struct.unpack_from("<6I", blob, 0)
+        P = struct.unpack_from("<I", blob, 32)[0]
+        assert magic == BLOB_MAGIC and version == 4, "not a version 4 key blob"
+        n, at = 1 << k, cls.cs_blob_len(blob)
+        widths = list(struct.unpack_from(f"<{F}I", blob, at))
+        at += 4 * F
+        payloads = []
+        for w in widths:
+            payloads.append(blob[at:at + n * w])
+            at += n * w
+        mapping = []
+        for _ in range(P):
+            pairs = np.frombuffer(blob, dtype="<u4", count=2 * n, offset=at).reshape(n, 2)
+            mapping.append([(int(a), int(b)) for a, b in pairs])
+            at += 8 * n
+        assert at == len(blob), "trailing or missing bytes in a version 4 key blob"
+        return widths, payloads, mapping
