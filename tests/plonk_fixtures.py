@@ -246,3 +246,44 @@ def build_evm_circuit(k: int, seed: int = 1, states: int = 6, per_state: int = 1
         c.copy((plonk.ADVICE, spec["ctr"], row), (plonk.INSTANCE, 0, j))
     c.evm_spec = spec
     return c, adv, inst
+
+
+def build_plan_knob_circuit(k: int = 5):
+    """A constraint system (no witness comes with it) on which the quotient planner's knobs each leave a trace, for the tests
+    of the plan a key caches (tests/test_gpu_evm_shape.py).  Degree 7, so E = 3 and the classes hold degrees <= 2, 3, 4..5, 6..9.
+
+    columns: fixed  0 q | 1 q2 | 2 t            advice 0..3 a b c d | 4..11 e_i | 12 w | 13 x | 14..19 f_1..f_6 | 20..23 leaves
+    gates:   q (a b c d - e_i), i < 8           degree 5; the additive split takes q e_i (degree 2, a column each) down to class 0 and the
+                                                cost gate keeps that plan: ZK_QUOTIENT_ADDSPLIT=0 and ZK_QUOTIENT_SPLIT=0 give other plans
+             q2 (a b c - w)                     shares a b c with the gates above: a value parked in one term of class 2 and read in another
+             ((s_i f_(i+1)) ... f_1), i < 6     s_i = x^(6-i): degree 7, nested common factors six levels deep ...
+             ((T f_6) ... f_1)                  ... around a balanced sum T of 512 leaves (ten stack slots): compiled through the expression
+                                                graph this class needs more stack slots than the 14 the evaluator runs, so it is
+                                                assembled by assemble_grouped -- or folded term by term under ZK_QUOTIENT_GROUP=0
+    lookups: (q a) in (t), (q b) in (t)         single tuples into one table: tau = t + beta parked by the first and read by the second (a
+                                                shared intermediate); ZK_LOOKUP_PLAIN=1 writes the identity without it"""
+    c = plonk.Circuit(k, num_fixed=3, num_advice=24, num_instance=0, blinding_factors=5)
+    q, q2, t = (c.fixed_col(i) for i in range(3))
+    a, b_, cc, d_ = (c.advice_col(i) for i in range(4))
+    w, x = c.advice_col(12), c.advice_col(13)
+    f = [c.advice_col(14 + i) for i in range(6)]
+    for i in range(8):
+        c.add_gate(q * (a * b_ * cc * d_ - c.advice_col(4 + i)))
+    c.add_gate(q2 * (a * b_ * cc - w))
+    leaves = [c.advice_col(20 + j % 4, j // 4 % 3) for j in range(512)]
+    while len(leaves) > 1:
+        leaves = [leaves[j] + leaves[j + 1] for j in range(0, len(leaves), 2)]
+    for i in range(7):
+        s = leaves[0]
+        if i < 6:
+            s = x
+            for _ in range(5 - i):
+                s = s * x
+        for j in range(min(i, 5), -1, -1):
+            s = s * f[j]
+        c.add_gate(s)
+    c.add_lookup([q * a], [t])
+    c.add_lookup([q * b_], [t])
+    for row in range(c.u):                            # a key can be made of it: selectors and a table that are not all zero
+        c.fixed[0][row], c.fixed[1][row], c.fixed[2][row] = row % 2, 1, row
+    return c

@@ -121,6 +121,62 @@ def test_the_plan_cache_follows_the_chunk_knob(ctx, cref, monkeypatch):
         srs.destroy()
 
 
+# one setting off its default per input of the plan (csrc/quotient_plan.hpp QuotientKnobs)
+PLAN_KNOBS = (("ZK_QUOTIENT_SPLIT", "0"), ("ZK_QUOTIENT_ADDSPLIT", "0"), ("ZK_QUOTIENT_GROUP", "0"), ("ZK_QUOTIENT_DAG", "0"), ("ZK_QUOTIENT_COSTGATE", "0"),
+              ("ZK_QUOTIENT_MAC", "0"), ("ZK_QUOTIENT_CHUNK", "1"), ("ZK_LOOKUP_PLAIN", "1"))
+
+
+def test_the_plan_cache_follows_every_knob(ctx, cref, monkeypatch):
+    """A key keeps its quotient plan; every one of the planner's eight knobs is part of what decides whether the kept plan still holds.  For
+    each knob: zk_pk_quotient_plan with the environment clean, with the knob set (the plan zk_host_quotient_plan makes under the same
+    environment, and another one than before), and clean again (the first one).  The readings are the full summaries (8 + 14 (E + 1) words).
+
+    Two keys, because no single constraint system shows all eight: the candidates are (classes + additive split), (classes), (one class);
+    ZK_QUOTIENT_COSTGATE=0 takes the first one and ZK_QUOTIENT_ADDSPLIT=0 leaves the cheaper of the last two, so wherever the default plan is
+    the first candidate the cost gate changes nothing, and wherever it is not, switching the additive split off changes nothing.  The
+    knob circuit's default plan uses the additive split (SPLIT, ADDSPLIT, GROUP, DAG, CHUNK, LOOKUP_PLAIN change it), the small EVM shape's
+    does not (DAG, COSTGATE, MAC, CHUNK, LOOKUP_PLAIN change it).  The premise -- every knob changes the summary on at least one of the
+    two -- is asserted, from zk_host_quotient_plan alone.  k = 5 and 6, one lookup or two, gates of degree 5 .. 9, tau = t + beta of the
+    knob circuit's table shared by two constraints."""
+    import ctypes
+    from plonk_fixtures import build_plan_knob_circuit
+    from zkevm_circuits_amd import binding
+    lib = binding.lib()
+    for name, _ in PLAN_KNOBS:
+        monkeypatch.delenv(name, raising=False)
+    changed_somewhere = set()
+    for circ in (build_plan_knob_circuit(5), build_evm_circuit(6, seed=2)[0]):
+        cs, words = circ.cs_blob(), 8 + 14 * (circ.extended_k() - circ.k + 1)
+
+        def host():
+            out, n_ = np.zeros(words, dtype=np.uint32), ctypes.c_uint32()
+            assert lib.zk_host_quotient_plan(cs, ctypes.c_size_t(len(cs)), out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(words), ctypes.c_uint32(0xFFFFFFFF), None,
+                                             ctypes.c_size_t(0), ctypes.byref(n_)) == 0
+            return list(out)
+        srs = ctx.srs_setup_with_s(circ.k, cref.fr_const(S_SECRET))
+        pk = ctx.pk_create(srs, circ.blob())
+
+        def of_key():
+            out = np.zeros(words, dtype=np.uint32)
+            ctx._ck(lib.zk_pk_quotient_plan(ctx.h, pk.h, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(words)))
+            return list(out)
+        try:
+            first = of_key()
+            assert first == host()
+            for name, value in PLAN_KNOBS:
+                monkeypatch.setenv(name, value)
+                want, got = host(), of_key()
+                assert got == want, (name, value)
+                if want != first:
+                    changed_somewhere.add(name)
+                monkeypatch.delenv(name)
+                assert of_key() == first, (name, value)
+        finally:
+            pk.destroy()
+            srs.destroy()
+    assert changed_somewhere == {name for name, _ in PLAN_KNOBS}
+
+
 def test_the_benched_evm_configuration_at_k20(ctx, cref):
     from test_gpu_headline_config import require_host_memory
     require_host_memory(64)

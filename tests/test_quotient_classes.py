@@ -1,4 +1,4 @@
-"""CPU: the degree-class assembly of constraint programs that share intermediates (csrc/prover.hip TmpSplit, through the
+"""CPU: the degree-class assembly of constraint programs that share intermediates (csrc/quotient_plan.hip TmpSplit, through the
 host-only hook zk_host_split_programs).  halo2's GraphEvaluator shares intermediates between gates; the exported programs
 carry them as TEE_TMP / PUSH_TMP.  A degree class evaluates only its own constraints, so an intermediate parked by another
 class's constraint has to be re-materialised -- every constraint must keep its value whichever class it lands in."""

@@ -348,7 +348,7 @@ def test_malformed_programs_are_refused_not_executed():
         assert rc != 0, prog
 
 
-# ---- the class programs of round 5: one weighted sum (csrc/prover.hip assemble_grouped) -----------------------------------
+# ---- the class programs of round 5: one weighted sum (csrc/quotient_plan.hip assemble_grouped) -----------------------------------
 def test_grouped_class_programs_keep_every_bound():
     """a class program as the prover assembles it since round 5 -- terms under a shared single-column factor collected, weights
     y^(K-1-i) as constants, one closing FOLD -- lowered and executed limb by limb with every column at p - 1, 0, 1 and random:

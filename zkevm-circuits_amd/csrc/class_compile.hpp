@@ -22,6 +22,18 @@
 //      acc = sum_t y^(last - cons_t) term_t          (last = the largest constraint index of the class)
 // and the caller scales by y^(K-1-last) as before.  ZK_QUOTIENT_DAG=0 keeps round 5's assembly (assemble_grouped / folding).
 #pragma once
+#include <algorithm>
+#include <array>
+#include <cstdio>
+#include <cstdlib>
+#include <functional>
+#include <unordered_map>
+#include <vector>
+
+#include "quotient_plan.hpp"
+
+namespace zk {
+namespace qplan {
 
 struct ClassCompileStats { uint32_t nodes = 0, parked = 0, max_live = 0, products = 0, instrs = 0, groups = 0; int depth = 0; };
 
@@ -194,18 +206,7 @@ struct ClassCompiler {
             else { if (n.x >= 0) work.push_back(n.x); if (n.y >= 0) work.push_back(n.y); }
         }
     }
-    void count_uses(int32_t root) {
-        uses.assign(nd.size(), 0);
-        std::vector<int32_t> work{root};
-        while (!work.empty()) {
-            const int32_t v = work.back();
-            work.pop_back();
-            if (uses[v]++) continue;
-            const Node& n = nd[v];
-            if (n.op == OP_HSUM) for (const Item& it : hs[n.a]) work.push_back(it.node);
-            else { if (n.x >= 0) work.push_back(n.x); if (n.y >= 0) work.push_back(n.y); }
-        }
-    }
+    void count_uses(int32_t root) { count_uses_from({root}); }
     void emit(int32_t v, bool top) {
         if (vslot[v] >= 0) { out.push_back({Q_PUSH_TMP, (uint32_t)vslot[v], 0}); return; }
         const Node n = nd[v];
@@ -283,8 +284,9 @@ struct ClassCompiler {
     }
 };
 
-// terms of one class (constraint index, program) -> its program; false: the caller keeps the old assembly
-static bool compile_class(const std::vector<ClassTerm>& terms, uint32_t K, Prog& out, uint32_t* last, ClassCompileStats* stats_out = nullptr) {
+// terms of one class (constraint index, program) -> its program; false: the caller keeps the old assembly.  chunk (QuotientKnobs::chunk):
+// 1 the program is emitted term by term so that the evaluator can slice it, 0 one parking scope for the whole class, -1 by node count
+inline bool compile_class(const std::vector<ClassTerm>& terms, uint32_t K, int chunk, Prog& out, uint32_t* last, ClassCompileStats* stats_out = nullptr) {
     if (terms.empty() || K >= 0xFFFFu) return false;
     ClassCompiler cc;
     std::unordered_map<uint32_t, int32_t> slots;
@@ -302,10 +304,7 @@ static bool compile_class(const std::vector<ClassTerm>& terms, uint32_t K, Prog&
         root = cc.fresh(ClassCompiler::OP_HSUM, (uint32_t)cc.hs.size() - 1, 0, -1, -1);
     }
     cc.count_uses(root);
-    {   // large programs are emitted term by term so that the evaluator can slice them (ZK_QUOTIENT_CHUNK=0: one parking scope for the whole class)
-        const char* e = getenv("ZK_QUOTIENT_CHUNK");
-        cc.chunked = e ? atoi(e) != 0 : cc.nd.size() >= 4096;
-    }
+    cc.chunked = chunk < 0 ? cc.nd.size() >= 4096 : chunk != 0;       // large programs are emitted term by term so that the evaluator can slice them
     cc.prod_memo.assign(cc.nd.size(), -1);
     cc.no_park.assign(cc.nd.size(), 0);
     // Parking pays by (uses - 1) x (products the value cost): tau = t + beta of a lookup table is ONE product and is read by every
@@ -342,13 +341,8 @@ static bool compile_class(const std::vector<ClassTerm>& terms, uint32_t K, Prog&
         price *= 2;
     }
     int sp = 0, mx = 0;
-    for (const Instr& in : cc.out) {
-        if (in.op == Q_PUSH_COL || in.op == Q_PUSH_CONST || in.op == Q_PUSH_TMP) ++sp;
-        else if (in.op == Q_ADD || in.op == Q_SUB || in.op == Q_MUL || in.op == Q_FOLD) --sp;
-        mx = std::max(mx, sp);
-    }
-    if (sp != 0 || mx > 14) { if (getenv("ZK_QUOTIENT_TRACE")) fprintf(stderr, "[zk quotient] compile_class: stack depth %d (final %d): kept in the old form\n", mx, sp); return false; }
-    for (const Instr& in : cc.out) if (in.op == Q_MUL || in.op == Q_SQUARE || in.op == Q_MUL_CONST || in.op == Q_FOLD) ++cc.stats.products;
+    if (!fits_evaluator_stack(cc.out, &mx, &sp)) { if (getenv("ZK_QUOTIENT_TRACE")) fprintf(stderr, "[zk quotient] compile_class: stack depth %d (final %d): kept in the old form\n", mx, sp); return false; }
+    cc.stats.products = count_products(cc.out);
     cc.stats.nodes = (uint32_t)cc.nd.size();
     cc.stats.instrs = (uint32_t)cc.out.size();
     cc.stats.depth = mx;
@@ -357,3 +351,6 @@ static bool compile_class(const std::vector<ClassTerm>& terms, uint32_t K, Prog&
     if (stats_out) *stats_out = cc.stats;
     return true;
 }
+
+}  // namespace qplan
+}  // namespace zk

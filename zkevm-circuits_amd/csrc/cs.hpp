@@ -1,6 +1,6 @@
 // The constraint-system part of a key blob (INTEGRATION.md has the layout): the shape, phases, query lists, permutation
 // columns, constants and the gate / lookup programs -- everything a key holds before its column data.  One parser, parse_cs
-// (prover.hip), reads it for the proving key (zk_pk_create), the verifying key (zk_vk_create) and the host-only hooks.
+// (cs.hip), reads it for the proving key (zk_pk_create), the verifying key (zk_vk_create) and the host-only hooks.
 // The programs are postfix over abstract column and constant references; the prover lowers them for the device evaluator
 // (quotient.hip), the verifier evaluates them at one point (verifier.hip).
 #pragma once
@@ -28,6 +28,7 @@ constexpr uint32_t C_THETA = 0xFFFF0000u, C_BETA = 0xFFFF0001u, C_GAMMA = 0xFFFF
 inline uint32_t colref(uint32_t type, uint32_t idx) { return (type << 24) | idx; }
 
 struct Instr { uint32_t op, a, b; };
+inline bool operator==(const Instr& x, const Instr& y) { return x.op == y.op && x.a == y.a && x.b == y.b; }
 typedef std::vector<Instr> Prog;
 
 struct Query { uint32_t type, idx; int32_t rot; };

@@ -14,6 +14,8 @@
 //   host   : transcript (built-in Blake2b or the caller's object through a callback table), the
 //            blinding-row RNG (XorShift), program assembly, a handful of scalar field operations
 //            per challenge; for multi-GPU sessions the all-gather callbacks
+// The key blob's constraint system is parsed by cs.hip; the quotient's plan (degree classes, class programs) is made by
+// quotient_plan.hip from the constraint system and the knobs alone, and kept here per key (zk_pk::qplan).
 //
 // Protocol (mv-lookup/logUp lookups as in the Scroll halo2 fork, SURVEY note L):
 //   vk_repr, instances | per phase: advice commitments, the phase's challenges | theta |
@@ -43,10 +45,12 @@
 #include "ctx.hpp"
 #include "host_hash.hpp"
 #include "cs.hpp"
+#include "quotient_plan.hpp"
 
 using namespace zk;
 using zk::host::F4;
 using namespace zk::cs;
+using namespace zk::qplan;
 
 extern "C" int zk_quotient_eval(zk_ctx*, const uint32_t*, uint32_t, const void* const*, uint32_t, const void*, uint32_t, uint32_t, uint32_t, int, void*);
 extern "C" int zk_fr_powers(zk_ctx*, const void*, const void*, void*, size_t);
@@ -134,7 +138,6 @@ struct StageTrace {
 
 }  // namespace
 
-struct QuotientPlan;
 struct zk_pk : zk::cs::ConstraintSystem {   // the constraint system (cs.hpp) and what keygen derives from it
     // device-resident key material
     std::vector<DevBuf> fixed_lag, fixed_coeff, sigma_lag, sigma_coeff;
@@ -205,9 +208,8 @@ size_t device_free_bytes(bool* ok = nullptr) {
     return free_b;
 }
 
-// Degree class e of 0 .. E is evaluated on the cosets r that are multiples of 2^(E - e) (see the quotient stage).
-inline bool class_on_coset(uint32_t E, uint32_t e, uint32_t r) { return (r & ((1u << (E - e)) - 1u)) == 0; }
-// ... and, in a sharded session, by the rank the (class, coset) pair was dealt to: a table filled once, when the deal is made
+// Degree class e is evaluated on the cosets class_on_coset(E, e, r) names (quotient_plan.hpp) and, in a sharded session, by the rank
+// the (class, coset) pair was dealt to: a table filled once, when the deal is made
 struct PairOwners {
     uint32_t E = 0, rank = 0;
     bool sharded = false;
@@ -375,74 +377,6 @@ const Fr* coeff_of(const zk_pk* pk, uint32_t ref, const std::vector<DevBuf>& adv
     }
 }
 
-// ---- small program builder ----------------------------------------------------------------------
-struct PB {
-    Prog g;
-    PB& col(uint32_t type, uint32_t idx, int32_t rot = 0) { g.push_back({Q_PUSH_COL, colref(type, idx), (uint32_t)rot}); return *this; }
-    PB& cst(uint32_t ref) { g.push_back({Q_PUSH_CONST, ref, 0}); return *this; }
-    PB& op(uint32_t o) { g.push_back({o, 0, 0}); return *this; }
-    PB& mulc(uint32_t ref) { g.push_back({Q_MUL_CONST, ref, 0}); return *this; }
-    PB& addc(uint32_t ref) { g.push_back({Q_ADD_CONST, ref, 0}); return *this; }
-    PB& fold(uint32_t ref) { g.push_back({Q_FOLD, ref, 0}); return *this; }
-    PB& append(const Prog& o) { g.insert(g.end(), o.begin(), o.end()); return *this; }
-};
-// theta-compression of a list of expressions: ((e0 * theta + e1) * theta + e2) ...
-// An expression of the form F * X or X * F with F a single column read: X (postfix) and F; false for any other shape.
-// (The inputs of a zkEVM lookup are `q_enable * value`, all of a tuple under the same q_enable.)
-static bool split_leaf_factor(const Prog& g, bool factor_first, Prog* rest, Instr* factor) {
-    if (g.size() < 3 || g.back().op != Q_MUL) return false;
-    if (factor_first) {
-        if (g[0].op != Q_PUSH_COL) return false;
-        *factor = g[0];
-        rest->assign(g.begin() + 1, g.end() - 1);
-    } else {
-        if (g[g.size() - 2].op != Q_PUSH_COL) return false;
-        *factor = g[g.size() - 2];
-        rest->assign(g.begin(), g.end() - 2);
-    }
-    // `rest` must be ONE complete expression (the other operand of the product at the root)
-    int sp = 0;
-    for (const Instr& in : *rest) {
-        switch (in.op) {
-            case Q_PUSH_COL: case Q_PUSH_CONST: case Q_PUSH_TMP: ++sp; break;
-            case Q_ADD: case Q_SUB: case Q_MUL: if (sp < 2) return false; --sp; break;
-            case Q_TEE_TMP: return false;
-            default: if (sp < 1) return false; break;
-        }
-    }
-    return sp == 1;
-}
-void push_compressed(PB& b, const std::vector<Prog>& exprs) {
-    // sum_i theta^(N-1-i) (F x_i) = F * sum_i theta^(N-1-i) x_i: one product by F instead of N (exact: same polynomial)
-    if (exprs.size() >= 2) {
-        for (int first = 1; first >= 0; --first) {
-            std::vector<Prog> rest(exprs.size());
-            Instr f0{0, 0, 0};
-            bool all = true;
-            for (size_t i = 0; i < exprs.size() && all; ++i) {
-                Instr f{0, 0, 0};
-                all = split_leaf_factor(exprs[i], first != 0, &rest[i], &f) && (i == 0 || (f.a == f0.a && f.b == f0.b));
-                if (i == 0) f0 = f;
-            }
-            if (!all) continue;
-            for (size_t i = 0; i < rest.size(); ++i) {
-                if (i) b.mulc(C_THETA);
-                b.append(rest[i]);
-                if (i) b.op(Q_ADD);
-            }
-            b.g.push_back(f0);
-            b.op(Q_MUL);
-            return;
-        }
-    }
-    for (size_t i = 0; i < exprs.size(); ++i) {
-        if (i) b.mulc(C_THETA);
-        b.append(exprs[i]);
-        if (i) b.op(Q_ADD);
-    }
-}
-void push_perm_col(PB& b, const std::pair<uint32_t, uint32_t>& c) { b.col(c.first, c.second, 0); }
-
 // Results of `count` items that a sharded session deals round-robin (item i to rank i % world), `elem` bytes each.  `local`
 // holds this rank's results in its own order, share_size() of them with the unused tail zeroed; they are all-gathered, and
 // `out` receives all `count` in item order -- on every rank the same, so the transcripts stay identical.
@@ -570,101 +504,6 @@ std::vector<F4> interpolate(const std::vector<std::vector<F4>>& basis, const std
     return out;
 }
 F4 eval_small(const std::vector<F4>& c, const F4& at) { F4 acc = host::fr_zero(); for (size_t t = c.size(); t-- > 0;) acc = host::fr_add(host::fr_mul(acc, at), c[t]); return acc; }
-
-}  // namespace
-
-// The constraint-system part of a key blob (everything before the column data) into `cs`: shape, phases, query lists,
-// permutation columns, constants, gate and lookup programs -- with every count checked against what the blob can hold and the
-// declared degree against what the programs need.  No device, no SRS (zk_pk_create goes on from here; zk_vk_create and the host-only hooks stop here).
-int zk::cs::parse_cs(Reader& r, ConstraintSystem* pk, size_t blob_len, bool with_columns, std::string* err) {
-    char msg[256];
-    auto fail = [&](int code, const char* fmt, auto... args) { snprintf(msg, sizeof msg, fmt, args...); *err = msg; return code; };
-    if (r.u32() != 0x4B505A4Bu) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad magic");
-    const uint32_t version = r.u32();
-    if (version != 3u && version != 4u) return fail(ZK_ERR_INVALID_ARG, "pk blob: unsupported version %u (this library reads versions 3 and 4)", version);
-    pk->version = version;
-    pk->k = r.u32(); pk->bf = r.u32(); pk->d = r.u32(); pk->F = r.u32(); pk->A = r.u32(); pk->I = r.u32(); pk->P = r.u32(); pk->L = r.u32();
-    const uint32_t ngates = r.u32(), nconsts = r.u32();
-    // halo2: cs.degree() >= 3 (the permutation argument); the extended domain has at most 2^28 rows
-    if (!r.ok || pk->k < 2 || pk->k > 27 || pk->d < 3 || pk->d > 17) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad header (k=%u, degree=%u)", pk->k, pk->d);
-    const size_t n = (size_t)1 << pk->k;
-    if (pk->bf + 2 >= n) return fail(ZK_ERR_INVALID_ARG, "pk blob: too many blinding rows");
-    // every count of the header is checked against what the blob can hold before anything is sized by it
-    if ((size_t)pk->A * 4 > r.left || (size_t)pk->P * 8 > r.left || (size_t)nconsts * 32 > r.left || (size_t)ngates * 4 > r.left || (size_t)pk->L * 8 > r.left ||
-        (with_columns && version == 3u && ((size_t)pk->F + pk->P) > r.left / (n * 32)) ||
-        (with_columns && version == 4u && ((size_t)pk->F > r.left / (n + 4) || (size_t)pk->P > (r.left - (size_t)pk->F * (n + 4)) / (n * 8))) ||      // a width word and at least one byte per fixed cell, eight per mapping pair
-        pk->A > 0xFFFFFFu || pk->F > 0xFFFFFFu || pk->I > 0xFFFFFFu)
-        return fail(ZK_ERR_INVALID_ARG, "pk blob: header counts exceed the blob (%zu bytes)", blob_len);
-    pk->u = (uint32_t)n - pk->bf - 1;
-    pk->chunk = pk->d - 2;
-    pk->C = pk->P ? (pk->P + pk->chunk - 1) / pk->chunk : 0;
-    pk->ext_k = pk->k;
-    while (((size_t)1 << pk->ext_k) < n * (pk->d - 1)) ++pk->ext_k;
-    if (pk->ext_k > 28) return fail(ZK_ERR_INVALID_ARG, "pk blob: extended domain 2^%u exceeds the two-adicity of Fr", pk->ext_k);
-    pk->adv_phase.assign(pk->A, 0);
-    {   // phases: [num_challenges][A x advice phase][num_challenges x challenge phase]
-        const uint32_t nch = r.count(4);
-        if (nch > 4096) return fail(ZK_ERR_INVALID_ARG, "pk blob: too many challenges");
-        for (uint32_t i = 0; i < pk->A && r.ok; ++i) { pk->adv_phase[i] = r.u32(); if (pk->adv_phase[i] + 1 > pk->num_phases) pk->num_phases = pk->adv_phase[i] + 1; }
-        for (uint32_t i = 0; i < nch && r.ok; ++i) { pk->chal_phase.push_back(r.u32()); if (pk->chal_phase[i] + 1 > pk->num_phases) pk->num_phases = pk->chal_phase[i] + 1; }
-        if (!r.ok || pk->num_phases > 16) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad phase table");
-    }
-    // cs.advice_queries / fixed_queries / instance_queries: (column, rotation) in registration order
-    r.queries(&pk->adv_q, CT_ADVICE, pk->A);
-    r.queries(&pk->fix_q, CT_FIXED, pk->F);
-    r.queries(&pk->inst_q, CT_INSTANCE, pk->I);
-    if (!r.ok) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad query lists");
-    for (uint32_t i = 0; i < pk->P && r.ok; ++i) { uint32_t t = r.u32(), x = r.u32(); pk->perm_cols.push_back({t, x}); }
-    for (uint32_t i = 0; i < nconsts && r.ok; ++i) { const uint8_t* b = r.bytes(32); F4 v; if (b) memcpy(v.l, b, 32); pk->consts.push_back(v); }
-    for (uint32_t i = 0; i < ngates && r.ok; ++i) pk->gates.push_back(r.prog());
-    for (uint32_t i = 0; i < pk->L && r.ok; ++i) {
-        ConstraintSystem::Lookup lk;
-        const uint32_t m = r.u32(), ninputs = r.count(4);
-        if (!r.ok || m == 0 || ninputs == 0 || (size_t)m * 4 > r.left || (size_t)m * ninputs > r.left / 4) { r.ok = false; break; }
-        for (uint32_t j = 0; j < m && r.ok; ++j) lk.tables.push_back(r.prog());
-        for (uint32_t a = 0; a < ninputs && r.ok; ++a) {
-            lk.inputs.emplace_back();
-            for (uint32_t j = 0; j < m && r.ok; ++j) lk.inputs.back().push_back(r.prog());
-        }
-        pk->lookups.push_back(std::move(lk));
-    }
-    if (!r.ok) return fail(ZK_ERR_INVALID_ARG, "pk blob: truncated or malformed constraint system");
-    // The degree the blob declares must cover what its own programs need (halo2 ConstraintSystem::degree:
-    // permutation argument 3, mv_lookup::Argument::required_degree, every gate polynomial): with a
-    // smaller one the quotient would not fit its d - 1 pieces and the proof would be rejected.
-    {
-        uint32_t need = 3;
-        std::vector<int> tmp_deg;
-        for (const Prog& g : pk->gates) {
-            const int dg = program_degree(g, &tmp_deg);
-            if (dg < 0) return fail(ZK_ERR_INVALID_ARG, "pk blob: malformed gate program");
-            need = std::max(need, (uint32_t)dg);
-        }
-        for (const auto& lk : pk->lookups) {
-            std::vector<int> none;
-            int table_degree = 0, inputs_degree = 0;
-            for (const Prog& g : lk.tables) { const int dg = program_degree(g, &none); if (dg < 0) return fail(ZK_ERR_INVALID_ARG, "pk blob: malformed lookup table program"); table_degree = std::max(table_degree, dg); }
-            for (const auto& in : lk.inputs) {
-                int one = 0;
-                for (const Prog& g : in) { const int dg = program_degree(g, &none); if (dg < 0) return fail(ZK_ERR_INVALID_ARG, "pk blob: malformed lookup input program"); one = std::max(one, dg); }
-                inputs_degree += one;
-            }
-            need = std::max(need, std::max((uint32_t)(3 + lk.inputs.size()), (uint32_t)(table_degree + inputs_degree + 2)));
-        }
-        if (pk->d < need) return fail(ZK_ERR_INVALID_ARG, "pk blob: declared degree %u is below the %u its gates and lookup arguments require", pk->d, need);
-    }
-    for (const auto& pc : pk->perm_cols) {          // halo2: enable_equality queries the column at Rotation::cur()
-        if (pc.first > CT_INSTANCE) return fail(ZK_ERR_INVALID_ARG, "pk blob: bad permutation column type %u", pc.first);
-        if (pc.first == CT_INSTANCE) continue;
-        const std::vector<Query>& qs = pc.first == CT_ADVICE ? pk->adv_q : pk->fix_q;
-        bool seen = false;
-        for (const Query& q : qs) if (q.idx == pc.second && q.rot == 0) { seen = true; break; }
-        if (!seen) return fail(ZK_ERR_INVALID_ARG, "pk blob: permutation column (%u, %u) is not queried at rotation 0", pc.first, pc.second);
-    }
-    return ZK_OK;
-}
-
-namespace {
 
 // The column data of a version 4 key blob: F cell widths, the F fixed payloads (1-16-byte unsigned integers or
 // Montgomery elements), the permutation mapping.  Sixteen columns at a time cross the link on the copy stream into one staging
@@ -1417,667 +1256,33 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
     return ZK_OK;
 }
 
-// The quotient's constraints in halo2's order: gates, permutation, lookups (folded with y by the caller).  A pure function of
-// the key: challenges enter as constant indices, so the programs -- and with them which column is read on which coset -- are
-// known before any witness exists (the advice phase uses that to transform columns ahead of time, advice_coset_plan).
-static void build_constraints(const zk_pk* pk, std::vector<Prog>& cons, bool& gates_share_tmps_out) {
-    PB q;
-    auto end_c = [&] { cons.push_back(std::move(q.g)); q.g.clear(); };
-    for (const Prog& g : pk->gates) cons.push_back(g);
-    const int32_t rot_last = -(int32_t)(pk->bf + 1);
-    if (pk->C) {
-        q.col(CT_SPECIAL, SP_L0).cst(C_ONE).col(CT_PERM_Z, 0).op(Q_SUB).op(Q_MUL); end_c();                                   // l0 (1 - Z_0)
-        q.col(CT_SPECIAL, SP_LLAST).col(CT_PERM_Z, pk->C - 1).op(Q_SQUARE).col(CT_PERM_Z, pk->C - 1).op(Q_SUB).op(Q_MUL); end_c();   // l_last (Z^2 - Z)
-        for (uint32_t c = 1; c < pk->C; ++c) {
-            q.col(CT_SPECIAL, SP_L0).col(CT_PERM_Z, c).col(CT_PERM_Z, c - 1, rot_last).op(Q_SUB).op(Q_MUL);          // l0 (Z_c - Z_{c-1}(w^last X))
-            end_c();
-        }
-        for (uint32_t c = 0; c < pk->C; ++c) {
-            const uint32_t j0 = c * pk->chunk, j1 = std::min(pk->P, j0 + pk->chunk);
-            q.col(CT_SPECIAL, SP_LACTIVE);
-            q.col(CT_PERM_Z, c, 1);
-            for (uint32_t j = j0; j < j1; ++j) { push_perm_col(q, pk->perm_cols[j]); q.col(CT_SIGMA, j).mulc(C_BETA).op(Q_ADD).addc(C_GAMMA).op(Q_MUL); }
-            q.col(CT_PERM_Z, c, 0);
-            for (uint32_t j = j0; j < j1; ++j) { push_perm_col(q, pk->perm_cols[j]); q.col(CT_SPECIAL, SP_X).mulc(C_DELTA0 + j).op(Q_ADD).addc(C_GAMMA).op(Q_MUL); }
-            q.op(Q_SUB).op(Q_MUL); end_c();
-        }
-    }
-    // lookup identities (plonk::evaluation, mv-lookup): with phi_a = f_a + beta and tau = t + beta,
-    //   l_active * ( tau * prod_a phi_a * (phi(wX) - phi(X))  -  prod_a phi_a * (tau * sum_a 1/phi_a - m) )
-    // An argument with several input tuples parks tau and the phi_a of a row in intermediates (slots
-    // above the ones the gate programs use) and forms sum_a prod_{b != a} phi_b from them.
-    uint32_t tmp_base = 0;
-    for (const Prog& g : pk->gates) for (const Instr& in : g) if (in.op == Q_TEE_TMP || in.op == Q_PUSH_TMP) tmp_base = std::max(tmp_base, in.a + 1);
-    const bool gates_share_tmps = tmp_base != 0;
-    // Single-tuple lookups share the table side: tau = t + beta of a table is parked by the first lookup into it and read back by the
-    // others (slots above the ones the multi-tuple form reuses; defined once each, so degree classes re-materialise them, TmpSplit).
-    uint32_t max_tuples = 0;
-    for (uint32_t l = 0; l < pk->L; ++l) if (pk->lookups[l].inputs.size() > 1) max_tuples = std::max<uint32_t>(max_tuples, (uint32_t)pk->lookups[l].inputs.size());
-    const uint32_t table_slot0 = tmp_base + (max_tuples ? max_tuples + 2 : 0);
-    std::vector<const std::vector<Prog>*> parked_tables;               // table of slot table_slot0 + i
-    static const bool lk_plain = getenv("ZK_LOOKUP_PLAIN") && atoi(getenv("ZK_LOOKUP_PLAIN")) == 1;      // measurement knob: the identity as halo2 writes it
-    auto same_tables = [](const std::vector<Prog>& x, const std::vector<Prog>& y) {
-        if (x.size() != y.size()) return false;
-        for (size_t i = 0; i < x.size(); ++i) {
-            if (x[i].size() != y[i].size()) return false;
-            for (size_t j = 0; j < x[i].size(); ++j) if (x[i][j].op != y[i][j].op || x[i][j].a != y[i][j].a || x[i][j].b != y[i][j].b) return false;
-        }
-        return true;
-    };
-    for (uint32_t l = 0; l < pk->L; ++l) {
-        const auto& lk = pk->lookups[l];
-        const uint32_t N = (uint32_t)lk.inputs.size();
-        q.col(CT_SPECIAL, SP_L0).col(CT_LK_PHI, l).op(Q_MUL); end_c();
-        q.col(CT_SPECIAL, SP_LLAST).col(CT_LK_PHI, l).op(Q_MUL); end_c();
-        q.col(CT_SPECIAL, SP_LACTIVE);
-        if (N == 1 && lk_plain) {
-            // (phi(wX) - phi(X)) (f+beta)(t+beta) - ((t+beta) - m (f+beta))
-            q.col(CT_LK_PHI, l, 1).col(CT_LK_PHI, l, 0).op(Q_SUB);
-            push_compressed(q, lk.inputs[0]); q.addc(C_BETA).op(Q_MUL);
-            push_compressed(q, lk.tables); q.addc(C_BETA).op(Q_MUL);
-            push_compressed(q, lk.tables); q.addc(C_BETA);
-            q.col(CT_LK_M, l); push_compressed(q, lk.inputs[0]); q.addc(C_BETA).op(Q_MUL);
-            q.op(Q_SUB).op(Q_SUB).op(Q_MUL); end_c();
-            continue;
-        }
-        if (N == 1) {
-            // the same polynomial with phi_f = f + beta and tau = t + beta each computed once:
-            //   (phi(wX) - phi(X)) phi_f tau - (tau - m phi_f)  =  phi_f ((phi(wX) - phi(X)) tau + m) - tau
-            // four products instead of twelve on a two-column tuple under one selector (push_compressed takes the selector out)
-            size_t ti = 0;
-            while (ti < parked_tables.size() && !same_tables(*parked_tables[ti], lk.tables)) ++ti;
-            const bool first_use = ti == parked_tables.size();
-            if (first_use) parked_tables.push_back(&lk.tables);
-            const uint32_t slot = table_slot0 + (uint32_t)ti;
-            q.col(CT_LK_PHI, l, 1).col(CT_LK_PHI, l, 0).op(Q_SUB);
-            if (first_use) { push_compressed(q, lk.tables); q.addc(C_BETA); q.g.push_back({Q_TEE_TMP, slot, 0}); }
-            else q.g.push_back({Q_PUSH_TMP, slot, 0});
-            q.op(Q_MUL);
-            q.col(CT_LK_M, l).op(Q_ADD);
-            push_compressed(q, lk.inputs[0]); q.addc(C_BETA).op(Q_MUL);
-            q.g.push_back({Q_PUSH_TMP, slot, 0});
-            q.op(Q_SUB).op(Q_MUL); end_c();
-            continue;
-        }
-        const uint32_t t_tau = tmp_base, t_phi = tmp_base + 1;          // reused by every multi-input lookup: a row's values are consumed right away
-        auto tmp = [&](uint32_t op, uint32_t slot) { q.g.push_back({op, slot, 0}); };
-        // prod = phi_0 * ... * phi_{N-1}, each factor parked on the way
-        for (uint32_t a = 0; a < N; ++a) {
-            push_compressed(q, lk.inputs[a]); q.addc(C_BETA);
-            tmp(Q_TEE_TMP, t_phi + a);
-            if (a) q.op(Q_MUL);
-        }
-        tmp(Q_TEE_TMP, t_phi + N);                                       // prod
-        // lhs = tau * prod * (phi(wX) - phi(X))
-        push_compressed(q, lk.tables); q.addc(C_BETA);
-        tmp(Q_TEE_TMP, t_tau);
-        q.op(Q_MUL);
-        q.col(CT_LK_PHI, l, 1).col(CT_LK_PHI, l, 0).op(Q_SUB).op(Q_MUL);
-        // rhs = tau * sum_a prod_{b != a} phi_b - prod * m
-        for (uint32_t a = 0; a < N; ++a) {
-            bool first = true;
-            for (uint32_t b2 = 0; b2 < N; ++b2) {
-                if (b2 == a) continue;
-                tmp(Q_PUSH_TMP, t_phi + b2);
-                if (!first) q.op(Q_MUL);
-                first = false;
-            }
-            if (a) q.op(Q_ADD);
-        }
-        tmp(Q_PUSH_TMP, t_tau); q.op(Q_MUL);
-        tmp(Q_PUSH_TMP, t_phi + N); q.col(CT_LK_M, l).op(Q_MUL);
-        q.op(Q_SUB);
-        q.op(Q_SUB).op(Q_MUL); end_c();
-    }
-    gates_share_tmps_out = gates_share_tmps;
-}
-// e = ceil(log2(degree - 1)) of every constraint (its degree class, see zk_proof_finish), or E for all when classes are off
-static int classify_constraints(std::string* err, const zk_pk* pk, const std::vector<Prog>& cons, bool split, uint32_t E, std::vector<uint32_t>& cls) {
-    cls.assign(cons.size(), E);
-    std::vector<int> tmp_deg;
-    char msg[160];
-    for (uint32_t i = 0; i < cons.size(); ++i) {
-        const int dg = program_degree(cons[i], &tmp_deg);
-        if (dg < 0) { snprintf(msg, sizeof msg, "prover: malformed constraint program %u", i); *err = msg; return ZK_ERR_INVALID_ARG; }
-        if ((uint32_t)dg > pk->d) { snprintf(msg, sizeof msg, "prover: constraint %u has degree %d above the circuit degree %u", i, dg, pk->d); *err = msg; return ZK_ERR_INVALID_ARG; }
-        uint32_t e = 0;
-        while (e < E && ((uint32_t)1 << e) < (uint32_t)std::max(dg - 1, 1)) ++e;
-        cls[i] = split ? e : E;
-    }
-    return ZK_OK;
-}
-// Additive split of a constraint over degree classes.  h is linear in the constraints, so a constraint that is a SUM of terms of
-// different degrees -- q (a b - c): the product is of degree 3, q c of degree 2 -- may put each term into the class of ITS degree,
-// all with the constraint's own power of y: the term q c is then evaluated on one coset instead of two, and a column that occurs
-// only in such low-degree terms (the outputs of multiplication gates, every linearly constrained cell) is transformed to fewer
-// cosets.  Recognised shapes (the program's top): SUM, F * SUM and SUM * F with SUM a tree of + / - / negations; the factor F (a
-// selector, as a rule) multiplies every group.  The groups sum to the constraint, but only the constraint vanishes on H: what a group
-// that moves to a lower class is on H travels with it as a remainder polynomial (zk_proof_finish, CT_SPLIT_R), so that every class
-// still divides by X^n - 1 exactly.  Exact field arithmetic: h and every proof byte stay what they were.  Programs that park or
-// read shared intermediates are left whole.  ZK_QUOTIENT_ADDSPLIT=0 turns it off.
-struct ClassPiece { uint32_t cons, cls; Prog prog; };
-static int TmpSplitArity(uint32_t op) {
-    switch (op) {
-        case Q_PUSH_COL: case Q_PUSH_CONST: case Q_PUSH_TMP: return 0;
-        case Q_ADD: case Q_SUB: case Q_MUL: return 2;
-        default: return 1;                        // NEG, DOUBLE, SQUARE, ADD_CONST, MUL_CONST, TEE_TMP
-    }
-}
-static uint32_t class_of_degree(int dg, uint32_t E) {
-    uint32_t e = 0;
-    while (e < E && ((uint32_t)1 << e) < (uint32_t)std::max(dg - 1, 1)) ++e;
-    return e;
-}
-static bool additive_split(const Prog& g, uint32_t E, uint32_t whole_cls, std::vector<std::pair<uint32_t, Prog>>& out) {
-    struct Node { Instr in; int l, r; };
-    std::vector<Node> nd;
-    std::vector<int> st;
-    for (const Instr& in : g) {
-        if (in.op == Q_TEE_TMP || in.op == Q_PUSH_TMP || in.op == Q_FOLD || in.op == Q_END) return false;
-        const int ar = TmpSplitArity(in.op);
-        Node n_{in, -1, -1};
-        if (ar == 2) { if (st.size() < 2) return false; n_.r = st.back(); st.pop_back(); n_.l = st.back(); st.pop_back(); }
-        else if (ar == 1) { if (st.empty()) return false; n_.l = st.back(); st.pop_back(); }
-        nd.push_back(n_);
-        st.push_back((int)nd.size() - 1);
-    }
-    if (st.size() != 1) return false;
-    const int root = st[0];
-    std::function<void(int, Prog&)> emit = [&](int v, Prog& o) {
-        if (nd[v].l >= 0) emit(nd[v].l, o);
-        if (nd[v].r >= 0) emit(nd[v].r, o);
-        o.push_back(nd[v].in);
-    };
-    auto is_sum = [&](int v) { return nd[v].in.op == Q_ADD || nd[v].in.op == Q_SUB || nd[v].in.op == Q_NEG; };
-    int factor = -1, sum = root;
-    if (nd[root].in.op == Q_MUL) {
-        if (is_sum(nd[root].r)) { factor = nd[root].l; sum = nd[root].r; }
-        else if (is_sum(nd[root].l)) { factor = nd[root].r; sum = nd[root].l; }
-        else return false;
-    } else if (!is_sum(root)) return false;
-    std::vector<std::pair<int, bool>> terms;            // (node, negative)
-    std::function<void(int, bool)> collect = [&](int v, bool neg_) {
-        const uint32_t op = nd[v].in.op;
-        if (op == Q_ADD) { collect(nd[v].l, neg_); collect(nd[v].r, neg_); }
-        else if (op == Q_SUB) { collect(nd[v].l, neg_); collect(nd[v].r, !neg_); }
-        else if (op == Q_NEG) collect(nd[v].l, !neg_);
-        else terms.push_back({v, neg_});
-    };
-    collect(sum, false);
-    if (terms.size() < 2 || terms.size() > 4096) return false;
-    std::vector<int> no_tmps;
-    Prog fprog;
-    int fdeg = 0;
-    if (factor >= 0) { emit(factor, fprog); fdeg = program_degree(fprog, &no_tmps); if (fdeg < 0) return false; }
-    std::vector<Prog> tprog(terms.size());
-    std::vector<uint32_t> tcls(terms.size());
-    for (size_t t = 0; t < terms.size(); ++t) {
-        emit(terms[t].first, tprog[t]);
-        const int tdeg = program_degree(tprog[t], &no_tmps);
-        if (tdeg < 0) return false;
-        tcls[t] = class_of_degree(fdeg + tdeg, E);
-    }
-    std::vector<Prog> group(E + 1);
-    std::vector<uint8_t> started(E + 1, 0);
-    for (uint32_t e = 0; e <= E; ++e) {
-        int lead = -1;                                   // a positive term first (no negation to spend), else the first term negated
-        for (size_t t = 0; t < terms.size() && lead < 0; ++t) if (tcls[t] == e && !terms[t].second) lead = (int)t;
-        for (size_t t = 0; t < terms.size() && lead < 0; ++t) if (tcls[t] == e) lead = (int)t;
-        if (lead < 0) continue;
-        started[e] = 1;
-        group[e] = tprog[lead];
-        if (terms[lead].second) group[e].push_back({Q_NEG, 0, 0});
-        for (size_t t = 0; t < terms.size(); ++t) {
-            if (tcls[t] != e || (int)t == lead) continue;
-            group[e].insert(group[e].end(), tprog[t].begin(), tprog[t].end());
-            group[e].push_back({terms[t].second ? Q_SUB : Q_ADD, 0, 0});
-        }
-    }
-    uint32_t used = 0;
-    for (uint32_t e = 0; e <= E; ++e) used += started[e] != 0;
-    if (used < 2) return false;
-    (void)whole_cls;
-    for (uint32_t e = 0; e <= E; ++e) {
-        if (!started[e]) continue;
-        Prog pg = fprog;
-        pg.insert(pg.end(), group[e].begin(), group[e].end());
-        if (factor >= 0) pg.push_back({Q_MUL, 0, 0});
-        out.push_back({e, std::move(pg)});
-    }
-    return true;
-}
-// the pieces the classes evaluate, in constraint order (a constraint's pieces by ascending class)
-static bool quotient_addsplit_enabled() {
-    const char* env = getenv("ZK_QUOTIENT_ADDSPLIT");
-    return !(env && atoi(env) == 0);
-}
-static void class_pieces(const std::vector<Prog>& cons, const std::vector<uint32_t>& cls, bool split, bool addsplit, uint32_t E, std::vector<ClassPiece>& out) {
-    const bool on = split && addsplit;
-    for (uint32_t i = 0; i < cons.size(); ++i) {
-        std::vector<std::pair<uint32_t, Prog>> parts;
-        if (on && cls[i] > 0 && additive_split(cons[i], E, cls[i], parts)) {
-            for (auto& pt : parts) out.push_back({i, pt.first, std::move(pt.second)});
-        } else out.push_back({i, cls[i], cons[i]});
-    }
-}
-// A class program as ONE weighted sum (round 5).  The class's accumulator used to fold its terms one by one, acc = acc * y^gap + term:
-// a product per term, and every term carried its selector -- q (a b), q' c, l_active (...) -- as a product of its own.  The sum
-//      sum_i y^(K-1-i) t_i      (t_i = the terms of this class, i = the constraint a term belongs to)
-// is the same polynomial when the terms that share a single-column factor F are collected first:
-//      sum_F F * (sum_{i in F} y^(K-1-i) r_i) + sum_{others} y^(K-1-i) t_i,        t_i = F r_i
-// -- one product by F per group instead of one per term, and no product for the folding.  Exact field arithmetic: h and every proof
-// byte are unchanged (tests/test_quotient_classes.py evaluates both forms; the GPU proof tests compare bytes with the oracle prover).
-// A term may use parked intermediates: it joins a group only if everything it reads was parked before the group's first term, and a
-// term that parks something only ever opens a group, so definitions stay ahead of their readers when later terms move up.
-// ZK_QUOTIENT_GROUP=0 keeps the folded form.
-struct ClassTerm { uint32_t cons; Prog prog; };
-static bool assemble_grouped(const std::vector<ClassTerm>& terms, uint32_t K, Prog& out) {
-    if (terms.empty() || K >= 0xFFFFu) return false;
-    struct Info { bool has_factor[2] = {false, false}; Instr factor[2]; Prog rest[2]; std::vector<uint32_t> reads, defs; int pick = -1; };
-    std::vector<Info> info(terms.size());
-    auto key = [](const Instr& f) { return ((uint64_t)f.a << 32) | f.b; };
-    std::unordered_map<uint64_t, uint32_t> count;
-    for (size_t t = 0; t < terms.size(); ++t) {
-        const Prog& g = terms[t].prog;
-        for (const Instr& in : g) {
-            if (in.op == Q_PUSH_TMP) info[t].reads.push_back(in.a);
-            else if (in.op == Q_TEE_TMP) info[t].defs.push_back(in.a);
-            else if (in.op == Q_FOLD || in.op == Q_END) return false;
-        }
-        for (int first = 0; first < 2; ++first) {
-            info[t].has_factor[first] = split_leaf_factor(g, first != 0, &info[t].rest[first], &info[t].factor[first]);
-            if (info[t].has_factor[first] && !(first == 1 && info[t].has_factor[0] && key(info[t].factor[0]) == key(info[t].factor[1]))) ++count[key(info[t].factor[first])];
-        }
-    }
-    for (size_t t = 0; t < terms.size(); ++t) {
-        uint32_t best = 1;          // a factor no other term shares is left where it is
-        for (int first = 1; first >= 0; --first)
-            if (info[t].has_factor[first] && count[key(info[t].factor[first])] > best) { best = count[key(info[t].factor[first])]; info[t].pick = first; }
-    }
-    // groups in the order of their first terms
-    struct Group { std::vector<uint32_t> members; bool factored; std::vector<uint32_t> known; };       // known: what was parked before (and by) the first term
-    std::vector<Group> groups;
-    std::unordered_map<uint64_t, uint32_t> open;
-    std::vector<uint32_t> parked;                      // slots parked by the terms seen so far (original order)
-    std::unordered_map<uint32_t, uint32_t> ndefs;      // a slot that is parked more than once (reused) is only read where it stands
-    for (const Info& ti : info) for (uint32_t d : ti.defs) ++ndefs[d];
-    auto stable = [&](const std::vector<uint32_t>& reads) { for (uint32_t v : reads) { auto it = ndefs.find(v); if (it == ndefs.end() || it->second != 1) return false; } return true; };
-    auto subset = [](const std::vector<uint32_t>& x, const std::vector<uint32_t>& of) { for (uint32_t v : x) if (std::find(of.begin(), of.end(), v) == of.end()) return false; return true; };
-    for (size_t t = 0; t < terms.size(); ++t) {
-        const Info& ti = info[t];
-        bool joined = false;
-        if (ti.pick >= 0 && ti.defs.empty() && stable(ti.reads)) {
-            auto it = open.find(key(ti.factor[ti.pick]));
-            if (it != open.end() && subset(ti.reads, groups[it->second].known)) { groups[it->second].members.push_back((uint32_t)t); joined = true; }
-        }
-        if (!joined) {
-            Group gnew;
-            gnew.members.push_back((uint32_t)t);
-            gnew.factored = ti.pick >= 0;
-            gnew.known = parked;
-            // what the first term parks inside its OWN co-factor is computed before any other member's co-factor is
-            if (ti.pick >= 0) for (const Instr& in : ti.rest[ti.pick]) if (in.op == Q_TEE_TMP) gnew.known.push_back(in.a);
-            groups.push_back(std::move(gnew));
-            if (ti.pick >= 0) open[key(ti.factor[ti.pick])] = (uint32_t)groups.size() - 1;
-        }
-        for (uint32_t d : ti.defs) parked.push_back(d);
-    }
-    out.clear();
-    auto weight = [&](uint32_t cons) { if (K - 1 - cons) out.push_back({Q_MUL_CONST, C_YPOW0 + (K - 1 - cons), 0}); };
-    bool first_item = true;
-    for (const Group& gr : groups) {
-        if (gr.factored && gr.members.size() >= 2) {
-            const Info& lead = info[gr.members[0]];
-            for (size_t j = 0; j < gr.members.size(); ++j) {
-                const uint32_t t = gr.members[j];
-                const Prog& r = info[t].rest[info[t].pick];
-                out.insert(out.end(), r.begin(), r.end());
-                weight(terms[t].cons);
-                if (j) out.push_back({Q_ADD, 0, 0});
-            }
-            out.push_back(lead.factor[lead.pick]);
-            out.push_back({Q_MUL, 0, 0});
-        } else {
-            for (size_t j = 0; j < gr.members.size(); ++j) {          // a lone term (a group nobody joined)
-                const uint32_t t = gr.members[j];
-                out.insert(out.end(), terms[t].prog.begin(), terms[t].prog.end());
-                weight(terms[t].cons);
-                if (j) out.push_back({Q_ADD, 0, 0});
-            }
-        }
-        if (!first_item) out.push_back({Q_ADD, 0, 0});
-        first_item = false;
-    }
-    out.push_back({Q_FOLD, C_ONE, 0});                  // acc = 0 * 1 + the sum
-    // depth of the caller's stack machine (Q_MAX_STACK in quotient.hip is 16): beyond it the folded form is kept
-    int sp = 0, mx = 0;
-    for (const Instr& in : out) {
-        if (in.op == Q_PUSH_COL || in.op == Q_PUSH_CONST || in.op == Q_PUSH_TMP) ++sp;
-        else if (in.op == Q_ADD || in.op == Q_SUB || in.op == Q_MUL || in.op == Q_FOLD) --sp;
-        mx = std::max(mx, sp);
-    }
-    return sp == 0 && mx <= 14;
-}
-static bool quotient_group_enabled() {
-    const char* env = getenv("ZK_QUOTIENT_GROUP");
-    return !(env && atoi(env) == 0);
-}
-#include "class_compile.hpp"
-static bool quotient_dag_enabled() {
-    const char* env = getenv("ZK_QUOTIENT_DAG");
-    return !(env && atoi(env) == 0);
-}
-// Intermediates shared between constraints (TEE_TMP in one gate, PUSH_TMP in a later one: the common-subexpression
-// elimination of halo2's GraphEvaluator as it survives the export) and degree classes: a class evaluates only ITS constraints,
-// so a class that reads an intermediate another class parked must compute it itself.  `TmpSplit` re-materialises: walking the
-// constraints in order, a PUSH_TMP whose definition this class has not emitted yet is replaced by the defining sub-expression
-// (its own PUSH_TMPs resolved the same way) followed by the TEE_TMP; afterwards the class reads the slot like any other.
-// Classes run as separate launches over the same parking area, each defining what it reads before reading it.
-// Not handled (ok() == false, the caller evaluates everything as one class, as before): a slot that is defined more than once
-// AND read by a constraint other than the one that defined it (slot reuse with cross-constraint lifetime).
-struct TmpSplit {
-    std::vector<Prog> defs;                       // slot -> defining sub-expression (postfix, without the TEE)
-    std::vector<uint32_t> ver;                    // slot -> number of definitions seen so far
-    std::vector<std::vector<uint32_t>> have;      // class -> slot -> version this class has emitted (0 = none)
-    bool conflict = false;
-    static int arity(uint32_t op) {
-        switch (op) {
-            case Q_PUSH_COL: case Q_PUSH_CONST: case Q_PUSH_TMP: return 0;
-            case Q_ADD: case Q_SUB: case Q_MUL: return 2;
-            default: return 1;                    // NEG, DOUBLE, SQUARE, ADD_CONST, MUL_CONST, TEE_TMP (peeks: one in, one out)
-        }
-    }
-    // the sub-expression whose value is on top of the stack after instruction t - 1 of g
-    static Prog sub_expression(const Prog& g, size_t t) {
-        int need = 1;
-        size_t start = t;
-        while (start > 0 && need > 0) { --start; need += arity(g[start].op) - 1; }
-        return Prog(g.begin() + start, g.begin() + t);
-    }
-    explicit TmpSplit(size_t classes) : have(classes) {}
-    void grow(uint32_t s) {
-        if (s >= ver.size()) { ver.resize(s + 1, 0); defs.resize(s + 1); }
-        for (auto& h : have) if (s >= h.size()) h.resize(s + 1, 0);
-    }
-    void emit_push(uint32_t s, uint32_t e, Prog& out, int depth = 0) {
-        grow(s);
-        if (have[e][s] == ver[s] && ver[s]) { out.push_back({Q_PUSH_TMP, s, 0}); return; }
-        if (!ver[s] || depth > 64) { conflict = true; out.push_back({Q_PUSH_TMP, s, 0}); return; }     // read before any definition: malformed
-        for (const Instr& in : defs[s]) {
-            if (in.op == Q_PUSH_TMP) emit_push(in.a, e, out, depth + 1);
-            else {
-                if (in.op == Q_TEE_TMP) { grow(in.a); have[e][in.a] = ver[in.a]; }
-                out.push_back(in);
-            }
-        }
-        out.push_back({Q_TEE_TMP, s, 0});
-        have[e][s] = ver[s];
-    }
-    // appends constraint g (class e) to out with its intermediates resolved for that class
-    void append(const Prog& g, uint32_t e, Prog& out) {
-        for (size_t t = 0; t < g.size(); ++t) {
-            const Instr& in = g[t];
-            if (in.op == Q_TEE_TMP) {
-                grow(in.a);
-                defs[in.a] = sub_expression(g, t);
-                ++ver[in.a];
-                have[e][in.a] = ver[in.a];
-                out.push_back(in);
-            } else if (in.op == Q_PUSH_TMP) emit_push(in.a, e, out);
-            else out.push_back(in);
-        }
-    }
-};
-// slot reuse with cross-constraint lifetime (see TmpSplit): such keys keep the single-class evaluation
-static bool tmp_slots_conflict(const std::vector<Prog>& cons) {
-    std::vector<uint32_t> ndef, def_at;
-    std::vector<uint8_t> cross;
-    auto grow = [&](uint32_t s) { if (s >= ndef.size()) { ndef.resize(s + 1, 0); def_at.resize(s + 1, 0); cross.resize(s + 1, 0); } };
-    for (uint32_t i = 0; i < cons.size(); ++i)
-        for (const Instr& in : cons[i]) {
-            if (in.op == Q_TEE_TMP) { grow(in.a); ++ndef[in.a]; def_at[in.a] = i; }
-            else if (in.op == Q_PUSH_TMP) { grow(in.a); if (!ndef[in.a]) return true; if (def_at[in.a] != i) cross[in.a] = 1; }
-        }
-    for (size_t s_ = 0; s_ < ndef.size(); ++s_) if (ndef[s_] > 1 && cross[s_]) return true;
-    return false;
-}
-static bool quotient_split_enabled(bool sharded, bool gates_share_tmps) {
-    const char* split_env = getenv("ZK_QUOTIENT_SPLIT");
-    (void)gates_share_tmps;                   // shared intermediates are re-materialised per class (TmpSplit); slot-reuse conflicts are checked by the caller
-    (void)sharded;                            // sharded sessions distribute (class, coset) pairs over the ranks (zk_proof_finish)
-    return !(split_env && atoi(split_env) == 0);
-}
-// ---- the quotient's plan: which constraint (or part of one) is evaluated in which degree class, and each class's program --------
-// A pure function of the key and of the measurement knobs, so it is made once per key (zk_pk::qplan) and shared by the advice
-// phases (which cosets read which column) and zk_proof_finish.  Candidates: degree classes with the additive split, degree
-// classes alone, one class -- the cheapest by a count of what each would execute (below) is taken; ZK_QUOTIENT_COSTGATE=0 takes
-// the most split one the knobs allow, as rounds 3-5 did.
-struct QPlanClass { Prog prog; std::vector<uint32_t> refs; uint32_t last = 0; bool used = false; uint32_t products = 0, parked = 0, max_live = 0, groups = 0, fused = 0, mac2 = 0, mac_stk = 0, declined = 0, reductions = 0; };
-struct QPlanRem { uint32_t t = 0, e = 0; Prog prog; uint32_t last = 0; bool used = false; uint32_t products = 0; };
-struct QuotientPlan {
-    std::string key;                 // the knob values the plan was made under
-    uint32_t K = 0, E = 0;
-    bool split = false, addsplit = false, dag = false;
-    std::vector<QPlanClass> cls;     // E + 1 classes
-    std::vector<QPlanRem> rems;      // remainder polynomials of the additive split: evaluated per proof over the Lagrange forms
-    std::vector<uint32_t> refs;      // every column any class reads
-    double cost = 0;                 // the estimate the candidates were compared by (units: one product over n rows)
-};
-static uint32_t count_products(const Prog& g) {
-    uint32_t c = 0;
-    for (const Instr& in : g) c += in.op == Q_MUL || in.op == Q_SQUARE || in.op == Q_MUL_CONST || in.op == Q_FOLD;
-    return c;
-}
-// Horner steps of a class program that the evaluator runs as one fused multiply-accumulate (K_MAC_COL of csrc/quotient.hip: two products, one
-// reduction) when ZK_QUOTIENT_MAC is on: the program lowered as zk_quotient_eval lowers it, constants numbered densely first
-// fuse = 3: K_MAC_COL alone (out4 unused); fuse = 7: out4 = { MAC2_COL, MAC_STK, MAC2_COL fusions declined for stack depth, MAC_COL } of that stream
-static uint32_t count_fused(const Prog& g, int fuse = 3, uint32_t* out4 = nullptr) {
-    std::vector<uint32_t> w;
-    w.reserve(3 * g.size() + 3);
-    std::unordered_map<uint32_t, uint32_t> cix;
-    for (const Instr& in : g) {
-        const bool c = in.op == Q_PUSH_CONST || in.op == Q_MUL_CONST || in.op == Q_ADD_CONST || in.op == Q_FOLD;
-        w.push_back(in.op); w.push_back(c ? cix.emplace(in.a, (uint32_t)cix.size()).first->second : in.a); w.push_back(in.b);
-    }
-    uint32_t n = 0;
-    int depth = 0;
-    uint32_t decl = 0;
-    if (zk_host_quotient_lower2(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, nullptr, 0, &n, &depth, &decl)) return 0;
-    std::vector<uint32_t> out(3 * (size_t)n);
-    if (zk_host_quotient_lower2(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, out.data(), out.size(), &n, &depth, &decl)) return 0;
-    uint32_t f = 0, f2 = 0, fs = 0;
-    for (uint32_t i = 0; i < n; ++i) { const uint32_t o = out[3 * i] & 0xffu; f += o == 22u; f2 += o == 24u; fs += o == 25u; }
-    if (out4) { out4[0] = f2; out4[1] = fs; out4[2] = decl; out4[3] = f; }
-    return f;
-}
-static int quotient_mac_level() { const char* e = getenv("ZK_QUOTIENT_MAC"); return e ? atoi(e) : 2; }      // 0: no fused steps, 1: K_MAC_COL alone, otherwise all (csrc/quotient.hip)
-static bool quotient_mac_enabled() { return quotient_mac_level() != 0; }
-static int make_quotient_plan(const zk_pk* pk, bool split_req, bool addsplit_req, QuotientPlan& qp, std::string* err) {
-    std::vector<Prog> cons;
-    bool gates_share_tmps = false;
-    build_constraints(pk, cons, gates_share_tmps);
-    const uint32_t E = pk->ext_k - pk->k, K = (uint32_t)cons.size();
-    const bool conflict = tmp_slots_conflict(cons);
-    const bool split = split_req && !conflict;
-    qp.K = K; qp.E = E; qp.split = split; qp.addsplit = split && addsplit_req; qp.dag = quotient_dag_enabled();
-    qp.cls.assign(E + 1, QPlanClass());
-    qp.rems.clear();
-    qp.refs.clear();
-    std::vector<uint32_t> cls;
-    PK_TRY(classify_constraints(err, pk, cons, split, E, cls));
-    TmpSplit tmps(E + 1);
-    std::vector<ClassPiece> cpieces;
-    class_pieces(cons, cls, split, qp.addsplit, E, cpieces);
-    // A constraint vanishes on H; a PART of it does not, and only multiples of X^n - 1 may be divided class by class.  So the
-    // parts that leave their constraint's class t for a lower class e take their values on H along: R_(t,e) = the polynomial of
-    // degree < n that agrees on H with the y-weighted sum of those parts (evaluated over the Lagrange forms, one pass, one
-    // inverse transform).  Class e evaluates (its parts - R), class t (its parts + R): both vanish on H again, the total is
-    // unchanged.  R is read like a column (CT_SPLIT_R) on the cosets of the two classes.
-    std::vector<std::vector<ClassTerm>> cterms(E + 1);       // the terms of every class in constraint order: (constraint, program)
-    {
-        std::vector<uint32_t> top(K, 0);
-        for (const ClassPiece& pc : cpieces) top[pc.cons] = std::max(top[pc.cons], pc.cls);
-        for (const ClassPiece& pc : cpieces) {
-            const uint32_t i = pc.cons;
-            cterms[pc.cls].emplace_back();
-            cterms[pc.cls].back().cons = i;
-            tmps.append(pc.prog, pc.cls, cterms[pc.cls].back().prog);                   // the constraint (or its terms of this class), shared intermediates resolved for this class
-            if (pc.cls < top[i]) {
-                size_t at = 0;
-                while (at < qp.rems.size() && !(qp.rems[at].t == top[i] && qp.rems[at].e == pc.cls)) ++at;
-                if (at == qp.rems.size()) { qp.rems.emplace_back(); qp.rems.back().t = top[i]; qp.rems.back().e = pc.cls; }
-                QPlanRem& rm = qp.rems[at];
-                rm.prog.insert(rm.prog.end(), pc.prog.begin(), pc.prog.end());
-                rm.prog.push_back({Q_FOLD, rm.used ? C_YPOW0 + (i - rm.last) : C_Y, 0});
-                rm.last = i;
-                rm.used = true;
-            }
-        }
-    }
-    if (tmps.conflict) { *err = "prover: a constraint reads an intermediate before any constraint parked it"; return ZK_ERR_INVALID_ARG; }
-    for (size_t j = 0; j < qp.rems.size(); ++j) {
-        // both classes take R in as one more term at the very end of the constraint list (weight y^0)
-        const uint32_t ref = colref(CT_SPLIT_R, (uint32_t)j);
-        cterms[qp.rems[j].e].push_back({K - 1, Prog{{Q_PUSH_COL, ref, 0}, {Q_NEG, 0, 0}}});
-        cterms[qp.rems[j].t].push_back({K - 1, Prog{{Q_PUSH_COL, ref, 0}}});
-        qp.rems[j].products = count_products(qp.rems[j].prog);
-    }
-    // the class programs: compiled through the expression graph (class_compile.hpp); knob off or a program too deep for the evaluator's
-    // stack: one weighted sum (assemble_grouped, round 5) or the terms folded one by one, acc = acc * y^gap + term
-    const bool grouped = quotient_group_enabled() && !conflict;
-    for (uint32_t e = 0; e <= E; ++e) {
-        QPlanClass& c = qp.cls[e];
-        if (cterms[e].empty()) continue;
-        c.used = true;
-        ClassCompileStats st;
-        bool done = qp.dag && compile_class(cterms[e], K, c.prog, &c.last, &st);
-        if (done) { c.parked = st.parked; c.max_live = st.max_live; c.groups = st.groups; }
-        if (!done && grouped && assemble_grouped(cterms[e], K, c.prog)) { c.last = K - 1; done = true; }
-        if (!done) {
-            c.prog.clear();
-            bool any = false;
-            for (const ClassTerm& t : cterms[e]) {
-                c.prog.insert(c.prog.end(), t.prog.begin(), t.prog.end());
-                c.prog.push_back({Q_FOLD, any ? C_YPOW0 + (t.cons - c.last) : C_Y, 0});       // acc = acc * y^(gap) + g_i
-                c.last = t.cons;
-                any = true;
-            }
-        }
-        c.products = count_products(c.prog);
-        c.fused = quotient_mac_enabled() ? count_fused(c.prog) : 0;
-        c.reductions = c.products - c.fused;
-        if (quotient_mac_enabled() && quotient_mac_level() != 1) {
-            uint32_t f4[4] = {0, 0, 0, 0};
-            count_fused(c.prog, 7, f4);
-            c.mac2 = f4[0]; c.mac_stk = f4[1]; c.declined = f4[2];
-            c.reductions = c.products - f4[3] - 2 * f4[0] - f4[1];
-        }
-    }
-    for (QPlanClass& c : qp.cls) {
-        std::unordered_set<uint32_t> seen;
-        for (const Instr& in : c.prog)
-            if (in.op == Q_PUSH_COL && seen.insert(in.a).second) {
-                c.refs.push_back(in.a);
-                if (std::find(qp.refs.begin(), qp.refs.end(), in.a) == qp.refs.end()) qp.refs.push_back(in.a);
-            }
-    }
-    // What the plan executes per proof, in units of one field product over n rows (~10 us at k = 20): a coset transform of a
-    // witness-side column ~ 10 of them (the key's own columns are transformed once per key and cached), a remainder its program
-    // over H, an inverse transform, and the transforms the two classes that read it already count.
-    auto of_key = [](uint32_t ref) { const uint32_t t = ref >> 24; return t == CT_FIXED || t == CT_SIGMA || t == CT_SPECIAL; };
-    const double C_T = 10.0;
-    qp.cost = 0;
-    for (uint32_t e = 0; e <= E; ++e) {
-        if (!qp.cls[e].used) continue;
-        uint32_t moving = 0;
-        for (uint32_t ref : qp.cls[e].refs) moving += !of_key(ref);
-        qp.cost += (double)(1u << e) * (moving * C_T + (double)qp.cls[e].products + 2.0);
-    }
-    for (const QPlanRem& rm : qp.rems) qp.cost += (double)rm.products + C_T + 4.0;
-    return ZK_OK;
-}
-static std::string quotient_plan_key() {
-    std::string k;
-    for (const char* name : {"ZK_QUOTIENT_SPLIT", "ZK_QUOTIENT_ADDSPLIT", "ZK_QUOTIENT_GROUP", "ZK_QUOTIENT_DAG", "ZK_QUOTIENT_COSTGATE", "ZK_QUOTIENT_MAC", "ZK_QUOTIENT_CHUNK"}) { const char* v = getenv(name); k += v ? v : "-"; k += '|'; }
-    return k;
-}
-static int quotient_plan(const zk_pk* pk, std::shared_ptr<const QuotientPlan>* out, std::string* err) {
-    const std::string key = quotient_plan_key();
-    if (pk->qplan && pk->qplan->key == key) { *out = pk->qplan; return ZK_OK; }
-    const bool split_on = quotient_split_enabled(false, false), add_on = quotient_addsplit_enabled();
-    const char* gate_env = getenv("ZK_QUOTIENT_COSTGATE");
-    const bool gate = !(gate_env && atoi(gate_env) == 0);
-    std::shared_ptr<QuotientPlan> best;
-    std::vector<std::pair<bool, bool>> cand;
-    if (split_on && add_on) cand.push_back({true, true});
-    if (split_on && (gate || !add_on)) cand.push_back({true, false});
-    if (!split_on || gate) cand.push_back({false, false});
-    for (const auto& c : cand) {
-        auto qp = std::make_shared<QuotientPlan>();
-        PK_TRY(make_quotient_plan(pk, c.first, c.second, *qp, err));
-        if (getenv("ZK_QUOTIENT_TRACE")) {
-            fprintf(stderr, "[zk quotient] plan split=%d addsplit=%d dag=%d: cost %.0f, %zu remainders;", (int)qp->split, (int)qp->addsplit, (int)qp->dag, qp->cost, qp->rems.size());
-            for (uint32_t e = 0; e <= qp->E; ++e) if (qp->cls[e].used) fprintf(stderr, " class %u: %zu instr, %u products, %zu columns, %u parked (%u live), %u groups;", e, qp->cls[e].prog.size(), qp->cls[e].products, qp->cls[e].refs.size(), qp->cls[e].parked, qp->cls[e].max_live, qp->cls[e].groups);
-            fprintf(stderr, "\n");
-        }
-        if (!best || (gate && qp->cost < best->cost)) best = qp;
-        if (!gate) break;
-    }
-    best->key = key;
-    pk->qplan = best;
-    *out = best;
-    return ZK_OK;
-}
-// For every advice column: the set of cosets r (bit r) of the extended domain on which some constraint class active there reads it.
-static int advice_coset_plan(zk_ctx* ctx, const zk_pk* pk, bool sharded, std::vector<uint32_t>& mask, size_t* key_slots = nullptr) {
-    (void)sharded;
-    std::shared_ptr<const QuotientPlan> qp;
-    {
+// The quotient's plan of a key (quotient_plan.hpp): a pure function of the constraint system and of the knobs, so it is made once
+// per key (zk_pk::qplan), again when a knob changed since, and shared by the advice phases (which cosets read which column) and
+// zk_proof_finish.
+static int quotient_plan(zk_ctx* ctx, const zk_pk* pk, std::shared_ptr<const QuotientPlan>* out) {
+    const QuotientKnobs knobs = QuotientKnobs::read();
+    if (!pk->qplan || pk->qplan->key != knobs.key()) {
         std::string err;
-        const int rc = quotient_plan(pk, &qp, &err);
+        const int rc = choose_quotient_plan(*pk, knobs, &pk->qplan, &err);
         if (rc) return ctx->fail(rc, "%s", err.c_str());
     }
-    const uint32_t E = qp->E;
-    mask.assign(pk->A, 0u);
-    if (E > 5) return ZK_OK;           // more than 32 cosets: no plan (the quotient transforms everything itself)
-    std::unordered_map<uint32_t, uint32_t> key_mask;
-    for (uint32_t e = 0; e <= E; ++e) {
-        uint32_t cosets = 0;
-        for (uint32_t r = 0; r < (1u << E); ++r) if (class_on_coset(E, e, r)) cosets |= 1u << r;
-        for (uint32_t ref : qp->cls[e].refs) {
-            const uint32_t t = ref >> 24;
-            if (t == CT_ADVICE && (ref & 0xFFFFFFu) < pk->A) mask[ref & 0xFFFFFFu] |= cosets;
-            else if (t == CT_FIXED || t == CT_SIGMA || t == CT_SPECIAL) key_mask[ref] |= cosets;      // (column of the key, coset) pairs the quotient reads: what the key's coset cache will hold
-        }
-    }
-    if (key_slots) {
-        size_t cnt = 0;
-        for (const auto& kv : key_mask) cnt += (size_t)__builtin_popcount(kv.second);
-        *key_slots = cnt;
-    }
+    *out = pk->qplan;
+    return ZK_OK;
+}
+// advice_coset_masks / advice_lagrange_readers (quotient_plan.hpp) of the key's plan
+static int advice_coset_plan(zk_ctx* ctx, const zk_pk* pk, std::vector<uint32_t>& mask, size_t* key_slots = nullptr) {
+    std::shared_ptr<const QuotientPlan> qp;
+    PK_TRY(quotient_plan(ctx, pk, &qp));
+    advice_coset_masks(*pk, *qp, mask, key_slots);
+    return ZK_OK;
+}
+static int advice_lagrange_readers(zk_ctx* ctx, const zk_pk* pk, std::vector<uint8_t>* need) {
+    std::shared_ptr<const QuotientPlan> qp;
+    PK_TRY(quotient_plan(ctx, pk, &qp));
+    advice_lagrange_readers(*pk, *qp, need);
     return ZK_OK;
 }
 
-// Which advice columns some program over the LAGRANGE domain reads inside a session: the tuples of the lookup arguments, the permutation argument's columns, the
-// remainder polynomials of the additive split (quotient plan of the key).  Everything else -- gates only -- is read through coefficient forms (cosets, evaluations).
-static int advice_lagrange_readers(zk_ctx* ctx, const zk_pk* pk, std::vector<uint8_t>* need) {
-    need->assign(pk->A, 0);
-    auto scan = [&](const Prog& g) {
-        for (const Instr& in : g)
-            if (in.op == Q_PUSH_COL && (in.a >> 24) == CT_ADVICE && (in.a & 0xFFFFFFu) < pk->A) (*need)[in.a & 0xFFFFFFu] = 1;
-    };
-    for (const auto& lk : pk->lookups) {
-        for (const Prog& g : lk.tables) scan(g);
-        for (const auto& tuple : lk.inputs) for (const Prog& g : tuple) scan(g);
-    }
-    for (const auto& pc : pk->perm_cols) if (pc.first == CT_ADVICE && pc.second < pk->A) (*need)[pc.second] = 1;
-    std::shared_ptr<const QuotientPlan> qplan;
-    std::string err;
-    const int rc = quotient_plan(pk, &qplan, &err);
-    if (rc) return ctx->fail(rc, "%s", err.c_str());
-    for (const QPlanRem& r : qplan->rems) scan(r.prog);
-    return ZK_OK;
-}
 
 // Which cosets of which advice columns this session computes ahead, during its advice phases (zk_proof::pre_mask, adv_coset).
 // Cosets are taken in the order of how many advice columns they serve, as long as the buffers fit what the device can spare:
@@ -2097,7 +1302,7 @@ static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr) {
     if (sharded || cap <= 0 || pk->A == 0) return ZK_OK;
     std::vector<uint32_t> mask;
     size_t key_slots = 0;
-    PK_TRY(advice_coset_plan(ctx, pk, sharded, mask, &key_slots));
+    PK_TRY(advice_coset_plan(ctx, pk, mask, &key_slots));
     const uint32_t E = pk->ext_k - pk->k, R = 1u << E;
     if (E > 5) return ZK_OK;
     const double col_bytes = (double)((size_t)1 << pk->k) * 32.0;
@@ -2143,169 +1348,16 @@ static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr) {
     return ZK_OK;
 }
 
-// Host only (no device), for tests: the degree-class assembly of constraint programs with shared intermediates, exactly as
-// zk_proof_finish performs it (TmpSplit).  words: 3 per instruction, the `count` programs back to back (lens[i] instructions
-// each); cls[i] < classes.  Output: the class programs back to back (out_lens[e] instructions each), every constraint followed
-// by the marker {Q_FOLD, i, 0} so that a test can tell the constraints' values apart.  *conflict = 1 when the programs reuse a
-// slot across constraints (the prover then keeps a single class).
-int zk_host_split_programs(const uint32_t* words, const uint32_t* lens, const uint32_t* cls, uint32_t count, uint32_t classes,
-                           uint32_t* out_words, size_t out_cap_words, uint32_t* out_lens, int* conflict) {
-    if (!words || !lens || !cls || !out_lens || !conflict || classes == 0) return ZK_ERR_INVALID_ARG;
-    std::vector<Prog> cons(count);
-    size_t at = 0;
-    for (uint32_t i = 0; i < count; ++i) {
-        if (cls[i] >= classes) return ZK_ERR_INVALID_ARG;
-        for (uint32_t j = 0; j < lens[i]; ++j, ++at) cons[i].push_back({words[3 * at], words[3 * at + 1], words[3 * at + 2]});
-    }
-    *conflict = tmp_slots_conflict(cons) ? 1 : 0;
-    std::vector<Prog> progs(classes);
-    TmpSplit tmps(classes);
-    for (uint32_t i = 0; i < count; ++i) {
-        tmps.append(cons[i], cls[i], progs[cls[i]]);
-        progs[cls[i]].push_back({Q_FOLD, i, 0});
-    }
-    if (tmps.conflict) *conflict = 1;
-    size_t total = 0;
-    for (uint32_t e = 0; e < classes; ++e) { out_lens[e] = (uint32_t)progs[e].size(); total += progs[e].size(); }
-    if (!out_words) return ZK_OK;
-    if (3 * total > out_cap_words) return ZK_ERR_INVALID_ARG;
-    size_t w = 0;
-    for (const Prog& pg : progs) for (const Instr& in : pg) { out_words[w++] = in.op; out_words[w++] = in.a; out_words[w++] = in.b; }
-    return ZK_OK;
-}
-
-// Host only (no device), for tests: the additive split of ONE constraint program over the degree classes 0 .. E exactly as
-// zk_proof_finish applies it (additive_split above).  Output: the pieces back to back (out_lens[j] instructions of class
-// out_cls[j] each), *num_pieces of them -- one piece, the program itself in the class of its degree, when it is not split.
-int zk_host_additive_split(const uint32_t* words, uint32_t num_instr, uint32_t E, uint32_t* out_words, size_t out_cap_words, uint32_t* out_cls, uint32_t* out_lens,
-                           uint32_t cap_pieces, uint32_t* num_pieces) {
-    if (!words || !num_pieces || E > 8) return ZK_ERR_INVALID_ARG;
-    Prog g(num_instr);
-    for (uint32_t j = 0; j < num_instr; ++j) g[j] = {words[3 * j], words[3 * j + 1], words[3 * j + 2]};
-    std::vector<int> tmp_deg;
-    const int dg = program_degree(g, &tmp_deg);
-    if (dg < 0) return ZK_ERR_INVALID_ARG;
-    std::vector<std::pair<uint32_t, Prog>> parts;
-    const uint32_t whole = class_of_degree(dg, E);
-    if (!(whole > 0 && additive_split(g, E, whole, parts))) { parts.clear(); parts.push_back({whole, g}); }
-    *num_pieces = (uint32_t)parts.size();
-    if (!out_words) return ZK_OK;
-    if (!out_cls || !out_lens || parts.size() > cap_pieces) return ZK_ERR_INVALID_ARG;
-    size_t w = 0;
-    for (size_t j = 0; j < parts.size(); ++j) {
-        out_cls[j] = parts[j].first;
-        out_lens[j] = (uint32_t)parts[j].second.size();
-        if (w + 3 * parts[j].second.size() > out_cap_words) return ZK_ERR_INVALID_ARG;
-        for (const Instr& in : parts[j].second) { out_words[w++] = in.op; out_words[w++] = in.a; out_words[w++] = in.b; }
-    }
-    return ZK_OK;
-}
-
-int zk_host_group_terms(const uint32_t* words, const uint32_t* lens, const uint32_t* cons, uint32_t count, uint32_t K, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr) {
-    if (!words || !lens || !cons || !out_instr) return ZK_ERR_INVALID_ARG;
-    std::vector<ClassTerm> terms(count);
-    size_t at = 0;
-    for (uint32_t t = 0; t < count; ++t) {
-        if (cons[t] >= K) return ZK_ERR_INVALID_ARG;
-        terms[t].cons = cons[t];
-        terms[t].prog.resize(lens[t]);
-        for (uint32_t j = 0; j < lens[t]; ++j, ++at) terms[t].prog[j] = {words[3 * at], words[3 * at + 1], words[3 * at + 2]};
-    }
-    Prog out;
-    if (!assemble_grouped(terms, K, out)) return ZK_ERR_UNSUPPORTED;
-    *out_instr = (uint32_t)out.size();
-    if (!out_words) return ZK_OK;
-    if (out_cap_words < 3 * out.size()) return ZK_ERR_INVALID_ARG;
-    for (size_t j = 0; j < out.size(); ++j) { out_words[3 * j] = out[j].op; out_words[3 * j + 1] = out[j].a; out_words[3 * j + 2] = out[j].b; }
-    return ZK_OK;
-}
-
-// Host only, for tests: compile_class (class_compile.hpp) over the terms of one class.  out_stats[0..5] = graph nodes, values parked,
-// parking slots alive at once, products, factor groups, stack depth; *out_last = the constraint index the program's sum is aligned to
-// (the caller scales by y^(K-1-last)).
-int zk_host_compile_class(const uint32_t* words, const uint32_t* lens, const uint32_t* cons, uint32_t count, uint32_t K, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr,
-                          uint32_t* out_last, uint32_t* out_stats) {
-    if (!words || !lens || !cons || !out_instr || !out_last) return ZK_ERR_INVALID_ARG;
-    std::vector<ClassTerm> terms(count);
-    size_t at = 0;
-    for (uint32_t t = 0; t < count; ++t) {
-        if (cons[t] >= K) return ZK_ERR_INVALID_ARG;
-        terms[t].cons = cons[t];
-        terms[t].prog.resize(lens[t]);
-        for (uint32_t j = 0; j < lens[t]; ++j, ++at) terms[t].prog[j] = {words[3 * at], words[3 * at + 1], words[3 * at + 2]};
-    }
-    Prog out;
-    ClassCompileStats st;
-    if (!compile_class(terms, K, out, out_last, &st)) return ZK_ERR_UNSUPPORTED;
-    *out_instr = (uint32_t)out.size();
-    if (out_stats) { out_stats[0] = st.nodes; out_stats[1] = st.parked; out_stats[2] = st.max_live; out_stats[3] = st.products; out_stats[4] = st.groups; out_stats[5] = (uint32_t)st.depth; }
-    if (!out_words) return ZK_OK;
-    if (out_cap_words < 3 * out.size()) return ZK_ERR_INVALID_ARG;
-    for (size_t j = 0; j < out.size(); ++j) { out_words[3 * j] = out[j].op; out_words[3 * j + 1] = out[j].a; out_words[3 * j + 2] = out[j].b; }
-    return ZK_OK;
-}
-
-// Host only (no device, no SRS): the quotient plan zk_proof_finish will follow for a constraint system -- `cs_blob` is the
-// constraint-system part of a key blob (the column data may be missing).  out_summary: [0] E = ext_k - k, [1] K constraints,
-// [2] degree classes on, [3] additive split on, [4] compiled through the expression graph, [5] remainder polynomials, [6] the cost
-// estimate the candidates were compared by, [7] columns read; then 8 words per class e <= E: used, instructions, products, columns
-// read, values parked, parking slots alive at once, factor groups, last.  class_index <= E with out_words: that class's program.
-// With room for 8 + 10 (E + 1) words: per class the reductions and K_MAC_COL steps of the fuse = 3 stream (reductions + fused = products, whatever
-// else the knob turns on); with room for 8 + 14 (E + 1): per class, for the stream ZK_QUOTIENT_MAC puts in force, MAC2_COL steps, MAC_STK steps,
-// MAC2_COL fusions declined for stack depth, reductions.  Earlier words never depend on the room given.
-static int write_plan_summary(const std::shared_ptr<const QuotientPlan>& qp, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr);
-int zk_host_quotient_plan(const void* cs_blob, size_t blob_len, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr) {
-    if (!cs_blob || !out_summary) return ZK_ERR_INVALID_ARG;
-    Reader r{(const uint8_t*)cs_blob, blob_len};
-    zk_pk pk;
-    std::string err;
-    int rc = parse_cs(r, &pk, blob_len, false, &err);
-    if (rc) { fprintf(stderr, "zk_host_quotient_plan: %s\n", err.c_str()); return rc; }
-    std::shared_ptr<const QuotientPlan> qp;
-    rc = quotient_plan(&pk, &qp, &err);
-    if (rc) { fprintf(stderr, "zk_host_quotient_plan: %s\n", err.c_str()); return rc; }
-    return write_plan_summary(qp, out_summary, cap_summary, class_index, out_words, out_cap_words, out_instr);
-}
 // The plan of a key (what zk_proof_finish follows for it under the knobs in force): same summary as zk_host_quotient_plan.
 int zk_pk_quotient_plan(zk_ctx* ctx, const zk_pk* pk, uint32_t* out_summary, size_t cap_summary) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
     ZK_REQUIRE(ctx, pk && out_summary, "null pointer");
     std::shared_ptr<const QuotientPlan> qp;
-    std::string err;
-    const int rc = quotient_plan(pk, &qp, &err);
-    if (rc) return ctx->fail(rc, "%s", err.c_str());
-    if (write_plan_summary(qp, out_summary, cap_summary, 0xFFFFFFFFu, nullptr, 0, nullptr)) return ctx->fail(ZK_ERR_INVALID_ARG, "zk_pk_quotient_plan: the summary needs %u words", 8 + 8 * (qp->E + 1));
+    PK_TRY(quotient_plan(ctx, pk, &qp));
+    if (write_plan_summary(*qp, out_summary, cap_summary, 0xFFFFFFFFu, nullptr, 0, nullptr)) return ctx->fail(ZK_ERR_INVALID_ARG, "zk_pk_quotient_plan: the summary needs %u words", 8 + 8 * (qp->E + 1));
     return ZK_OK;
 }
-static int write_plan_summary(const std::shared_ptr<const QuotientPlan>& qp, uint32_t* out_summary, size_t cap_summary, uint32_t class_index, uint32_t* out_words, size_t out_cap_words, uint32_t* out_instr) {
-    if (cap_summary < 8 + 8 * (size_t)(qp->E + 1)) return ZK_ERR_INVALID_ARG;
-    out_summary[0] = qp->E; out_summary[1] = qp->K; out_summary[2] = qp->split; out_summary[3] = qp->addsplit; out_summary[4] = qp->dag;
-    out_summary[5] = (uint32_t)qp->rems.size(); out_summary[6] = (uint32_t)std::min(qp->cost, 4.0e9); out_summary[7] = (uint32_t)qp->refs.size();
-    for (uint32_t e = 0; e <= qp->E; ++e) {
-        const QPlanClass& c = qp->cls[e];
-        uint32_t* o = out_summary + 8 + 8 * e;
-        o[0] = c.used; o[1] = (uint32_t)c.prog.size(); o[2] = c.products; o[3] = (uint32_t)c.refs.size(); o[4] = c.parked; o[5] = c.max_live; o[6] = c.groups; o[7] = c.last;
-    }
-    if (cap_summary >= 8 + 10 * (size_t)(qp->E + 1))         // a caller that asks for them: 2 more words per class -- reductions, fused multiply-accumulates
-        for (uint32_t e = 0; e <= qp->E; ++e) {
-            uint32_t* o = out_summary + 8 + 8 * (qp->E + 1) + 2 * e;
-            o[0] = qp->cls[e].products - qp->cls[e].fused; o[1] = qp->cls[e].fused;
-        }
-    if (cap_summary >= 8 + 14 * (size_t)(qp->E + 1))         // ... and 4 more for the stream in force: MAC2_COL, MAC_STK, fusions declined for stack depth, its reductions
-        for (uint32_t e = 0; e <= qp->E; ++e) {
-            uint32_t* o = out_summary + 8 + 10 * (qp->E + 1) + 4 * e;
-            o[0] = qp->cls[e].mac2; o[1] = qp->cls[e].mac_stk; o[2] = qp->cls[e].declined; o[3] = qp->cls[e].reductions;
-        }
-    if (out_instr && class_index <= qp->E) {
-        const Prog& g = qp->cls[class_index].prog;
-        *out_instr = (uint32_t)g.size();
-        if (out_words) {
-            if (out_cap_words < 3 * g.size()) return ZK_ERR_INVALID_ARG;
-            for (size_t j = 0; j < g.size(); ++j) { out_words[3 * j] = g[j].op; out_words[3 * j + 1] = g[j].a; out_words[3 * j + 2] = g[j].b; }
-        }
-    }
-    return ZK_OK;
-}
+
 
 // ================================================================================================
 // The finishing pass: everything after the advice phases.  One function per stage of the protocol, called by zk_proof_finish
@@ -2388,7 +1440,7 @@ static int stage_late_advice_cosets(Finish& f) {
     if (f.sharded || !(cap > 0) || !pk->A || E > 5 || !ctx->ensure_aux()) return ZK_OK;
     std::vector<uint32_t> mask;
     size_t key_slots = 0;
-    PK_TRY(advice_coset_plan(ctx, pk, false, mask, &key_slots));
+    PK_TRY(advice_coset_plan(ctx, pk, mask, &key_slots));
     if (pr->adv_coset.empty()) { pr->adv_coset.resize(R); for (auto& v : pr->adv_coset) v.resize(pk->A); }
     const double col_bytes = (double)n * 32.0;
     const size_t free_b = device_free_bytes();          // unknown counts as none
@@ -2540,9 +1592,9 @@ static int stage_permutation_products(Finish& f) {
         PB pn, pd;
         const uint32_t j0 = c * pk->chunk, j1 = std::min(pk->P, j0 + pk->chunk);
         for (uint32_t j = j0; j < j1; ++j) {
-            push_perm_col(pn, pk->perm_cols[j]); pn.col(CT_SPECIAL, SP_X).mulc(C_DELTA0 + j).op(Q_ADD).addc(C_GAMMA);
+            pn.col(pk->perm_cols[j]).col(CT_SPECIAL, SP_X).mulc(C_DELTA0 + j).op(Q_ADD).addc(C_GAMMA);
             if (j > j0) pn.op(Q_MUL);
-            push_perm_col(pd, pk->perm_cols[j]); pd.col(CT_SIGMA, j).mulc(C_BETA).op(Q_ADD).addc(C_GAMMA);
+            pd.col(pk->perm_cols[j]).col(CT_SIGMA, j).mulc(C_BETA).op(Q_ADD).addc(C_GAMMA);
             if (j > j0) pd.op(Q_MUL);
         }
         pn.fold(C_ONE); pd.fold(C_ONE);
@@ -2758,16 +1810,11 @@ struct CosetPass {
     DevBuf rtmp, gbuf;                        // the exchange: one received block (host transport), world of them (device transports)
     HostStaging host;
 };
-static bool key_column(uint32_t ref) { const uint32_t t = ref >> 24; return t == CT_FIXED || t == CT_SIGMA || t == CT_SPECIAL; }
 
 // the plan, the powers of y, the remainders of the split constraints, one buffer per class
 static int quotient_prepare(Finish& f, Quotient& q) {
     zk_ctx* ctx = f.ctx; const zk_pk* pk = f.pk; const size_t n = f.n;
-    {
-        std::string err;
-        const int rc_plan = quotient_plan(pk, &q.plan, &err);
-        if (rc_plan) return ctx->fail(rc_plan, "%s", err.c_str());
-    }
+    PK_TRY(quotient_plan(ctx, pk, &q.plan));
     q.E = f.ext_k - f.k; q.K = q.plan->K; q.nparts = 1u << q.E;
     const uint32_t E = q.E, K = q.K;
     q.h.resize(E + 1);
