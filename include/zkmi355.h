@@ -391,6 +391,33 @@ int zk_msm_plan(const zk_srs* srs, size_t n, int* window_bits, int* windows);
 /* Host only: the merged-window plan for an SRS of 2^k points, with the shift applied to the top window's digit (the top window
  * holds only the leading bits of a scalar; its digit is scaled so that its entries spread over the bucket range). */
 int zk_host_msm_plan(uint32_t k, int* window_bits, int* windows, int* top_shift);
+/* Host only (no context, no device): the plan of one batch of `count` commitments of n points (1 <= n <= 2^k, k <= 28) over an
+ * SRS of 2^k points that has its merged-window table, as the library decides it under the ZK_MSM_* knobs in force at the call.
+ * hints (nullable): one byte per column, as zk_commit_batch_hint's; blinded_tail: the rows at the end of the hint-1 columns that
+ * the prover commits apart; window_table: the SRS also has the per-window table of its small-valued columns; group_cap: 0, or the
+ * bound on a group's columns that the retry with less memory applies; prof_on, graph_broken: the two context states that turn
+ * graph replay off.  *out_count receives the length of the record in 64-bit words, out_words (cap_words of room; NULL with 0 to
+ * ask for the length) the record:
+ *   head, ZK_MSM_BATCH_PLAN_HEAD words: status (0; 1: the batch exceeds the 32-bit entry space -- the record ends with the head),
+ *     any small-valued column, tail rows, rows in front of the tail, digit-matrix row stride, columns per group, groups take the
+ *     GM sort, GM bucket sets, GM range bits, GM partitions per column, GM bucket numbering, GM partition workgroups, words of
+ *     the per-window / GM / merged sort layouts, words per workspace copy, copies, one-launch partition sort, range bits, chunk,
+ *     staged scatter, partition workgroups, pipelines, graph replay, points per bucket buffer, next group_cap to try (0: none),
+ *     merged window bits / windows / top shift, per-window window bits / windows, reduction blocks per bucket set of a group
+ *   three sort layouts (per-window, GM, merged): words, regions, then per region (id, offset, length) in words, ascending --
+ *     ids: 0 slice counters, 1 slice offsets, 2 bucket counts, 3 the cleared region (size bins, counters, window flags,
+ *     done-counters), 4 bucket offsets, 5 bucket order, 6 tasks per bucket, 7 task offsets, 8 / 9 / 10 block totals of the
+ *     slice / bucket / histogram scans, 11 partition histogram, 12 its offsets, 13 sorted indices, 14 digit matrix, 15 entries;
+ *     a layout the batch does not use has 0 words and 0 regions
+ *   four bucket layouts, one per kind of step (0 per-window sort, 1 dense column with the one-launch sort, 2 dense column with the
+ *     sliced sort, 3 GM group): buckets and task bound of a full group, points, regions, then per region (id, offset, length) in
+ *     points -- ids: 0 buckets, 1 partials of the reduction, 2 task partials, 3 folded windows; all 0 for a kind the batch lacks
+ *   steps: their number, then (first column, columns, kind) each
+ *   graph key, the plan's part: its length, then n, merged window bits, per-window window bits, top shift, table stride, words
+ *     per copy, staged scatter, range bits, rows in front of the tail, partition workgroups                                   */
+#define ZK_MSM_BATCH_PLAN_HEAD 32
+int zk_host_msm_batch_plan(uint32_t k, size_t n, size_t count, const uint8_t* hints, uint32_t blinded_tail, int window_table, uint32_t group_cap, int prof_on, int graph_broken,
+                           uint64_t* out_words, size_t cap_words, size_t* out_count);
 
 /* Host-only: out = sum of n affine points (no context, no device).  Used to finish a point-sharded
  * MSM: each rank's 64-byte partial result is all-gathered as bytes (RCCL has no EC reduce op) and

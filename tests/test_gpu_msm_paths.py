@@ -288,6 +288,33 @@ def test_narrow_and_gm_paths(ctx, cref, monkeypatch, k):
     srs.destroy()
 
 
+def test_graph_replay_mixes_the_three_step_kinds(ctx, cref, srs12, bases12, monkeypatch, capfd):
+    """One batch of nine columns hinted 0 / 1 / 2 in turn over the Lagrange basis, n = 2^12 - 5: dense columns (one-launch sort),
+    small-valued columns (per-window sort) and hint-2 columns that the run path leaves to the ordinary one (sliced sort: their
+    scalars are independent, n random values have about n runs against the run path's cap of n / 16, and it takes no column
+    below 4096 rows at all).  ZK_MSM_NARROW_GROUP=1 keeps the columns single, which graph mode asks for.  Under ZK_MSM_GRAPH x
+    ZK_MSM_PIPES every commitment = best_multiexp, and the trace says "(graph replay)" exactly when graphs are on."""
+    n, count = (1 << 12) - 5, 9
+    rng = random.Random(8100)
+    hints = [i % 3 for i in range(count)]
+    cols = [cref.to_mont([rng.randrange(1 << 30) if rng.random() < 0.7 else 0 for _ in range(n)]) if h == 1 else cref.rand_fr_stream(8100 + i, n) for i, h in enumerate(hints)]
+    want = [_want(cref, col, bases12[True], ("k12", True), n) for col in cols]
+    bufs = [ctx.to_device(col) for col in cols]
+    monkeypatch.setenv("ZK_MSM_NARROW_GROUP", "1")
+    monkeypatch.setenv("ZK_MSM_TRACE", "1")
+    for pipes, graph in _pipeline_settings():
+        monkeypatch.setenv("ZK_MSM_PIPES", pipes)
+        monkeypatch.setenv("ZK_MSM_GRAPH", graph)
+        capfd.readouterr()
+        got = ctx.commit_batch(srs12, [b_.ptr for b_ in bufs], n, lagrange=True, narrow=hints)
+        err = capfd.readouterr().err
+        bad = [i for i in range(count) if not np.array_equal(got[i], want[i])]
+        assert not bad, f"PIPES={pipes} GRAPH={graph}: columns {bad} (hints {hints}) differ from best_multiexp"
+        assert ("(graph replay)" in err) == (graph == "1"), f"PIPES={pipes} GRAPH={graph}: trace {err!r}"
+    for b_ in bufs:
+        b_.free()
+
+
 @pytest.fixture(scope="module")
 def random_bases(cref):
     """2^16 unstructured points with the identity, repeated points and P, -P pairs among them (test_msm_edge_cases)"""

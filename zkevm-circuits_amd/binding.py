@@ -277,6 +277,61 @@ def host_ntt_plan(log_n: int, columns: int = 1, tables: bool = True, coset_pass:
     return {"per_launch": head[0], "columns": head[1], "passes": head[2], "tables": bool(head[3]), "launches": launches}
 
 
+MSM_BATCH_PLAN_HEAD = ("status", "any_narrow", "tail_rows", "n_narrow", "n_pad", "NG", "gm", "SG", "range_bits_G", "bpcG", "perm_G", "nwgG", "words_N", "words_G", "words_M", "words",
+                       "copies", "binsort", "range_bits", "chunk", "staged_scatter", "nwg", "npipe", "graph", "npts29", "smaller_cap", "c", "W", "top_shift", "c_n", "W_n", "red_blocks_N")
+MSM_SORT_REGIONS = ("slice_counts", "slice_off", "counts", "cleared", "offsets", "order", "ntasks", "toff", "block_tot_s", "block_tot", "block_tot_h", "hist", "hist_off", "idx", "dig", "entries")
+MSM_BUCKET_REGIONS = ("buckets", "partial", "task_partial", "folded")
+MSM_STEP_KINDS = ("window", "dense", "dense_sliced", "gm")
+
+
+def host_msm_batch_plan_words(k: int, n: int, count: int, hints=None, blinded_tail: int = 0, window_table: bool = True, group_cap: int = 0,
+                              prof_on: bool = False, graph_broken: bool = False) -> list:
+    """zk_host_msm_batch_plan (no device): the raw record, a list of ints"""
+    hb = bytes(hints) if hints is not None else None
+    if hb is not None and len(hb) != count:
+        raise ZkError(f"{len(hb)} hints for {count} columns")
+    out, cnt = (ctypes.c_uint64 * (512 + 3 * count))(), ctypes.c_size_t()      # head, <= 43 regions of three words, the steps, the key part
+    rc = lib().zk_host_msm_batch_plan(ctypes.c_uint32(k), ctypes.c_size_t(n), ctypes.c_size_t(count), hb, ctypes.c_uint32(blinded_tail), ctypes.c_int(1 if window_table else 0),
+                                      ctypes.c_uint32(group_cap), ctypes.c_int(1 if prof_on else 0), ctypes.c_int(1 if graph_broken else 0), out, ctypes.c_size_t(len(out)), ctypes.byref(cnt))
+    if rc != 0:
+        raise ZkError(f"zk_host_msm_batch_plan({k}, {n}, {count}) failed with status {rc}")
+    return list(out[:cnt.value])
+
+
+def host_msm_batch_plan(*args, **kwargs) -> dict:
+    """zk_host_msm_batch_plan as a dict: the head's fields by name, `sort` (layouts "N", "G", "M": words and regions name -> (offset, length)),
+    `buckets` (per step kind: nb, tasks, points, regions), `steps` [(first, columns, kind)] and `key` (the plan's part of a graph key)"""
+    w = host_msm_batch_plan_words(*args, **kwargs)
+    plan = dict(zip(MSM_BATCH_PLAN_HEAD, w))
+    for name in ("any_narrow", "gm", "binsort", "staged_scatter", "graph"):
+        plan[name] = bool(plan[name])
+    plan.update(sort={}, buckets={}, steps=[], key=[])
+    if plan["status"]:
+        return plan
+    at = len(MSM_BATCH_PLAN_HEAD)
+
+    def regions(names):
+        nonlocal at
+        total, cnt = w[at], w[at + 1]
+        regs = {names[w[at + 2 + 3 * i]]: (w[at + 3 + 3 * i], w[at + 4 + 3 * i]) for i in range(cnt)}
+        at += 2 + 3 * cnt
+        return total, regs
+    for layout in "NGM":
+        words, regs = regions(MSM_SORT_REGIONS)
+        plan["sort"][layout] = {"words": words, "regions": regs}
+    for kind in MSM_STEP_KINDS:
+        nb, tasks = w[at], w[at + 1]
+        at += 2
+        points, regs = regions(MSM_BUCKET_REGIONS)
+        if regs:
+            plan["buckets"][kind] = {"nb": nb, "tasks": tasks, "points": points, "regions": regs}
+    nsteps = w[at]
+    plan["steps"] = [(w[at + 1 + 3 * i], w[at + 2 + 3 * i], MSM_STEP_KINDS[w[at + 3 + 3 * i]]) for i in range(nsteps)]
+    at += 1 + 3 * nsteps
+    plan["key"] = w[at + 1:at + 1 + w[at]]
+    return plan
+
+
 TRANSCRIPT_BLAKE2B, TRANSCRIPT_POSEIDON, TRANSCRIPT_EVM = 0, 1, 2
 
 

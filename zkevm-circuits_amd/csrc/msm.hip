@@ -35,36 +35,16 @@
 #include "ctx.hpp"
 #include "ec29.hip.hpp"
 #include "host_fq.hpp"
+#include "msm_plan.hpp"
 
 namespace zk {
 
-constexpr int MSM_MAX_C = 16;
 constexpr uint32_t NEG_BIT = 0x80000000u;
-
-struct MsmPlan {
-    int c;          // window bits
-    int W;          // windows
-    uint32_t B;     // buckets per window = 2^(c-1)
-    int top_shift = 0;   // merged-window path: the top window's digit is scaled by 2^top_shift (its table entry is 2^(c (W-1) - top_shift) P)
-};
 
 // Graph replay of small batches (msm_batch_merged, graph mode): what differs from column to column -- where the scalars are,
 // where the result goes -- is read from a device-side table, cols[*ctr], so that the launch sequence of a column can be
 // captured once and replayed with one API call; the last kernel of the sequence advances *ctr to the pipeline's next column.
 struct MsmCol { const Fr* scalars; G1Xyzz* out; };
-
-static MsmPlan make_plan(size_t n) {
-    int lg = 0;
-    while ((1ull << (lg + 1)) <= n) ++lg;
-    int c = lg - 4;
-    if (c < 4) c = 4;
-    if (c > MSM_MAX_C) c = MSM_MAX_C;
-    MsmPlan p;
-    p.c = c;
-    p.W = (256 + c - 1) / c;
-    p.B = 1u << (c - 1);
-    return p;
-}
 
 // ---- sort phase --------------------------------------------------------------------------------
 // 1. k_msm_digits: every scalar leaves Montgomery form once and is recoded; digit codes go to a
@@ -77,7 +57,6 @@ static MsmPlan make_plan(size_t n) {
 //    alone -- partial lines merge in its XCD's L2 instead of costing one 64 B HBM write per index.
 //    Every workgroup does the same n digit tests whatever the scalar distribution: no skew.
 constexpr uint32_t DIG_ZERO = 0xFFFFu;
-constexpr int MSM_RANGE_MAX_BITS = 11;   // <= 2048 buckets per workgroup
 
 // wflag[w] is raised when window w holds at least one non-zero digit: the sweeps skip the others
 // (selector / boolean / small-value columns leave most windows empty).
@@ -139,7 +118,6 @@ static void launch_digits(int c, dim3 grid, hipStream_t st, const Fr* scalars, u
 // windows empty, and with one workgroup per (range, window) the few non-empty windows would keep
 // only a quarter of the CUs busy while each still streams a whole row.  Counters are laid out
 // [bucket][slice], so one exclusive scan over the flat array yields every (bucket, slice) cursor.
-constexpr int MSM_SLICES = 4;        // == SCAN_ITEMS: a scan thread sees the slices of one bucket
 template <bool SCATTER>
 __global__ void __launch_bounds__(1024) k_msm_lds_sweep(const uint16_t* __restrict__ dig, uint64_t n_pad, int range_bits, uint32_t B,
                                                         uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, uint32_t* __restrict__ idx, const uint32_t* __restrict__ wflag, uint32_t nwin) {
@@ -224,9 +202,6 @@ __global__ void __launch_bounds__(1024) k_msm_lds_sweep(const uint16_t* __restri
 // ---- merged-window sort (SRS bases with window tables) -------------------------------------------
 // Window bits C up to 22: digit magnitudes no longer fit the u16 codes of the per-window path.
 // code = 0xFFFFFFFF for a zero digit, else bit 31 = sign, bits 0..21 = |d| - 1 (the bucket).
-constexpr int MSM_M_MIN_C = 8, MSM_M_MAX_C = 22;
-constexpr uint32_t MSM_M_MAX_BINS = 1u << (MSM_M_MAX_C - 1 - MSM_RANGE_MAX_BITS);     // 1024 partitions of 2048 buckets
-constexpr uint32_t MSM_M_CHUNK = 2048;                                                   // scalars per workgroup of the partition passes
 constexpr uint32_t CODE_ZERO = 0xFFFFFFFFu;
 // The top window holds only the few leading bits of a scalar (14 of 20 at C = 20): its digits would all land in the
 // lowest buckets -- a handful of partitions with ten times the entries of the others.  Its digit is therefore scaled
@@ -330,7 +305,6 @@ __global__ void __launch_bounds__(256) k_msm_m_partition(const Fr* __restrict__ 
 }
 // The same pass over the columns of a GM group in ONE launch (blockIdx.y = column of the group): a column's 512 workgroups of 256
 // threads leave three quarters of the device's wave slots empty; eight columns fill them.
-constexpr int GM_MAX_COLS = 16;
 struct GmCols { const Fr* p[GM_MAX_COLS]; };
 template <int C, bool SCATTER>
 __global__ void __launch_bounds__(256) k_msm_gm_partition(GmCols cols, uint64_t n, int range_bits, uint32_t* __restrict__ hist, const uint32_t* __restrict__ hist_off,
@@ -344,7 +318,6 @@ __global__ void __launch_bounds__(256) k_msm_gm_partition(GmCols cols, uint64_t 
 // per partition in LDS, lays them out partition by partition in a staging buffer and copies the buffer out
 // with consecutive lanes on consecutive entries: every (workgroup, partition) run leaves as one contiguous
 // burst.  Dynamic LDS: cnt[1024] | gdelta[1024] | wtot[16] | stage[1024 W] (u64) | pid[1024 W] (u16).
-constexpr uint32_t MSM_M_SCHUNK = 1024;                 // scalars per workgroup of the staged scatter (and of its histogram pass)
 template <int C>
 __global__ void __launch_bounds__(1024) k_msm_m_scatter_staged(const Fr* __restrict__ scalars_arg, uint64_t n, int range_bits, const uint32_t* __restrict__ hist_off,
                                                                uint64_t* __restrict__ entries, uint64_t tab_stride, int top_shift, const MsmCol* __restrict__ cols = nullptr, const uint32_t* __restrict__ ctr = nullptr) {
@@ -407,7 +380,6 @@ __global__ void __launch_bounds__(1024) k_msm_m_scatter_staged(const Fr* __restr
     __syncthreads();
     for (uint32_t e = threadIdx.x; e < total; e += blockDim.x) entries[gdelta[pid[e]] + e] = stage[e];
 }
-static size_t scatter_staged_lds(int W) { return (size_t)(2 * MSM_M_MAX_BINS + 16) * 4 + (size_t)MSM_M_SCHUNK * W * 10; }
 // Per-partition LDS counting sort: workgroup (bin, slice) streams its quarter of the partition's
 // entries; counters are laid out [bucket][slice] exactly as in the per-window path, so the same
 // scans produce every (bucket, slice) cursor.
@@ -457,7 +429,6 @@ __global__ void __launch_bounds__(1024) k_msm_m_bin(const uint64_t* __restrict__
 // scatter above wrote 10x its payload through L2).  Also leaves counts[], the size histogram and the
 // closing offsets[nb] that the task split reads.  A partition larger than the staging buffer (skewed
 // scalars) scatters straight to global memory instead.
-constexpr uint32_t MSM_M_STAGE = 15u * 1024u;      // 60 KiB of indices + 8 KiB of counters: two workgroups per CU
 constexpr uint32_t MSM_SIZE_BINS = 256;            // == SIZE_BINS below
 __global__ void __launch_bounds__(1024) k_msm_m_binsort(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ hist_off, uint32_t nwg, int range_bits, uint32_t nb,
                                                         uint32_t* __restrict__ offsets, uint32_t* __restrict__ counts, uint32_t* __restrict__ size_hist, uint32_t* __restrict__ idx) {
@@ -563,7 +534,6 @@ __global__ void __launch_bounds__(1024) k_msm_m_binsort(const uint64_t* __restri
 }
 
 // ---- exclusive scan of the bucket counts, three small kernels (4096 counts per block) ----------
-constexpr int SCAN_T = 1024, SCAN_ITEMS = 4;
 __device__ __forceinline__ uint32_t block_scan_u32(uint32_t v, uint32_t* sh, uint32_t* total) {
     sh[threadIdx.x] = v;
     __syncthreads();
@@ -608,11 +578,7 @@ __global__ void __launch_bounds__(SCAN_T) k_scan_u32_b(uint32_t* block_tot, uint
 // start of every (bucket, slice)), derives the per-bucket view (offsets[b] = slice_off[b][0],
 // counts[b] = sum of its slices) and bins every bucket by size (descending order of size -> a wave
 // works on buckets of equal length; big ones start first).
-constexpr uint32_t SIZE_BINS = 256;
-constexpr uint32_t MSM_WFLAGS = 256;           // window flags of one sort (behind nmulti + 4): up to eight small-valued columns of 16 windows share a launch sequence
-constexpr uint32_t TASK_DONE_MAX = 1u << 17;   // done-counters (behind nmulti + 4 + MSM_WFLAGS) of the split buckets that straddle a wave boundary inside k_msm_buckets: positions below this
-constexpr uint32_t TASK_INLINE_MAX = 8;    // ... when they were split into at most this many tasks
-constexpr uint32_t TASK_CAP = 48;       // points per task, see "skew-proof work split" below
+constexpr uint32_t TASK_INLINE_MAX = 8;    // the done-counters (TASK_DONE_MAX, msm_plan.hpp) serve the split buckets that were split into at most this many tasks
 __global__ void __launch_bounds__(SCAN_T) k_scan_u32_c(const uint32_t* __restrict__ slice_counts, uint32_t nbuckets, uint32_t* __restrict__ slice_off, const uint32_t* __restrict__ block_tot,
                                                        uint32_t* __restrict__ offsets, uint32_t* __restrict__ counts, uint32_t* __restrict__ size_hist) {
     __shared__ uint32_t lh[SIZE_BINS];
@@ -641,7 +607,6 @@ static_assert(SCAN_ITEMS == MSM_SLICES, "k_scan_u32_a scans MSM_SLICES entries p
 // windows empty, and one lane per 32-point bucket would be 2 waves per SIMD) -- so that about
 // 2^18 tasks exist either way.  nmulti[0] = M = buckets with more points than one task,
 // nmulti[1] = the task size.
-constexpr uint32_t TASK_MIN = 8, TASK_TARGET = 1u << 18;
 #ifndef ZK_TASK_TMIN
 #define ZK_TASK_TMIN (1u << 16)
 #endif
@@ -1020,8 +985,6 @@ __device__ __forceinline__ G1Xyzz29 mul_small(const G1Xyzz29& p, uint32_t k) {
     return k ? acc : identity29();
 }
 
-constexpr int RED_G_WIDE = 8, RED_G_FOLDED = 2, RED_G_MERGED = 16;
-constexpr int RED_THREADS = 256;
 // grid: (groups_per_window / RED_THREADS, W); each block writes one partial per (window, block)
 // G = buckets folded per lane: 8 keeps the work low when W windows are reduced; 2 keeps the
 // dependent chain short when the window tables have already folded everything into one window.
@@ -1193,105 +1156,10 @@ static int wsum_enqueue(zk_ctx* ctx, hipStream_t st, const G1Xyzz29* buckets, ui
 // functions below over one SortWs; no other code launches the sort, accumulation, combination or reduction kernels.
 #define PK_TRY_MSM(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
 
-// Measurement knobs.  read_knobs() is called at the top of every call that applies one and its result is never kept: a
-// process may change the environment between two calls.  A field is the variable's atoi, KNOB_UNSET when it is not
-// set; the range of a knob is checked where it is applied.
-constexpr int KNOB_UNSET = INT_MIN;
-struct MsmKnobs {
-    int c, top_shift;                                       // ZK_MSM_C, ZK_MSM_TOP_SHIFT: the merged plan (make_plan_merged)
-    int binsort, staged, chunk;                             // ZK_MSM_BINSORT, ZK_MSM_STAGED, ZK_MSM_CHUNK: the merged sort
-    int pipes, graph;                                       // ZK_MSM_PIPES, ZK_MSM_GRAPH: pipelines of a small batch
-    int narrow, narrow_group, narrow_gm, gm_sets;           // ZK_MSM_NARROW, ZK_MSM_NARROW_GROUP, ZK_MSM_NARROW_GM, ZK_MSM_GM_SETS: small-valued columns
-    double table_gb;                                        // ZK_MSM_TABLE_GB: largest window table per basis (default 32 GiB)
-    bool trace;                                             // ZK_MSM_TRACE (set at all): host enqueue / device drain times of every batch on stderr
-};
-static MsmKnobs read_knobs() {
-    auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : KNOB_UNSET; };
-    MsmKnobs k;
-    k.c = num("ZK_MSM_C");
-    k.top_shift = num("ZK_MSM_TOP_SHIFT");
-    k.binsort = num("ZK_MSM_BINSORT");
-    k.staged = num("ZK_MSM_STAGED");
-    k.chunk = num("ZK_MSM_CHUNK");
-    k.pipes = num("ZK_MSM_PIPES");
-    k.graph = num("ZK_MSM_GRAPH");
-    k.narrow = num("ZK_MSM_NARROW");
-    k.narrow_group = num("ZK_MSM_NARROW_GROUP");
-    k.narrow_gm = num("ZK_MSM_NARROW_GM");
-    k.gm_sets = num("ZK_MSM_GM_SETS");
-    const char* gb = getenv("ZK_MSM_TABLE_GB");
-    k.table_gb = gb ? atof(gb) : 32.0;
-    k.trace = getenv("ZK_MSM_TRACE") != nullptr;
-    return k;
-}
-
-// Sort workspace.  A bump allocator over u32 words describes a layout once: over a null base it only counts -- the size
-// to ask for --, over the workspace it hands out the pointers, so the two cannot disagree.
-struct WsCarver {
-    uint32_t* base;
-    size_t at = 0;
-    uint32_t* take(size_t nwords, size_t align_words = 1) {
-        at = (at + align_words - 1) / align_words * align_words;
-        uint32_t* p = base ? base + at : nullptr;
-        at += nwords;
-        return p;
-    }
-};
-static inline uint32_t scan_blocks_of(uint32_t cnt) { return (cnt + SCAN_T * SCAN_ITEMS - 1) / (SCAN_T * SCAN_ITEMS); }
-// size_hist[SIZE_BINS] | nmulti[4] | window flags[MSM_WFLAGS] | done-counters[TASK_DONE_MAX]: the kernels find the flags
-// and the counters behind nmulti, and every sort starts by clearing the four with ONE memset -- they are one region
-constexpr uint32_t MSM_CLEARED_WORDS = SIZE_BINS + 4 + MSM_WFLAGS + TASK_DONE_MAX;
-// The three layouts by their dimensions:
-//   per-window "N" (msm_batch_tab, small-valued columns):  slices, idx[n * windows], digit matrix
-//   merged "M":                                            slices (the sliced sort), partition histogram, idx and entries[n * W]
-//   grouped "GM":                                          partition histogram, idx and entries[n * W * columns]
-struct SortDims {
-    uint32_t nb;            // buckets
-    bool slices;            // [bucket][slice] counters and offsets of a sort by MSM_SLICES workgroups per bucket range
-    uint32_t hist_cnt;      // partition histogram: partitions x workgroups (0: no partition pass)
-    uint64_t idx_cnt;       // sorted indices, worst case
-    size_t dig_words;       // u16 digit matrix, in words (0: none)
-    bool entries;           // u64 (bucket, table index) entries, idx_cnt of them
-};
-struct SortWs {
-    uint32_t *slice_counts, *slice_off, *block_tot_s;       // slices (both 16-B aligned: k_scan_u32_c reads the MSM_SLICES words of a bucket as one uint4)
-    uint32_t *counts, *offsets, *order, *ntasks, *toff, *block_tot;
-    uint32_t *cleared, *size_hist, *nmulti, *wflag;         // the cleared region and its named parts
-    uint32_t *hist, *hist_off, *block_tot_h;                // partition pass
-    uint32_t* idx;
-    uint16_t* dig;                                          // 16-B aligned
-    uint64_t* entries;                                      // 8-B aligned
-    size_t words;                                           // of the whole layout
-};
-static SortWs carve_sort_ws(const SortDims& d, uint32_t* base) {
-    WsCarver c{base};
-    SortWs w{};
-    if (d.slices) {
-        w.slice_counts = c.take((size_t)d.nb * MSM_SLICES, 4);
-        w.slice_off = c.take((size_t)d.nb * MSM_SLICES + 4, 4);
-    }
-    w.counts = c.take(d.nb);
-    w.cleared = c.take(MSM_CLEARED_WORDS);
-    w.size_hist = w.cleared;
-    w.nmulti = w.size_hist + SIZE_BINS;
-    w.wflag = w.nmulti + 4;
-    w.offsets = c.take((size_t)d.nb + 1);
-    w.order = c.take(d.nb);
-    w.ntasks = c.take(d.nb);
-    w.toff = c.take((size_t)d.nb + 1);
-    if (d.slices) w.block_tot_s = c.take(scan_blocks_of(d.nb * MSM_SLICES));
-    w.block_tot = c.take(scan_blocks_of(d.nb));
-    if (d.hist_cnt) {
-        w.block_tot_h = c.take(scan_blocks_of(d.hist_cnt));
-        w.hist = c.take(d.hist_cnt);
-        w.hist_off = c.take((size_t)d.hist_cnt + 1);
-    }
-    w.idx = c.take(d.idx_cnt);
-    if (d.dig_words) w.dig = reinterpret_cast<uint16_t*>(c.take(d.dig_words, 4));
-    if (d.entries) w.entries = reinterpret_cast<uint64_t*>(c.take(2 * (size_t)d.idx_cnt, 2));
-    w.words = c.at;
-    return w;
-}
+// The knobs (MsmKnobs, read_knobs), the sort workspace (SortDims, SortWs, carve_sort_ws), the bucket regions (carve_buckets) and the
+// plan of a batch (plan_batch) are host-only and live in msm_plan.hpp.
+static_assert(sizeof(G1Affine) == MSM_AFFINE_BYTES && FR_MODULUS[0] == FrP::M(0) && FR_MODULUS[1] == FrP::M(1) && FR_MODULUS[2] == FrP::M(2) && FR_MODULUS[3] == FrP::M(3) &&
+              FR_MODULUS[4] == FrP::M(4) && FR_MODULUS[5] == FrP::M(5) && FR_MODULUS[6] == FrP::M(6) && FR_MODULUS[7] == FrP::M(7), "msm_plan.hpp restates the table entry size and the modulus");
 
 // exclusive scan of in[cnt] into out[cnt], the total to *total_out (nullable); block_tot: scan_blocks_of(cnt) words.
 // Block-local offsets: k_task_offsets (exclusive_scan) or the slice scan's own last pass adds the block totals.
@@ -1379,6 +1247,24 @@ static int reduce_window(zk_ctx* ctx, hipStream_t st, const G1Xyzz29* buckets, u
     return ZK_OK;
 }
 
+// The side streams and events of the batch pipelines, created on first use: stream2 and the ev_p1 / ev_p2 hand-over events
+// (msm_batch_tab); rotation: also stream2b, stream2c and ev_pipe (msm_batch_merged).
+static int ensure_side_streams(zk_ctx* ctx, bool rotation) {
+    if (!ctx->stream2) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+    if (!ctx->ev_p1[0])
+        for (int i = 0; i < 3; ++i) {
+            ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p1[i], hipEventDisableTiming));
+            ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[i], hipEventDisableTiming));
+        }
+    if (!rotation) return ZK_OK;
+    if (!ctx->stream2b) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2b, hipStreamNonBlocking));
+    if (!ctx->stream2c) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2c, hipStreamNonBlocking));
+    if (!ctx->ev_pipe) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_pipe, hipEventDisableTiming));
+    return ZK_OK;
+}
+// the context's stream is put back when a batch that switches it between its pipelines returns, error returns included
+struct StreamRestore { zk_ctx* c; hipStream_t s; ~StreamRestore() { c->stream = s; } };
+
 // bases_rp: device bases already in R' form (SRS cache) or nullptr -> converted into scratch
 // d_table (nullable): fixed-base window table for exactly this plan (W windows of tab_stride points)
 int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_bases, const G1Affine* d_bases_rp, const G1Affine* d_table, size_t tab_stride,
@@ -1402,7 +1288,9 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     const int red_g = short_chain ? RED_G_FOLDED : RED_G_WIDE;
     const uint32_t red_blocks = ((pl.B + red_g - 1) / red_g + RED_THREADS - 1) / RED_THREADS;
     const size_t max_tasks = (size_t)nb + std::max(((size_t)n * pl.W) / TASK_CAP, (size_t)TASK_TARGET) + 1;   // tasks <= points / task size + buckets
-    const size_t npts29 = (size_t)nb + (size_t)pl.W * red_blocks + max_tasks + pl.B;
+    // buckets | a partial per (window, reduction block) | task partials | the folded window
+    auto regions = [&](G1Xyzz29* base) { return carve_bucket_regions(nb, (size_t)pl.W * red_blocks, max_tasks, pl.B, base); };
+    const size_t npts29 = regions(nullptr).points;
     if (!d_table) tab_stride = 0; else d_bases_rp = d_table;
     const int red_W = d_table ? 1 : pl.W;     // windows the weighted reduction has to handle
     // bucket state is double-buffered: the reduction of MSM i (side stream) overlaps phase 1 of MSM i+1
@@ -1413,12 +1301,7 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     // fold on the side stream reads them while the main stream already recodes the next column)
     G1Xyzz* wsum_all = (G1Xyzz*)ctx->get_scratch(SC_MSM_RESULTS, sizeof(G1Xyzz) * pl.W * count + 4 * MSM_WFLAGS * count);
     if (!bkbuf[0] || !bkbuf[1] || !wsum_all) return ZK_ERR_OOM;
-    if (!ctx->stream2) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    if (!ctx->ev_p1[0])
-        for (int i = 0; i < 3; ++i) {
-            ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p1[i], hipEventDisableTiming));
-            ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[i], hipEventDisableTiming));
-        }
+    PK_TRY_MSM(ensure_side_streams(ctx, false));
 
     const dim3 gs((unsigned)((n + 255) / 256)), ts(256);
     if (!d_bases_rp) {
@@ -1432,10 +1315,7 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
     if (stage) { int rc = stage(stage_user, 0); if (rc) return rc; }
   for (size_t it = 0; it < count; ++it) {
     const int par = (int)(it & 1);
-    G1Xyzz29* buckets = (G1Xyzz29*)bkbuf[par];
-    G1Xyzz29* partial = buckets + nb;
-    G1Xyzz29* task_partial = partial + (size_t)pl.W * red_blocks;
-    G1Xyzz29* folded = task_partial + max_tasks;
+    const BucketRegions<G1Xyzz29> r = regions((G1Xyzz29*)bkbuf[par]);
     G1Xyzz* wsum = wsum_all + it * pl.W;
     uint32_t* wflag_it = reinterpret_cast<uint32_t*>(wsum_all + (size_t)pl.W * count) + it * MSM_WFLAGS;
     if (it >= 2) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[par], 0));   // reduce(it-2) must be done with this buffer
@@ -1444,12 +1324,12 @@ int msm_batch_tab(zk_ctx* ctx, const Fr* const* d_scalar_ptrs, size_t count, con
         PK_TRY_MSM(sort_digits(ctx, ctx->stream, w, pl, d_scalar_ptrs + it, 1, (uint64_t)n, n_pad, nullptr, nullptr));
     }
     ZK_HIP(ctx, hipMemcpyAsync(wflag_it, w.wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets", d_bases_rp, w, nb, max_tasks, buckets, task_partial, pl.c - 1, (uint64_t)tab_stride, w.wflag, 0, 0));
+    PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets", d_bases_rp, w, nb, max_tasks, r.buckets, r.task_partial, pl.c - 1, (uint64_t)tab_stride, w.wflag, 0, 0));
     ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
     ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_p1[par], 0));
     {   // latency-bound tail on the side stream: it hides under the next MSM's phase 1
         ZkProfScope ps(ctx, "msm_reduce", ctx->stream2);
-        PK_TRY_MSM(reduce_window(ctx, ctx->stream2, buckets, pl.B, d_table ? pl.W : 0, folded, wflag_it, (uint32_t)red_W, 1, short_chain, partial, wsum, nullptr, nullptr, 0));
+        PK_TRY_MSM(reduce_window(ctx, ctx->stream2, r.buckets, pl.B, d_table ? pl.W : 0, r.folded, wflag_it, (uint32_t)red_W, 1, short_chain, r.partial, wsum, nullptr, nullptr, 0));
     }
     ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], ctx->stream2));
     if (stage && it + 1 < count) { int rc = stage(stage_user, it + 1); if (rc) return rc; }
@@ -1504,33 +1384,6 @@ __global__ void __launch_bounds__(1024) k_msm_tails(const Fr* const* __restrict_
     }
 }
 // ---- merged-window MSM over an SRS window table ----------------------------------------------------
-static MsmPlan make_plan_merged(uint32_t k_srs, const MsmKnobs& kn) {
-    int c = (int)k_srs;
-    if (c < MSM_M_MIN_C) c = MSM_M_MIN_C;
-    if (c > MSM_M_MAX_C) c = MSM_M_MAX_C;
-    if (kn.c >= MSM_M_MIN_C && kn.c <= MSM_M_MAX_C) c = kn.c;   // measurement knob
-    MsmPlan p;
-    p.c = c;
-    p.W = (256 + c - 1) / c;
-    p.B = 1u << (c - 1);
-    // largest shift that keeps the top digit (leading bits of a canonical scalar, plus the carry of the window below)
-    // at or below 2^(c-1)
-    const int low = c * (p.W - 1);
-    uint64_t top_max = 1;
-    if (low < 254) {
-        uint64_t v = 0;      // (modulus - 1) >> low, from the 8 x 32-bit limbs (the modulus is odd: -1 only clears bit 0)
-        for (int b = 0; b < 40 && low + b < 256; ++b) {
-            const int bit = low + b;
-            const uint32_t limb = bit < 32 ? FrP::M(0) - 1u : FrP::M(bit >> 5);
-            v |= (uint64_t)((limb >> (bit & 31)) & 1u) << b;
-        }
-        top_max = v + 1;
-    }
-    p.top_shift = 0;
-    while (p.top_shift + 1 <= c - 1 && (top_max << (p.top_shift + 1)) <= (1ull << (c - 1))) ++p.top_shift;
-    if (kn.top_shift >= 0 && kn.top_shift <= p.top_shift) p.top_shift = kn.top_shift;   // measurement knob
-    return p;
-}
 template <bool SCATTER>
 static void launch_partition(int c, dim3 grid, hipStream_t st, const Fr* scalars, uint64_t n, int range_bits, uint32_t* hist, const uint32_t* hist_off, uint64_t* entries, uint64_t tab_stride, int top_shift,
                              const MsmCol* cols = nullptr, const uint32_t* ctr = nullptr) {
@@ -1608,358 +1461,146 @@ static int sort_gm(zk_ctx* ctx, hipStream_t st, const SortWs& w, const MsmPlan& 
     ZK_CHECK_LAUNCH(ctx);
     return sort_entries(ctx, st, w, nbins, nwg, range_bits, cnt * sets * pl.B, true);
 }
-// d_table: [W][tab_stride] affine points, table[w][i] = 2^(c w) * P_i in R' form, built for plan `pl`.
+// ---- a batch over an SRS with its merged-window table ---------------------------------------------------------------------
+// d_table: [W][tab_stride] affine points, table[w][i] = 2^(c w) * P_i in R' form, built for the merged plan.
 // Same pipelining as msm_batch_tab: the reduction of MSM i runs on the side stream under MSM i + 1.
-// narrow[it] != 0 (with d_table_n, the per-window table of plan pl_n): column `it` is expected to fill
-// only a few windows (witness columns of small values, selectors, lookup multiplicities) and takes the
-// per-window path -- bucket sets of empty windows are never touched there, whereas the merged path
-// always pays for its 2^(c-1) shared buckets.  The two paths alternate freely inside one pipelined batch.
-// group_cap != 0: upper bound on the columns of a GM group.  When the sort workspace of the groups does not fit,
-// *smaller_cap receives the next cap to try (see msm_batch_merged) and nothing has been enqueued.
-static int msm_batch_merged_capped(zk_ctx* ctx, const MsmKnobs& kn, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_table, size_t tab_stride, const MsmPlan& pl,
-                                   size_t n, G1Affine* h_out, MsmStageFn stage, void* stage_user, const G1Affine* d_table_n, const MsmPlan* pl_n, const uint8_t* narrow, uint32_t group_cap, uint32_t* smaller_cap) {
-    if (count == 0) return ZK_OK;
-    if (n == 0) { memset(h_out, 0, sizeof(G1Affine) * count); return ZK_OK; }
-    const auto t_batch0 = std::chrono::steady_clock::now();
-    bool any_narrow = false;
-    if (d_table_n && pl_n && narrow) for (size_t i = 0; i < count; ++i) any_narrow |= narrow[i] == 1;
-    // the per-window path indexes n * W entries with 32 bits; decided BEFORE the blinded tails are split off: a column that
-    // takes the merged path over all n rows must not have its tail committed a second time by k_msm_tails
-    if (any_narrow && (uint64_t)n * pl_n->W >= (1ull << 32)) any_narrow = false;
-    // blinded tails of the hint-1 columns (zk_ctx::msm_blinded_tail): committed by k_msm_tails, the main MSM stops in front of them
-    const uint32_t tail_rows = (any_narrow && ctx->msm_blinded_tail && (size_t)ctx->msm_blinded_tail + 1024 <= n && ctx->msm_blinded_tail <= 256) ? ctx->msm_blinded_tail : 0u;
-    const uint64_t n_narrow = (uint64_t)n - tail_rows;
-    // ---- per-window ("narrow") path: sizes and workspace, as in msm_batch_tab with a window table
-    const MsmPlan pn = any_narrow ? *pl_n : MsmPlan{4, 64, 8};
-    // Consecutive small-valued columns share ONE launch sequence: column j of a group owns windows [j W, (j + 1) W) of a
-    // (group x W)-window MSM over the same per-window table -- digits, LDS sweeps, scans, task split, accumulation and
-    // combination run once per group, the fold / reduction with the column on blockIdx.y.  Such a column is a chain of sixteen
-    // small, latency-bound launches (a few hundred thousand entries); a group amortises every launch over up to eight columns
-    // (MSM_WFLAGS window flags).  ZK_MSM_NARROW_GROUP=1 turns it off, 2 / 4 / 8 set the group size (measurement knob; 2^20 rows,
-    // 30-bit values: 0.68 / 0.51 / 0.43 / 0.38 ms per column, tools/gpu_r3u.sh).
-    uint32_t NG = 1;
-    if (any_narrow) {
-        NG = std::min<uint32_t>((uint32_t)GM_MAX_COLS, MSM_WFLAGS / (uint32_t)pn.W);       // sixteen at c = 16: a group's dozen short launches (scans, size bins, task split) cost the same for eight
-                                                                                            // columns or sixteen -- 60/30/10 columns 0.265 -> 0.255 ms each in a batch, the sort 0.81 ms per eight -> 1.45 per sixteen
-        if (kn.narrow_group >= 1 && kn.narrow_group <= GM_MAX_COLS) NG = std::min<uint32_t>((uint32_t)kn.narrow_group, MSM_WFLAGS / (uint32_t)pn.W);
-        if (group_cap && NG > group_cap) NG = group_cap;
-        while (NG > 1 && (uint64_t)n * pn.W * NG >= (1ull << 32)) --NG;
-        if (NG < 1) NG = 1;
+// narrow[it] == 1 (with d_table_n, the per-window table): column `it` is expected to fill only a few windows (witness columns
+// of small values, selectors, lookup multiplicities) and takes the per-window table -- bucket sets of empty windows are never
+// touched there, whereas the merged path always pays for its 2^(c-1) shared buckets.  The kinds of step alternate freely
+// inside one pipelined batch.  plan_batch (msm_plan.hpp) decides every size, mode and step; the functions below execute a
+// plan and compute no size or offset themselves.
+struct MsmBatchIo {
+    const Fr* const* d_scalar_ptrs;
+    const uint8_t* narrow;
+    const G1Affine *d_table, *d_table_n;
+    G1Affine* h_out;
+    MsmStageFn stage;
+    void* stage_user;
+    std::chrono::steady_clock::time_point t_batch0;
+    uint32_t* ws;                   // plan.copies sort workspaces of plan.words
+    char* bkbuf[MSM_GRAPH_PIPES];   // bucket buffers of plan.npts29 points: three in rotation, graph mode one per pipeline
+    G1Xyzz* wsum_all;               // one window sum per MSM, then one private copy of the window flags per MSM of the per-window sort
+};
+// One step's own inputs and outputs.  What differs between the plain launches and a captured step is a field here, set by the driver.
+struct MsmStepIo {
+    const Fr* const* scalars;       // the step's columns; nullptr (graph mode): the column is cols[*ctr]
+    const MsmCol* cols;             // graph mode: the device column table, this pipeline's counter and what the last kernel adds to it
+    uint32_t* ctr;
+    uint32_t ctr_step;
+    G1Xyzz* out;                    // window sum of the step's first column; nullptr (graph mode): cols[*ctr].out
+    hipStream_t st, side;           // sort and accumulation; weighted bucket sum
+    uint32_t* wflag_copy;           // per-window step: private copy of the window flags for the fold on the side stream (the next sort of this
+                                    // workspace clears them meanwhile); nullptr: the fold comes behind the sort on one stream and reads the sort's own
+    hipEvent_t buckets_free;        // nullable: the accumulation waits for it -- the reduction that used this bucket buffer last
+    hipEvent_t accumulated;         // nullable: recorded behind the combination, `side` waits for it; nullptr: side == st
+    bool levelled_sum;              // dense step: the levelled reduction (wsum_enqueue) instead of the one-launch one
+};
+// sort -> accumulate / combine -> reduce of one step: the argument lists of the stage functions per kind of step
+static int enqueue_step(zk_ctx* ctx, const MsmBatchPlan& bp, const MsmBatchIo& io, const MsmStep& s, const SortWs& w, const BucketRegions<G1Xyzz29>& r, const MsmStepIo& sio) {
+    const MsmPlan &pl = bp.pl, &pn = bp.pn;
+    const uint64_t tab_stride = (uint64_t)bp.tab_stride;
+    const bool nar = s.kind == STEP_WINDOW || s.kind == STEP_GM;
+    const uint32_t* fold_flags = sio.wflag_copy ? sio.wflag_copy : w.wflag;
+    {
+        ZkProfScope ps(ctx, "msm_sort", sio.st);
+        if (s.kind == STEP_GM) PK_TRY_MSM(sort_gm(ctx, sio.st, w, pn, sio.scalars, s.cols, bp.n_narrow, tab_stride, bp.range_bits_G, bp.nwgG, bp.bpcG, bp.SG));
+        else if (s.kind == STEP_WINDOW) {
+            PK_TRY_MSM(sort_digits(ctx, sio.st, w, pn, sio.scalars, s.cols, bp.n_narrow, bp.n_pad, sio.cols, sio.ctr));
+            if (sio.wflag_copy) ZK_HIP(ctx, hipMemcpyAsync(sio.wflag_copy, w.wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, sio.st));
+        } else PK_TRY_MSM(sort_partitioned(ctx, sio.st, w, pl, sio.scalars ? sio.scalars[0] : nullptr, (uint64_t)bp.n, tab_stride, bp.range_bits, bp.nwg, bp.staged_scatter, s.kind == STEP_DENSE, sio.cols, sio.ctr));
     }
-    const uint32_t Wg = (uint32_t)pn.W * NG;
-    const uint32_t nbN = Wg * pn.B;
-    const uint64_t n_pad = ((uint64_t)n + 16 * MSM_SLICES - 1) & ~(uint64_t)(16 * MSM_SLICES - 1);
-    const SortDims dims_N{nbN, true, 0, (uint64_t)n * Wg, (size_t)(n_pad * Wg + 1) / 2 + 4, false};
-    // Groups of small-valued columns, sorted like the merged path ("GM"; ZK_MSM_NARROW_GM=0 keeps the digit matrix + LDS sweeps):
-    // the digit matrix of a group is 16 x n codes per column of which a witness-like column fills a tenth, and every row of it
-    // was streamed by sixteen range workgroups, twice -- 0.22 ms of sort per column for 0.12 ms of accumulation.  Here the non-zero
-    // digits become entries keyed by (column, bucket) -- the per-window table gives every window's bucket b the same weight, so a
-    // column needs ONE set of 2^(c-1) buckets, not one per window -- and go through the merged path's partition / one-launch
-    // counting sort: column j of the group owns partitions [j * bpc, (j + 1) * bpc) and buckets [j B, (j + 1) B); the fold of the
-    // windows disappears (the accumulation already sums them), reduction and window sum run per column as before.
-    const bool gm = any_narrow && pn.c >= MSM_M_MIN_C && pn.c <= 16 && NG <= (uint32_t)GM_MAX_COLS && kn.narrow_gm != 0;
-    // A column's windows are dealt over SG bucket sets (window w -> set w mod SG): a witness-like column (10 % field-sized cells) puts
-    // ~2 M entries into its buckets -- 61 per bucket with one set of 2^15, every bucket split into two unequal tasks and put together
-    // again afterwards (accumulation + combination 2.2 ms per group of eight against the 1.0 ms the additions cost); with two sets
-    // the buckets hold 26-35 entries, one task each.  ZK_MSM_GM_SETS = 1 / 2 / 4 (measurement knob).
-    uint32_t SG = 2;
-    if (kn.gm_sets == 1 || kn.gm_sets == 2 || kn.gm_sets == 4) SG = (uint32_t)kn.gm_sets;
-    int range_bits_G = pn.c - 1 - 7;                                  // 128 * SG partitions per column of 2^(c-8) buckets each
-    if (range_bits_G < 0) range_bits_G = 0;
-    const uint32_t bpcG = (SG * pn.B) >> range_bits_G;                // partitions per column
-    const uint32_t perm_G = ((uint32_t)range_bits_G << 8) | (uint32_t)(pn.c - 1 - range_bits_G);      // the GM sort numbers buckets low bits first (perm_true)
-    const uint32_t nwgG = (uint32_t)((n_narrow + MSM_M_CHUNK - 1) / MSM_M_CHUNK);      // partition workgroups per column
-    const SortDims dims_G{NG * SG * pn.B, false, NG * bpcG * nwgG, (uint64_t)n * pn.W * NG, 0, true};      // entries, worst case: every digit of every column non-zero
-    const size_t words_N = any_narrow ? std::max(carve_sort_ws(dims_N, nullptr).words, gm ? carve_sort_ws(dims_G, nullptr).words : 0) : 0;
-    const uint32_t red_blocks_N = ((pn.B + RED_G_WIDE - 1) / RED_G_WIDE + RED_THREADS - 1) / RED_THREADS;
-    const size_t max_tasks_N = (size_t)nbN + std::max(((size_t)n * Wg) / TASK_CAP, (size_t)TASK_TARGET) + 1;
-    const size_t npts29_N = any_narrow ? (size_t)nbN + (size_t)red_blocks_N * NG * 4 + max_tasks_N + (size_t)pn.B * NG : 0;      // x 4: the GM path reduces up to four bucket sets per column
-    const uint32_t nb = pl.B;
-    const uint64_t max_entries = (uint64_t)n * pl.W;
-    // table indices carry the sign in bit 31, cursors are 32-bit
-    if ((uint64_t)pl.W * tab_stride >= (1ull << 31) || max_entries >= (1ull << 32)) return ctx->fail(ZK_ERR_UNSUPPORTED, "MSM of %zu points x %d windows exceeds the 32-bit entry space: split it", n, pl.W);
-    int range_bits = pl.c - 1;
-    if (range_bits > MSM_RANGE_MAX_BITS) range_bits = MSM_RANGE_MAX_BITS;
-    // one-launch partition sort (k_msm_m_binsort) when 1024 partitions are small enough for its LDS staging buffer;
-    // ZK_MSM_BINSORT=0 keeps the sliced count / scan / scatter sequence (measurement knob)
-    bool binsort = kn.binsort != 0;
-    if (binsort) {
-        int rb = pl.c - 1 - 10;
-        if (rb < 0) rb = 0;
-        const uint64_t per_partition = max_entries / (nb >> rb);
-        if (per_partition + per_partition / 8 <= MSM_M_STAGE) range_bits = rb;
-        else binsort = false;
+    // only the accumulation writes the bucket buffer: the sort of this MSM runs while the reduction that used the buffer last finishes
+    if (sio.buckets_free) ZK_HIP(ctx, hipStreamWaitEvent(sio.st, sio.buckets_free, 0));
+    // GM: one bucket set per column and set, accumulated like a merged MSM (idx holds table indices); per-window: the table window from the bucket
+    if (s.kind == STEP_GM) PK_TRY_MSM(accumulate_combine(ctx, sio.st, "msm_buckets_narrow", io.d_table_n, w, r.nb, r.tasks, r.buckets, r.task_partial, 0, 0, nullptr, 0, bp.perm_G));
+    else if (s.kind == STEP_WINDOW) PK_TRY_MSM(accumulate_combine(ctx, sio.st, "msm_buckets_narrow", io.d_table_n, w, r.nb, r.tasks, r.buckets, r.task_partial, pn.c - 1, tab_stride, fold_flags, s.cols > 1 ? (uint32_t)pn.W : 0u, 0));
+    else PK_TRY_MSM(accumulate_combine(ctx, sio.st, "msm_buckets", io.d_table, w, r.nb, r.tasks, r.buckets, r.task_partial, 0, 0, nullptr, 0, 0));
+    if (sio.accumulated) {
+        ZK_HIP(ctx, hipEventRecord(sio.accumulated, sio.st));
+        ZK_HIP(ctx, hipStreamWaitEvent(sio.side, sio.accumulated, 0));
     }
-    uint32_t chunk = MSM_M_CHUNK;
-    if (kn.chunk >= 256 && kn.chunk <= 65536) chunk = (uint32_t)kn.chunk;   // measurement knob
-    // scatter with LDS-staged runs (k_msm_m_scatter_staged): window sizes whose 1024 x W entries fit the LDS, and only next to the
-    // one-launch partition sort (same 1024-partition layout); ZK_MSM_STAGED=0 keeps the direct scatter (measurement knob)
-    const bool staged_scatter = binsort && pl.c >= 19 && scatter_staged_lds(pl.W) <= (size_t)150 * 1024 && kn.staged != 0;
-    if (staged_scatter) chunk = MSM_M_SCHUNK;
-    const uint32_t nwg = (uint32_t)((n + chunk - 1) / chunk);
-    const SortDims dims_M{nb, true, (nb >> range_bits) * nwg, max_entries, 0, true};
-    const size_t words_M = carve_sort_ws(dims_M, nullptr).words;
-    const size_t words = (std::max(words_M, words_N) + 63) & ~(size_t)63;      // per copy: every copy starts 256-B aligned
-    // Below 2^20 points an MSM does not fill the device: its sort / accumulation / combination is a chain of some twenty
-    // short launches.  Two such chains then run side by side -- even columns on the context's stream, odd columns on the
-    // third side stream, each with its own sort workspace -- and hide each other's latency.  ZK_MSM_PIPES overrides.
-    int npipe = (n <= ((size_t)1 << 19) && count >= 2) ? 2 : 1;
-    if (kn.pipes == 1 || (kn.pipes == 2 && count >= 2)) npipe = kn.pipes;
-    // Graph mode (below): the launch sequence of a column is captured once per pipeline and replayed -- at these sizes the
-    // host's launch rate, ~30 API calls per column, is what bounds a batch.  ZK_MSM_GRAPH=0 disables it.
-    const bool want_graph = n <= ((size_t)1 << 19) && n >= 1024 && count >= 4 && !ctx->prof_on && !ctx->msm_graph_broken && kn.graph != 0 && !(any_narrow && NG > 1);
-    constexpr int GP = 4;                     // pipelines of the graph mode: the context's stream and the three side streams
-    uint32_t* ws = (uint32_t*)ctx->get_scratch(SC_MSM_KEYS, words * 4 * (want_graph ? GP : npipe));      // one copy per pipeline
-    if (!ws && any_narrow && NG > 1 && words_N > words_M) {
-        (void)hipGetLastError();
-        *smaller_cap = NG / 2;
-        return ZK_ERR_OOM;
-    }
-    if (!ws) return ZK_ERR_OOM;
-    const uint32_t red_pts = nb / 4 + 1024;       // scratch of the weighted bucket sum (group sums of every level, partials)
-    const size_t max_tasks = (size_t)nb + std::max((size_t)(max_entries / TASK_CAP), (size_t)TASK_TARGET) + 1;
-    const size_t npts29 = std::max((size_t)nb + red_pts + max_tasks, npts29_N);
-    // three bucket buffers in rotation: the reduction of MSM it (a latency-bound chain on a side stream, about as long
-    // as a whole MSM) must only be finished when MSM it + 3 starts to accumulate
-    char* bkbuf[3];
-    bkbuf[0] = (char*)ctx->get_scratch(SC_MSM_BUCKETS, sizeof(G1Xyzz29) * npts29);
-    bkbuf[1] = count > 1 ? (char*)ctx->get_scratch(SC_MSM_BUCKETS2, sizeof(G1Xyzz29) * npts29) : bkbuf[0];
-    bkbuf[2] = count > 2 ? (char*)ctx->get_scratch(SC_MSM_BUCKETS3, sizeof(G1Xyzz29) * npts29) : bkbuf[0];
-    // one window sum per MSM, then one private copy of the window flags per MSM of the per-window path
-    G1Xyzz* wsum_all = (G1Xyzz*)ctx->get_scratch(SC_MSM_RESULTS, sizeof(G1Xyzz) * count + 4 * MSM_WFLAGS * count);
-    if (!bkbuf[0] || !bkbuf[1] || !bkbuf[2] || !wsum_all) return ZK_ERR_OOM;
-    if (!ctx->stream2) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    if (!ctx->ev_p1[0])
-        for (int i = 0; i < 3; ++i) {
-            ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p1[i], hipEventDisableTiming));
-            ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_p2[i], hipEventDisableTiming));
-        }
-    // The reductions of consecutive MSMs rotate over three side streams: each is a chain of short
-    // launches (latency, not throughput), and with witness columns that fill few windows it can take
-    // longer than the sort + accumulation of the next column.
-    if (!ctx->stream2b) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2b, hipStreamNonBlocking));
-    if (!ctx->stream2c) ZK_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2c, hipStreamNonBlocking));
-    if (!ctx->ev_pipe) ZK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_pipe, hipEventDisableTiming));
-    // enqueues the tails kernel on the context's stream (all columns are on the device by then) and returns where its results land
+    ZkProfScope ps(ctx, nar ? "msm_reduce_narrow" : "msm_reduce", sio.side);
+    // GM: the SG sets of a column are SG "windows" of equal weight: reduced separately, their partials summed with the column's;
+    // per-window: the occupied windows of every column of the group are folded, one window reduced per column
+    if (s.kind == STEP_GM) return reduce_window(ctx, sio.side, r.buckets, pn.B, 0, nullptr, nullptr, s.cols, bp.SG, false, r.partial, sio.out, sio.cols, sio.ctr, sio.ctr_step);
+    if (s.kind == STEP_WINDOW) return reduce_window(ctx, sio.side, r.buckets, pn.B, pn.W, r.folded, fold_flags, s.cols, 1, false, r.partial, sio.out, sio.cols, sio.ctr, sio.ctr_step);
+    // dense: one launch with a scalar multiplication per lane has the shorter dependent chain (about 60 additions against 150 over
+    // the levels of wsum_enqueue), at twice the work
+    if (sio.levelled_sum) return wsum_enqueue(ctx, sio.side, r.buckets, r.nb, r.partial, sio.out);
+    return reduce_window(ctx, sio.side, r.buckets, r.nb, 0, nullptr, nullptr, 1, 1, false, r.partial, sio.out, sio.cols, sio.ctr, sio.ctr_step);
+}
+// the batch is enqueued: the blinded tails (all columns are on the device by now), one download of the window sums and tails
+// behind everything on the context's stream, host tails
+static int finish_batch(zk_ctx* ctx, const MsmKnobs& kn, const MsmBatchPlan& bp, const MsmBatchIo& io, const char* how) {
+    const size_t count = bp.count;
     G1Xyzz* tails_dev = nullptr;
-    auto enqueue_tails = [&]() -> int {
-        if (!tail_rows) return ZK_OK;
+    if (bp.tail_rows) {
         const size_t off_flags = (sizeof(void*) * count + 255) & ~(size_t)255, off_out = (off_flags + count + 255) & ~(size_t)255;
         char* tb = (char*)ctx->get_scratch(SC_MSM_TAILS, off_out + sizeof(G1Xyzz) * count);
         if (!tb) return ZK_ERR_OOM;
-        ZK_HIP(ctx, hipMemcpyAsync(tb, d_scalar_ptrs, sizeof(void*) * count, hipMemcpyHostToDevice, ctx->stream));
-        ZK_HIP(ctx, hipMemcpyAsync(tb + off_flags, narrow, count, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(ctx, hipMemcpyAsync(tb, io.d_scalar_ptrs, sizeof(void*) * count, hipMemcpyHostToDevice, ctx->stream));
+        ZK_HIP(ctx, hipMemcpyAsync(tb + off_flags, io.narrow, count, hipMemcpyHostToDevice, ctx->stream));
         tails_dev = (G1Xyzz*)(tb + off_out);
-        hipLaunchKernelGGL(k_msm_tails, dim3((unsigned)count), dim3(1024), 0, ctx->stream, (const Fr* const*)tb, (const uint8_t*)(tb + off_flags), n_narrow, tail_rows,
-                           d_table, (uint64_t)tab_stride, pl.c, pl.W, pl.top_shift, tails_dev);
+        hipLaunchKernelGGL(k_msm_tails, dim3((unsigned)count), dim3(1024), 0, ctx->stream, (const Fr* const*)tb, (const uint8_t*)(tb + off_flags), bp.n_narrow, bp.tail_rows,
+                           io.d_table, (uint64_t)bp.tab_stride, bp.pl.c, bp.pl.W, bp.pl.top_shift, tails_dev);
         ZK_CHECK_LAUNCH(ctx);
-        return ZK_OK;
-    };
-    // the batch is enqueued: one download of the window sums (and tails) behind everything on the context's stream, host tails
-    auto finish = [&](const char* how) -> int {
-        PK_TRY_MSM(enqueue_tails());
-        std::vector<G1Xyzz> hw(count), ht(tail_rows ? count : 0);
-        if (tail_rows) ZK_HIP(ctx, hipMemcpyAsync(ht.data(), tails_dev, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
-        ZK_HIP(ctx, hipMemcpyAsync(hw.data(), wsum_all, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
-        const auto t_enq = std::chrono::steady_clock::now();
-        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (kn.trace) {
-            const auto t_done = std::chrono::steady_clock::now();
-            fprintf(stderr, "[zk msm] batch of %zu x 2^%.0f%s: host enqueue %.3f ms, device drained %.3f ms later\n", count, log2((double)n), how,
-                    std::chrono::duration<double, std::milli>(t_enq - t_batch0).count(), std::chrono::duration<double, std::milli>(t_done - t_enq).count());
-        }
-        for (size_t it = 0; it < count; ++it) {
-            if (tail_rows && narrow[it] == 1) host::msm_tail2(hw.data() + it, ht.data() + it, h_out + it);
-            else host::msm_tail(hw.data() + it, 1, pl.c, h_out + it);
-        }
-        return ZK_OK;
-    };
-    if (want_graph) {
-        // ---- graph mode: GP linear pipelines, column it on pipeline it % GP (stream, sort workspace and bucket buffer of its own;
-        // the reduction runs on the same stream: one launch, short chain), one hipGraphLaunch per column.
-        hipStream_t P[GP] = {ctx->stream, ctx->stream2, ctx->stream2b, ctx->stream2c};
-        char* bk[GP] = {bkbuf[0], bkbuf[1], bkbuf[2], (char*)ctx->get_scratch(SC_MSM_BUCKETS4, sizeof(G1Xyzz29) * npts29)};
-        char* desc = (char*)ctx->get_scratch(SC_MSM_DESC, sizeof(MsmCol) * count + 256);
-        if (!bk[3] || !desc) return ZK_ERR_OOM;
-        uint32_t* ctr_dev = (uint32_t*)desc;                                  // GP counters, then the table
-        MsmCol* cols_dev = (MsmCol*)(desc + 256);
-        {
-            std::vector<MsmCol> hcols(count);
-            for (size_t i = 0; i < count; ++i) hcols[i] = MsmCol{d_scalar_ptrs[i], wsum_all + i};
-            const uint32_t hctr[GP] = {0, 1, 2, 3};
-            ZK_HIP(ctx, hipMemcpyAsync(cols_dev, hcols.data(), sizeof(MsmCol) * count, hipMemcpyHostToDevice, P[0]));
-            ZK_HIP(ctx, hipMemcpyAsync(ctr_dev, hctr, sizeof(hctr), hipMemcpyHostToDevice, P[0]));
-            ZK_HIP(ctx, hipStreamSynchronize(P[0]));                          // the host copies live on this stack frame
-        }
-        ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, P[0]));
-        for (int p = 1; p < GP; ++p) ZK_HIP(ctx, hipStreamWaitEvent(P[p], ctx->ev_pipe, 0));
-        struct StreamRestoreG { zk_ctx* c; hipStream_t s; ~StreamRestoreG() { c->stream = s; } } restore_g{ctx, ctx->stream};
-        // the launch sequence of one column of `kind` on pipeline p, enqueued on ctx->stream (being captured): the stage functions
-        // of the plain path as one linear chain, the column read through (cols_dev, ctr_dev + p); groups are off here (NG == 1)
-        auto enqueue = [&](int kind, int p) -> int {
-            hipStream_t st = ctx->stream;
-            G1Xyzz29* buckets = (G1Xyzz29*)bk[p];
-            uint32_t* ctr = ctr_dev + p;
-            if (kind == 0) {           // per-window path over the narrow table
-                const SortWs w = carve_sort_ws(dims_N, ws + (size_t)p * words);
-                G1Xyzz29* partialN = buckets + nbN;
-                G1Xyzz29* task_partialN = partialN + (size_t)red_blocks_N * NG;
-                G1Xyzz29* folded = task_partialN + max_tasks_N;
-                PK_TRY_MSM(sort_digits(ctx, st, w, pn, nullptr, 1, n_narrow, n_pad, cols_dev, ctr));
-                PK_TRY_MSM(accumulate_combine(ctx, st, "msm_buckets_narrow", d_table_n, w, nbN, max_tasks_N, buckets, task_partialN, pn.c - 1, (uint64_t)tab_stride, w.wflag, 0, 0));
-                // the window flags are still this column's when the fold reads them: the next column of this pipeline comes behind it on the same stream
-                return reduce_window(ctx, st, buckets, pn.B, pn.W, folded, w.wflag, 1, 1, false, partialN, nullptr, cols_dev, ctr, (uint32_t)GP);
-            }
-            // merged-window path (kind 1: one-launch partition sort, kind 2: sliced sort)
-            const SortWs w = carve_sort_ws(dims_M, ws + (size_t)p * words);
-            G1Xyzz29* partial = buckets + nb;
-            G1Xyzz29* task_partial = partial + red_pts;
-            PK_TRY_MSM(sort_partitioned(ctx, st, w, pl, nullptr, (uint64_t)n, (uint64_t)tab_stride, range_bits, nwg, staged_scatter, kind == 1, cols_dev, ctr));
-            PK_TRY_MSM(accumulate_combine(ctx, st, "msm_buckets", d_table, w, nb, max_tasks, buckets, task_partial, 0, 0, nullptr, 0, 0));
-            return reduce_window(ctx, st, buckets, nb, 0, nullptr, nullptr, 1, 1, false, partial, nullptr, cols_dev, ctr, (uint32_t)GP);
-        };
-        if (stage) { int rc = stage(stage_user, 0); if (rc) return rc; }
-        bool fallback = false;
-        for (size_t it = 0; it < count && !fallback; ++it) {
-            const int p = (int)(it % GP);
-            const int kind = (any_narrow && narrow[it] == 1) ? 0 : ((binsort && !(narrow && narrow[it] == 2)) ? 1 : 2);
-            ctx->stream = P[p];
-            // A graph is tied to every value baked into a kernel argument or a grid of `enqueue`, and the key holds them all.  They are
-            // the arguments of the stage functions there: the two plans (c fixes W, B and the sweep's range bits; top_shift apart), both
-            // tables and their stride, n and n_narrow (n_pad, the task bounds), the merged sort's range_bits, nwg and staged scatter
-            // (kind holds binsort), the column table and counters (desc), the bucket buffer, and the workspace: its base, the
-            // stride of a copy and the pipeline give the copy, the dimensions above (functions of the plans, n, range_bits and nwg)
-            // every pointer into it.  ZK_MSM_TOP_SHIFT and ZK_MSM_CHUNK change top_shift and nwg without changing any address.
-            const std::vector<uint64_t> key_tuple = {(uint64_t)kind, (uint64_t)p, (uint64_t)n, (uint64_t)pl.c, (uint64_t)pn.c, (uint64_t)(uintptr_t)d_table, (uint64_t)(uintptr_t)d_table_n, (uint64_t)tab_stride,
-                                                     (uint64_t)(uintptr_t)ws, (uint64_t)words, (uint64_t)(uintptr_t)bk[p], (uint64_t)(uintptr_t)desc, (uint64_t)staged_scatter, (uint64_t)range_bits, n_narrow,
-                                                     (uint64_t)pl.top_shift, (uint64_t)nwg};
-            uint64_t key = 1469598103934665603ull;
-            for (uint64_t v : key_tuple) key = (key ^ v) * 1099511628211ull;
-            hipGraphExec_t exec = nullptr;
-            auto found = ctx->msm_graphs.find(key);
-            if (found != ctx->msm_graphs.end() && ctx->msm_graph_keys[key] != key_tuple) {       // a 64-bit hash collision: the stale graph goes
-                (void)hipGraphExecDestroy((hipGraphExec_t)found->second);
-                ctx->msm_graphs.erase(found);
-                found = ctx->msm_graphs.end();
-            }
-            if (found != ctx->msm_graphs.end()) exec = (hipGraphExec_t)found->second;
-            else {
-                // graphs bake scratch addresses in; when the scratch arenas were reallocated since, the old entries can never be
-                // hit again: the cache is emptied when it grows past what one key / size mix needs
-                if (ctx->msm_graphs.size() >= 48) {
-                    ZK_HIP(ctx, hipStreamSynchronize(P[0]));
-                    for (int q = 1; q < GP; ++q) ZK_HIP(ctx, hipStreamSynchronize(P[q]));
-                    for (auto& kv : ctx->msm_graphs) (void)hipGraphExecDestroy((hipGraphExec_t)kv.second);
-                    ctx->msm_graphs.clear();
-                    ctx->msm_graph_keys.clear();
-                }
-                hipGraph_t graph = nullptr;
-                bool ok = hipStreamBeginCapture(P[p], hipStreamCaptureModeRelaxed) == hipSuccess;
-                int rc_e = ok ? enqueue(kind, p) : ZK_ERR_HIP;
-                if (ok) ok = hipStreamEndCapture(P[p], &graph) == hipSuccess && graph != nullptr;
-                ok = ok && rc_e == ZK_OK && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (graph) (void)hipGraphDestroy(graph);
-                if (!ok) {
-                    const hipError_t e = hipGetLastError();
-                    if (kn.trace) fprintf(stderr, "[zk msm] graph capture failed (rc %d, %s): plain launches from now on\n", rc_e, hipGetErrorString(e));
-                    ctx->msm_graph_broken = true; fallback = true; break;
-                }
-                ctx->msm_graphs[key] = (void*)exec;
-                ctx->msm_graph_keys[key] = key_tuple;
-            }
-            if (hipGraphLaunch(exec, P[p]) != hipSuccess) {
-                const hipError_t e = hipGetLastError();
-                if (kn.trace) fprintf(stderr, "[zk msm] graph replay failed (%s): plain launches from now on\n", hipGetErrorString(e));
-                ctx->msm_graph_broken = true; fallback = true; break;
-            }
-            if (stage && it + 1 < count) { ctx->stream = P[(it + 1) % GP]; int rc = stage(stage_user, it + 1); if (rc) return rc; }
-        }
-        ctx->stream = P[0];
-        for (int p = 1; p < GP; ++p) {
-            ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[p - 1], P[p]));
-            ZK_HIP(ctx, hipStreamWaitEvent(P[0], ctx->ev_p2[p - 1], 0));
-        }
-        if (!fallback) return finish(" (graph replay)");
-        // capture or replay failed: drain what was launched and take the plain path below for the whole batch (a staging
-        // callback is simply asked again: uploading a column twice and redoing its transform are idempotent)
-        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    std::vector<G1Xyzz> hw(count), ht(bp.tail_rows ? count : 0);
+    if (bp.tail_rows) ZK_HIP(ctx, hipMemcpyAsync(ht.data(), tails_dev, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
+    ZK_HIP(ctx, hipMemcpyAsync(hw.data(), io.wsum_all, sizeof(G1Xyzz) * count, hipMemcpyDeviceToHost, ctx->stream));
+    const auto t_enq = std::chrono::steady_clock::now();
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (kn.trace) {
+        const auto t_done = std::chrono::steady_clock::now();
+        fprintf(stderr, "[zk msm] batch of %zu x 2^%.0f%s: host enqueue %.3f ms, device drained %.3f ms later\n", count, log2((double)bp.n), how,
+                std::chrono::duration<double, std::milli>(t_enq - io.t_batch0).count(), std::chrono::duration<double, std::milli>(t_done - t_enq).count());
+    }
+    for (size_t it = 0; it < count; ++it) {
+        if (bp.tail_rows && io.narrow[it] == 1) host::msm_tail2(hw.data() + it, ht.data() + it, io.h_out + it);
+        else host::msm_tail(hw.data() + it, 1, bp.pl.c, io.h_out + it);
+    }
+    return ZK_OK;
+}
+// Plain launches.  Three bucket buffers in rotation: the reduction of step i (a latency-bound chain on a side stream, about as
+// long as a whole MSM) must only be finished when step i + 3 starts to accumulate.  The reductions of consecutive steps rotate
+// over three side streams: each is a chain of short launches (latency, not throughput), and with witness columns that fill few
+// windows it can take longer than the sort + accumulation of the next column.
+static int run_batch_plain(zk_ctx* ctx, const MsmKnobs& kn, const MsmBatchPlan& bp, const MsmBatchIo& io) {
+    const size_t count = bp.count, nsteps = bp.steps.size();
+    const int npipe = bp.npipe;
     hipStream_t mains[2] = {ctx->stream, npipe == 2 ? ctx->stream2c : ctx->stream};
-    struct StreamRestore { zk_ctx* c; hipStream_t s; ~StreamRestore() { c->stream = s; } } restore{ctx, ctx->stream};     // error returns included
+    StreamRestore restore{ctx, ctx->stream};
     if (npipe == 2) {           // the second pipeline starts behind everything already enqueued on the context's stream
         ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, mains[0]));
         ZK_HIP(ctx, hipStreamWaitEvent(mains[1], ctx->ev_pipe, 0));
     }
-    auto is_narrow = [&](size_t it) { return any_narrow && narrow[it] == 1; };
-    // the group of columns column `it` starts: up to NG consecutive small-valued columns, or the column alone
-    auto group_of = [&](size_t it) -> size_t {
-        if (!is_narrow(it)) return 1;
-        size_t g = 1;
-        while (g < NG && it + g < count && is_narrow(it + g)) ++g;
-        return g;
-    };
-    if (stage) { int rc = stage(stage_user, 0); if (rc) return rc; }
-    size_t staged = stage ? 1 : count;            // columns [0, staged) have been handed to the staging callback
-    size_t stepno = 0;                            // groups / columns enqueued so far: rotates bucket buffers, side streams, pipelines
-    for (size_t it = 0; it < count; ++stepno) {
-        const size_t grp = group_of(it);          // columns this step commits (a group of small-valued columns, or one column)
+    if (io.stage) { int rc = io.stage(io.stage_user, 0); if (rc) return rc; }
+    size_t staged = io.stage ? 1 : count;         // columns [0, staged) have been handed to the staging callback
+    for (size_t stepno = 0; stepno < nsteps; ++stepno) {          // stepno rotates bucket buffers, side streams, pipelines
+        const MsmStep& s = bp.steps[stepno];
         const int par = (int)(stepno % 3), pipe = (int)(stepno % (size_t)npipe);
         hipStream_t side = npipe == 2 ? ((stepno & 1) ? ctx->stream2b : ctx->stream2) : (par == 0 ? ctx->stream2 : par == 1 ? ctx->stream2b : ctx->stream2c);
         ctx->stream = mains[pipe];
-        for (; staged < it + grp; ++staged) { int rc = stage(stage_user, staged); if (rc) return rc; }      // every column of the group is on its way before its sort is enqueued
-        // the step by kind: a GM group, a per-window group (cnt columns each), or one merged column; its sort workspace is the pipeline's copy
-        const bool nar = is_narrow(it), grouped = nar && gm;
-        const uint32_t cnt = (uint32_t)grp;
-        const uint32_t nbc = grouped ? cnt * SG * pn.B : nar ? cnt * (uint32_t)pn.W * pn.B : nb;
-        const size_t tasks = nar ? (size_t)nbc + std::max(((size_t)n * cnt * pn.W) / TASK_CAP, (size_t)TASK_TARGET) + 1 : max_tasks;
-        const SortWs w = carve_sort_ws(grouped ? dims_G : nar ? dims_N : dims_M, ws + (size_t)pipe * words);
-        uint32_t* wflag_it = reinterpret_cast<uint32_t*>(wsum_all + count) + it * MSM_WFLAGS;
-        // bucket buffer: buckets | partials of the reduction | task partials | (per-window path) the folded windows
-        G1Xyzz29* buckets = (G1Xyzz29*)bkbuf[par];
-        G1Xyzz29* partial = buckets + (nar ? nbN : nb);
-        G1Xyzz29* task_partial = partial + (grouped ? (size_t)red_blocks_N * NG * 4 : nar ? (size_t)red_blocks_N * NG : red_pts);
-        G1Xyzz29* folded = task_partial + max_tasks_N;
-        {
-            ZkProfScope ps(ctx, "msm_sort");
-            if (grouped) PK_TRY_MSM(sort_gm(ctx, ctx->stream, w, pn, d_scalar_ptrs + it, cnt, n_narrow, (uint64_t)tab_stride, range_bits_G, nwgG, bpcG, SG));
-            else if (nar) {
-                PK_TRY_MSM(sort_digits(ctx, ctx->stream, w, pn, d_scalar_ptrs + it, cnt, n_narrow, n_pad, nullptr, nullptr));
-                ZK_HIP(ctx, hipMemcpyAsync(wflag_it, w.wflag, MSM_WFLAGS * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            } else {
-                // hint 2: long runs of equal scalars (running products) put whole runs into one partition; four slice-workgroups per
-                // partition stream them faster than one
-                PK_TRY_MSM(sort_partitioned(ctx, ctx->stream, w, pl, d_scalar_ptrs[it], (uint64_t)n, (uint64_t)tab_stride, range_bits, nwg, staged_scatter, binsort && !(narrow && narrow[it] == 2), nullptr, nullptr));
-            }
-        }
-        // reduce(step - 3) must be done with this bucket buffer -- but only the accumulation writes it: the sort of this MSM
-        // runs while that reduction finishes
-        if (stepno >= 3) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[par], 0));
-        // GM: one bucket set per column and set, accumulated like a merged MSM (idx holds table indices); per-window: the table window from the bucket
-        if (grouped) PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets_narrow", d_table_n, w, nbc, tasks, buckets, task_partial, 0, 0, nullptr, 0, perm_G));
-        else if (nar) PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets_narrow", d_table_n, w, nbc, tasks, buckets, task_partial, pn.c - 1, (uint64_t)tab_stride, wflag_it, cnt > 1 ? (uint32_t)pn.W : 0u, 0));
-        else PK_TRY_MSM(accumulate_combine(ctx, ctx->stream, "msm_buckets", d_table, w, nb, tasks, buckets, task_partial, 0, 0, nullptr, 0, 0));
-        ZK_HIP(ctx, hipEventRecord(ctx->ev_p1[par], ctx->stream));
-        ZK_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_p1[par], 0));
-        {   // weighted bucket sum on a side stream: hides under the next MSMs
-            ZkProfScope ps(ctx, nar ? "msm_reduce_narrow" : "msm_reduce", side);
-            // GM: the SG sets of a column are SG "windows" of equal weight: reduced separately, their partials summed with the column's;
-            // per-window: the occupied windows of every column of the group are folded, one window reduced per column
-            if (grouped) PK_TRY_MSM(reduce_window(ctx, side, buckets, pn.B, 0, nullptr, nullptr, cnt, SG, false, partial, wsum_all + it, nullptr, nullptr, 0));
-            else if (nar) PK_TRY_MSM(reduce_window(ctx, side, buckets, pn.B, pn.W, folded, wflag_it, cnt, 1, false, partial, wsum_all + it, nullptr, nullptr, 0));
-            // the caller waits for the reductions of the last two MSMs of a batch (and of a lone one): one launch with a
-            // scalar multiplication per lane has the shorter dependent chain (about 60 additions against 150 over the
-            // levels of wsum_enqueue), at twice the work; its <= nb / 2048 + 1 partials fit red_pts
-            else if (it + 2 >= count) PK_TRY_MSM(reduce_window(ctx, side, buckets, nb, 0, nullptr, nullptr, 1, 1, false, partial, wsum_all + it, nullptr, nullptr, 0));
-            else PK_TRY_MSM(wsum_enqueue(ctx, side, buckets, nb, partial, wsum_all + it));
-        }
+        for (; staged < (size_t)s.first + s.cols; ++staged) { int rc = io.stage(io.stage_user, staged); if (rc) return rc; }      // every column of the group is on its way before its sort is enqueued
+        const SortWs w = carve_sort_ws(sort_dims_of(bp, s.kind), io.ws + (size_t)pipe * bp.words);       // the pipeline's copy
+        const BucketRegions<G1Xyzz29> r = carve_buckets(bp, s.kind, s.cols, (G1Xyzz29*)io.bkbuf[par]);
+        MsmStepIo sio{};
+        sio.scalars = io.d_scalar_ptrs + s.first;
+        sio.out = io.wsum_all + s.first;
+        sio.st = ctx->stream;
+        sio.side = side;
+        if (s.kind == STEP_WINDOW) sio.wflag_copy = reinterpret_cast<uint32_t*>(io.wsum_all + count) + (size_t)s.first * MSM_WFLAGS;
+        if (stepno >= 3) sio.buckets_free = ctx->ev_p2[par];           // reduce(step - 3) must be done with this bucket buffer
+        sio.accumulated = ctx->ev_p1[par];
+        sio.levelled_sum = (size_t)s.first + 2 < count;                // the caller waits for the reductions of the last two MSMs of a batch (and of a lone one): the short chain
+        PK_TRY_MSM(enqueue_step(ctx, bp, io, s, w, r, sio));
         ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[par], side));
-        if (stage && it + grp < count) {
+        if (io.stage && stepno + 1 < nsteps) {
             // the columns of the NEXT step start crossing the link now, under this step's accumulation
             ctx->stream = mains[(stepno + 1) % (size_t)npipe];
-            const size_t upto = it + grp + group_of(it + grp);
-            for (; staged < upto; ++staged) { int rc = stage(stage_user, staged); if (rc) return rc; }
+            const size_t upto = (size_t)bp.steps[stepno + 1].first + bp.steps[stepno + 1].cols;
+            for (; staged < upto; ++staged) { int rc = io.stage(io.stage_user, staged); if (rc) return rc; }
         }
-        it += grp;
     }
     ctx->stream = mains[0];
     if (npipe == 2) {
@@ -1967,20 +1608,149 @@ static int msm_batch_merged_capped(zk_ctx* ctx, const MsmKnobs& kn, const Fr* co
         ZK_HIP(ctx, hipStreamWaitEvent(mains[0], ctx->ev_pipe, 0));
     }
     ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[0], 0));
-    if (stepno > 1) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[1], 0));
-    if (stepno > 2) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[2], 0));
-    return finish("");
+    if (nsteps > 1) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[1], 0));
+    if (nsteps > 2) ZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_p2[2], 0));
+    return finish_batch(ctx, kn, bp, io, "");
 }
-// The sort workspace of a group of small-valued columns is sized for the worst case (every digit of all its columns non-zero:
-// 3 GiB per copy at 2^20 rows and sixteen columns): with memory short, groups of half the size are tried before the batch is
-// given up, down to single columns.
+// Graph cache.  A captured step is tied to every value baked into a kernel argument or a grid of enqueue_step, and those
+// come from three places only: the plan (graph_key_part names its fields), the step (its kind; a captured step has one column,
+// read through the column table) with its pipeline, and the addresses below -- both tables, the workspace (with plan.words and
+// the pipeline: every pointer into the copy), the pipeline's bucket buffer, and the column table with its counters.
+struct MsmGraphAddrs { const G1Affine *d_table, *d_table_n; const uint32_t* ws; const char *bk, *desc; };
+static std::vector<uint64_t> graph_key(const MsmBatchPlan& bp, MsmStepKind kind, int p, const MsmGraphAddrs& a) {
+    std::vector<uint64_t> key = graph_key_part(bp);
+    for (uint64_t v : {(uint64_t)kind, (uint64_t)p, (uint64_t)(uintptr_t)a.d_table, (uint64_t)(uintptr_t)a.d_table_n, (uint64_t)(uintptr_t)a.ws, (uint64_t)(uintptr_t)a.bk, (uint64_t)(uintptr_t)a.desc}) key.push_back(v);
+    return key;
+}
+// The graph of `key_tuple` from the context's cache, or captured now: `enqueue` puts the step on stream st.  *exec stays
+// nullptr when capture or instantiation failed; graph mode is then off for this context (msm_graph_broken).
+template <class Enqueue>
+static int graph_lookup_or_capture(zk_ctx* ctx, bool trace, const std::vector<uint64_t>& key_tuple, hipStream_t const (&P)[MSM_GRAPH_PIPES], hipStream_t st, Enqueue enqueue, hipGraphExec_t* exec) {
+    *exec = nullptr;
+    uint64_t key = 1469598103934665603ull;
+    for (uint64_t v : key_tuple) key = (key ^ v) * 1099511628211ull;
+    auto found = ctx->msm_graphs.find(key);
+    if (found != ctx->msm_graphs.end() && ctx->msm_graph_keys[key] != key_tuple) {       // a 64-bit hash collision: the stale graph goes
+        (void)hipGraphExecDestroy((hipGraphExec_t)found->second);
+        ctx->msm_graphs.erase(found);
+        found = ctx->msm_graphs.end();
+    }
+    if (found != ctx->msm_graphs.end()) { *exec = (hipGraphExec_t)found->second; return ZK_OK; }
+    // graphs bake scratch addresses in; when the scratch arenas were reallocated since, the old entries can never be
+    // hit again: the cache is emptied when it grows past what one key / size mix needs
+    if (ctx->msm_graphs.size() >= 48) {
+        for (hipStream_t q : P) ZK_HIP(ctx, hipStreamSynchronize(q));
+        for (auto& kv : ctx->msm_graphs) (void)hipGraphExecDestroy((hipGraphExec_t)kv.second);
+        ctx->msm_graphs.clear();
+        ctx->msm_graph_keys.clear();
+    }
+    hipGraph_t graph = nullptr;
+    bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) == hipSuccess;
+    const int rc_e = ok ? enqueue() : ZK_ERR_HIP;
+    if (ok) ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph != nullptr;
+    ok = ok && rc_e == ZK_OK && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) == hipSuccess;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!ok) {
+        const hipError_t e = hipGetLastError();
+        if (trace) fprintf(stderr, "[zk msm] graph capture failed (rc %d, %s): plain launches from now on\n", rc_e, hipGetErrorString(e));
+        *exec = nullptr;
+        ctx->msm_graph_broken = true;
+        return ZK_OK;
+    }
+    ctx->msm_graphs[key] = (void*)*exec;
+    ctx->msm_graph_keys[key] = key_tuple;
+    return ZK_OK;
+}
+// Graph mode: MSM_GRAPH_PIPES linear pipelines, column it on pipeline it % MSM_GRAPH_PIPES (stream, sort workspace and bucket
+// buffer of its own; the reduction runs on the same stream: one launch, short chain), one hipGraphLaunch per column.  What
+// differs from column to column is read from the device column table (MsmCol).  *broke: capture or replay failed, what was
+// launched has been drained, and the caller runs the whole batch again with plain launches (a staging callback is simply asked
+// again: uploading a column twice and redoing its transform are idempotent).
+static int run_batch_graph(zk_ctx* ctx, const MsmKnobs& kn, const MsmBatchPlan& bp, const MsmBatchIo& io, bool* broke) {
+    constexpr int GP = MSM_GRAPH_PIPES;
+    const size_t count = bp.count;
+    *broke = false;
+    const hipStream_t P[GP] = {ctx->stream, ctx->stream2, ctx->stream2b, ctx->stream2c};
+    char* desc = (char*)ctx->get_scratch(SC_MSM_DESC, sizeof(MsmCol) * count + 256);
+    if (!desc) return ZK_ERR_OOM;
+    uint32_t* ctr_dev = (uint32_t*)desc;                                  // GP counters, then the table
+    MsmCol* cols_dev = (MsmCol*)(desc + 256);
+    {
+        std::vector<MsmCol> hcols(count);
+        for (size_t i = 0; i < count; ++i) hcols[i] = MsmCol{io.d_scalar_ptrs[i], io.wsum_all + i};
+        const uint32_t hctr[GP] = {0, 1, 2, 3};
+        ZK_HIP(ctx, hipMemcpyAsync(cols_dev, hcols.data(), sizeof(MsmCol) * count, hipMemcpyHostToDevice, P[0]));
+        ZK_HIP(ctx, hipMemcpyAsync(ctr_dev, hctr, sizeof(hctr), hipMemcpyHostToDevice, P[0]));
+        ZK_HIP(ctx, hipStreamSynchronize(P[0]));                          // the host copies live on this stack frame
+    }
+    ZK_HIP(ctx, hipEventRecord(ctx->ev_pipe, P[0]));
+    for (int p = 1; p < GP; ++p) ZK_HIP(ctx, hipStreamWaitEvent(P[p], ctx->ev_pipe, 0));
+    StreamRestore restore{ctx, ctx->stream};
+    if (io.stage) { int rc = io.stage(io.stage_user, 0); if (rc) return rc; }
+    for (size_t it = 0; it < count && !*broke; ++it) {         // graph mode has no groups: step it is column it
+        const MsmStep& s = bp.steps[it];
+        const int p = (int)(it % GP);
+        ctx->stream = P[p];
+        const MsmGraphAddrs addrs{io.d_table, io.d_table_n, io.ws, io.bkbuf[p], desc};
+        hipGraphExec_t exec = nullptr;
+        PK_TRY_MSM(graph_lookup_or_capture(ctx, kn.trace, graph_key(bp, s.kind, p, addrs), P, P[p], [&]() -> int {
+            // one linear chain on the pipeline's stream; the window flags are still this column's when the fold reads them: the next
+            // column of this pipeline comes behind it on the same stream
+            MsmStepIo sio{};
+            sio.cols = cols_dev;
+            sio.ctr = ctr_dev + p;
+            sio.ctr_step = (uint32_t)GP;
+            sio.st = sio.side = P[p];
+            return enqueue_step(ctx, bp, io, MsmStep{0, 1, s.kind}, carve_sort_ws(sort_dims_of(bp, s.kind), io.ws + (size_t)p * bp.words), carve_buckets(bp, s.kind, 1, (G1Xyzz29*)io.bkbuf[p]), sio);
+        }, &exec));
+        if (exec && hipGraphLaunch(exec, P[p]) != hipSuccess) {
+            const hipError_t e = hipGetLastError();
+            if (kn.trace) fprintf(stderr, "[zk msm] graph replay failed (%s): plain launches from now on\n", hipGetErrorString(e));
+            ctx->msm_graph_broken = true;
+        }
+        *broke = ctx->msm_graph_broken;
+        if (!*broke && io.stage && it + 1 < count) { ctx->stream = P[(it + 1) % GP]; int rc = io.stage(io.stage_user, it + 1); if (rc) return rc; }
+    }
+    ctx->stream = P[0];
+    for (int p = 1; p < GP; ++p) {
+        ZK_HIP(ctx, hipEventRecord(ctx->ev_p2[p - 1], P[p]));
+        ZK_HIP(ctx, hipStreamWaitEvent(P[0], ctx->ev_p2[p - 1], 0));
+    }
+    if (!*broke) return finish_batch(ctx, kn, bp, io, " (graph replay)");
+    ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ZK_OK;
+}
+// Plans the batch, gets its buffers and runs it.  The sort workspace of a group of small-valued columns is sized for the worst
+// case (every digit of all its columns non-zero: 3 GiB per copy at 2^20 rows and sixteen columns): with memory short, the plan's
+// smaller_cap -- groups of half the size -- is tried before the batch is given up, down to single columns; nothing has been
+// enqueued by then.  A batch whose graph mode broke is planned again (the context now says so) and takes the plain launches.
 int msm_batch_merged(zk_ctx* ctx, const MsmKnobs& kn, const Fr* const* d_scalar_ptrs, size_t count, const G1Affine* d_table, size_t tab_stride, const MsmPlan& pl,
                      size_t n, G1Affine* h_out, MsmStageFn stage, void* stage_user, const G1Affine* d_table_n = nullptr, const MsmPlan* pl_n = nullptr, const uint8_t* narrow = nullptr) {
+    if (count == 0) return ZK_OK;
+    if (n == 0) { memset(h_out, 0, sizeof(G1Affine) * count); return ZK_OK; }
+    MsmBatchIo io{d_scalar_ptrs, narrow, d_table, d_table_n, h_out, stage, stage_user, std::chrono::steady_clock::now()};
     for (uint32_t cap = 0;;) {
-        uint32_t smaller_cap = 0;
-        const int rc = msm_batch_merged_capped(ctx, kn, d_scalar_ptrs, count, d_table, tab_stride, pl, n, h_out, stage, stage_user, d_table_n, pl_n, narrow, cap, &smaller_cap);
-        if (!smaller_cap) return rc;
-        cap = smaller_cap;
+        const MsmBatchPlan bp = plan_batch(MsmBatchShape{n, count, tab_stride, pl, d_table_n ? pl_n : nullptr, narrow, ctx->msm_blinded_tail, ctx->prof_on, ctx->msm_graph_broken, cap}, kn);
+        if (bp.status == MSM_PLAN_ENTRY_SPACE) return ctx->fail(ZK_ERR_UNSUPPORTED, "MSM of %zu points x %d windows exceeds the 32-bit entry space: split it", n, pl.W);
+        io.ws = (uint32_t*)ctx->get_scratch(SC_MSM_KEYS, bp.words * 4 * bp.copies);
+        if (!io.ws && bp.smaller_cap) {
+            (void)hipGetLastError();
+            cap = bp.smaller_cap;
+            continue;
+        }
+        if (!io.ws) return ZK_ERR_OOM;
+        const size_t bucket_bytes = sizeof(G1Xyzz29) * bp.npts29;
+        io.bkbuf[0] = (char*)ctx->get_scratch(SC_MSM_BUCKETS, bucket_bytes);
+        io.bkbuf[1] = count > 1 ? (char*)ctx->get_scratch(SC_MSM_BUCKETS2, bucket_bytes) : io.bkbuf[0];
+        io.bkbuf[2] = count > 2 ? (char*)ctx->get_scratch(SC_MSM_BUCKETS3, bucket_bytes) : io.bkbuf[0];
+        io.bkbuf[3] = bp.graph ? (char*)ctx->get_scratch(SC_MSM_BUCKETS4, bucket_bytes) : io.bkbuf[0];
+        io.wsum_all = (G1Xyzz*)ctx->get_scratch(SC_MSM_RESULTS, sizeof(G1Xyzz) * count + 4 * MSM_WFLAGS * count);
+        if (!io.bkbuf[0] || !io.bkbuf[1] || !io.bkbuf[2] || !io.bkbuf[3] || !io.wsum_all) return ZK_ERR_OOM;
+        PK_TRY_MSM(ensure_side_streams(ctx, true));
+        if (!bp.graph) return run_batch_plain(ctx, kn, bp, io);
+        bool broke = false;
+        const int rc = run_batch_graph(ctx, kn, bp, io, &broke);
+        if (rc || !broke) return rc;
     }
 }
 // Per-window table of an SRS basis (plan make_plan(2^k): c = k - 4 <= 16), for the columns that fill
@@ -2005,6 +1775,22 @@ static int srs_window_table_narrow(zk_ctx* ctx, const zk_srs* srs, int basis, si
     *out = s->tabn[basis];
     return ZK_OK;
 }
+// A special path (runs.hip) has committed the columns with done[i] != 0: the others are submitted again as a batch of their
+// own and their results scattered back.  hint3_dense: a column hinted 3 goes on as a dense one.
+static int commit_rest(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_scalar_ptrs, size_t count, size_t n, const uint8_t* narrow, const std::vector<uint8_t>& done, bool hint3_dense,
+                       G1Affine* h_out) {
+    std::vector<size_t> rest;
+    for (size_t i = 0; i < count; ++i) if (!done[i]) rest.push_back(i);
+    if (rest.empty()) return ZK_OK;
+    std::vector<const Fr*> ptrs(rest.size());
+    std::vector<uint8_t> hints(rest.size());
+    std::vector<G1Affine> outs(rest.size());
+    for (size_t j = 0; j < rest.size(); ++j) { ptrs[j] = d_scalar_ptrs[rest[j]]; hints[j] = (hint3_dense && narrow[rest[j]] == 3) ? 0 : narrow[rest[j]]; }
+    const int rc = msm_batch_srs(ctx, srs, basis, ptrs.data(), rest.size(), n, outs.data(), nullptr, nullptr, hints.data());
+    if (rc) return rc;
+    for (size_t j = 0; j < rest.size(); ++j) h_out[rest[j]] = outs[j];
+    return ZK_OK;
+}
 // commitments over an SRS basis: the merged-window path when the basis has (or can get) its window
 // table -- columns flagged `narrow` take the per-window path over their own table --, the plain
 // per-window path otherwise.  ZK_MSM_NARROW=0 / 1 overrides the flags (measurement knob).
@@ -2018,21 +1804,9 @@ int msm_batch_srs(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_
             std::vector<uint8_t> done(count);
             int rc = msm_runs_try(ctx, srs, basis, d_scalar_ptrs, count, n, narrow, h_out, done.data());
             if (rc) return rc;
-            std::vector<size_t> rest;
-            for (size_t i = 0; i < count; ++i) if (!done[i]) rest.push_back(i);
-            if (rest.size() < count) {
-                if (rest.empty()) return ZK_OK;
-                std::vector<const Fr*> ptrs(rest.size());
-                std::vector<uint8_t> hints(rest.size());
-                std::vector<G1Affine> outs(rest.size());
-                for (size_t j = 0; j < rest.size(); ++j) { ptrs[j] = d_scalar_ptrs[rest[j]]; hints[j] = narrow[rest[j]]; }
-                {
-                    struct Tried { Tried() { runs_tried = true; } ~Tried() { runs_tried = false; } } tried;
-                    rc = msm_batch_srs(ctx, srs, basis, ptrs.data(), rest.size(), n, outs.data(), nullptr, nullptr, hints.data());
-                }
-                if (rc) return rc;
-                for (size_t j = 0; j < rest.size(); ++j) h_out[rest[j]] = outs[j];
-                return ZK_OK;
+            if (std::find(done.begin(), done.end(), 1) != done.end()) {
+                struct Tried { Tried() { runs_tried = true; } ~Tried() { runs_tried = false; } } tried;
+                return commit_rest(ctx, srs, basis, d_scalar_ptrs, count, n, narrow, done, false, h_out);
             }
         }
     }
@@ -2045,17 +1819,7 @@ int msm_batch_srs(zk_ctx* ctx, const zk_srs* srs, int basis, const Fr* const* d_
             std::vector<uint8_t> done(count);
             int rc3 = msm_diff_try(ctx, srs, basis, d_scalar_ptrs, count, n, narrow, h_out, done.data());
             if (rc3) return rc3;
-            std::vector<size_t> rest;
-            for (size_t i = 0; i < count; ++i) if (!done[i]) rest.push_back(i);
-            if (rest.empty()) return ZK_OK;
-            std::vector<const Fr*> ptrs(rest.size());
-            std::vector<uint8_t> hints(rest.size());
-            std::vector<G1Affine> outs(rest.size());
-            for (size_t j = 0; j < rest.size(); ++j) { ptrs[j] = d_scalar_ptrs[rest[j]]; hints[j] = narrow[rest[j]] == 3 ? 0 : narrow[rest[j]]; }
-            rc3 = msm_batch_srs(ctx, srs, basis, ptrs.data(), rest.size(), n, outs.data(), nullptr, nullptr, hints.data());
-            if (rc3) return rc3;
-            for (size_t j = 0; j < rest.size(); ++j) h_out[rest[j]] = outs[j];
-            return ZK_OK;
+            return commit_rest(ctx, srs, basis, d_scalar_ptrs, count, n, narrow, done, true, h_out);      // hint 3 has been tried: dense from here
         }
     }
     const G1Affine* b = basis == 2 ? srs->pfx[1] : (basis ? srs->g_lagrange : srs->g);
@@ -2091,8 +1855,7 @@ int srs_window_table(zk_ctx* ctx, const zk_srs* srs, int basis, size_t n, const 
     const MsmPlan pl = make_plan_merged(s->k, kn);
     const uint64_t ns = 1ull << s->k;
     const size_t bytes = sizeof(G1Affine) * ns * pl.W;
-    const double cap_gb = kn.table_gb;
-    if (n < 64 || (double)bytes > cap_gb * (double)(1ull << 30) || (uint64_t)pl.W * ns >= (1ull << 31)) return ZK_OK;
+    if (!merged_table_wanted(s->k, n, pl, kn)) return ZK_OK;
     // plan changed (measurement knobs): the top window's entries carry c - top_shift doublings, so a table is only valid for the
     // (c, top_shift) it was built for
     if (s->tab[basis] && (s->tab_c[basis] != pl.c || s->tab_shift[basis] != pl.top_shift)) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(s->tab[basis]); s->tab[basis] = nullptr; }
@@ -2275,15 +2038,24 @@ extern "C" int zk_host_msm_plan(uint32_t k, int* window_bits, int* windows, int*
     return ZK_OK;
 }
 
+// Host only: the plan of a batch of `count` commitments of n points over an SRS of 2^k points that has its merged-window table,
+// as msm_batch_merged would decide it under the ZK_MSM_* knobs in force; zkmi355.h gives the record (plan_record, msm_plan.hpp)
+extern "C" int zk_host_msm_batch_plan(uint32_t k, size_t n, size_t count, const uint8_t* hints, uint32_t blinded_tail, int window_table, uint32_t group_cap, int prof_on, int graph_broken,
+                                      uint64_t* out_words, size_t cap_words, size_t* out_count) {
+    if (!out_count || k > 28 || n == 0 || n > ((size_t)1 << k) || count == 0 || (!out_words && cap_words)) return ZK_ERR_INVALID_ARG;
+    const std::vector<uint64_t> rec = zk::plan_record(zk::plan_batch_of_srs(k, n, count, hints, blinded_tail, window_table != 0, group_cap, prof_on != 0, graph_broken != 0, zk::read_knobs()));
+    *out_count = rec.size();
+    if (rec.size() > cap_words) return cap_words ? ZK_ERR_INVALID_ARG : ZK_OK;
+    std::copy(rec.begin(), rec.end(), out_words);
+    return ZK_OK;
+}
+
 // window size / window count the commitments over this SRS use for an MSM of n points (introspection for benches)
 extern "C" int zk_msm_plan(const zk_srs* srs, size_t n, int* window_bits, int* windows) {
     if (!srs || !window_bits || !windows) return ZK_ERR_INVALID_ARG;
-    const uint64_t ns = 1ull << srs->k;
     const zk::MsmKnobs kn = zk::read_knobs();
     const zk::MsmPlan m = zk::make_plan_merged(srs->k, kn);
-    const double cap_gb = kn.table_gb;
-    const bool merged = n >= 64 && (double)(sizeof(zk::G1Affine) * ns * m.W) <= cap_gb * (double)(1ull << 30) && (uint64_t)m.W * ns < (1ull << 31);
-    const zk::MsmPlan pl = merged ? m : zk::make_plan(n);
+    const zk::MsmPlan pl = zk::merged_table_wanted(srs->k, n, m, kn) ? m : zk::make_plan(n);
     *window_bits = pl.c;
     *windows = pl.W;
     return ZK_OK;
