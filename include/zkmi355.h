@@ -44,7 +44,7 @@ typedef enum zk_status {
 } zk_status;
 
 enum { ZK_FIELD_FR = 0, ZK_FIELD_FQ = 1 };
-enum { ZK_OP_ADD = 0, ZK_OP_SUB = 1, ZK_OP_MUL = 2 };
+enum { ZK_OP_ADD = 0, ZK_OP_SUB = 1, ZK_OP_MUL = 2, ZK_OP_SCAN_AFFINE = 3, ZK_OP_SCAN_AFFINE_REV = 4 };
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -106,7 +106,16 @@ int zk_prof_names(zk_ctx* ctx, char* buf, size_t len);
  * out3 = {lanes with a difference, OR of the differing routines (1, 2, 4, 8; in-place 16, 32, 64, 128), lanes run}. */
 int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t seed, uint32_t* out3);
 
-/* ---- field vectors (halo2curves Fr/Fq Add/Sub/Mul, element-wise)  -- SURVEY 8a K4/K10 ---------- */
+/* ---- field vectors (halo2curves Fr/Fq Add/Sub/Mul)  -- SURVEY 8a K4/K10 ------------------------ */
+/* d_out = d_a (op) d_b over n Montgomery elements of 32 B, asynchronous on the context's stream; n = 0: ZK_OK.
+ * ZK_OP_ADD / ZK_OP_SUB / ZK_OP_MUL are element-wise, over Fr or Fq, and d_out may be d_a or d_b.
+ * The two scan ops run a first-order linear recurrence along the column, over Fr only (ZK_FIELD_FQ: ZK_ERR_INVALID_ARG):
+ *   ZK_OP_SCAN_AFFINE       out[0]   = b[0],    out[i] = a[i] * out[i-1] + b[i]  for 0 < i < n
+ *   ZK_OP_SCAN_AFFINE_REV   out[n-1] = b[n-1],  out[i] = a[i] * out[i+1] + b[i]  for i < n-1
+ * The state before the first element is 0, so a[0] (a[n-1] for the reverse op) is never used; a caller with a start value z0
+ * folds a * z0 into b[0] itself.  a[i] = 0 starts a new segment at i: a running RLC with resets z[i] = z[i-1] * r * (1 - is_first[i])
+ * + x[i] is a = r * (1 - is_first), b = x.  Results are canonical.  d_out must overlap neither d_a nor d_b (n * 32 B each):
+ * ZK_ERR_INVALID_ARG, nothing is launched.  Booked under the zk_prof name "fr_scan_affine" with n * 96 algorithmic bytes per call. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */
 int zk_fr_scale(zk_ctx* ctx, void* d_a, const void* h_s, size_t n);

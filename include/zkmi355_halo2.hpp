@@ -120,6 +120,13 @@ inline void fr_from_uint_batch(const Context& c, const std::vector<const void*>&
     if (cell_bytes.size() != d_packed.size() || d_out.size() != d_packed.size()) throw Error(ZK_ERR_INVALID_ARG, "fr_from_uint_batch: one cell width and one output per column");
     c.check(zk_fr_from_uint_batch(c.raw(), d_packed.data(), cell_bytes.data(), d_packed.size(), n, d_out.data()));
 }
+// out[0] = b[0], out[i] = a[i] * out[i - 1] + b[i] over n Montgomery Fr, device to device (zk_field_vec_op with ZK_OP_SCAN_AFFINE;
+// asynchronous on the context's stream); reverse: out[n - 1] = b[n - 1], out[i] = a[i] * out[i + 1] + b[i].  a[i] = 0 starts a new
+// segment: the running RLC with resets of a challenge-phase column is a = r * (1 - is_first), b = x.  out overlaps neither input.
+inline void scan_affine(const Context& c, const Context::Buffer& a, const Context::Buffer& b, Context::Buffer& out, size_t n, bool reverse = false) {
+    if (n * sizeof(Fr) > a.bytes() || n * sizeof(Fr) > b.bytes() || n * sizeof(Fr) > out.bytes()) throw Error(ZK_ERR_INVALID_ARG, "scan_affine: a buffer holds fewer than n elements");
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, reverse ? ZK_OP_SCAN_AFFINE_REV : ZK_OP_SCAN_AFFINE, a.ptr(), b.ptr(), out.ptr(), n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

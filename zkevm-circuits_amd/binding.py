@@ -22,6 +22,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "zkmi355.h")
 
 FIELD_FR, FIELD_FQ = 0, 1
 OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
+OP_SCAN_AFFINE, OP_SCAN_AFFINE_REV = 3, 4            # out[i] = a[i] * out[i -+ 1] + b[i] along the column, Fr only
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -648,6 +649,11 @@ class Context:
     # ---- field vectors
     def field_vec_op(self, field: int, op: int, a: DeviceBuffer, b: DeviceBuffer, out: DeviceBuffer, n: int):
         self._ck(lib().zk_field_vec_op(self.h, field, op, ctypes.c_void_p(a.ptr), ctypes.c_void_p(b.ptr), ctypes.c_void_p(out.ptr), ctypes.c_size_t(n)))
+
+    def scan_affine(self, a: DeviceBuffer, b: DeviceBuffer, out: DeviceBuffer, n: int, reverse: bool = False):
+        """out[0] = b[0], out[i] = a[i] * out[i - 1] + b[i] over n Montgomery Fr (zk_field_vec_op with ZK_OP_SCAN_AFFINE); reverse: from
+        the last element down, out[i] = a[i] * out[i + 1] + b[i].  a[i] = 0 starts a new segment; out overlaps neither input."""
+        self.field_vec_op(FIELD_FR, OP_SCAN_AFFINE_REV if reverse else OP_SCAN_AFFINE, a, b, out, n)
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

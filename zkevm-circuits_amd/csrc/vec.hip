@@ -2,6 +2,7 @@
 //   field vector add/sub/mul            halo2curves Add/Sub/Mul           
 //   batch inversion                     ff::BatchInvert                    (K12, K7, K8)
 //   prefix product / prefix sum         permutation & lookup grand product (K7, K8)
+//   affine scan z = a z + b             running RLCs with resets (challenge-phase witness columns)
 //   eval_polynomial, kate_division      halo2_proofs::arithmetic           (K9, K10, K11)
 // All kernels read/write 32-byte elements as two 16-byte transactions per lane, consecutive
 // lanes on consecutive elements (fully coalesced), grid-stride where a fixed grid is needed.
@@ -214,6 +215,133 @@ static int scan_run(zk_ctx* ctx, const Fr* d_a, Fr* d_z, uint64_t n) {
         hipLaunchKernelGGL((k_scan_c<Op>), dim3(blocks), dim3(SCAN_THREADS), 0, ctx->stream, d_z, totals, n);
         ZK_CHECK_LAUNCH(ctx);
     }
+    return ZK_OK;
+}
+
+// -------------------------------------------------- first-order linear recurrence (affine scan)
+// ZK_OP_SCAN_AFFINE: out[0] = b[0], out[i] = a[i] * out[i-1] + b[i] -- the running RLC with resets (a[i] = 0 starts a new segment).
+// Element i is the map z -> a[i] z + b[i] and maps compose: an Aff (A, B) stands for z -> A z + B, and "first p, then q" is
+// (q.A p.A, q.A p.B + q.B): associative, NOT commutative, so every combine names the earlier map first, like Op::f(earlier, later)
+// above.  The state before the first element is 0, hence what a block needs from the blocks before it is one Fr value, not a map.
+// Same tiling and three launches as scan_run, but no per-element intermediate in memory:
+//   A: each block folds its SCAN_THREADS * SCAN_PER elements into ONE map (thread-local fold, ordered pairwise reduction in LDS)
+//   B: one block turns the block maps into the value entering each block (windows of SCAN_THREADS maps, serial carry between them)
+//   C: each block folds its thread chunks again, scans the thread maps in LDS, applies the exclusive map to the entering value and
+//      walks its elements: z = a[i] z + b[i], stored as it goes.  a and b are read twice, out is written once.
+// REV mirrors the memory index (scan position j is element n - 1 - j) and nothing else: ZK_OP_SCAN_AFFINE_REV.
+struct Aff { Fr A, B; };
+__device__ __forceinline__ Aff aff_id() { return Aff{Fr::one(), Fr::zero()}; }
+__device__ __forceinline__ Aff aff_then(const Aff& p, const Aff& q) { return Aff{q.A * p.A, q.A * p.B + q.B}; }   // first p, then q
+__device__ __forceinline__ Fr aff_apply(const Aff& p, const Fr& z) { return p.A * z + p.B; }
+
+// composite map of this thread's SCAN_PER elements from scan position `start` on; positions at or past n are the identity and
+// are skipped.  Scan position j is element j, or n - 1 - j under REV.
+template <bool REV>
+__device__ __forceinline__ uint64_t aff_index(uint64_t j, uint64_t n) { return REV ? n - 1 - j : j; }
+template <bool REV>
+__device__ __forceinline__ Aff aff_chunk(const Fr* __restrict__ a, const Fr* __restrict__ b, uint64_t start, uint64_t n) {
+    Aff acc = aff_id();
+    for (int k = 0; k < SCAN_PER; ++k) {
+        const uint64_t j = start + k;
+        if (j >= n) break;
+        const uint64_t i = aff_index<REV>(j, n);
+        const Fr x = ldg(a + i);
+        acc.A = x * acc.A;
+        acc.B = x * acc.B + ldg(b + i);
+    }
+    return acc;
+}
+// composite of the block's SCAN_THREADS maps in thread order (valid in thread 0): neighbours pair up, the earlier one first
+__device__ __forceinline__ Aff aff_block_total(const Aff& v, Aff* sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int m = SCAN_THREADS / 2; m > 0; m >>= 1) {
+        Aff x;
+        if (t < m) x = aff_then(sh[2 * t], sh[2 * t + 1]);
+        __syncthreads();
+        if (t < m) sh[t] = x;
+        __syncthreads();
+    }
+    return sh[0];
+}
+// block_exclusive_scan over maps: returns the composite of the threads before this one; *total = the whole block's
+__device__ __forceinline__ Aff aff_block_exclusive_scan(const Aff& v, Aff* sh, Aff* total) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
+        Aff x = sh[t];
+        if (t >= off) x = aff_then(sh[t - off], x);
+        __syncthreads();
+        sh[t] = x;
+        __syncthreads();
+    }
+    *total = sh[SCAN_THREADS - 1];
+    Aff ex = t ? sh[t - 1] : aff_id();
+    __syncthreads();
+    return ex;
+}
+
+template <bool REV>
+__global__ void __launch_bounds__(SCAN_THREADS) k_affine_a(const Fr* __restrict__ a, const Fr* __restrict__ b, Aff* __restrict__ maps, uint64_t n) {
+    __shared__ Aff sh[SCAN_THREADS];
+    const uint64_t start = (uint64_t)blockIdx.x * (SCAN_THREADS * SCAN_PER) + (uint64_t)threadIdx.x * SCAN_PER;
+    const Aff total = aff_block_total(aff_chunk<REV>(a, b, start, n), sh);
+    if (threadIdx.x == 0) { stg(&maps[blockIdx.x].A, total.A); stg(&maps[blockIdx.x].B, total.B); }
+}
+// entering[i] = the recurrence's value after the blocks before block i (0 for block 0), from the cnt block maps
+__global__ void __launch_bounds__(SCAN_THREADS) k_affine_b(const Aff* __restrict__ maps, Fr* __restrict__ entering, uint32_t cnt) {
+    __shared__ Aff sh[SCAN_THREADS];
+    Fr carry = Fr::zero();
+    for (uint32_t base = 0; base < cnt; base += SCAN_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const Aff v = i < cnt ? Aff{ldg(&maps[i].A), ldg(&maps[i].B)} : aff_id();
+        Aff total;
+        const Aff ex = aff_block_exclusive_scan(v, sh, &total);
+        if (i < cnt) stg(entering + i, aff_apply(ex, carry));
+        carry = aff_apply(total, carry);
+    }
+}
+// entering == nullptr: a single block, nothing enters it
+template <bool REV>
+__global__ void __launch_bounds__(SCAN_THREADS) k_affine_c(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr* __restrict__ out, const Fr* __restrict__ entering, uint64_t n) {
+    __shared__ Aff sh[SCAN_THREADS];
+    const uint64_t start = (uint64_t)blockIdx.x * (SCAN_THREADS * SCAN_PER) + (uint64_t)threadIdx.x * SCAN_PER;
+    Aff total;
+    const Aff ex = aff_block_exclusive_scan(aff_chunk<REV>(a, b, start, n), sh, &total);
+    Fr z = entering ? aff_apply(ex, ldg(entering + blockIdx.x)) : ex.B;
+    for (int k = 0; k < SCAN_PER; ++k) {                  // the chunk again, from the caches this time
+        const uint64_t j = start + k;
+        if (j >= n) break;
+        const uint64_t i = aff_index<REV>(j, n);
+        z = ldg(a + i) * z + ldg(b + i);
+        stg(out + i, z);
+    }
+}
+
+template <bool REV>
+static int scan_affine_run(zk_ctx* ctx, const Fr* d_a, const Fr* d_b, Fr* d_out, uint64_t n) {
+    const uint64_t blocks = (n + SCAN_THREADS * SCAN_PER - 1) / (SCAN_THREADS * SCAN_PER);
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many elements for one scan");
+    // SC_POLY2 like scan_run: every user of the slot is enqueued on ctx->stream, so uses follow each other in stream order
+    Aff* maps = nullptr;
+    Fr* entering = nullptr;
+    if (blocks > 1) {
+        maps = (Aff*)ctx->get_scratch(SC_POLY2, (sizeof(Aff) + sizeof(Fr)) * blocks);
+        if (!maps) return ZK_ERR_OOM;
+        entering = (Fr*)(maps + blocks);
+    }
+    ZkProfScope prof(ctx, "fr_scan_affine");
+    prof.bytes = n * 3 * sizeof(Fr);
+    if (blocks > 1) {
+        hipLaunchKernelGGL((k_affine_a<REV>), dim3((unsigned)blocks), dim3(SCAN_THREADS), 0, ctx->stream, d_a, d_b, maps, n);
+        ZK_CHECK_LAUNCH(ctx);
+        hipLaunchKernelGGL(k_affine_b, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (const Aff*)maps, entering, (uint32_t)blocks);
+        ZK_CHECK_LAUNCH(ctx);
+    }
+    hipLaunchKernelGGL((k_affine_c<REV>), dim3((unsigned)blocks), dim3(SCAN_THREADS), 0, ctx->stream, d_a, d_b, d_out, (const Fr*)entering, n);
+    ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
 
@@ -608,6 +736,13 @@ int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void*
     if (!ctx) return ZK_ERR_INVALID_ARG;
     ZK_REQUIRE(ctx, d_a && d_b && d_out, "null device pointer");
     if (n == 0) return ZK_OK;
+    if (op == ZK_OP_SCAN_AFFINE || op == ZK_OP_SCAN_AFFINE_REV) {
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the scan ops are defined over Fr only");
+        const uintptr_t a = (uintptr_t)d_a, b = (uintptr_t)d_b, o = (uintptr_t)d_out, bytes = n * sizeof(Fr);
+        ZK_REQUIRE(ctx, (o + bytes <= a || a + bytes <= o) && (o + bytes <= b || b + bytes <= o), "the output of a scan op overlaps an input");
+        return op == ZK_OP_SCAN_AFFINE ? scan_affine_run<false>(ctx, (const Fr*)d_a, (const Fr*)d_b, (Fr*)d_out, n)
+                                       : scan_affine_run<true>(ctx, (const Fr*)d_a, (const Fr*)d_b, (Fr*)d_out, n);
+    }
     if (field == ZK_FIELD_FR) return vec_op_launch<Fr>(ctx, op, d_a, d_b, d_out, n);
     if (field == ZK_FIELD_FQ) return vec_op_launch<Fq>(ctx, op, d_a, d_b, d_out, n);
     return ctx->fail(ZK_ERR_INVALID_ARG, "unknown field %d", field);
