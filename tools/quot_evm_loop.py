@@ -1,7 +1,9 @@
 """The evaluator on the program it exists for: the compiled top-class program of the EVM-style constraint system
 (bench_proof.evm_block, EVM_DEFAULT: 5 258 constraints of degree <= 9 over 160 step columns; csrc/class_compile.hpp) over random
 columns at 2^k rows, `reps` launches -- the profiling loop of round 6 (tools/quot_loop.py is round 5's, two gate shapes).
-usage: python tools/quot_evm_loop.py [k] [reps] [distinct column buffers, 0 = one per column]"""
+usage: python tools/quot_evm_loop.py [k] [reps] [distinct column buffers, 0 = one per column]
+ZK_QUOTIENT_LOOP_RECORDS=1 times the record mode (coset operands as 2^261-form limb records, converted once per buffer before the timed launches);
+ZKMI355_LIB=<a build made with EXTRA=-DZK_REC29_AOS=1> the 36-byte array-of-structs layout of the records."""
 import ctypes
 import os
 import sys

@@ -97,6 +97,7 @@ void zk_ctx_destroy(zk_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     ctx->domains.clear();
     for (auto& kv : ctx->pow_tables) (void)hipFree(kv.second);
+    for (auto& kv : ctx->loop_records) (void)hipFree(kv.second);
     ctx->pool_trim();
     ctx->prof_resolve();
     for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
@@ -377,7 +378,7 @@ int zk_coeff_to_coset_batch(zk_ctx* ctx, const void* const* d_coeffs, uint32_t k
     ZK_REQUIRE(ctx, h_g, "null pointer");
     ZK_REQUIRE(ctx, k <= 28, "k exceeds the two-adicity of Fr (28)");
     for (size_t i = 0; i < count; ++i) ZK_REQUIRE(ctx, d_coeffs[i] && d_outs[i], "null column pointer");
-    return ntt_run_many(ctx, (Fr* const*)d_outs, (const Fr* const*)d_coeffs, count, k, fr_root_of_unity(k), nullptr, (const Fr*)h_g, nullptr, /*fuse_pre=*/true);
+    return coeff_to_coset_batch_fmt(ctx, d_coeffs, k, *(const Fr*)h_g, d_outs, count, false);
 }
 int zk_extended_to_coeff(zk_ctx* ctx, void* d_ext, uint32_t ext_k) {
     if (!ctx) return ZK_ERR_INVALID_ARG;

@@ -72,6 +72,7 @@ struct zk_ctx {
     uint32_t comm_rank = 0, comm_world = 1;
     std::map<uint64_t, std::shared_ptr<zk::NttDomain>> domains;   // key: log_n | kind << 8
     std::map<uint64_t, void*> pow_tables;                         // cached two-level power tables of the coset generators
+    std::map<const void*, void*> loop_records;                    // measurement only (ZK_QUOTIENT_LOOP_RECORDS, quotient.hip): column buffer -> its image as a coset record buffer
     std::vector<void*> pinned;   // small pinned host staging buffers
     // Device block pool for the prover's column buffers: a proof allocates and frees hundreds of
     // n x 32 B / 2^ext_k x 32 B blocks, and hipFree is a device-wide synchronisation.  Blocks are
@@ -227,6 +228,16 @@ int ntt_run(zk_ctx* ctx, Fr* d_data, uint32_t log_n, const Fr& omega, const Fr* 
             bool fuse_pre = false /*coset_pre from a cached full power table inside the first pass (no separate sweep)*/);
 // `count` transforms over one domain, NTT_BATCH columns per launch (d_srcs nullable: in place)
 int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_t count, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, bool fuse_pre);
+// the same with the output format chosen: records = the last pass writes coset records (ff29.hip.hpp REC29_BYTES per row, out of place only)
+int ntt_run_many_fmt(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_t count, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, bool fuse_pre,
+                     bool records);
+// Coset operands of the quotient's class programs, packed (what the exported functions of these names do) or as records of 32 x the
+// value (R' = 2^261 form, canonical limbs): zk_coeff_to_coset_batch, zk_fr_powers and zk_quotient_eval with the format chosen.
+// quotient_eval_fmt with records: EVERY column is a record buffer of 2^ext_k rows, the result is packed and holds 32 x the value.
+int coeff_to_coset_batch_fmt(zk_ctx* ctx, const void* const* d_coeffs, uint32_t k, const Fr& g, void* const* d_outs, size_t count, bool records);
+int fr_powers_fmt(zk_ctx* ctx, const Fr& base, const Fr& mul, void* d_out, size_t n, bool records);
+int quotient_eval_fmt(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr, const void* const* h_col_ptrs, uint32_t num_cols, const void* h_consts, uint32_t num_consts, uint32_t k, uint32_t ext_k,
+                      int divide_by_vanishing, void* d_out, bool records);
 int fr_scale_run(zk_ctx* ctx, Fr* d_a, const Fr& s, uint64_t n);
 // G1 encodings read on the device (params.hip k_g1_decode): 32 B compressed, 64 B Montgomery limbs, 64 B big-endian x || y (EVM)
 enum G1Enc : int { G1_ENC_COMPRESSED = 0, G1_ENC_RAW = 1, G1_ENC_BE_XY = 2 };

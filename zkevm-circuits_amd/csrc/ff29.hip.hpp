@@ -469,7 +469,7 @@ __host__ __device__ __forceinline__ F29<P> neg29k(const F29<P>& b) {
 // six bits that this replaces missed by up to 2 and paid three conditional subtractions -- 50 instructions per output of the NTT's
 // last pass).  ~half the work of multiplying by one just to reduce.
 template <class P>
-__host__ __device__ __forceinline__ Fp<typename P::P32> reduce_lazy29(const F29<P>& x) {
+__host__ __device__ __forceinline__ F29<P> reduce_lazy29_limbs(const F29<P>& x) {       // the step before the conditional subtraction: normalised, < (1 + 2^-20) m
     constexpr uint64_t mhi = ((uint64_t)P::P32::M(7) << 32) | P::P32::M(6);
     constexpr uint32_t C = (uint32_t)((((unsigned __int128)1) << 92) / ((unsigned __int128)mhi + 1));
     const uint32_t q = (uint32_t)(((uint64_t)x.l[8] * C) >> 52);
@@ -481,8 +481,58 @@ __host__ __device__ __forceinline__ Fp<typename P::P32> reduce_lazy29(const F29<
         r.l[i] = i < 8 ? (uint32_t)(s_ & MASK29) : (uint32_t)s_;
         c = s_ >> 29;
     }
-    return pack29_lt2p(r);          // r < (1 + 2^-20) m
+    return r;
 }
+template <class P>
+__host__ __device__ __forceinline__ Fp<typename P::P32> reduce_lazy29(const F29<P>& x) { return pack29_lt2p(reduce_lazy29_limbs(x)); }
+
+// ---- coset records: a field element as the nine limbs the 9 x 29 products compute on ----------------------------------------
+// The quotient evaluator reads every coset operand ~70 times per row; kept as packed 8 x 32 words each read pays 16-17 vector
+// instructions to get the limbs back.  A coset buffer of n rows is therefore written ONCE as records (split layout, 36 n bytes):
+//   bytes [0, 32 n):      row i = limbs 0 .. 7 of the canonical value (each below 2^29), 32-byte aligned like a packed element
+//   bytes [32 n, 36 n):   the plane of top limbs, one u32 per row
+// so a row is two 16-byte accesses at the address a packed element would have, plus one 4-byte access in the plane.
+// ZK_REC29_AOS=1 (A/B builds: make VARIANT=aos EXTRA=-DZK_REC29_AOS=1) lays the same 36 n bytes out as an array of 36-byte rows,
+// limbs 0 .. 8 in order: two 16-byte accesses and a 4-byte one at 4-byte alignment.  profiles/r19_coset_records.md has both measured.
+#ifndef ZK_REC29_AOS
+#define ZK_REC29_AOS 0
+#endif
+constexpr size_t REC29_BYTES = 36;
+// canonical limbs of a normalised value < 2p
+template <class P>
+__host__ __device__ __forceinline__ F29<P> canon29_lt2p(const F29<P>& a) {
+    F29<P> d;
+    int32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int32_t s_ = (int32_t)a.l[i] - (int32_t)P::M(i) + c;
+        d.l[i] = i < 8 ? ((uint32_t)s_ & MASK29) : (uint32_t)s_;
+        c = s_ >> 29;
+    }
+    const bool neg_ = (int32_t)d.l[8] < 0;
+    F29<P> r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.l[i] = neg_ ? a.l[i] : d.l[i];
+    return r;
+}
+#if defined(__HIPCC__)
+// row `idx` of the record buffer `base` of n rows <- v (canonical limbs)
+template <class P>
+__device__ __forceinline__ void rec29_store(Fp<typename P::P32>* base, uint64_t n, uint64_t idx, const F29<P>& v) {
+#if ZK_REC29_AOS
+    typedef uint32_t U4A __attribute__((ext_vector_type(4), aligned(4)));
+    char* p = reinterpret_cast<char*>(base) + idx * REC29_BYTES;
+    *reinterpret_cast<U4A*>(p) = U4A{v.l[0], v.l[1], v.l[2], v.l[3]};
+    *reinterpret_cast<U4A*>(p + 16) = U4A{v.l[4], v.l[5], v.l[6], v.l[7]};
+    *reinterpret_cast<uint32_t*>(p + 32) = v.l[8];
+#else
+    uint4* q = reinterpret_cast<uint4*>(base + idx);
+    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+    reinterpret_cast<uint32_t*>(base + n)[idx] = v.l[8];
+#endif
+}
+#endif
 
 // Montgomery square: the cross products a_i a_j (i < j) are taken once against the doubled limb,
 // 45 products instead of 81 in the operand part (the reduction part is unchanged): 126 vs 162.

@@ -89,7 +89,7 @@ struct Lds29 {
 };
 
 // out[j] = base^j * mul   (table builder; one thread per entry, square-and-multiply).
-// rprime != 0: store in R' = 2^261 Montgomery form.
+// rprime != 0: store in R' = 2^261 Montgomery form; rprime == 2: as a coset record of `count` rows (ff29.hip.hpp).
 __global__ void k_powers(Fr base, Fr mul, Fr* out, uint32_t count, int rprime) {
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= count) return;
@@ -100,7 +100,8 @@ __global__ void k_powers(Fr base, Fr mul, Fr* out, uint32_t count, int rprime) {
         b = sqr(b);
         e >>= 1;
     }
-    stg(out + j, rprime ? to_rprime(r) : r);
+    if (rprime == 2) rec29_store<Fr29P>(out, count, j, unpack29<Fr29P>(to_rprime(r)));
+    else stg(out + j, rprime ? to_rprime(r) : r);
 }
 
 __device__ __forceinline__ Fr two_level(const Fr* __restrict__ lo, const Fr* __restrict__ hi, int h, uint32_t e) {
@@ -351,14 +352,16 @@ __host__ __device__ __forceinline__ int ntt_row_pad(int log_np) { return log_np 
 // PRE: the coset shift, only when this is the only pass.  FOLDED: the output scale rode on the last inter-pass twiddle and the
 // outputs are only reduced; otherwise every output is multiplied by `fin` (1 or the inverse-transform scale, R' form), which
 // also brings the lazy sums back below 2p.  A digit of 2 or 4 (log_n = 1, 2) is one step, first and last at once.
-template <int R, bool FIRST, bool LAST, Opt PRE, Opt FOLDED>
+// REC: the outputs leave as coset records (ff29.hip.hpp: canonical limbs, split layout over the 2^log_n rows of dst) instead of packed
+// elements -- what the quotient evaluator computes on.  Records are only ever a destination, never read back by a transform.
+template <int R, bool FIRST, bool LAST, Opt PRE, Opt FOLDED, Opt REC>
 __device__ __forceinline__ void ntt_last_step(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw, const Fr* __restrict__ pre,
                                               const Fr29& fin29, const bool fin_folded, const int log_np, const int s, const int log_t, const int row,
-                                              const uint32_t blk, const uint32_t mid, const int log_mid, const int log_n1) {
+                                              const uint32_t blk, const uint32_t mid, const int log_mid, const int log_n1, const bool records) {
     static_assert(R == 2 || FIRST, "only the first step of a pass can be radix 2");
     constexpr int NE = 1 << R;
     const int hgt = 1 << s, T = 1 << log_t, items = (1 << (log_np + log_t)) >> R;
-    const bool has_pre = opt_on<PRE>(pre != nullptr), folded = opt_on<FOLDED>(fin_folded);
+    const bool has_pre = opt_on<PRE>(pre != nullptr), folded = opt_on<FOLDED>(fin_folded), rec = opt_on<REC>(records);
     for (int it = threadIdx.x; it < items; it += blockDim.x) {
         int c, b;
         if (LAST) { c = it & (T - 1); b = it >> log_t; }                              // c fastest: coalesced output
@@ -390,8 +393,11 @@ __device__ __forceinline__ void ntt_last_step(const Lds29& L, const Fr* __restri
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
             const int dl = lo_d + k * hgt;
-            if (LAST) stg(dst + (i1 + (((uint64_t)mid + ((uint64_t)dl << log_mid)) << log_n1)), folded ? reduce_lazy29(e[k]) : pack29_lt2p(mul29(e[k], fin29)));
-            else L.store(c * row + dl, e[k]);
+            if (LAST) {
+                const uint64_t oi = i1 + (((uint64_t)mid + ((uint64_t)dl << log_mid)) << log_n1);
+                if (rec) rec29_store<Fr29P>(dst, 1ull << (log_np + log_mid + log_n1), oi, canon29_lt2p(folded ? reduce_lazy29_limbs(e[k]) : mul29(e[k], fin29)));
+                else stg(dst + oi, folded ? reduce_lazy29(e[k]) : pack29_lt2p(mul29(e[k], fin29)));
+            } else L.store(c * row + dl, e[k]);
         }
     }
 }
@@ -406,7 +412,7 @@ __device__ __forceinline__ uint32_t last_tile(int xcd_remap) {
 
 // blockIdx.y = column; the same arguments for every last-pass kernel, as for the strided pass
 __global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_last(NttIo io, const Tw29* __restrict__ tw, int log_np, int log_t, int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap) {
+k_ntt_last(NttIo io, const Tw29* __restrict__ tw, int log_np, int log_t, int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap, int records) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const Fr* __restrict__ src = io.src[blockIdx.y];
     Fr* __restrict__ dst = io.dst[blockIdx.y];
@@ -418,7 +424,7 @@ k_ntt_last(NttIo io, const Tw29* __restrict__ tw, int log_np, int log_t, int log
         const int r = ((log_np - s) & 1) ? 1 : 2;
         const bool last = s + r == log_np;
         auto step = [&](auto R, auto FIRST, auto LAST) {
-            ntt_last_step<decltype(R)::value, decltype(FIRST)::value, decltype(LAST)::value, OPT_RUNTIME, OPT_RUNTIME>(L, src, dst, tw, pre, fin29, fin_folded != 0, log_np, s, log_t, row, blk, mid, log_mid, log_n1);
+            ntt_last_step<decltype(R)::value, decltype(FIRST)::value, decltype(LAST)::value, OPT_RUNTIME, OPT_RUNTIME, OPT_RUNTIME>(L, src, dst, tw, pre, fin29, fin_folded != 0, log_np, s, log_t, row, blk, mid, log_mid, log_n1, records != 0);
         };
         if (s == 0 && last) { if (r == 1) step(Int<1>{}, Bool<true>{}, Bool<true>{}); else step(Int<2>{}, Bool<true>{}, Bool<true>{}); }
         else if (s == 0) { if (r == 1) step(Int<1>{}, Bool<true>{}, Bool<false>{}); else step(Int<2>{}, Bool<true>{}, Bool<false>{}); }
@@ -429,24 +435,24 @@ k_ntt_last(NttIo io, const Tw29* __restrict__ tw, int log_np, int log_t, int log
     }
 }
 // the instances exist for digits of 2^7 and more: at least two steps, no coset shift (not the only pass), the scale folded
-template <int LOG_NP, int S>
+template <int LOG_NP, int S, bool REC>
 __device__ __forceinline__ void ntt_last_steps(const Lds29& L, const Fr* __restrict__ src, Fr* __restrict__ dst, const Tw29* __restrict__ tw,
                                                const int log_t, const int row, const uint32_t blk, const uint32_t mid, const int log_mid, const int log_n1) {
     constexpr int R = ((LOG_NP - S) & 1) ? 1 : 2;
     constexpr bool LAST = S + R == LOG_NP;
-    ntt_last_step<R, S == 0, LAST, OPT_NO, OPT_YES>(L, src, dst, tw, nullptr, Fr29{}, true, LOG_NP, S, log_t, row, blk, mid, log_mid, log_n1);
+    ntt_last_step<R, S == 0, LAST, OPT_NO, OPT_YES, REC ? OPT_YES : OPT_NO>(L, src, dst, tw, nullptr, Fr29{}, true, LOG_NP, S, log_t, row, blk, mid, log_mid, log_n1, REC);
     if constexpr (!LAST) {
         __syncthreads();
-        ntt_last_steps<LOG_NP, S + R>(L, src, dst, tw, log_t, row, blk, mid, log_mid, log_n1);
+        ntt_last_steps<LOG_NP, S + R, REC>(L, src, dst, tw, log_t, row, blk, mid, log_mid, log_n1);
     }
 }
-template <int LOG_NP>
+template <int LOG_NP, bool REC>
 __global__ void __launch_bounds__(NTT_THREADS)
-k_ntt_last_f(NttIo io, const Tw29* __restrict__ tw, int /* LOG_NP */, int log_t, int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap) {
+k_ntt_last_f(NttIo io, const Tw29* __restrict__ tw, int /* LOG_NP */, int log_t, int log_n1, int log_mid, Fr fin, const Fr* __restrict__ pre, int fin_folded, int xcd_remap, int /* REC */) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const int row = (1 << LOG_NP) + ntt_row_pad(LOG_NP);
     const uint32_t bx = last_tile(xcd_remap), mid = bx & ((1u << log_mid) - 1), blk = bx >> log_mid;
-    ntt_last_steps<LOG_NP, 0>(Lds29{smem, row << log_t}, io.src[blockIdx.y], io.dst[blockIdx.y], tw, log_t, row, blk, mid, log_mid, log_n1);
+    ntt_last_steps<LOG_NP, 0, REC>(Lds29{smem, row << log_t}, io.src[blockIdx.y], io.dst[blockIdx.y], tw, log_t, row, blk, mid, log_mid, log_n1);
 }
 
 __global__ void k_scale(Fr* a, Fr s, uint64_t n) {
@@ -693,12 +699,12 @@ static PassKernel pass_instance(int log_np, bool pre) {
         default: return pre ? k_ntt_pass_f<10, true> : k_ntt_pass_f<10, false>;
     }
 }
-static LastKernel last_instance(int log_np) {
+static LastKernel last_instance(int log_np, bool rec) {
     switch (log_np) {
-        case 7: return k_ntt_last_f<7>;
-        case 8: return k_ntt_last_f<8>;
-        case 9: return k_ntt_last_f<9>;
-        default: return k_ntt_last_f<10>;
+        case 7: return rec ? k_ntt_last_f<7, true> : k_ntt_last_f<7, false>;
+        case 8: return rec ? k_ntt_last_f<8, true> : k_ntt_last_f<8, false>;
+        case 9: return rec ? k_ntt_last_f<9, true> : k_ntt_last_f<9, false>;
+        default: return rec ? k_ntt_last_f<10, true> : k_ntt_last_f<10, false>;
     }
 }
 // strided pass p of the domain; `pre`: the coset shift table of a first pass, or null
@@ -721,12 +727,12 @@ static int launch_pass(zk_ctx* ctx, const NttDomain& dom, int p, size_t nb, cons
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
-// `pre`: the coset shift table when this is the only pass, or null
-static int launch_last(zk_ctx* ctx, const NttDomain& dom, size_t nb, const NttKnobs& kn, const NttIo& io, const Fr* pre) {
+// `pre`: the coset shift table when this is the only pass, or null; `records`: the outputs are coset records (36 bytes per row at io.dst)
+static int launch_last(zk_ctx* ctx, const NttDomain& dom, size_t nb, const NttKnobs& kn, const NttIo& io, const Fr* pre, bool records) {
     const int P = dom.npass;
     const NttPass& ps = dom.pass[P - 1];
     NttPlan pl = plan_last(dom, nb, kn);
-    LastKernel kernel = pl.fixed ? last_instance(ps.log_np) : k_ntt_last;
+    LastKernel kernel = pl.fixed ? last_instance(ps.log_np, records) : k_ntt_last;
     if (pl.fixed && !pass_kernel_ready(ctx, (const void*)kernel, NTT_LAST_MAX_LDS)) {
         NttKnobs generic = kn;
         generic.fixed = false;
@@ -737,7 +743,7 @@ static int launch_last(zk_ctx* ctx, const NttDomain& dom, size_t nb, const NttKn
     ZkProfScope pscope(ctx, "ntt_last");
     pscope.bytes = (uint64_t)nb * (1ull << dom.log_n) * 64 / (uint64_t)P;
     hipLaunchKernelGGL(kernel, pl.grid, dim3(pl.threads), pl.lds, ctx->stream, io, ps.tw, ps.log_np, pl.log_t, P == 1 ? 0 : dom.pass[0].log_np, P == 3 ? dom.pass[1].log_np : 0,
-                       dom.final_mul, pre, dom.fin_folded ? 1 : 0, pl.xcd);
+                       dom.final_mul, pre, dom.fin_folded ? 1 : 0, pl.xcd, records ? 1 : 0);
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
@@ -762,7 +768,18 @@ int ntt_run(zk_ctx* ctx, Fr* d_data, uint32_t log_n, const Fr& omega, const Fr* 
     return ntt_run_many(ctx, &d_data, d_src ? &d_src : nullptr, 1, log_n, omega, scale, coset_pre, coset_post, fuse_pre);
 }
 int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_t count, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, bool fuse_pre) {
+    return ntt_run_many_fmt(ctx, d_datas, d_srcs, count, log_n, omega, scale, coset_pre, coset_post, fuse_pre, false);
+}
+// records: d_datas[i] (36 bytes per row, ff29.hip.hpp) receives the transform as coset records, written by the last pass alone: every
+// transform needs a source of its own and no pass may follow the last one (coset_post).  Until then the buffer serves as it always did
+// (the first of three passes and a coset shift without a table park packed elements in its first 32 bytes per row).
+int ntt_run_many_fmt(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_t count, uint32_t log_n, const Fr& omega, const Fr* scale, const Fr* coset_pre, const Fr* coset_post, bool fuse_pre,
+                     bool records) {
     if (count == 0) return ZK_OK;
+    if (records) {
+        if (coset_post || log_n == 0 || !d_srcs) return ctx->fail(ZK_ERR_INVALID_ARG, "NTT: record output needs a source of its own, one row at least and no pass behind the transform");
+        for (size_t i = 0; i < count; ++i) if (!d_srcs[i] || d_srcs[i] == d_datas[i]) return ctx->fail(ZK_ERR_INVALID_ARG, "NTT: record output in place");
+    }
     const NttKnobs kn = read_ntt_knobs();
     if (log_n == 0) {   // size-1 transforms: identity (times the scale)
         for (size_t i = 0; i < count; ++i) {
@@ -815,11 +832,18 @@ int ntt_run_many(zk_ctx* ctx, Fr* const* d_datas, const Fr* const* d_srcs, size_
             for (size_t j = 0; j < nb; ++j) io.src[j] = io.dst[j];
         }
         for (size_t j = 0; j < nb; ++j) io.dst[j] = d_datas[first + j];
-        rc = launch_last(ctx, *dom, nb, kn, io, P == 1 ? pre_table : nullptr);
+        rc = launch_last(ctx, *dom, nb, kn, io, P == 1 ? pre_table : nullptr, records);
         if (rc) return rc;
         if (coset_post) for (size_t j = 0; j < nb; ++j) { rc = run_distribute(ctx, log_n, *coset_post, io.dst[j], io.dst[j]); if (rc) return rc; }
     }
     return ZK_OK;
+}
+
+// `count` polynomials on the coset g H, packed or as the records the quotient's class programs read: 32 x the value, the factor
+// being the transform's output scale (one more cached domain per size; it rides on the last inter-pass twiddle table for nothing)
+int coeff_to_coset_batch_fmt(zk_ctx* ctx, const void* const* d_coeffs, uint32_t k, const Fr& g, void* const* d_outs, size_t count, bool records) {
+    const Fr s32 = fr_from_u64(32);
+    return ntt_run_many_fmt(ctx, (Fr* const*)d_outs, (const Fr* const*)d_coeffs, count, k, fr_root_of_unity(k), records ? &s32 : nullptr, &g, nullptr, /*fuse_pre=*/true, records);
 }
 
 // ---- one transform spread over several GPUs (SURVEY 8e "domain halves": the 4-step split) ------

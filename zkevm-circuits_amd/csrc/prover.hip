@@ -43,6 +43,7 @@
 #include <tuple>
 #include <functional>
 #include "ctx.hpp"
+#include "ff29.hip.hpp"
 #include "host_hash.hpp"
 #include "cs.hpp"
 #include "quotient_plan.hpp"
@@ -149,6 +150,7 @@ struct zk_pk : zk::cs::ConstraintSystem {   // the constraint system (cs.hpp) an
     mutable std::vector<std::unordered_map<uint32_t, DevBuf>> part_cache;
     mutable int part_cache_state = -1;       // -1 undecided, 0 off, 1 on, 2 frozen (slots that exist are used, no new ones: an allocation failed)
     mutable size_t part_cache_bytes = 0;     // what this key's slots hold of the context's shared budget (zk_ctx::coset_cache_bytes)
+    mutable bool part_cache_records = false; // the slots hold coset records (quotient_records below); a session of the other format empties the cache and fills it again
     std::vector<G1Affine> fixed_com, sigma_com;
     F4 vk_repr;                              // vk.transcript_repr: the default, or what zk_pk_set_transcript_repr installed
     const zk_srs* srs = nullptr;
@@ -166,6 +168,7 @@ struct zk_proof {
     std::vector<std::vector<DevBuf>> adv_coset;
     std::vector<uint32_t> pre_mask;
     bool pre_planned = false;
+    int coset_fmt = -1;                       // what adv_coset holds: -1 nothing yet, 0 packed elements, 1 coset records (session_records)
     uint32_t phase = 0;
     int multiopen = ZK_MULTIOPEN_GWC;
     int vanishing_random = ZK_VANISHING_ONE;
@@ -206,6 +209,21 @@ size_t device_free_bytes(bool* ok = nullptr) {
     if (!got) { (void)hipGetLastError(); free_b = 0; }
     if (ok) *ok = got;
     return free_b;
+}
+
+// The cosets of the columns are read by the quotient's class programs and by nothing else, so they are written as what those programs
+// compute on: coset records of 32 x the value (ff29.hip.hpp; the last pass of the transform writes them, k_quotient_eval2's record mode
+// reads them without unpacking).  ZK_QUOTIENT_RECORDS=0 keeps packed elements, and so does the older kernel (ZK_QUOTIENT_KERNEL=1), which
+// has no record mode.  Read where a session first makes a coset and again where its quotient starts: the tests flip both knobs in one process.
+bool quotient_records(uint32_t k) {
+    const char* r = getenv("ZK_QUOTIENT_RECORDS");
+    const char* q = getenv("ZK_QUOTIENT_KERNEL");
+    return !(r && atoi(r) == 0) && !(q && atoi(q) == 1) && k >= 2 && k <= 26;        // the record mode addresses a row with 32-bit byte offsets
+}
+size_t coset_row_bytes(bool records) { return records ? REC29_BYTES : sizeof(Fr); }
+bool session_records(zk_proof* pr) {
+    if (pr->coset_fmt < 0) pr->coset_fmt = quotient_records(pr->pk->k) ? 1 : 0;
+    return pr->coset_fmt == 1;
 }
 
 // Degree class e is evaluated on the cosets class_on_coset(E, e, r) names (quotient_plan.hpp) and, in a sharded session, by the rank
@@ -349,15 +367,16 @@ int concretise(zk_ctx* ctx, const Env& e, const Prog& g, Concrete* c) {
 }
 // Every form the prover evaluates over has n = 2^k rows (Lagrange values, or one coset of the
 // extended domain), so a rotation is a plain index shift modulo n.
-int run_program(zk_ctx* ctx, const Env& e, const Prog& g, void* d_out) {
+// records: the columns of `e` are coset records (a class program on one coset); d_out then holds 32 x the values
+int run_program(zk_ctx* ctx, const Env& e, const Prog& g, void* d_out, bool records = false) {
     Concrete c;
     PK_TRY(concretise(ctx, e, g, &c));
     {   // measurement knob (results are WRONG): every operand read from ONE column -- the same instruction stream with its loads served by the caches
         static const int alias = getenv("ZK_QUOTIENT_ALIAS") ? atoi(getenv("ZK_QUOTIENT_ALIAS")) : 0;      // N: the class programs read N distinct columns in all
         if (alias > 0 && ctx->prof_tag && !strcmp(ctx->prof_tag, "quotient_coset")) for (size_t i = 0; i < c.cols.size(); ++i) c.cols[i] = c.cols[i % (size_t)alias];
     }
-    return zk_quotient_eval(ctx, c.words.data(), (uint32_t)(c.words.size() / 3), c.cols.data(), (uint32_t)c.cols.size(),
-                            c.consts.empty() ? nullptr : c.consts.data(), (uint32_t)c.consts.size(), e.pk->k, e.pk->k, 0, d_out);
+    return quotient_eval_fmt(ctx, c.words.data(), (uint32_t)(c.words.size() / 3), c.cols.data(), (uint32_t)c.cols.size(),
+                             c.consts.empty() ? nullptr : c.consts.data(), (uint32_t)c.consts.size(), e.pk->k, e.pk->k, 0, d_out, records);
 }
 // coefficient form of an abstract column (nullptr for X, which has no stored polynomial)
 const Fr* coeff_of(const zk_pk* pk, uint32_t ref, const std::vector<DevBuf>& adv, const std::vector<DevBuf>& inst, const std::vector<DevBuf>& pz,
@@ -1021,14 +1040,14 @@ static int advice_phase_impl(zk_ctx* ctx, zk_proof* pr, const uint32_t* col_inde
                     const uint32_t gc = col[c_];
                     if (!(pr->pre_mask[gc] >> r & 1u)) continue;
                     DevBuf& slot = pr->adv_coset[r][gc];
-                    if (!slot.alloc(n_ * 32)) {          // the estimate was too generous: stop computing ahead, the quotient transforms the rest itself
+                    if (!slot.alloc(n_ * coset_row_bytes(session_records(pr)))) {          // the estimate was too generous: stop computing ahead, the quotient transforms the rest itself
                         for (uint32_t& m_ : pr->pre_mask) m_ = 0;
                         break;
                     }
                     csrc.push_back(coeff[c_]->p);
                     cdst.push_back(slot.p);
                 }
-                if (!csrc.empty()) PK_TRY(zk_coeff_to_coset_batch(ctx, csrc.data(), pk->k, &g_of_r[r], cdst.data(), csrc.size()));
+                if (!csrc.empty()) PK_TRY(coeff_to_coset_batch_fmt(ctx, csrc.data(), pk->k, g_of_r[r], cdst.data(), csrc.size(), session_records(pr)));
             }
             pending.clear();
             return ZK_OK;
@@ -1306,18 +1325,20 @@ static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr) {
     const uint32_t E = pk->ext_k - pk->k, R = 1u << E;
     if (E > 5) return ZK_OK;
     const double col_bytes = (double)((size_t)1 << pk->k) * 32.0;
+    const double coset_bytes = (double)((size_t)1 << pk->k) * (double)coset_row_bytes(session_records(pr));       // a coset buffer, in the session's format
     bool mem_known = false;
     const size_t free_b = device_free_bytes(&mem_known);
     if (!mem_known) return ZK_OK;            // nothing is computed ahead on a guess
     // columns' worth of buffers still to come, the advice columns' own coset buffers aside (counted below, per choice of cosets):
     // Lagrange + coefficient forms of the advice columns, of m / phi / Z with their temporaries, their coset buffers, h, slack
     // (a witness handed over in place brings its Lagrange forms along)
-    const double cols_ahead = (pr->advice_in_place ? 1.0 : 2.0) * pk->A + 3.0 * (2.0 * pk->L + pk->C) + (2.0 * pk->L + pk->C + pk->I + 8.0) + 2.0 * R + 32.0;
-    double avail = (double)free_b + (double)ctx->pool_bytes - cols_ahead * col_bytes - 16.0 * (double)(1ull << 30);
+    const double cols_ahead = (pr->advice_in_place ? 1.0 : 2.0) * pk->A + 3.0 * (2.0 * pk->L + pk->C) + 2.0 * R + 32.0, cosets_ahead = 2.0 * pk->L + pk->C + pk->I + 8.0;
+    const double reserve = cols_ahead * col_bytes + cosets_ahead * coset_bytes;
+    double avail = (double)free_b + (double)ctx->pool_bytes - reserve - 16.0 * (double)(1ull << 30);
     if (pk->part_cache_state < 0 || (pk->part_cache_state == 1 && pk->part_cache_bytes == 0)) {
         // the key's own cosets (fixed, sigma, l_0 ...) are still to be cached by this proof's quotient: reserved, counted from the
         // class programs (a fixed column read only by low-degree gates is cached on two cosets, not on all)
-        const double key_need = (double)key_slots * col_bytes;
+        const double key_need = (double)key_slots * coset_bytes;
         const char* kenv = getenv("ZK_PK_COSET_CACHE_GB");
         const double kcap = std::min((kenv ? atof(kenv) : 96.0) * (double)(1ull << 30), (double)ctx->prop.totalGlobalMem / 3.0);
         if (key_need <= kcap) avail -= std::max(0.0, key_need - (double)pk->part_cache_bytes);
@@ -1329,13 +1350,13 @@ static int plan_advice_cosets(zk_ctx* ctx, zk_proof* pr) {
     for (const auto& cr : by_count) {
         uint32_t rest = 0;                       // advice columns the quotient still has to transform itself (one coset buffer each)
         for (uint32_t m_ : mask) rest += (m_ & ~(chosen | 1u << cr.second)) != 0;
-        if (used + cr.first * col_bytes > cap || used + (cr.first + rest) * col_bytes > avail) break;
-        used += cr.first * col_bytes;
+        if (used + cr.first * coset_bytes > cap || used + (cr.first + rest) * coset_bytes > avail) break;
+        used += cr.first * coset_bytes;
         chosen |= 1u << cr.second;
     }
     if (getenv("ZK_PROVER_TRACE")) {
         fprintf(stderr, "[zk prover] advice coset plan: free %.1f + pooled %.1f GiB, reserve %.1f GiB, budget %.1f GiB, cosets by columns served:", free_b / 1073741824.0, ctx->pool_bytes / 1073741824.0,
-                (cols_ahead * col_bytes) / 1073741824.0 + 16.0, budget / 1073741824.0);
+                reserve / 1073741824.0 + 16.0, budget / 1073741824.0);
         for (const auto& cr : by_count) fprintf(stderr, " r%u:%u", cr.second, cr.first);
         fprintf(stderr, " -> chosen 0x%x\n", chosen);
     }
@@ -1380,6 +1401,7 @@ struct Finish {
     const bool shard_args;
     std::vector<uint32_t> act;                // the arguments this rank works on, in order
     bool late_cosets = false;                 // the auxiliary stream holds coset transforms of this session's advice columns
+    bool records = false;                     // the cosets of this session are coset records (finish_coset_format)
     // lookups: compressed inputs and tables (until the grand sums have read them), m and phi in Lagrange form
     std::vector<std::vector<DevBuf>> lk_f;
     std::vector<DevBuf> lk_t, lk_m, lk_phi;
@@ -1442,7 +1464,7 @@ static int stage_late_advice_cosets(Finish& f) {
     size_t key_slots = 0;
     PK_TRY(advice_coset_plan(ctx, pk, mask, &key_slots));
     if (pr->adv_coset.empty()) { pr->adv_coset.resize(R); for (auto& v : pr->adv_coset) v.resize(pk->A); }
-    const double col_bytes = (double)n * 32.0;
+    const double col_bytes = (double)n * (double)coset_row_bytes(f.records);        // everything counted below is, or is taken to be as large as, a coset buffer
     const size_t free_b = device_free_bytes();          // unknown counts as none
     // still to come: m / phi / Z in Lagrange and coefficient form with their temporaries, their coset buffers, h, slack;
     // the key's own cosets if its cache is still empty
@@ -1464,7 +1486,7 @@ static int stage_late_advice_cosets(Finish& f) {
         for (uint32_t c = 0; c < pk->A && ok; ++c) {
             if (!todo(cr.second, c)) continue;
             DevBuf& slot = pr->adv_coset[cr.second][c];
-            if (!slot.alloc(n * 32)) { ok = false; break; }
+            if (!slot.alloc(n * coset_row_bytes(f.records))) { ok = false; break; }
             csrc.push_back(pr->adv_coeff[c].p);
             cdst.push_back(slot.p);
         }
@@ -1474,7 +1496,7 @@ static int stage_late_advice_cosets(Finish& f) {
         }
         ctx->stream = ctx->stream_aux;
         f.late_cosets = true;
-        if (!csrc.empty()) PK_TRY(zk_coeff_to_coset_batch(ctx, csrc.data(), f.k, &g, cdst.data(), csrc.size()));
+        if (!csrc.empty()) PK_TRY(coeff_to_coset_batch_fmt(ctx, csrc.data(), f.k, g, cdst.data(), csrc.size(), f.records));
         ctx->stream = main_stream;
         used += csrc.size() * col_bytes;
         if (!ok) break;
@@ -1869,8 +1891,9 @@ static void quotient_decide_key_cache(Finish& f, const Quotient& q) {
     double budget = (env ? atof(env) : 96.0) * (double)(1ull << 30);
     budget = std::min(budget, (double)ctx->prop.totalGlobalMem / 3.0) - (double)ctx->coset_cache_bytes;
     const size_t free_b = device_free_bytes();          // unknown counts as none
-    const double need = (double)key_slots * n * 32.0;
-    const double session = (double)refs.size() * n * 32.0 + (double)((size_t)n << q.E) * 32.0 * 2.0;       // this proof's own coset buffers and h
+    const double row = (double)coset_row_bytes(f.records);
+    const double need = (double)key_slots * n * row;
+    const double session = (double)refs.size() * n * row + (double)((size_t)n << q.E) * 32.0 * 2.0;       // this proof's own coset buffers and h
     pk->part_cache_state = (need <= budget && need + session <= (double)free_b + (double)ctx->pool_bytes) ? 1 : 0;
     if (pk->part_cache_state) pk->part_cache.resize(q.nparts);
 }
@@ -1917,6 +1940,7 @@ static int quotient_transform(Finish& f, const Quotient& q, CosetPass& cp, Coset
     std::vector<DevBuf>& bufs = cp.part_buf;
     const bool cache_on = cp.cache_on;
     const uint32_t k = f.k;
+    const size_t coset_bytes = n * coset_row_bytes(f.records);
     const Fr w_n = fr_root_of_unity(k);
     auto pre_coset = [&](uint32_t ref, uint32_t r) -> const void* {      // an advice column's coset r computed during the advice phases, if any
         if ((ref >> 24) != CT_ADVICE || r >= pr->adv_coset.size()) return nullptr;
@@ -1936,7 +1960,7 @@ static int quotient_transform(Finish& f, const Quotient& q, CosetPass& cp, Coset
         for (uint32_t e : w.active) needed |= q.reads(e, refs[i]);
         if (!needed) continue;
         if (const void* pre = pre_coset(refs[i], r_)) { w.part_of[refs[i]] = pre; continue; }
-        if (!(cache_on && key_column(refs[i])) && !bufs[i].p) PK_ALLOC(ctx, bufs[i], n * 32);
+        if (!(cache_on && key_column(refs[i])) && !bufs[i].p) PK_ALLOC(ctx, bufs[i], coset_bytes);
         void* dst = bufs[i].p;
         DevBuf fresh;                             // a cache slot being filled: published only once it holds the coset
         const bool cached = cache_on && key_column(refs[i]);
@@ -1947,22 +1971,22 @@ static int quotient_transform(Finish& f, const Quotient& q, CosetPass& cp, Coset
             // pool's parked blocks back and retry; if that fails too, freeze the cache (existing slots stay in use) and
             // compute this coset into a session buffer like any witness column's -- the proof goes on, uncached.
             const char* env_fail = getenv("ZK_PK_COSET_CACHE_FAIL_AFTER");        // test knob: the device "runs out" after this many slots
-            const bool inject = env_fail && pk->part_cache_bytes / (n * 32) + fresh_slots.size() >= (size_t)atoll(env_fail);
-            bool got = pk->part_cache_state == 1 && !inject && fresh.alloc_unpooled(n * 32);
+            const bool inject = env_fail && pk->part_cache_bytes / coset_bytes + fresh_slots.size() >= (size_t)atoll(env_fail);
+            bool got = pk->part_cache_state == 1 && !inject && fresh.alloc_unpooled(coset_bytes);
             if (!got && pk->part_cache_state == 1) {
                 (void)hipGetLastError();
                 ctx->pool_trim();
-                got = !inject && fresh.alloc_unpooled(n * 32);
+                got = !inject && fresh.alloc_unpooled(coset_bytes);
                 if (!got) { (void)hipGetLastError(); pk->part_cache_state = 2; }
             }
             if (got) dst = fresh.p;
             else {
-                if (!bufs[i].p) PK_ALLOC(ctx, bufs[i], n * 32);
+                if (!bufs[i].p) PK_ALLOC(ctx, bufs[i], coset_bytes);
                 dst = bufs[i].p;
             }
         }
         w.part_of[refs[i]] = dst;
-        if (refs[i] == colref(CT_SPECIAL, SP_X)) PK_TRY(zk_fr_powers(ctx, &w_n, &w.g, dst, n));   // X on the coset: g * omega^i
+        if (refs[i] == colref(CT_SPECIAL, SP_X)) PK_TRY(fr_powers_fmt(ctx, w_n, w.g, dst, n, f.records));   // X on the coset: g * omega^i
         else {
             const Fr* cf = (refs[i] >> 24) == CT_SPLIT_R ? ((refs[i] & 0xFFFFFFu) < f.rem_coeff.size() ? f.rem_coeff[refs[i] & 0xFFFFFFu].fr() : nullptr)
                                                          : coeff_of(pk, refs[i], pr->adv_coeff, pr->inst_coeff, f.pz_coeff, f.m_coeff, f.phi_coeff);
@@ -1972,10 +1996,10 @@ static int quotient_transform(Finish& f, const Quotient& q, CosetPass& cp, Coset
         }
         if (cached && fresh.p) fresh_slots.emplace_back(refs[i], std::move(fresh));
     }
-    PK_TRY(zk_coeff_to_coset_batch(ctx, bat_src.data(), k, &w.g, bat_dst.data(), bat_src.size()));
+    PK_TRY(coeff_to_coset_batch_fmt(ctx, bat_src.data(), k, w.g, bat_dst.data(), bat_src.size(), f.records));
     for (auto& fs : fresh_slots) {
-        pk->part_cache_bytes += n * 32;
-        ctx->coset_cache_bytes += n * 32;
+        pk->part_cache_bytes += coset_bytes;
+        ctx->coset_cache_bytes += coset_bytes;
         pk->part_cache[r_][fs.first] = std::move(fs.second);
     }
     return ZK_OK;
@@ -1994,10 +2018,10 @@ static int quotient_programs(Finish& f, Quotient& q, CosetPass& cp, CosetWork& w
     part.part = &w.part_of;
     Fr gn = w.g;
     for (uint32_t i = 0; i < k; ++i) gn = sqr(gn);
-    const Fr vinv = fr_inv_host(gn - Fr::one());
+    const Fr vinv = fr_inv_host(gn - Fr::one()), inv32 = fr_inv_host(fr_from_u64(32));
     for (uint32_t e : w.active) {
         ctx->prof_tag = "quotient_coset";
-        const int rc_q = run_program(ctx, part, q.cls(e).prog, hpart.p);
+        const int rc_q = run_program(ctx, part, q.cls(e).prog, hpart.p, f.records);
         ctx->prof_tag = nullptr;
         PK_TRY(rc_q);
         // class e lags (K - 1 - last) positions behind the end of the constraint list: its sum still takes y^(K-1-last)
@@ -2005,6 +2029,7 @@ static int quotient_programs(Finish& f, Quotient& q, CosetPass& cp, CosetWork& w
         Fr scale;
         memcpy((void*)&scale, yp.l, 32);
         scale = scale * vinv;
+        if (f.records) scale = scale * inv32;          // a class program over records leaves 32 x its values
         if (sharded) {                 // peers receive the finished values: keep them until the exchange
             PK_TRY(zk_fr_scale(ctx, hpart.p, &scale, n));
             DevBuf keep;
@@ -2061,12 +2086,29 @@ static int quotient_to_coeff(Finish& f, Quotient& q) {
     return ZK_OK;
 }
 
+// The key's coset cache outlives sessions: one that finds it in the other format (the knobs changed in between) gives the slots back
+// and decides and fills it again like the key's first proof.
+static int key_cache_format(Finish& f) {
+    zk_ctx* ctx = f.ctx; const zk_pk* pk = f.pk;
+    if (pk->part_cache_records == f.records) return ZK_OK;
+    if (pk->part_cache_bytes || !pk->part_cache.empty()) {
+        ZK_HIP(ctx, hipStreamSynchronize(ctx->stream));       // an earlier proof's programs may still be reading the slots
+        pk->part_cache.clear();
+        ctx->coset_cache_bytes -= std::min(ctx->coset_cache_bytes, pk->part_cache_bytes);
+        pk->part_cache_bytes = 0;
+    }
+    pk->part_cache_state = -1;
+    pk->part_cache_records = f.records;
+    return ZK_OK;
+}
+
 static int stage_quotient(Finish& f) {
     zk_ctx* ctx = f.ctx;
     Quotient q;
     PK_TRY(quotient_prepare(f, q));
     {
         CosetPass cp;                         // its buffers go back to the pool before the classes are transformed back
+        PK_TRY(key_cache_format(f));
         if (f.pk->part_cache_state < 0) quotient_decide_key_cache(f, q);
         cp.cache_on = f.pk->part_cache_state >= 1;
         cp.part_buf.resize(q.plan->refs.size());
@@ -2383,6 +2425,20 @@ static int write_proof_out(zk_ctx* ctx, const host::Transcript& tr, void* h_proo
     return ZK_OK;
 }
 
+// The format of this session's cosets, as the knobs stand now.  Cosets computed ahead under other knobs (set between the advice phases
+// and this call) are dropped: the quotient transforms those columns itself.
+static int finish_coset_format(Finish& f) {
+    zk_proof* pr = f.pr;
+    f.records = quotient_records(f.k);
+    if (pr->coset_fmt >= 0 && (pr->coset_fmt == 1) != f.records) {
+        ZK_HIP(f.ctx, hipDeviceSynchronize());                // their transforms run on the auxiliary stream
+        pr->adv_coset.clear();
+        for (uint32_t& m_ : pr->pre_mask) m_ = 0;
+    }
+    pr->coset_fmt = f.records ? 1 : 0;
+    return ZK_OK;
+}
+
 // Everything after the advice phases: lookups, permutation, quotient, evaluations, multi-open -- the stages above, with the
 // transcript's challenges squeezed between them.  Consumes the session (it is freed whether or not the call succeeds).
 int zk_proof_finish(zk_ctx* ctx, zk_proof* pr_raw, void* h_proof, size_t proof_cap, size_t* proof_len) {
@@ -2397,6 +2453,7 @@ int zk_proof_finish(zk_ctx* ctx, zk_proof* pr_raw, void* h_proof, size_t proof_c
     // stages' in `f`, the advice columns and their cosets in `pr`) goes back to the pool, on every return path.
     AuxJoin aux_join{ctx, &f.late_cosets};
     f.lag.theta = tr.squeeze();
+    PK_TRY(finish_coset_format(f));
     PK_TRY(stage_late_advice_cosets(f));
     PK_TRY(stage_lookup_multiplicities(f));
     f.lag.beta = tr.squeeze();

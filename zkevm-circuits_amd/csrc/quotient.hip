@@ -430,9 +430,18 @@ enum QClass : uint32_t {
     C_UNPACK_T32 = 1u << 23, // spill (word 0's flags on the spilled entry), t0 <- 32 x memory operand     PUSH_COL32
     C_MAC2 = 1u << 24,       // t0 <- t0 * B + X * m1 + S * const, pop 3   MAC2_COL
     C_MACS = 1u << 25,       // t0 <- B * 32 t0 + S * const, pop (B popped by C_POP_B)   MAC_STK (under C_RARE)
+    // record mode only: a sum or difference takes its memory operand from the registers it arrived in, before the load of the next
+    // instruction is issued into them (no copy into B: nine v_mov for nine additions)
+    C_ADDM = 1u << 26,       // t0 <- t0 + memory operand                  ADD_COL
+    C_SUBM = 1u << 27,       // t0 <- t0 - memory operand                  SUB_COL
 };
-static uint32_t q_class_mask(uint32_t w0) {
+static uint32_t q_class_mask(uint32_t w0, bool records = false) {
     uint32_t m = 0;
+    if (records && ((w0 & 0xffu) == K_ADD_COL || (w0 & 0xffu) == K_SUB_COL)) {
+        m = C_HASMEM | ((w0 & 0xffu) == K_ADD_COL ? C_ADDM : C_SUBM);
+        if (w0 & (K_SETTLE0 | K_SETTLE1 | K_NORM0 | K_NORM1 | K_SETTLE0_8 | K_SETTLE1_8)) m |= C_FLAGS;
+        return m;
+    }
     switch (w0 & 0xffu) {
         case Q_PUSH_COL: m = C_SPILL | C_UNPACK_T | C_HASMEM; break;
         case Q_PUSH_CONST: m = C_SPILL | C_RARE | C_PUSHC; break;
@@ -463,7 +472,13 @@ static uint32_t q_class_mask(uint32_t w0) {
 
 // `prog`: 4-word instructions (word 0: opcode + settle bits [+ constant of FOLD_COL], 1 / 2: operands, 3: class mask), prog_len of them
 // followed by END quadruples for the fetch-ahead.
-template <bool FULL, bool ACC_MEM>
+// REC (the class programs of a proof): every column, parked intermediates included, is a coset record buffer of 2^ext_k rows (ff29.hip.hpp)
+// holding 32 x the value, i.e. the R' = 2^261 form of what a packed column holds in R form.  A memory operand then arrives as the limbs the
+// products take: no unpacking.  With EVERY value in R' form -- operands, stack, accumulator, additive constants (consts_rp) -- a product
+// reduced by 2^261 is R' again and sums are linear, so the x 32 variants are the plain ones and no stack product shifts: the same lowered
+// words, the result 32 x what the packed program gives (the caller's scale takes the 1/32).  Operands are canonical where the packed ones
+// were up to 32 p: every bound of lower_bounds holds as it stands.
+template <bool FULL, bool ACC_MEM, bool REC>
 __global__ void __launch_bounds__(Q_THREADS) Q_OCC_ATTR
 k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr* const* __restrict__ cols, const QC29* __restrict__ consts,
                  const QC29* __restrict__ consts_rp /* the same constants in R' form */, const Fr* __restrict__ t_evals /* R' form */, uint32_t ext_k, uint32_t k,
@@ -499,6 +514,9 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
         prog_len = slice_tab[2 * sl + 1];
         out += (size_t)sl << ext_k;
     }
+    // The trip count is the same for every lane; said outright, because the record-mode instantiations otherwise keep the loop counter in a
+    // vector register (decrement, compare and three stray v_readfirstlane: five vector instructions per interpreted instruction).
+    prog_len = __builtin_amdgcn_readfirstlane(prog_len);
     const uint32_t i = blk * blockDim.x + threadIdx.x;
     const bool live = FULL || i < (uint32_t)ne;
     const uint32_t rot_scale = 1u << (ext_k - k), row_mask = (uint32_t)ne - 1u;
@@ -510,13 +528,36 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
     using GU4 = const U32x4 __attribute__((address_space(1)));
     using GU1 = uint32_t __attribute__((address_space(1)));
     // The raw memory operand stays in the two 4-register tuples the loads write (unpacked from there: no copies between the load and its use)
-    struct Raw { U32x4 lo, hi; };
+    struct Raw { U32x4 lo, hi; uint32_t top; };                       // top: the ninth limb of a record (REC only)
     auto load = [&](uint32_t a, uint32_t b, Raw& r) {
         const uint32_t row = (i + b * rot_scale) & row_mask;          // b = the rotation as a two's complement word: wraps like the domain
         if (FULL || live) {
-            GU4* q = (GU4*)(uintptr_t)(cols[a] + row);
-            r.lo = q[0]; r.hi = q[1];
+            const Fr* col = cols[a];
+            if (REC && ZK_REC29_AOS) {                                 // 36-byte rows (A/B builds, ff29.hip.hpp)
+                typedef U32x4 U32x4A __attribute__((aligned(4)));
+                using GU4A = const U32x4A __attribute__((address_space(1)));
+                const char* p = (const char*)col + (size_t)row * REC29_BYTES;
+                r.lo = *(GU4A*)(uintptr_t)p; r.hi = *(GU4A*)(uintptr_t)(p + 16);
+                r.top = *(const GU1*)(uintptr_t)(p + 32);
+            } else if (REC) {
+                // record buffers have 2^26 rows at most (the host refuses more): the row's byte offsets fit 32 bits, and a wave-uniform base with
+                // a 32-bit lane offset is an addressing mode of the load -- no 64-bit address arithmetic per operand
+                using GC = const char __attribute__((address_space(1)));
+                GC* base = (GC*)(uintptr_t)col;
+                GC* p = base + (uint32_t)(row << 5);
+                r.lo = *(GU4*)p; r.hi = *(GU4*)(p + 16);
+                r.top = *(const GU1*)(base + (ne << 5) + (uint32_t)(row << 2));
+            } else {
+                GU4* q = (GU4*)(uintptr_t)(col + row);
+                r.lo = q[0]; r.hi = q[1];
+            }
         }
+    };
+    auto raw_limbs = [](Q29& d, Raw& r) {   // REC: the operand as it arrived (opaque for the same reason as raw_fr)
+        asm volatile("" : "+v"(r.lo), "+v"(r.hi), "+v"(r.top));
+        d.l[0] = r.lo.x; d.l[1] = r.lo.y; d.l[2] = r.lo.z; d.l[3] = r.lo.w;
+        d.l[4] = r.hi.x; d.l[5] = r.hi.y; d.l[6] = r.hi.z; d.l[7] = r.hi.w;
+        d.l[8] = r.top;
     };
     auto raw_fr = [](Raw& r) -> Fr {        // opaque: each unpack site unpacks for itself (the compiler otherwise unpacks on EVERY instruction and copies)
         asm volatile("" : "+v"(r.lo), "+v"(r.hi));
@@ -558,27 +599,31 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
     uint32_t w0 = prog[0], w1 = prog[1], w2 = prog[2], w3 = prog[3];
     uint32_t n0 = prog[4], n1 = prog[5], n2 = prog[6], n3 = prog[7];
     Raw m;
-    m.lo = U32x4{0, 0, 0, 0}; m.hi = U32x4{0, 0, 0, 0};
+    m.lo = U32x4{0, 0, 0, 0}; m.hi = U32x4{0, 0, 0, 0}; m.top = 0;
     if (w3 & C_HASMEM) load(w1, w2, m);
     for (uint32_t pc = 0; pc < prog_len; ++pc) {
         const uint32_t f0 = prog[4 * pc + 8], f1 = prog[4 * pc + 9], f2 = prog[4 * pc + 10], f3 = prog[4 * pc + 11];
-        if ((w0 & 0xffu) == Q_END) break;
+        // no test for END: it is the last of the prog_len instructions (the host counts it in) and its class mask is empty, so it runs as a
+        // step that does nothing.  A second way out of the loop made the record-mode instantiations keep the trip count in a vector register.
         // 1. operands: a memory operand leaves its raw registers (which then take the load for instruction pc + 1), a binary stack operation
         //    takes the entry below the top
         if (w3 & C_SPILL) { if (sp >= 1) st_put(sp - 1, t0); ++sp; }
-        if (w3 & C_UNPACK_T) q_unpack_to(t0, raw_fr(m));
+        if (w3 & C_UNPACK_T) { if (REC) raw_limbs(t0, m); else q_unpack_to(t0, raw_fr(m)); }
         if (w3 & C_UNPACK_T32) {                                            // PUSH_COL32: the flags are for the entry that leaves the registers (X of the MAC2_COL to come)
             if (w0 & K_SETTLE0) q_settle_ip(t0);
             if (w0 & K_NORM0) normalize29(t0);
             if (w0 & K_SETTLE0_8) q_settle8_ip(t0);
             st_put(sp - 1, t0);
             ++sp;
-            q_unpack_x32_to(t0, raw_fr(m));
+            if (REC) raw_limbs(t0, m); else q_unpack_x32_to(t0, raw_fr(m));
         }
-        if (w3 & C_UNPACK_B) q_unpack_to(B, raw_fr(m));
-        if (w3 & C_UNPACK_B32) q_unpack_x32_to(B, raw_fr(m));
+        if (REC) { if (w3 & (C_UNPACK_B | C_UNPACK_B32)) raw_limbs(B, m); }
+        else {
+            if (w3 & C_UNPACK_B) q_unpack_to(B, raw_fr(m));
+            if (w3 & C_UNPACK_B32) q_unpack_x32_to(B, raw_fr(m));
+        }
         if (w3 & C_POP_B) { st_get(sp - 2, B); --sp; }
-        if (n3 & C_HASMEM) load(n1, n2, m);
+        if (!REC) { if (n3 & C_HASMEM) load(n1, n2, m); }
         // 2. settle / carry-propagation requests of the lowering (bit 0: the top, bit 1: the entry below it = B)
         if (w3 & C_FLAGS) {
             if (w0 & K_SETTLE0) q_settle_ip(t0);
@@ -587,6 +632,24 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
             if (w0 & K_NORM1) normalize29(B);
             if (w0 & K_SETTLE0_8) q_settle8_ip(t0);
             if (w0 & K_SETTLE1_8) q_settle8_ip(B);
+        }
+        if (REC) {
+            // ADD_COL / SUB_COL read the operand where it arrived (behind the requests for t0: one instruction in four has any), and only
+            // then do those registers take the load for instruction pc + 1
+            // (two single-armed ifs like every other step: an if / else has a join, and the join copies t0)
+            if (w3 & C_ADDM) {
+                Q29 M;
+                raw_limbs(M, m);                       // names for the arrived registers: read once each, no copy survives
+#pragma unroll
+                for (int q = 0; q < 9; ++q) t0.l[q] += M.l[q];
+            }
+            if (w3 & C_SUBM) {                         // canonical subtrahend: its top limb is below that of 2p, no borrow
+                Q29 M;
+                raw_limbs(M, m);
+#pragma unroll
+                for (int q = 0; q < 9; ++q) t0.l[q] = t0.l[q] + kp_balanced<Fr29P>(2, q) - M.l[q];
+            }
+            if (n3 & C_HASMEM) load(n1, n2, m);
         }
         // 3. the operation, on t0 in place
         if (w3 & C_MULV) mul29_ipa(t0, B);
@@ -616,12 +679,12 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
         if (w3 & C_FOLDC) fold(w0, cst(consts_rp, w0 >> K_CONST_SHIFT), B);
         if (w3 & C_RARE) {
             if (w3 & C_PUSHC) {
-                const Q29 c = cst(consts, w1);
+                const Q29 c = cst(REC ? consts_rp : consts, w1);
 #pragma unroll
                 for (int q = 0; q < 9; ++q) t0.l[q] = c.l[q];
             }
             if (w3 & C_ADDC) {
-                const Q29 c = cst(consts, w1);
+                const Q29 c = cst(REC ? consts_rp : consts, w1);
 #pragma unroll
                 for (int q = 0; q < 9; ++q) t0.l[q] += c.l[q];
             }
@@ -630,12 +693,12 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
                 for (int q = 0; q < 9; ++q) t0.l[q] = B.l[q] + kp_balanced<Fr29P>(2, q) - t0.l[q];
                 normalize29(t0);
             }
-            if (w3 & C_MULS) { q_shl5_ip(t0); mul29_ipb(t0, B); }            // t0 <- mul29(B, 32 t0)
+            if (w3 & C_MULS) { if (!REC) q_shl5_ip(t0); mul29_ipb(t0, B); }  // t0 <- mul29(B, 32 t0)
             if (w3 & C_MACS) {                                              // t0 <- mul2add29(B, 32 t0, S, const): t0 settled, B popped above, S below it
                 Q29 S;
                 st_get(sp - 2, S);
                 --sp;
-                q_shl5_ip(t0);
+                if (!REC) q_shl5_ip(t0);
                 mul2add29_ub_ipb(t0, B, S, cst(consts_rp, w0 >> K_CONST_SHIFT));
             }
             if (w3 & C_NEG) {
@@ -643,12 +706,17 @@ k_quotient_eval2(const uint32_t* __restrict__ prog, uint32_t prog_len, const Fr*
                 for (int q = 0; q < 9; ++q) t0.l[q] = kp_balanced<Fr29P>(2, q) - t0.l[q];
                 normalize29(t0);
             }
-            if (w3 & C_SQ) { Q29 s2 = t0; q_shl5_ip(s2); mul29_ipa(t0, s2); }
+            if (w3 & C_SQ) { Q29 s2 = t0; if (!REC) q_shl5_ip(s2); mul29_ipa(t0, s2); }
             if (w3 & C_DBL) {
 #pragma unroll
                 for (int q = 0; q < 9; ++q) t0.l[q] <<= 1;
             }
-            if (w3 & C_TEE) { if (live) stg(tmp + (((uint64_t)w1 << ext_k) + i), pack29_lt2p(t0)); }
+            if (w3 & C_TEE) {
+                if (live) {
+                    if (REC) rec29_store<Fr29P>((Fr*)((char*)tmp + (((uint64_t)w1 << ext_k) * REC29_BYTES)), ne, i, canon29_lt2p(t0));      // slot w1 of the record-sized slots
+                    else stg(tmp + (((uint64_t)w1 << ext_k) + i), pack29_lt2p(t0));
+                }
+            }
             if (w3 & C_FOLD) { fold(w0, cst(consts_rp, w1), t0); --sp; if (sp >= 1) st_get(sp - 1, t0); }
         }
         w0 = n0; w1 = n1; w2 = n2; w3 = n3;
@@ -1163,7 +1231,10 @@ extern "C" int zk_host_quotient_lower2(const uint32_t* h_program, uint32_t num_i
 // puts the partial sums P_s together afterwards (an S-term FOLD_COL chain through this same function).  A cut is only made where no parked
 // intermediate is alive; parking slots are renumbered per slice (slices run concurrently).  ZK_QUOTIENT_SLICES=0 turns it off, =N asks for N.
 struct SlicePlan { std::vector<uint32_t> cut; };       // cut[s] .. cut[s + 1]: the caller's instructions of slice s
-static bool plan_slices(const uint32_t* prog, uint32_t len, uint32_t ext_k, SlicePlan* out) {
+// row_bytes: what one operand of one row takes in memory (32, or REC29_BYTES where the columns are coset records: the working set that has
+// to fit the caches is an eighth larger then, and the headline's large class is cut into 20 slices instead of 17 -- measured, 88.1 -> 86.8 ms
+// per launch on the loop tool, where the packed program gains nothing from more slices)
+static bool plan_slices(const uint32_t* prog, uint32_t len, uint32_t ext_k, SlicePlan* out, size_t row_bytes = sizeof(Fr)) {
     const int knob = getenv("ZK_QUOTIENT_SLICES") ? atoi(getenv("ZK_QUOTIENT_SLICES")) : -1;        // read per call: the tests flip it
     if (knob == 0 || (knob < 0 && (len < 2048 || ext_k < 16)) || ext_k < 11) return false;     // a forced count (tests) slices small programs too
     std::vector<uint32_t> bpos;           // instruction index behind a top-level FOLD
@@ -1198,7 +1269,7 @@ static bool plan_slices(const uint32_t* prog, uint32_t len, uint32_t ext_k, Slic
     if (knob < 0 && reads < 4 * ops.size()) return false;           // operands read once or twice: nothing to keep in a cache
     // slices wanted: the operands of the rows in flight (~5 000 waves x 64) should be well inside the 256 MiB Infinity Cache
     const uint64_t rows_in_flight = std::min<uint64_t>(1ull << ext_k, 327680);
-    const uint64_t ws = colset.size() * 32ull * rows_in_flight;
+    const uint64_t ws = colset.size() * (uint64_t)row_bytes * rows_in_flight;
     uint32_t want = knob > 0 ? (uint32_t)knob : (uint32_t)std::min<uint64_t>(64, (ws + (96ull << 20) - 1) / (96ull << 20));
     if (want < 2) return false;
     // cuts at unblocked boundaries, by cost
@@ -1234,9 +1305,46 @@ extern "C" int zk_host_quotient_slices(const uint32_t* program, uint32_t num_ins
     return ZK_OK;
 }
 
+// packed column of n rows -> coset record buffer: row i <- the canonical limbs of 32 src[i]
+__global__ void k_to_records(const Fr* __restrict__ src, Fr* __restrict__ dst, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fr x = ldg(src + i);
+    for (int j = 0; j < 5; ++j) x = dbl(x);
+    rec29_store<Fr29P>(dst, n, i, unpack29<Fr29P>(x));
+}
+
 extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr, const void* const* h_col_ptrs, uint32_t num_cols,
                                 const void* h_consts, uint32_t num_consts, uint32_t k, uint32_t ext_k, int divide_by_vanishing, void* d_out) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
+    // Measurement knob (tools/quot_evm_loop.py): ZK_QUOTIENT_LOOP_RECORDS=1 runs the program in record mode over images of the caller's
+    // columns, converted ONCE per buffer address and kept until the context goes -- a buffer rewritten in between keeps its stale image,
+    // so this is for timing loops over fixed columns only.  The result is brought back from 32 x the value by one scaling pass.
+    static const bool loop_records = getenv("ZK_QUOTIENT_LOOP_RECORDS") && atoi(getenv("ZK_QUOTIENT_LOOP_RECORDS")) == 1;
+    if (loop_records && h_program && d_out && (h_col_ptrs || !num_cols) && ext_k >= 2 && ext_k <= 28) {
+        const uint64_t ne = 1ull << ext_k;
+        std::vector<const void*> recs(num_cols);
+        for (uint32_t c = 0; c < num_cols; ++c) {
+            ZK_REQUIRE(ctx, h_col_ptrs[c], "null column pointer");
+            auto it = ctx->loop_records.find(h_col_ptrs[c]);
+            if (it == ctx->loop_records.end()) {
+                void* img = nullptr;
+                ZK_HIP(ctx, hipMalloc(&img, ne * REC29_BYTES));
+                it = ctx->loop_records.emplace(h_col_ptrs[c], img).first;
+                hipLaunchKernelGGL(k_to_records, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, ctx->stream, (const Fr*)h_col_ptrs[c], (Fr*)img, ne);
+                ZK_CHECK_LAUNCH(ctx);
+            }
+            recs[c] = it->second;
+        }
+        int rc = zk::quotient_eval_fmt(ctx, h_program, num_instr, recs.data(), num_cols, h_consts, num_consts, k, ext_k, divide_by_vanishing, d_out, true);
+        if (rc) return rc;
+        return fr_scale_run(ctx, (Fr*)d_out, fr_inv_host(fr_from_u64(32)), ne);
+    }
+    return zk::quotient_eval_fmt(ctx, h_program, num_instr, h_col_ptrs, num_cols, h_consts, num_consts, k, ext_k, divide_by_vanishing, d_out, false);
+}
+
+int zk::quotient_eval_fmt(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr, const void* const* h_col_ptrs, uint32_t num_cols, const void* h_consts, uint32_t num_consts, uint32_t k,
+                          uint32_t ext_k, int divide_by_vanishing, void* d_out, bool records) {
     ZK_REQUIRE(ctx, h_program && d_out && (h_col_ptrs || !num_cols) && (h_consts || !num_consts), "null pointer");
     ZK_REQUIRE(ctx, k <= ext_k && ext_k <= 28, "need k <= ext_k <= 28");
     int depth = 0;
@@ -1245,6 +1353,8 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
     if (rc) return rc;
     const int kernel_knob = getenv("ZK_QUOTIENT_KERNEL") ? atoi(getenv("ZK_QUOTIENT_KERNEL")) : 2;       // 2: fixed register roles (k_quotient_eval2: one stack entry in registers, 4-word instructions); 1: round 5's kernel
     const bool v2 = kernel_knob != 1;
+    if (records && (!v2 || ext_k < 2 || ext_k > 26)) return ctx->fail(ZK_ERR_UNSUPPORTED, "quotient program: record operands need k_quotient_eval2 and 2^2 .. 2^26 rows");
+    const size_t tmp_row_bytes = records ? REC29_BYTES : sizeof(Fr);         // a parked intermediate is read back as a column: it has the columns' format
     // fused Horner steps (k_quotient_eval2 only).  ZK_QUOTIENT_MAC=0: the instruction stream without them; 1: K_MAC_COL alone; unset / 2: K_MAC2_COL and
     // K_MAC_STK as well (A/B runs, byte-equality tests)
     const int mac_level = getenv("ZK_QUOTIENT_MAC") ? atoi(getenv("ZK_QUOTIENT_MAC")) : 2;
@@ -1252,7 +1362,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
     const uint64_t ne = 1ull << ext_k;
     // a large sum of terms whose operands are read many times is cut into slices that share their rows' operands through the caches (plan_slices)
     SlicePlan plan;
-    const bool sliced = v2 && ((ne / Q_THREADS) & 7) == 0 && plan_slices(h_program, num_instr, ext_k, &plan);
+    const bool sliced = v2 && ((ne / Q_THREADS) & 7) == 0 && plan_slices(h_program, num_instr, ext_k, &plan, records ? REC29_BYTES : sizeof(Fr));
     const uint32_t S = sliced ? (uint32_t)plan.cut.size() - 1 : 1;
     // lower the program for the kernel (memory operands, settle bits, prefetch hazards); ZK_QUOTIENT_FUSE=0 keeps the
     // caller's instruction sequence (measurement knob: only the bounds pass runs)
@@ -1304,7 +1414,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
     if (depth < 1) depth = 1;
     Fr* d_tmp = nullptr;
     if (num_tmp) {
-        d_tmp = (Fr*)ctx->get_scratch(SC_QTMP, ((size_t)num_tmp << ext_k) * sizeof(Fr));
+        d_tmp = (Fr*)ctx->get_scratch(SC_QTMP, ((size_t)num_tmp << ext_k) * tmp_row_bytes);
         if (!d_tmp) return ZK_ERR_OOM;
     }
     uint32_t low_len = 0;
@@ -1352,7 +1462,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
     for (Fr& t : tev) t = times32(t);
     // column table = the caller's columns, then one pseudo-column per parked intermediate
     std::vector<const void*> col_tab(h_col_ptrs, h_col_ptrs + num_cols);
-    for (uint32_t t = 0; t < num_tmp; ++t) col_tab.push_back(d_tmp + ((size_t)t << ext_k));
+    for (uint32_t t = 0; t < num_tmp; ++t) col_tab.push_back((const char*)d_tmp + ((size_t)t << ext_k) * tmp_row_bytes);
     // sliced: the partial sums are columns num_cols + num_tmp + s of a last little program, acc = acc * k_s + P_s over the slices (and the vanishing division the
     // caller asked for), which rides in the same upload and is launched right behind the slices: no second call, no host synchronisation in between
     std::vector<LowInstr> comb;
@@ -1384,7 +1494,7 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
         size_t w = 0;
         for (uint32_t sl = 0; sl < S; ++sl) {
             slice_tab[2 * sl] = (uint32_t)w; slice_tab[2 * sl + 1] = (uint32_t)lows[sl].size() + 1;
-            for (const LowInstr& in : lows[sl]) { hp[w++] = in.w0; hp[w++] = in.a; hp[w++] = in.b; if (v2) hp[w++] = q_class_mask(in.w0); }
+            for (const LowInstr& in : lows[sl]) { hp[w++] = in.w0; hp[w++] = in.a; hp[w++] = in.b; if (v2) hp[w++] = q_class_mask(in.w0, records); }
             for (int e = 0; e < 4; ++e) { hp[w++] = Q_END; hp[w++] = 0; hp[w++] = 0; if (v2) hp[w++] = 0; }      // END + the instructions the kernel fetches ahead
         }
         comb_at = w;
@@ -1416,10 +1526,14 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+        ZK_HIP(ctx, hipFuncSetAttribute((const void*)k_quotient_eval2<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
         ctx->quotient_attr_set = true;
     }
     ZkProfScope ps(ctx, ctx->prof_tag ? ctx->prof_tag : "quotient_eval");
@@ -1452,19 +1566,23 @@ extern "C" int zk_quotient_eval(zk_ctx* ctx, const uint32_t* h_program, uint32_t
                                tev.empty() || sliced ? (const Fr*)nullptr : (const Fr*)d_tev, ext_k, k, sliced ? d_part : (Fr*)d_out, d_tmp, d_acc, sliced ? 0u : tile_alias,
                                (const uint32_t*)d_prog + slice_tab_at, sliced ? S : 0u);
         };
-        if (v2 && full && acc_in_mem) launch2(k_quotient_eval2<true, true>);
-        else if (v2 && full) launch2(k_quotient_eval2<true, false>);
-        else if (v2 && acc_in_mem) launch2(k_quotient_eval2<false, true>);
-        else if (v2) launch2(k_quotient_eval2<false, false>);
+        if (records && full && acc_in_mem) launch2(k_quotient_eval2<true, true, true>);
+        else if (records && full) launch2(k_quotient_eval2<true, false, true>);
+        else if (records && acc_in_mem) launch2(k_quotient_eval2<false, true, true>);
+        else if (records) launch2(k_quotient_eval2<false, false, true>);
+        else if (v2 && full && acc_in_mem) launch2(k_quotient_eval2<true, true, false>);
+        else if (v2 && full) launch2(k_quotient_eval2<true, false, false>);
+        else if (v2 && acc_in_mem) launch2(k_quotient_eval2<false, true, false>);
+        else if (v2) launch2(k_quotient_eval2<false, false, false>);
         else if (full && acc_in_mem) launch(k_quotient_eval<true, true>);
         else if (full) launch(k_quotient_eval<true, false>);
         else if (acc_in_mem) launch(k_quotient_eval<false, true>);
         else launch(k_quotient_eval<false, false>);
     }
     ZK_CHECK_LAUNCH(ctx);
-    if (sliced) {
+    if (sliced) {                 // the slices' sums are packed elements whatever the operands were: this launch reads forty-odd of them per row
         const dim3 grid((unsigned)((ne + Q_THREADS - 1) / Q_THREADS)), block(Q_THREADS);
-        hipLaunchKernelGGL((k_quotient_eval2<true, false>), grid, block, (size_t)9 * Q_THREADS * 4, ctx->stream, (const uint32_t*)d_prog + comb_at, S + 1, (const Fr* const*)d_cols, (const QC29*)d_consts,
+        hipLaunchKernelGGL((k_quotient_eval2<true, false, false>), grid, block, (size_t)9 * Q_THREADS * 4, ctx->stream, (const uint32_t*)d_prog + comb_at, S + 1, (const Fr* const*)d_cols, (const QC29*)d_consts,
                            (const QC29*)(d_consts + nc_all), tev.empty() ? (const Fr*)nullptr : (const Fr*)d_tev, ext_k, k, (Fr*)d_out, d_tmp, (uint32_t*)nullptr, 0u, (const uint32_t*)nullptr, 0u);
         ZK_CHECK_LAUNCH(ctx);
     }
@@ -1476,9 +1594,14 @@ namespace zk { __global__ void k_powers(Fr base, Fr mul, Fr* out, uint32_t count
 extern "C" int zk_fr_powers(zk_ctx* ctx, const void* h_base, const void* h_mul, void* d_out, size_t n) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
     ZK_REQUIRE(ctx, h_base && h_mul && d_out, "null pointer");
+    return zk::fr_powers_fmt(ctx, *(const Fr*)h_base, *(const Fr*)h_mul, d_out, n, false);
+}
+// records: d_out (REC29_BYTES per row) receives 32 x the powers as a coset record buffer of n rows
+int zk::fr_powers_fmt(zk_ctx* ctx, const Fr& base, const Fr& mul, void* d_out, size_t n, bool records) {
     ZK_REQUIRE(ctx, n <= (1ull << 28), "too many powers");
+    ZK_REQUIRE(ctx, !records || (n & 3) == 0, "a record buffer has a multiple of four rows");
     if (!n) return ZK_OK;
-    hipLaunchKernelGGL(zk::k_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, *(const Fr*)h_base, *(const Fr*)h_mul, (Fr*)d_out, (uint32_t)n, 0);
+    hipLaunchKernelGGL(zk::k_powers, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, base, mul, (Fr*)d_out, (uint32_t)n, records ? 2 : 0);
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
