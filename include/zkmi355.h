@@ -45,6 +45,13 @@ typedef enum zk_status {
 
 enum { ZK_FIELD_FR = 0, ZK_FIELD_FQ = 1 };
 enum { ZK_OP_ADD = 0, ZK_OP_SUB = 1, ZK_OP_MUL = 2, ZK_OP_SCAN_AFFINE = 3, ZK_OP_SCAN_AFFINE_REV = 4 };
+/* the row RLC of zk_field_vec_op (described there): its d_a is a HOST pointer to this table, itself made of host arrays */
+#define ZK_OP_ROW_RLC 8
+typedef struct zk_row_rlc {
+    uint32_t count;             /* columns                                                        */
+    const void* const* d_cols;  /* count device pointers                                          */
+    const uint8_t* widths;      /* count cell widths in bytes: 1, 2, 4, 8, 16 (packed) or 32 (Fr) */
+} zk_row_rlc;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -115,7 +122,25 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * The state before the first element is 0, so a[0] (a[n-1] for the reverse op) is never used; a caller with a start value z0
  * folds a * z0 into b[0] itself.  a[i] = 0 starts a new segment at i: a running RLC with resets z[i] = z[i-1] * r * (1 - is_first[i])
  * + x[i] is a = r * (1 - is_first), b = x.  Results are canonical.  d_out must overlap neither d_a nor d_b (n * 32 B each):
- * ZK_ERR_INVALID_ARG, nothing is launched.  Booked under the zk_prof name "fr_scan_affine" with n * 96 algorithmic bytes per call. */
+ * ZK_ERR_INVALID_ARG, nothing is launched.  Booked under the zk_prof name "fr_scan_affine" with n * 96 algorithmic bytes per call.
+ * ZK_OP_ROW_RLC (a #define, value 8; Fr only) is the RLC across the columns of a row, straight from packed typed cells:
+ *   d_out[i] = c + sum_j w_j * cell_j[i]  for i < n
+ * For this op only, d_a and d_b are HOST pointers: d_a points to a zk_row_rlc {count, d_cols, widths} whose d_cols and widths are
+ * host arrays of count entries (d_cols[j] itself is a device pointer), d_b to (count + 1) x 32 B Montgomery Fr in host memory: the
+ * constant c, then w_0 .. w_(count-1).  They are read before the call returns; the call is asynchronous on the context's stream.
+ * widths[j] in {1, 2, 4, 8, 16}: n little-endian unsigned cells at d_cols[j], aligned to the width, read like zk_fr_from_uint
+ * (nothing outside n * width bytes is read); widths[j] = 32: n canonical Montgomery Fr, 8-byte aligned (a word RLC made by an
+ * earlier call, say).  Several columns may name the same buffer; count = 0 gives the constant column; n = 0: ZK_OK.  A word RLC of 32
+ * byte columns is w_j = r^j; the eleven mixed-width columns of an RwRow under a leading one are c = r^11 with descending powers (or
+ * c = 1 with w_j = r^(j+1), the order RwRow::rlc folds in).  Results are canonical.
+ * A 32-byte cell that is not canonical (at or above the modulus) gives an undefined VALUE in its row (the one reduction assumes
+ * terms below p^2; no memory is touched that would not be otherwise) and no error.
+ * d_out (n x 32 B) must not overlap a narrow column; it may BE a 32-byte column (same address: a lane reads its row before it writes
+ * it; wherever such columns stand in the table, also past the 64th place, they are taken by the first launch) but not overlap one
+ * partially.  ZK_FIELD_FQ, any other width, a NULL or misaligned column, a forbidden overlap, NULL d_cols or
+ * widths with count > 0: ZK_ERR_INVALID_ARG before any launch, nothing is written.  64 columns per launch; a longer table runs as
+ * further launches that take the sum so far from d_out.  Booked under the zk_prof name "fr_row_rlc" with n * (sum of widths + 32)
+ * algorithmic bytes per launch (the sum so far counts as a 32-byte column).  Other op values (5, 6, 7, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */
 int zk_fr_scale(zk_ctx* ctx, void* d_a, const void* h_s, size_t n);

@@ -127,6 +127,20 @@ inline void scan_affine(const Context& c, const Context::Buffer& a, const Contex
     if (n * sizeof(Fr) > a.bytes() || n * sizeof(Fr) > b.bytes() || n * sizeof(Fr) > out.bytes()) throw Error(ZK_ERR_INVALID_ARG, "scan_affine: a buffer holds fewer than n elements");
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, reverse ? ZK_OP_SCAN_AFFINE_REV : ZK_OP_SCAN_AFFINE, a.ptr(), b.ptr(), out.ptr(), n));
 }
+// d_out[i] = constant + sum_j weights[j] * cell_j[i] for i < n, across typed columns on the device (zk_field_vec_op with
+// ZK_OP_ROW_RLC and a zk_row_rlc table; asynchronous on the context's stream, 64 columns per launch): d_cols[j] holds n cells of
+// cell_bytes[j] bytes -- 1, 2, 4, 8, 16: packed little-endian unsigned integers as for fr_from_uint; 32: Montgomery Fr.  rlc::value
+// over the 32 byte columns of a word is weights[j] = r^j; an RwRow under a leading one is constant = r^11 with descending powers (or
+// constant = 1 with weights[j] = r^(j + 1), the order RwRow::rlc folds in).  d_out (n x 32 B) may
+// be one of the 32-byte columns itself and overlaps no other column.
+inline void row_rlc(const Context& c, const std::vector<const void*>& d_cols, const std::vector<uint8_t>& cell_bytes, const std::vector<Fr>& weights, size_t n, void* d_out,
+                    const Fr& constant = Fr{}) {
+    if (cell_bytes.size() != d_cols.size() || weights.size() != d_cols.size()) throw Error(ZK_ERR_INVALID_ARG, "row_rlc: one cell width and one weight per column");
+    std::vector<Fr> host(1, constant);                                  // the constant, then the weights: host memory, read by the call
+    host.insert(host.end(), weights.begin(), weights.end());
+    const zk_row_rlc table{(uint32_t)d_cols.size(), d_cols.data(), cell_bytes.data()};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_ROW_RLC, &table, host.data(), d_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -44,6 +44,18 @@ pub const ZK_TRANSCRIPT_BLAKE2B: c_int = 0;
 pub const ZK_TRANSCRIPT_POSEIDON: c_int = 1;
 pub const ZK_TRANSCRIPT_EVM: c_int = 2;
 
+/// `zk_field_vec_op` op: `d_out[i] = c + sum_j w_j * cell_j[i]` across typed columns.  For this op `d_a` is a HOST pointer to a
+/// `zk_row_rlc` and `d_b` a HOST pointer to `(count + 1) x 32 B` Montgomery Fr (`c`, then the weights).
+pub const ZK_OP_ROW_RLC: c_int = 8;
+/// `zk_row_rlc`: the column table of `ZK_OP_ROW_RLC`; `d_cols` and `widths` are host arrays of `count` entries, each `d_cols[j]` a
+/// device pointer to `n` cells of `widths[j]` bytes (1, 2, 4, 8, 16: packed little-endian unsigned; 32: Montgomery Fr).
+#[repr(C)]
+pub struct zk_row_rlc {
+    pub count: u32,
+    pub d_cols: *const *const c_void,
+    pub widths: *const u8,
+}
+
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).
 #[repr(C)]

@@ -1,0 +1,80 @@
+// Test harness: the row RLC's limb routine (csrc/ff29.hip.hpp: rlc29_init / rlc29_mac / rlc29_carry / rlc29_reduce) compiled for the
+// HOST as a stand-alone program, run directly by tests/test_row_rlc_host.py (once plain, once under the address and
+// undefined-behaviour sanitizers).  It does to one row what a lane of k_fr_row_rlc (csrc/vec.hip) does: cells become limbs by
+// unpack29 (1, 1, 2, 3, 5 or 9 of them by width), every term goes through rlc29_mac, one rlc29_reduce, pack29_lt2p.
+// Input (file named by argv[1]), all numbers little-endian integers in hex:
+//   case <count>
+//   <k0>                          the constant's K = c 2^517 mod p
+//   <width> <cell> <K>            count lines; K = w 2^517 mod p (width <= 16) or w 2^261 mod p (width 32)
+// Output, one line per case: <packed result> <limb 0> .. <limb 8> <carry passes>
+#include <cinttypes>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../zkevm-circuits_amd/csrc/ff29.hip.hpp"
+
+using namespace zk;
+
+static bool read_hex(FILE* f, Fr* out) {
+    char buf[80];
+    if (fscanf(f, "%79s", buf) != 1) return false;
+    const size_t len = strlen(buf);
+    if (len == 0 || len > 64) return false;
+    *out = Fr::zero();
+    for (size_t i = 0; i < len; ++i) {
+        const char ch = buf[len - 1 - i];
+        const uint32_t d = ch >= '0' && ch <= '9' ? ch - '0' : ch >= 'a' && ch <= 'f' ? ch - 'a' + 10 : 16;
+        if (d > 15) return false;
+        out->l[i / 8] |= d << (4 * (i % 8));
+    }
+    return true;
+}
+
+template <int L>
+static void term(Rlc29<Fr29P>& t, const Fr& cell, const Fr& k, unsigned* passes) {
+    const Fr29 x = unpack29<Fr29P>(cell), kl = unpack29<Fr29P>(k);
+    for (int i = L; i < 9; ++i)
+        if (x.l[i]) { fprintf(stderr, "cell wider than its width\n"); exit(2); }
+    const uint32_t before = t.load;
+    rlc29_mac<L>(t, x.l, kl.l);
+    if (t.load != before + L) ++*passes;                               // rlc29_mac ran a carry pass first
+    if (t.load > RLC29_MAX_LOAD) { fprintf(stderr, "column load %u\n", t.load); exit(2); }
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) { fprintf(stderr, "usage: %s cases.txt\n", argv[0]); return 2; }
+    FILE* f = fopen(argv[1], "r");
+    if (!f) { perror(argv[1]); return 2; }
+    char word[16];
+    unsigned count;
+    while (fscanf(f, "%15s %u", word, &count) == 2) {
+        if (strcmp(word, "case")) { fprintf(stderr, "expected 'case'\n"); return 2; }
+        Fr k0;
+        if (!read_hex(f, &k0)) { fprintf(stderr, "bad constant\n"); return 2; }
+        Rlc29<Fr29P> t;
+        rlc29_init(t, unpack29<Fr29P>(k0).l);
+        unsigned passes = 0;
+        for (unsigned j = 0; j < count; ++j) {
+            unsigned width;
+            Fr cell, k;
+            if (fscanf(f, "%u", &width) != 1 || !read_hex(f, &cell) || !read_hex(f, &k)) { fprintf(stderr, "bad column line\n"); return 2; }
+            switch (width) {
+                case 1: case 2: term<1>(t, cell, k, &passes); break;
+                case 4: term<2>(t, cell, k, &passes); break;
+                case 8: term<3>(t, cell, k, &passes); break;
+                case 16: term<5>(t, cell, k, &passes); break;
+                case 32: term<9>(t, cell, k, &passes); break;
+                default: fprintf(stderr, "bad width %u\n", width); return 2;
+            }
+        }
+        const Fr29 r = rlc29_reduce(t);
+        const Fr v = pack29_lt2p(r);
+        for (int i = 7; i >= 0; --i) printf("%08" PRIx32, v.l[i]);
+        for (int i = 0; i < 9; ++i) printf(" %" PRIx32, r.l[i]);
+        printf(" %u\n", passes);
+    }
+    fclose(f);
+    return 0;
+}

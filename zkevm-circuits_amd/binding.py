@@ -23,6 +23,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "zkmi355.h")
 FIELD_FR, FIELD_FQ = 0, 1
 OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
 OP_SCAN_AFFINE, OP_SCAN_AFFINE_REV = 3, 4            # out[i] = a[i] * out[i -+ 1] + b[i] along the column, Fr only
+OP_ROW_RLC = 8                                        # out[i] = c + sum_j w_j * cell_j[i] across typed columns, Fr only (ZK_OP_ROW_RLC)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -71,6 +72,11 @@ def lib():
         _lib.zk_proof_advice_phase_typed_dev.restype = ctypes.c_int
         _lib.zk_proof_advice_phase_typed_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, u32p, vpp, u8p, ctypes.c_uint32, ctypes.c_void_p, u32p]
     return _lib
+
+
+class _RowRlc(ctypes.Structure):
+    """zk_row_rlc: the column table of ZK_OP_ROW_RLC (host memory)"""
+    _fields_ = [("count", ctypes.c_uint32), ("d_cols", ctypes.POINTER(ctypes.c_void_p)), ("widths", ctypes.POINTER(ctypes.c_uint8))]
 
 
 def _host_ptr(a: np.ndarray):
@@ -654,6 +660,24 @@ class Context:
         """out[0] = b[0], out[i] = a[i] * out[i - 1] + b[i] over n Montgomery Fr (zk_field_vec_op with ZK_OP_SCAN_AFFINE); reverse: from
         the last element down, out[i] = a[i] * out[i + 1] + b[i].  a[i] = 0 starts a new segment; out overlaps neither input."""
         self.field_vec_op(FIELD_FR, OP_SCAN_AFFINE_REV if reverse else OP_SCAN_AFFINE, a, b, out, n)
+
+    def row_rlc(self, cols, widths, weights, n, out, constant=None):
+        """out[i] = constant + sum_j weights[j] * cell_j[i] for i < n (zk_field_vec_op with ZK_OP_ROW_RLC), one launch per 64 columns.
+        cols[j]: DeviceBuffer or device pointer of n cells of widths[j] bytes -- 1, 2, 4, 8, 16: packed little-endian unsigned cells,
+        read like fr_from_uint; 32: Montgomery Fr.  weights: count x 4 uint64 Montgomery, constant: 4 uint64 Montgomery (default 0).
+        out (DeviceBuffer or pointer, n x 32 B) may be one of the 32-byte columns itself and must not overlap any other column."""
+        ptr_of = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        cnt = len(cols)
+        assert len(widths) == cnt
+        hk = np.zeros((cnt + 1, 4), dtype=np.uint64)
+        if constant is not None:
+            hk[0] = np.asarray(constant, dtype=np.uint64).reshape(4)
+        if cnt:
+            hk[1:] = np.asarray(weights, dtype=np.uint64).reshape(cnt, 4)
+        pp = (ctypes.c_void_p * max(cnt, 1))(*[ptr_of(p) for p in cols])
+        wd = (ctypes.c_uint8 * max(cnt, 1))(*widths)
+        desc = _RowRlc(cnt, ctypes.cast(pp, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(wd, ctypes.POINTER(ctypes.c_uint8)))
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_ROW_RLC, ctypes.byref(desc), _host_ptr(hk), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

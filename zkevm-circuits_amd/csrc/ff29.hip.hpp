@@ -674,6 +674,83 @@ __host__ __device__ inline Fp<typename P29::P32> inv_via29(const Fp<typename P29
     return pack29_lt2p(mul29(r, unpack29<P29>(F::one())));                 // x 2^256 / 2^261: R' -> R
 }
 
+// ---- sum of short products under ONE reduction: T = sum_j x_j K_j, then T 2^-261 mod p (the row RLC of csrc/vec.hip) ---------
+// x_j is an integer of L_j <= 9 limbs and K_j a plain normalised constant below p; both have limbs below 2^29, so every product
+// is below 2^58.  The sum is kept as 18 integer column sums c[k] of weight 2^(29 k) (x_i K_j goes to column i + j <= 16, column 17
+// only ever takes carries), in 64-bit words, and nothing is reduced until rlc29_reduce.  Plain C on the host and on the device
+// (a term is L_j x 9 multiply-adds whose second factor sits in scalar registers when K_j is wave-uniform); two bounds hold it up:
+//   (1) columns.  The reduction adds to a column its nine products m_i M_(k-i) and a carry below 2^36, so a column may hold at most
+//       RLC29_MAX_LOAD = 54 products when it starts: (54 + 9) 2^58 + 2^36 < 2^64.  `load` counts, for the fullest column, the
+//       products taken since the last carry pass (a term of L limbs adds at most L to any column); rlc29_mac runs rlc29_carry
+//       BEFORE a term that would pass the limit.  A carry pass leaves every column below 2^29 (counted as one product) and moves
+//       less than 2^35 into the next one.  Bytes (L = 1) get 53 terms between passes, 16-byte cells 10, full elements 5.
+//   (2) the sum.  rlc29_reduce needs T < 2^261 p, like mul29; its result is then normalised and below 2p.  A narrow term (x below
+//       2^128) is below 2^128 p, so their number does not matter; a full-size one (x < p) is below p^2 and 2^261 / p = 169.2 of
+//       those fit in Fr (147.6 in Fq).  The caller counts them: csrc/vec.hip puts at most RR_BATCH = 64 terms under one reduction.
+// rlc29_room(t, need) makes room for `need` products ahead of a run of terms whose limb counts add up to `need`: the tests that
+// rlc29_mac still makes for every term of the run then cannot fire.  `load` is a runtime value; where the run is unrolled with a
+// constant `need`, the compiler's range propagation (load <= MAX - need after the call) can remove those tests and their copies
+// of the carry pass (k_fr_row_rlc: 18.3 k -> 11.3 k lines of ISA), but nothing depends on that: the bound is kept by the tests.
+constexpr uint32_t RLC29_MAX_LOAD = 54;
+template <class P>
+struct Rlc29 {
+    uint64_t c[18];
+    uint32_t load;
+};
+// T = the plain normalised value k (one product per column at most: the constant term, taken with the cell 1), or 0
+template <class P>
+__host__ __device__ __forceinline__ void rlc29_init(Rlc29<P>& t, const uint32_t* k) {
+#pragma unroll
+    for (int i = 0; i < 18; ++i) t.c[i] = i < 9 ? k[i] : 0;
+    t.load = 1;
+}
+template <class P>
+__host__ __device__ __forceinline__ void rlc29_carry(Rlc29<P>& t) {
+#pragma unroll
+    for (int i = 0; i < 17; ++i) { t.c[i + 1] += t.c[i] >> 29; t.c[i] &= MASK29; }
+    t.load = 1;
+}
+template <class P>
+__host__ __device__ __forceinline__ void rlc29_room(Rlc29<P>& t, uint32_t need) {       // need < RLC29_MAX_LOAD
+    if (t.load > RLC29_MAX_LOAD - need) rlc29_carry(t);
+}
+// T += x K for x of L limbs and K of nine, all below 2^29
+template <int L, class P>
+__host__ __device__ __forceinline__ void rlc29_mac(Rlc29<P>& t, const uint32_t* x, const uint32_t* k) {
+    static_assert(L >= 1 && L <= 9 && L + 1 <= RLC29_MAX_LOAD, "a term is one to nine limbs");
+    rlc29_room(t, L);
+    t.load += L;
+#pragma unroll
+    for (int i = 0; i < L; ++i)
+#pragma unroll
+        for (int j = 0; j < 9; ++j) t.c[i + j] += (uint64_t)x[i] * k[j];
+}
+// T 2^-261 mod p for T < 2^261 p: normalised, below 2p.  The column sums stand where mul29_c has its a[i] b[k - i] products.
+template <class P>
+__host__ __device__ __forceinline__ F29<P> rlc29_reduce(const Rlc29<P>& t) {
+    uint32_t m[9];
+    F29<P> r;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 17; ++k) {
+        const int lo = k < 9 ? 0 : k - 8, nm = k < 9 ? k : 17 - k;
+        uint32_t ks[9];
+#pragma unroll
+        for (int i = 0; i < nm; ++i) ks[i] = P::M(k - lo - i);
+        acc += t.c[k];
+        acc = dotk(m + lo, ks, nm, acc);
+        if (k < 9) {
+            m[k] = ((uint32_t)acc * P::INV) & MASK29;
+            acc += (uint64_t)m[k] * P::M(0);
+        } else {
+            r.l[k - 9] = (uint32_t)acc & MASK29;
+        }
+        acc >>= 29;
+    }
+    r.l[8] = (uint32_t)(acc + t.c[17]);
+    return r;
+}
+
 using Fq29 = F29<Fq29P>;
 using Fr29 = F29<Fr29P>;
 

@@ -3,6 +3,7 @@
 //   batch inversion                     ff::BatchInvert                    (K12, K7, K8)
 //   prefix product / prefix sum         permutation & lookup grand product (K7, K8)
 //   affine scan z = a z + b             running RLCs with resets (challenge-phase witness columns)
+//   row RLC z = c + sum w_j cell_j      rlc::value / RwRow::rlc across typed columns, one reduction per row
 //   eval_polynomial, kate_division      halo2_proofs::arithmetic           (K9, K10, K11)
 // All kernels read/write 32-byte elements as two 16-byte transactions per lane, consecutive
 // lanes on consecutive elements (fully coalesced), grid-stride where a fixed grid is needed.
@@ -557,51 +558,99 @@ int fr_add_const_many(zk_ctx* ctx, const void* const* d_src, void* const* d_dst,
 // virtual index v = i + head; a packed word that is not wholly inside [head, head + n) -- only the first and the last can be --
 // is put together from loads of its valid cells alone, so nothing outside the caller's n * W bytes is read.
 constexpr int FU_CELLS = 4;
+// The packed word (W < 4: FU_CELLS cells, cell t in bits [8 W t, 8 W (t + 1))) at virtual cell q, a multiple of FU_CELLS: one load
+// when it lies wholly inside [head, end), else put together from its valid cells alone (none: 0).
 template <int W>
-__device__ __forceinline__ void fr_from_uint_wave(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, Fr* __restrict__ out, const Fr& c517_plain, uint64_t wave) {
+__device__ __forceinline__ uint2 fu_packed_word(const uint8_t* __restrict__ src, uint64_t q, uint32_t head, uint64_t end) {
+    static_assert(FU_CELLS == 4, "a packed word holds four cells");
+    uint32_t lo = 0, hi = 0;
+    if (q >= head && q + FU_CELLS <= end) {
+        if constexpr (W == 1) lo = *reinterpret_cast<const uint32_t*>(src + q);
+        else { const uint2 p = *reinterpret_cast<const uint2*>(src + q * 2); lo = p.x; hi = p.y; }
+    } else {
+#pragma unroll
+        for (int t = 0; t < FU_CELLS; ++t) {
+            if (q + t < head || q + t >= end) continue;
+            if constexpr (W == 1) lo |= (uint32_t)src[q + t] << (8 * t);
+            else {
+                const uint32_t c = *reinterpret_cast<const uint16_t*>(src + (q + t) * 2);
+                if (t < 2) lo |= c << (16 * t); else hi |= c << (16 * (t - 2));
+            }
+        }
+    }
+    return make_uint2(lo, hi);
+}
+// The loader of both typed-cell kernels, in two halves so that a caller may put the loads of several columns in flight before it
+// touches the first cell.  Together: x[j] = the cell at virtual index wave * FU_CELLS * 64 + j * 64 + lane + shift as up to four 32-bit
+// words, 0 where that index is outside [head, head + n).  shift is wave-uniform and below FU_CELLS.  k_fr_from_uint* address their
+// lanes by virtual index and pass 0; the row RLC, whose lanes own ROWS (the same row in every column, whatever the column's head),
+// passes shift = head: the packed words are still loaded at their aligned places, each lane then takes the upper cells of its own
+// word and the lower ones of its neighbour's (a shuffle; lane 63 loads the wave's 65th word) -- a funnel shift by `shift` cells -- and
+// the sweeps fetch their cells as before.  W >= 4 has head = 0 and takes no shift.
+//   fu_load_raw: the loads and nothing else.  W < 4: raw[0] = {this lane's packed word (two halves), lane 63's extra word when shift};
+//                W >= 4: raw[j] = the lane's cell of sweep j.
+//   fu_cells:    raw -> x (W < 4: the funnel shift and the fetch from the owning lane; W >= 4: a copy)
+template <int W>
+__device__ __forceinline__ void fu_load_raw(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, uint64_t wave, uint32_t shift, uint32_t (&raw)[FU_CELLS][4]) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t v0 = wave * (FU_CELLS * 64), end = head + n;         // virtual cells [v0, v0 + 256) of this wave; valid: head <= v < end
-    uint32_t x[FU_CELLS][4];
 #pragma unroll
-    for (int j = 0; j < FU_CELLS; ++j) x[j][0] = x[j][1] = x[j][2] = x[j][3] = 0;
+    for (int j = 0; j < FU_CELLS; ++j) raw[j][0] = raw[j][1] = raw[j][2] = raw[j][3] = 0;
     if constexpr (W < 4) {
-        static_assert(FU_CELLS == 4, "a packed word holds four cells");
         const uint64_t q = v0 + (uint64_t)FU_CELLS * lane;              // first virtual cell of this lane's packed word
-        uint32_t lo = 0, hi = 0;                                        // cell t of the word: bits [8 W t, 8 W (t + 1)) of hi:lo
-        if (q >= head && q + FU_CELLS <= end) {
-            if constexpr (W == 1) lo = *reinterpret_cast<const uint32_t*>(src + q);
-            else { const uint2 p = *reinterpret_cast<const uint2*>(src + q * 2); lo = p.x; hi = p.y; }
-        } else {
+        const uint2 w = fu_packed_word<W>(src, q, head, end);           // cell t of the word: bits [8 W t, 8 W (t + 1)) of y:x
+        raw[0][0] = w.x; raw[0][1] = w.y;
+        if (shift && lane == 63u) { const uint2 nx = fu_packed_word<W>(src, q + FU_CELLS, head, end); raw[0][2] = nx.x; raw[0][3] = nx.y; }
+    } else {
 #pragma unroll
-            for (int t = 0; t < FU_CELLS; ++t) {
-                if (q + t < head || q + t >= end) continue;
-                if constexpr (W == 1) lo |= (uint32_t)src[q + t] << (8 * t);
-                else {
-                    const uint32_t c = *reinterpret_cast<const uint16_t*>(src + (q + t) * 2);
-                    if (t < 2) lo |= c << (16 * t); else hi |= c << (16 * (t - 2));
-                }
-            }
+        for (int j = 0; j < FU_CELLS; ++j) {
+            const uint64_t v = v0 + (uint64_t)j * 64 + lane;
+            if (v >= end) continue;                                     // head == 0 here
+            if constexpr (W == 4) raw[j][0] = *reinterpret_cast<const uint32_t*>(src + v * 4);
+            else if constexpr (W == 8) { const uint2 p = *reinterpret_cast<const uint2*>(src + v * 8); raw[j][0] = p.x; raw[j][1] = p.y; }
+            else { const uint4 p = *reinterpret_cast<const uint4*>(src + v * 16); raw[j][0] = p.x; raw[j][1] = p.y; raw[j][2] = p.z; raw[j][3] = p.w; }
+        }
+    }
+}
+template <int W>
+__device__ __forceinline__ void fu_cells(const uint32_t (&raw)[FU_CELLS][4], uint32_t shift, uint32_t (&x)[FU_CELLS][4]) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int j = 0; j < FU_CELLS; ++j) { x[j][0] = raw[j][0]; x[j][1] = raw[j][1]; x[j][2] = raw[j][2]; x[j][3] = raw[j][3]; }
+    if constexpr (W < 4) {
+        uint32_t lo = raw[0][0], hi = raw[0][1];
+        if (shift) {
+            uint2 nx = make_uint2(__shfl_down(lo, 1), __shfl_down(hi, 1));
+            if (lane == 63u) nx = make_uint2(raw[0][2], raw[0][3]);
+            const uint64_t cur = lo | (uint64_t)hi << 32, nxt = nx.x | (uint64_t)nx.y << 32;
+            if constexpr (W == 1) lo = (uint32_t)((lo | nxt << 32) >> (8 * shift));
+            else { const uint64_t f = cur >> (16 * shift) | nxt << (64 - 16 * shift); lo = (uint32_t)f; hi = (uint32_t)(f >> 32); }
         }
 #pragma unroll
         for (int j = 0; j < FU_CELLS; ++j) {                            // cell j * 64 + lane of the wave sits in lane (j * 64 + lane) / 4, position lane % 4
             const int owner = j * (64 / FU_CELLS) + (int)(lane >> 2);
             const uint32_t t = lane & 3u;
+            x[j][1] = x[j][2] = x[j][3] = 0;
             if constexpr (W == 1) x[j][0] = (__shfl(lo, owner) >> (8 * t)) & 0xffu;
             else {
                 const uint32_t a = __shfl(lo, owner), b = __shfl(hi, owner);
                 x[j][0] = ((t & 2u ? b : a) >> (16 * (t & 1u))) & 0xffffu;
             }
         }
-    } else {
-#pragma unroll
-        for (int j = 0; j < FU_CELLS; ++j) {
-            const uint64_t v = v0 + (uint64_t)j * 64 + lane;
-            if (v >= end) continue;                                     // head == 0 here
-            if constexpr (W == 4) x[j][0] = *reinterpret_cast<const uint32_t*>(src + v * 4);
-            else if constexpr (W == 8) { const uint2 p = *reinterpret_cast<const uint2*>(src + v * 8); x[j][0] = p.x; x[j][1] = p.y; }
-            else { const uint4 p = *reinterpret_cast<const uint4*>(src + v * 16); x[j][0] = p.x; x[j][1] = p.y; x[j][2] = p.z; x[j][3] = p.w; }
-        }
     }
+}
+template <int W>
+__device__ __forceinline__ void fu_load_wave(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, uint64_t wave, uint32_t shift, uint32_t (&x)[FU_CELLS][4]) {
+    uint32_t raw[FU_CELLS][4];
+    fu_load_raw<W>(src, head, n, wave, shift, raw);
+    fu_cells<W>(raw, shift, x);
+}
+template <int W>
+__device__ __forceinline__ void fr_from_uint_wave(const uint8_t* __restrict__ src, uint32_t head, uint64_t n, Fr* __restrict__ out, const Fr& c517_plain, uint64_t wave) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t v0 = wave * (FU_CELLS * 64), end = head + n;
+    uint32_t x[FU_CELLS][4];
+    fu_load_wave<W>(src, head, n, wave, 0, x);
     const Fr29 c517 = unpack29<Fr29P>(c517_plain);
 #pragma unroll
     for (int j = 0; j < FU_CELLS; ++j) {
@@ -688,6 +737,181 @@ int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d
     return ZK_OK;
 }
 
+// ---- row RLC of typed cells: out[i] = c + sum_j w_j * cell_j[i] (ZK_OP_ROW_RLC) ----------------------------------------------------
+// The RLC ACROSS the columns of a row (rlc::value over the bytes of a word, RwRow::rlc over mixed-width fields), from the packed cells
+// themselves: nothing is expanded to 32 bytes and no term is reduced.  A lane owns one row per sweep in the wave, sweep and store shape
+// of fr_from_uint_wave (a wave covers FU_CELLS * 64 consecutive rows, fu_load_raw / fu_cells fetch every column's cells of those rows), keeps one
+// Rlc29 (csrc/ff29.hip.hpp: 18 integer column sums) per sweep and walks the columns in a wave-uniform loop: cell limbs (1, 1, 2, 3, 5
+// for 1, 2, 4, 8, 16 bytes; 9 for a 32-byte Montgomery element) times the nine limbs of the column's constant K_j, which sit in scalar
+// registers.  The host prepares K_j as plain normalised limbs: w_j 2^517 for a narrow column (x K_j / 2^261 = w_j x 2^256, the Montgomery
+// image, as in k_fr_from_uint), w_j 2^261 for a 32-byte column (whose cells carry their 2^256 already), c 2^517 for the constant, which
+// starts the sums.  ONE reduction by 2^261 and one conditional subtraction per row.  Bounds (kept by rlc29_mac and by RR_BATCH, see
+// ff29.hip.hpp): a carry pass before a column sum could overflow, and at most RR_BATCH <= 64 terms below p^2 under one reduction, far
+// inside the 169 that T < 2^261 p admits.  The table (pointer, width, K limbs: 48 B a column) travels as a kernel argument: no upload,
+// no host synchronisation.  More than RR_BATCH columns: the next launch takes d_out as its first column, 32 bytes wide with weight one
+// -- a lane reads all its rows before it writes them, so that column may be the output itself.  The same holds for a caller's column
+// that is d_out, but only inside one launch: fr_row_rlc_run gives every such column to the FIRST launch (merged into one term).
+constexpr int RR_BATCH = 64;
+struct RrColumn { const void* src; uint32_t width; uint32_t k[9]; };
+struct RrBatch { RrColumn col[RR_BATCH]; uint32_t k0[9]; uint32_t count; };
+static_assert(RR_BATCH <= 64 && sizeof(RrBatch) < 4096 - 64, "terms under one reduction (T < 2^261 p), kernel argument size");
+// The terms of a run of up to G columns of one width, from column j on; returns how many it took.  The host has sorted the table by
+// width (the order of a sum is free), so runs are long; all loads of a run are issued before its first product -- a byte column is
+// ONE 4-byte load per lane, and a wave that waited for each of them by itself would spend its time on memory latency.
+template <int W>
+__device__ __forceinline__ uint32_t row_rlc_terms(const RrBatch& b, uint32_t j, uint64_t n, uint64_t wave, Rlc29<Fr29P> (&acc)[FU_CELLS]) {
+    constexpr int L = W <= 2 ? 1 : W == 4 ? 2 : W == 8 ? 3 : W == 16 ? 5 : 9;
+    constexpr int G = W <= 2 ? 8 : W == 4 ? 4 : W <= 16 ? 2 : 1;
+    if constexpr (W == 32) {
+        const RrColumn& col = b.col[j];
+        const uint32_t lane = threadIdx.x & 63u;
+        const uint2* src = (const uint2*)col.src;                       // 8-byte aligned
+        uint2 v[FU_CELLS][4];
+#pragma unroll
+        for (int s = 0; s < FU_CELLS; ++s) {
+            const uint64_t row = wave * (FU_CELLS * 64) + (uint64_t)s * 64 + lane;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[s][q] = row < n ? src[row * 4 + q] : make_uint2(0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < FU_CELLS; ++s) {
+            const Fr cell{{v[s][0].x, v[s][0].y, v[s][1].x, v[s][1].y, v[s][2].x, v[s][2].y, v[s][3].x, v[s][3].y}};
+            const Fr29 x = unpack29<Fr29P>(cell);
+            rlc29_mac<9>(acc[s], x.l, col.k);
+        }
+        return 1;
+    } else {
+        constexpr uint32_t load_bytes = W < 4 ? W * FU_CELLS : W;
+        uint32_t g = 1;
+        while (g < (uint32_t)G && j + g < b.count && b.col[j + g].width == (uint32_t)W) ++g;
+        static_assert(G * L < (int)RLC29_MAX_LOAD, "a run fits between two carry passes");
+#pragma unroll
+        for (int s = 0; s < FU_CELLS; ++s) rlc29_room(acc[s], G * L);   // one test and one place for the carry pass per run and sweep
+        uint32_t raw[G][FU_CELLS][4];
+#pragma unroll
+        for (int c = 0; c < G; ++c) {
+            if ((uint32_t)c >= g) break;                                // wave-uniform
+            const uint8_t* src = (const uint8_t*)b.col[j + c].src;
+            const uint32_t head = (uint32_t)((uintptr_t)src % load_bytes) / W;
+            fu_load_raw<W>(src - (size_t)head * W, head, n, wave, head, raw[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < G; ++c) {
+            if ((uint32_t)c >= g) break;
+            const RrColumn& col = b.col[j + c];
+            const uint32_t head = (uint32_t)((uintptr_t)col.src % load_bytes) / W;
+            uint32_t x[FU_CELLS][4];
+            fu_cells<W>(raw[c], head, x);
+#pragma unroll
+            for (int s = 0; s < FU_CELLS; ++s) {                        // rows at or past n read as 0 and are not stored
+                const Fr cell{{x[s][0], x[s][1], x[s][2], x[s][3], 0, 0, 0, 0}};
+                const Fr29 xl = unpack29<Fr29P>(cell);
+                rlc29_mac<L>(acc[s], xl.l, col.k);
+            }
+        }
+        return g;
+    }
+}
+__global__ void __launch_bounds__(256) k_fr_row_rlc(RrBatch b, uint64_t n, Fr* out) {
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave * (FU_CELLS * 64) >= n) return;                            // whole waves only: the shuffles stay inside a wave
+    const uint32_t lane = threadIdx.x & 63u;
+    Rlc29<Fr29P> acc[FU_CELLS];
+#pragma unroll
+    for (int s = 0; s < FU_CELLS; ++s) rlc29_init(acc[s], b.k0);
+    for (uint32_t j = 0; j < b.count;) {                                // wave-uniform, and so is the width
+        switch (b.col[j].width) {
+            case 1: j += row_rlc_terms<1>(b, j, n, wave, acc); break;
+            case 2: j += row_rlc_terms<2>(b, j, n, wave, acc); break;
+            case 4: j += row_rlc_terms<4>(b, j, n, wave, acc); break;
+            case 8: j += row_rlc_terms<8>(b, j, n, wave, acc); break;
+            case 16: j += row_rlc_terms<16>(b, j, n, wave, acc); break;
+            default: j += row_rlc_terms<32>(b, j, n, wave, acc); break;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < FU_CELLS; ++s) {
+        const uint64_t row = wave * (FU_CELLS * 64) + (uint64_t)s * 64 + lane;
+        if (row < n) stg(out + row, pack29_lt2p(rlc29_reduce(acc[s])));
+    }
+}
+// desc->count columns, RR_BATCH per launch; everything is validated before the first launch, so a refused call has written nothing.
+// h_k: the constant and the count weights, Montgomery Fr in host memory.
+int fr_row_rlc_run(zk_ctx* ctx, const zk_row_rlc* desc, const void* h_k, Fr* d_out, uint64_t n) {
+    const size_t count = desc->count;
+    if (count && (!desc->d_cols || !desc->widths)) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC: NULL column or width table");
+    const uintptr_t o = (uintptr_t)d_out, o_end = o + n * sizeof(Fr);
+    for (size_t c = 0; c < count; ++c) {
+        const uint32_t width = desc->widths[c];
+        const uintptr_t p = (uintptr_t)desc->d_cols[c], p_end = p + n * width;
+        if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16 && width != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu: cell width %u: must be 1, 2, 4, 8, 16 or 32 bytes", c, width);
+        if (!p) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu: NULL pointer", c);
+        if (p % (width == 32 ? 8 : width)) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu: cells of %u bytes at a misaligned address", c, width);
+        // a lane reads its rows of every column before it writes them: the output may BE a 32-byte column (taken by the first
+        // launch, below), and nothing else
+        if (n && !(width == 32 && p == o) && p < o_end && o < p_end) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu overlaps the output", c);
+    }
+    if (!n) return ZK_OK;
+    const uint64_t per_block = (uint64_t)FU_CELLS * 256, blocks = (n + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many rows for one launch");
+    static const Fr c261 = [] { Fr c = Fr::one(); for (int i = 0; i < 261 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^261 mod r
+    const uint8_t* hk = (const uint8_t*)h_k;
+    auto limbs_of = [](uint32_t* k, const Fr& mont, const Fr& by) {     // plain normalised limbs of (value of mont) * by: canonical, below 2^29 each
+        const Fr29 l = unpack29<Fr29P>(mont * by);
+        for (int i = 0; i < 9; ++i) k[i] = l.l[i];
+    };
+    // The terms in launch order.  "A lane reads its rows before it writes them" holds inside ONE launch only: the first launch
+    // overwrites d_out, so every column that IS d_out must be read by it.  All of them (there may be several) become one term with
+    // the sum of their constants, at the head of the list; the others follow in table order.
+    struct Term { RrColumn col; uint32_t booked; };
+    std::vector<Term> terms;
+    terms.reserve(count + 1);
+    Fr alias_k = Fr::zero();
+    uint32_t alias_bytes = 0;
+    for (size_t c = 0; c < count; ++c) {
+        Fr w;
+        memcpy(&w, hk + (1 + c) * sizeof(Fr), sizeof w);
+        const uint32_t width = desc->widths[c];
+        if (width == 32 && (uintptr_t)desc->d_cols[c] == o) { alias_k = alias_k + w * c261; alias_bytes += 32; continue; }   // products are canonical: the sum is
+        Term t{{desc->d_cols[c], width, {}}, width};
+        limbs_of(t.col.k, w, width == 32 ? c261 : fr_c517());
+        terms.push_back(t);
+    }
+    if (alias_bytes) {
+        Term t{{d_out, 32, {}}, alias_bytes};                           // booked as the table states it: 32 B per aliased column
+        limbs_of(t.col.k, alias_k, Fr::one());                          // times Montgomery one: the value itself
+        terms.insert(terms.begin(), t);
+    }
+    size_t c0 = 0;
+    do {
+        RrBatch b;
+        memset(&b, 0, sizeof b);
+        ZkProfScope prof(ctx, "fr_row_rlc");
+        uint64_t width_sum = 0;
+        uint32_t cnt = 0;
+        if (c0 == 0) {
+            Fr c;
+            memcpy(&c, hk, sizeof c);
+            limbs_of(b.k0, c, fr_c517());
+        } else {                                                        // the sum so far: a 32-byte column of weight one (k0 stays 0)
+            b.col[cnt] = {d_out, 32, {}};
+            limbs_of(b.col[cnt].k, Fr::one(), c261);
+            width_sum += 32;
+            ++cnt;
+        }
+        for (; cnt < RR_BATCH && c0 < terms.size(); ++cnt, ++c0) {
+            b.col[cnt] = terms[c0].col;
+            width_sum += terms[c0].booked;
+        }
+        b.count = cnt;
+        std::stable_sort(b.col, b.col + cnt, [](const RrColumn& x, const RrColumn& y) { return x.width < y.width; });   // runs of one width for the kernel
+        prof.bytes = n * (width_sum + 32ull);
+        hipLaunchKernelGGL(k_fr_row_rlc, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, b, n, d_out);
+    } while (c0 < terms.size());
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+
 // ---- sigma columns from the permutation mapping: out[j][i] = delta^j' * omega^i' for mapping[j][i] = (j', i') ------------------------
 // halo2's permutation::keygen::Assembly::mapping names, for cell i of permutation column j, the next cell (j', i') of its cycle; the
 // sigma polynomial's value there is delta^j' * omega^i'.  Up to SM_BATCH columns per launch in the manner of k_fr_from_uint_batch:
@@ -735,6 +959,10 @@ extern "C" {
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
     ZK_REQUIRE(ctx, d_a && d_b && d_out, "null device pointer");
+    if (op == ZK_OP_ROW_RLC) {                                          // d_a, d_b: HOST pointers (column table; constant and weights)
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the row RLC is defined over Fr only");
+        return fr_row_rlc_run(ctx, (const zk_row_rlc*)d_a, d_b, (Fr*)d_out, n);
+    }
     if (n == 0) return ZK_OK;
     if (op == ZK_OP_SCAN_AFFINE || op == ZK_OP_SCAN_AFFINE_REV) {
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the scan ops are defined over Fr only");
