@@ -267,9 +267,24 @@ int zk_host_quotient_lower2(const uint32_t* program, uint32_t num_instr, uint32_
  * acc = acc * c_f + term_f whose operands are read many times is evaluated slice by slice over the same rows at the same time so
  * that the slices find each other's operands in the caches; cuts only at top-level FOLDs that no parked intermediate is alive
  * across).  out_cuts receives the first instruction of every slice and the end of the program (*out_count entries; 0 = the program
- * runs in one piece).  ZK_QUOTIENT_SLICES=0 / N turns the slicing off / asks for N slices.  No counterpart in halo2's evaluate_h
+ * runs in one piece).  The cuts are those for packed columns (32-byte rows); a proof's class programs read coset records of 36-byte
+ * rows and may be cut finer: zk_host_quotient_launch shows those.  ZK_QUOTIENT_SLICES=0 / N turns the slicing off / asks for N slices.  No counterpart in halo2's evaluate_h
  * (plonk/evaluation.rs, external crate), which walks one row at a time on the CPU.                                              */
 int zk_host_quotient_slices(const uint32_t* program, uint32_t num_instr, uint32_t ext_k, uint32_t* out_cuts, size_t cap, uint32_t* out_count);
+/* Host only (no context, no device): what a launch of `program` over 2^ext_k rows looks like under the ZK_QUOTIENT_* knobs in force at the
+ * call -- everything zk_quotient_eval decides before it touches the device (csrc/quotient_lower.hpp: plan_quotient_launch).  records != 0: the
+ * columns are coset record buffers, as in a proof's class programs (36-byte rows: the slicer cuts for those).  out_head receives
+ * ZK_QUOTIENT_LAUNCH_HEAD words: kernel (1 k_quotient_eval, 2 k_quotient_eval2), record operands, the grid covers the domain exactly (FULL),
+ * accumulator in memory (ACC_MEM), sliced, slices (1: whole), lowered stack depth, LDS bytes per workgroup, parking slots (renumbered per slice),
+ * lowered instructions, folds among them, words per instruction (3 or 4), word offset of the combining program, word offset of the slice table,
+ * bytes of the program / column-table / constant regions of the upload, the row-tile alias passed to the kernel.  *out_count receives the
+ * length of the program region in words and out_words (cap_words of room; NULL with 0 to ask for the length) the region as uploaded: per slice
+ * its lowered instructions (w0, a, b and, for kernel 2, the class mask) and four END records; for a sliced launch the combining program
+ * (FOLD_COL | (num_consts + s) << 16 reading column num_cols + parking slots + s, s = 0 .. slices - 1), its four END records and the slice table,
+ * (first word, instructions + 1) per slice.  A program zk_quotient_eval refuses gives that status. */
+#define ZK_QUOTIENT_LAUNCH_HEAD 18
+int zk_host_quotient_launch(const uint32_t* program, uint32_t num_instr, uint32_t num_cols, uint32_t num_consts, uint32_t ext_k, int records,
+                            uint32_t* out_head, uint32_t* out_words, size_t cap_words, size_t* out_count);
 
 /* Host only, for tests: how the prover distributes constraint programs over its degree classes when the programs share
  * intermediates (TEE_TMP in one constraint, PUSH_TMP in a later one -- halo2's GraphEvaluator intermediates as exported): a

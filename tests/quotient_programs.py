@@ -190,16 +190,27 @@ def slice_cuts(prog, ext_k):
     return [int(x) for x in out[:cnt.value]]
 
 
+def fuse_of(env):
+    """the `fuse` argument of zk_host_quotient_lower that gives the stream zk_quotient_eval runs under the knobs `env`: the caller's sequence
+    under ZK_QUOTIENT_FUSE=0; memory operands alone (1) for k_quotient_eval and under ZK_QUOTIENT_MAC=0; K_MAC_COL too (3) under
+    ZK_QUOTIENT_MAC=1; every fused step (7) otherwise"""
+    if env.get("ZK_QUOTIENT_FUSE") == "0":
+        return 0
+    if env.get("ZK_QUOTIENT_KERNEL") == "1" or env.get("ZK_QUOTIENT_MAC") == "0":
+        return 1
+    return 3 if env.get("ZK_QUOTIENT_MAC") == "1" else 7
+
+
 def variant(prog, ncols, ext_k, env):
-    """which kernel zk_quotient_eval launches for this program under the knobs `env` (ZK_QUOTIENT_KERNEL / MAC / FUSE / SLICES), by the
-    host's own predicate: ("sliced",) or (kernel, FULL, ACC_MEM) with kernel "v2" (k_quotient_eval2) or "v1" (k_quotient_eval).
-    ZK_QUOTIENT_SLICES must be set in os.environ as in `env` (zk_host_quotient_slices reads it)."""
+    """which kernel zk_quotient_eval launches for this program (packed columns) under the knobs `env` (ZK_QUOTIENT_KERNEL / MAC / FUSE /
+    SLICES), restated from the rules of the launch: ("sliced",) or (kernel, FULL, ACC_MEM) with kernel "v2" (k_quotient_eval2) or "v1"
+    (k_quotient_eval).  ZK_QUOTIENT_SLICES must be set in os.environ as in `env` (zk_host_quotient_slices reads it).
+    tests/test_quotient_launch.py holds this against the library's launch plan on every (case, setting)."""
     v2 = env.get("ZK_QUOTIENT_KERNEL") != "1"
     ne = 1 << ext_k
     if v2 and ((ne // 256) & 7) == 0 and slice_cuts(prog, ext_k):
         return ("sliced",)
-    fuse = 0 if env.get("ZK_QUOTIENT_FUSE") == "0" else (3 if v2 and env.get("ZK_QUOTIENT_MAC") != "0" else 1)
-    words, _ = lower(prog, ncols, fuse)
+    words, _ = lower(prog, ncols, fuse_of(env))
     ops = [int(w) & 0xff for w in words[0::3]]
     folds = sum(1 for o in ops if o in (Q_FOLD, K_FOLD_COL))
     acc_mem = folds > 0 and folds * 16 <= len(ops)
@@ -374,7 +385,7 @@ class knobs:
 def setting_streams(case, env):
     """the lowered stream(s) zk_quotient_eval runs for the case under `env` (knobs must be in force): the whole program, or its slices"""
     v2 = env.get("ZK_QUOTIENT_KERNEL") != "1"
-    fuse = 0 if env.get("ZK_QUOTIENT_FUSE") == "0" else (3 if v2 and env.get("ZK_QUOTIENT_MAC") != "0" else 1)
+    fuse = fuse_of(env)
     cuts = slice_cuts(case.prog, case.ext_k) if v2 and (((1 << case.ext_k) // 256) & 7) == 0 else []
     if not cuts:
         return [lower(case.prog, case.ncols, fuse)[0]]

@@ -1,4 +1,4 @@
-"""The expression evaluator's lowering pass (csrc/quotient.hip: lower_fuse, lower_bounds), checked on the CPU.
+"""The expression evaluator's lowering pass (csrc/quotient_lower.hpp: lower_fuse, lower_bounds), checked on the CPU.
 
 `zk_host_quotient_lower` returns the instruction stream the kernel runs for a caller's postfix program.  This test
 executes that stream the way the kernel does -- nine 29-bit limbs in 32-bit words, 64-bit column sums, unsettled sums --

@@ -1,4 +1,4 @@
-"""The evaluator's fused Horner steps (csrc/quotient.hip: lower_fuse with mac, K_MAC_COL; zk_host_quotient_lower with fuse & 2), checked on
+"""The evaluator's fused Horner steps (csrc/quotient_lower.hpp: lower_fuse with mac, K_MAC_COL; zk_host_quotient_lower with fuse & 2), checked on
 the CPU.
 
 A Horner step of a compiled class program,  S MUL_CONST y^gap <X> MUL_COL m [SUB_COL n ...] ADD,  becomes  S <X> MAC_COL(m, y^gap)

@@ -1,4 +1,4 @@
-"""Sums of two column products and stack products under one reduction (csrc/quotient.hip: lower_fuse with mac2; PUSH_COL32, MAC2_COL,
+"""Sums of two column products and stack products under one reduction (csrc/quotient_lower.hpp: lower_fuse with mac2; PUSH_COL32, MAC2_COL,
 MAC_STK; zk_host_quotient_lower with fuse & 4), checked on the CPU.
 
 A Horner step over a sum of two column products,  S MUL_CONST c <X> MUL_COL m1 <Y> MUL_COL m2 ADD [chain] ADD,  becomes

@@ -1,4 +1,4 @@
-"""CPU: where zk_quotient_eval cuts a program into slices (zk_host_quotient_slices; csrc/quotient.hip: plan_slices) and that the cut is sound:
+"""CPU: where zk_quotient_eval cuts a program into slices (zk_host_quotient_slices; csrc/quotient_lower.hpp: plan_slices) and that the cut is sound:
 the partial sums of the slices, put together with the products of the slices' fold constants, are the value of the whole program (big-int).
 The device side of the same thing is tests/test_gpu_quotient.py::test_sliced_program_matches_oracle."""
 import ctypes

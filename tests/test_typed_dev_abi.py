@@ -62,7 +62,7 @@ def test_header_and_library_have_the_same_entry_points(zk):
     exported = _exported(zk)
     assert declared == exported, (sorted(set(declared) - set(exported)), sorted(set(exported) - set(declared)))
     readme = open(os.path.join(ROOT, "README.md")).read()
-    assert f"The C ABI has {len(exported)} entry points" in readme and len(exported) == 145
+    assert f"The C ABI has {len(exported)} entry points" in readme and len(exported) == 146
 
 
 def test_without_a_context_both_calls_fail_cleanly(zk):

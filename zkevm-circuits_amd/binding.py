@@ -284,6 +284,31 @@ def host_ntt_plan(log_n: int, columns: int = 1, tables: bool = True, coset_pass:
     return {"per_launch": head[0], "columns": head[1], "passes": head[2], "tables": bool(head[3]), "launches": launches}
 
 
+QUOTIENT_LAUNCH_HEAD = ("kernel", "records", "full", "acc_in_mem", "sliced", "S", "depth", "lds", "num_tmp", "low_len", "folds", "words_per_instr", "comb_at", "slice_tab_at",
+                        "prog_bytes", "col_bytes", "const_bytes", "tile_alias")
+
+
+def host_quotient_launch(prog, num_cols: int, num_consts: int, ext_k: int, records: bool = False) -> dict:
+    """zk_host_quotient_launch (no device): the launch plan of a postfix program [(op, a, b), ...] under the ZK_QUOTIENT_* knobs in force -- the head's
+    fields by name (full, acc_in_mem, sliced, records as bools) and `words`, the program region of the upload"""
+    flat = [int(x) & 0xFFFFFFFF for ins in prog for x in ins]
+    n = len(flat) // 3
+    words = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+    head, cnt = (ctypes.c_uint32 * len(QUOTIENT_LAUNCH_HEAD))(), ctypes.c_size_t()
+    out = (ctypes.c_uint32 * (32 * (n + 16)))()       # room: at most 2 n lowered instructions of 4 words, and 22 words of END records, combining step and table entry per slice (two folds at least)
+    rc = lib().zk_host_quotient_launch(words, ctypes.c_uint32(n), ctypes.c_uint32(num_cols), ctypes.c_uint32(num_consts), ctypes.c_uint32(ext_k), ctypes.c_int(1 if records else 0),
+                                       head, out, ctypes.c_size_t(len(out)), ctypes.byref(cnt))
+    if rc != 0:
+        err = ZkError(f"zk_host_quotient_launch({n} instructions, 2^{ext_k} rows) failed with status {rc}")
+        err.status = rc         # the status zk_quotient_eval would return for the program
+        raise err
+    plan = dict(zip(QUOTIENT_LAUNCH_HEAD, head))
+    for name in ("records", "full", "acc_in_mem", "sliced"):
+        plan[name] = bool(plan[name])
+    plan["words"] = list(out[:cnt.value])
+    return plan
+
+
 MSM_BATCH_PLAN_HEAD = ("status", "any_narrow", "tail_rows", "n_narrow", "n_pad", "NG", "gm", "SG", "range_bits_G", "bpcG", "perm_G", "nwgG", "words_N", "words_G", "words_M", "words",
                        "copies", "binsort", "range_bits", "chunk", "staged_scatter", "nwg", "npipe", "graph", "npts29", "smaller_cap", "c", "W", "top_shift", "c_n", "W_n", "red_blocks_N")
 MSM_SORT_REGIONS = ("slice_counts", "slice_off", "counts", "cleared", "offsets", "order", "ntasks", "toff", "block_tot_s", "block_tot", "block_tot_h", "hist", "hist_off", "idx", "dig", "entries")

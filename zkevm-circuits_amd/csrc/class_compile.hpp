@@ -190,7 +190,7 @@ struct ClassCompiler {
     std::vector<uint32_t> uses;
     std::vector<int32_t> vslot;          // node -> virtual slot once parked
     Prog out;
-    // Chunked emission (round 6, for the sliced launches of csrc/quotient.hip: plan_slices): a parked value is only visible inside the top-level term that
+    // Chunked emission (round 6, for the sliced launches of csrc/quotient_lower.hpp: plan_slices): a parked value is only visible inside the top-level term that
     // parked it -- the next term recomputes (and, if it reads the value twice itself, parks) it again.  Every top-level FOLD is then a point where nothing
     // parked is alive, i.e. where the evaluator may cut the program into slices that run side by side.  `uses` are counted per term for the same reason.
     bool chunked = false;

@@ -4,13 +4,14 @@
 // The programs are postfix over abstract column and constant references; the prover lowers them for the device evaluator
 // (quotient.hip), the verifier evaluates them at one point (verifier.hip).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
 
-#include "host_fq.hpp"
+#include "host_f4.hpp"
 
 namespace zk {
 namespace cs {

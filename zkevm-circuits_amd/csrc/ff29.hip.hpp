@@ -624,7 +624,7 @@ __host__ __device__ __forceinline__ void mul29_ub_ipa(F29<P>& x, const F29<P>& y
 #endif
 }
 // x <- mul2add29(x, y, s, c) = (x y + s c) / 2^261 mod p, c wave-uniform (scalar registers): the evaluator's fused Horner step t0 B + S y^gap.
-// Operand bounds as the caller keeps them (csrc/quotient.hip, lower_bounds): y, c normalised, limbs of x below L_x 2^29 and of s below
+// Operand bounds as the caller keeps them (csrc/quotient_lower.hpp, lower_bounds): y, c normalised, limbs of x below L_x 2^29 and of s below
 // L_s 2^29 with L_x + L_s <= 6 (a column then holds below 9 (L_x + L_s + 1) 2^58 + 2^35 < 2^64), x y + s c < 2^261 p.
 template <class P>
 __host__ __device__ __forceinline__ void mul2add29_ub_ipa(F29<P>& x, const F29<P>& y, const F29<P>& s, const F29<P>& c) {

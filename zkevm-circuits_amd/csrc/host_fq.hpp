@@ -7,12 +7,12 @@
 #include <cstring>
 
 #include "ec.hip.hpp"
+#include "host_f4.hpp"
 
 namespace zk {
 namespace host {
 
 typedef unsigned __int128 u128;
-struct F4 { uint64_t l[4]; };
 
 struct FqC {
     static constexpr uint64_t M[4] = {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};

@@ -47,6 +47,7 @@
 #include "host_hash.hpp"
 #include "cs.hpp"
 #include "quotient_plan.hpp"
+#include "quotient_lower.hpp"
 
 using namespace zk;
 using zk::host::F4;
@@ -217,8 +218,7 @@ size_t device_free_bytes(bool* ok = nullptr) {
 // has no record mode.  Read where a session first makes a coset and again where its quotient starts: the tests flip both knobs in one process.
 bool quotient_records(uint32_t k) {
     const char* r = getenv("ZK_QUOTIENT_RECORDS");
-    const char* q = getenv("ZK_QUOTIENT_KERNEL");
-    return !(r && atoi(r) == 0) && !(q && atoi(q) == 1) && k >= 2 && k <= 26;        // the record mode addresses a row with 32-bit byte offsets
+    return !(r && atoi(r) == 0) && records_supported(QuotientEvalKnobs::read(), k);        // a coset has 2^k rows
 }
 size_t coset_row_bytes(bool records) { return records ? REC29_BYTES : sizeof(Fr); }
 bool session_records(zk_proof* pr) {

@@ -1,5 +1,5 @@
 // The quotient's planner (quotient_plan.hpp): constraint system and knobs in, degree-class programs out.  Host only, so that it
-// links with cs.hip and the host side of quotient.hip into a stand-alone program (tools/quotient_plan_check.cpp).
+// links with cs.hip alone into a stand-alone program (tools/quotient_plan_check.cpp); the evaluator's lowering comes from quotient_lower.hpp.
 #include <algorithm>
 #include <array>
 #include <cstdio>
@@ -10,6 +10,7 @@
 
 #include "../../include/zkmi355.h"
 #include "quotient_plan.hpp"
+#include "quotient_lower.hpp"
 #include "class_compile.hpp"
 
 namespace zk {
@@ -466,7 +467,7 @@ bool tmp_slots_conflict(const std::vector<Prog>& cons) {
     for (size_t s_ = 0; s_ < ndef.size(); ++s_) if (ndef[s_] > 1 && cross[s_]) return true;
     return false;
 }
-// Horner steps of a class program that the evaluator runs as one fused multiply-accumulate (K_MAC_COL of csrc/quotient.hip: two products, one
+// Horner steps of a class program that the evaluator runs as one fused multiply-accumulate (K_MAC_COL of csrc/quotient_lower.hpp: two products, one
 // reduction) when ZK_QUOTIENT_MAC is on: the program lowered as zk_quotient_eval lowers it, constants numbered densely first
 // fuse = 3: K_MAC_COL alone (out4 unused); fuse = 7: out4 = { MAC2_COL, MAC_STK, MAC2_COL fusions declined for stack depth, MAC_COL } of that stream
 static uint32_t count_fused(const Prog& g, int fuse = 3, uint32_t* out4 = nullptr) {
@@ -477,14 +478,13 @@ static uint32_t count_fused(const Prog& g, int fuse = 3, uint32_t* out4 = nullpt
         const bool c = in.op == Q_PUSH_CONST || in.op == Q_MUL_CONST || in.op == Q_ADD_CONST || in.op == Q_FOLD;
         w.push_back(in.op); w.push_back(c ? cix.emplace(in.a, (uint32_t)cix.size()).first->second : in.a); w.push_back(in.b);
     }
-    uint32_t n = 0;
     int depth = 0;
     uint32_t decl = 0;
-    if (zk_host_quotient_lower2(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, nullptr, 0, &n, &depth, &decl)) return 0;
-    std::vector<uint32_t> out(3 * (size_t)n);
-    if (zk_host_quotient_lower2(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, out.data(), out.size(), &n, &depth, &decl)) return 0;
+    std::vector<LowInstr> low;
+    if (check_program(w.data(), (uint32_t)g.size(), false).status) return 0;
+    if (lower_program(w.data(), (uint32_t)g.size(), 0x80000000u, fuse, QuotientEvalKnobs::read().relaxed != 0, &low, &depth, &decl)) return 0;
     uint32_t f = 0, f2 = 0, fs = 0;
-    for (uint32_t i = 0; i < n; ++i) { const uint32_t o = out[3 * i] & 0xffu; f += o == 22u; f2 += o == 24u; fs += o == 25u; }
+    for (const LowInstr& in : low) { const uint32_t o = in.w0 & 0xffu; f += o == K_MAC_COL; f2 += o == K_MAC2_COL; fs += o == K_MAC_STK; }
     if (out4) { out4[0] = f2; out4[1] = fs; out4[2] = decl; out4[3] = f; }
     return f;
 }

@@ -33,7 +33,7 @@ bool split_leaf_factor(const Prog& g, bool factor_first, Prog* rest, Instr* fact
 // theta-compression of a list of expressions: ((e0 * theta + e1) * theta + e2) ...
 void push_compressed(PB& b, const std::vector<Prog>& exprs);
 
-// What the evaluator's stack machine can run (Q_MAX_STACK in quotient.hip is 16): the program leaves nothing on the stack and never
+// What the evaluator's stack machine can run (Q_MAX_STACK in quotient_lower.hpp is 16): the program leaves nothing on the stack and never
 // holds more than 14 values.  *depth: the most it holds, *left: what it leaves.
 inline bool fits_evaluator_stack(const Prog& g, int* depth = nullptr, int* left = nullptr) {
     int sp = 0, mx = 0;
@@ -82,7 +82,7 @@ struct QuotientKnobs {
     int group = 1;          // ZK_QUOTIENT_GROUP=0: class programs folded term by term where the compiler is off or gives up
     int dag = 1;            // ZK_QUOTIENT_DAG=0: class programs not compiled through the expression graph (class_compile.hpp)
     int costgate = 1;       // ZK_QUOTIENT_COSTGATE=0: the most split candidate the knobs allow, whatever it costs
-    int mac = 2;            // ZK_QUOTIENT_MAC: 0 no fused steps counted, 1 K_MAC_COL alone, unset or anything else all (csrc/quotient.hip)
+    int mac = 2;            // ZK_QUOTIENT_MAC: 0 no fused steps counted, 1 K_MAC_COL alone, unset or anything else all (csrc/quotient_lower.hpp: lower_fuse)
     int chunk = -1;         // ZK_QUOTIENT_CHUNK: 0 / 1 class programs emitted in one parking scope / term by term, unset: by node count
     int lookup_plain = 0;   // ZK_LOOKUP_PLAIN=1: the single-tuple lookup identity as halo2 writes it
     static QuotientKnobs read();
