@@ -52,6 +52,10 @@ typedef struct zk_row_rlc {
     const void* const* d_cols;  /* count device pointers                                          */
     const uint8_t* widths;      /* count cell widths in bytes: 1, 2, 4, 8, 16 (packed) or 32 (Fr) */
 } zk_row_rlc;
+/* the running RLC of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct */
+#define ZK_OP_SCAN_RLC 9
+#define ZK_OP_SCAN_RLC_REV 10
+typedef struct zk_scan_rlc { const void* d_cells; uint32_t width; const uint8_t* d_kinds; } zk_scan_rlc;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -140,7 +144,24 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * partially.  ZK_FIELD_FQ, any other width, a NULL or misaligned column, a forbidden overlap, NULL d_cols or
  * widths with count > 0: ZK_ERR_INVALID_ARG before any launch, nothing is written.  64 columns per launch; a longer table runs as
  * further launches that take the sum so far from d_out.  Booked under the zk_prof name "fr_row_rlc" with n * (sum of widths + 32)
- * algorithmic bytes per launch (the sum so far counts as a 32-byte column).  Other op values (5, 6, 7, ...) are refused. */
+ * algorithmic bytes per launch (the sum so far counts as a 32-byte column).
+ * ZK_OP_SCAN_RLC and ZK_OP_SCAN_RLC_REV (#defines, values 9 and 10; Fr only) are the RLC ALONG a column, straight from packed typed
+ * cells and a one-byte kind column -- Keccak data_rlc, bytecode value_rlc, the copy circuit's reverse rlc_acc:
+ *   kind_i = d_kinds ? (d_kinds[i] & 3) : 0      (only the low two bits of the byte are read; the others are ignored)
+ *   ZK_OP_SCAN_RLC       out[-1] = z0,  out[i] = m[kind_i] * out[i-1] + w[kind_i] * cell[i]  for 0 <= i < n
+ *   ZK_OP_SCAN_RLC_REV   out[n]  = z0,  out[i] = m[kind_i] * out[i+1] + w[kind_i] * cell[i]  for n > i >= 0
+ * As for ZK_OP_ROW_RLC, d_a and d_b are HOST pointers for these ops: d_a points to a zk_scan_rlc {d_cells, width, d_kinds} (the two
+ * pointers in it are device pointers), d_b to 9 x 32 B Montgomery Fr in host memory: z0, then the table m_0, w_0, m_1, w_1, m_2, w_2,
+ * m_3, w_3.  Both are read before the call returns; the call is asynchronous on the context's stream.  The usual table is
+ * step (r, 1), start (0, 1), hold (1, 0), clear (0, 0).  width in {1, 2, 4, 8, 16}: n little-endian unsigned cells at d_cells,
+ * aligned to the width only, read like zk_fr_from_uint (nothing outside n * width bytes is read); width = 32: n canonical Montgomery
+ * Fr, 8-byte aligned -- a non-canonical 32-byte cell gives undefined VALUES from its row on, in scan order, and touches no memory
+ * that would not be touched otherwise.  d_kinds: n bytes at any alignment, or NULL (every row kind 0: the plain Horner running RLC);
+ * d_cells and d_kinds may name the same or overlapping memory.  Results are canonical.  d_out (n x 32 B) overlaps neither the cells
+ * nor the kinds.  ZK_FIELD_FQ, any other width, NULL or misaligned d_cells, a forbidden overlap: ZK_ERR_INVALID_ARG before any
+ * launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.  Booked under the zk_prof
+ * name "fr_scan_rlc" with n * (width + (d_kinds ? 1 : 0) + 32) algorithmic bytes per call.
+ * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */
 int zk_fr_scale(zk_ctx* ctx, void* d_a, const void* h_s, size_t n);

@@ -18,6 +18,7 @@
 //   (reference call sites: circuit-benchmarks/src/super_circuit.rs:104-132, zkevm-circuits/src/test_util.rs:272,
 //    prover/src/common/prover/utils.rs:31,55, prover/src/utils.rs:77)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -140,6 +141,21 @@ inline void row_rlc(const Context& c, const std::vector<const void*>& d_cols, co
     host.insert(host.end(), weights.begin(), weights.end());
     const zk_row_rlc table{(uint32_t)d_cols.size(), d_cols.data(), cell_bytes.data()};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_ROW_RLC, &table, host.data(), d_out, n));
+}
+// d_out[i] = m[kind_i] * d_out[i - 1] + w[kind_i] * cell[i] for i < n with d_out[-1] = z0, along one typed column on the device
+// (zk_field_vec_op with ZK_OP_SCAN_RLC and a zk_scan_rlc; asynchronous on the context's stream); reverse: from the last row down,
+// d_out[i] = m[kind_i] * d_out[i + 1] + w[kind_i] * cell[i] with d_out[n] = z0 (ZK_OP_SCAN_RLC_REV).  d_cells holds n cells of
+// cell_bytes bytes (1, 2, 4, 8, 16: packed little-endian unsigned integers as for fr_from_uint; 32: Montgomery Fr), d_kinds n bytes
+// whose low two bits are the row's kind, or nullptr for kind 0 everywhere.  table = {m_0, w_0, m_1, w_1, m_2, w_2, m_3, w_3}: the
+// running RLC with restarts and padding rows is step (r, 1), start (0, 1), hold (1, 0), clear (0, 0).  d_out (n x 32 B) overlaps
+// neither the cells nor the kinds.
+inline void scan_rlc(const Context& c, const void* d_cells, uint32_t cell_bytes, const uint8_t* d_kinds, const std::array<Fr, 8>& table, size_t n, void* d_out,
+                     const Fr& z0 = Fr{}, bool reverse = false) {
+    std::array<Fr, 9> host;                                             // z0, then the table: host memory, read by the call
+    host[0] = z0;
+    std::copy(table.begin(), table.end(), host.begin() + 1);
+    const zk_scan_rlc desc{d_cells, cell_bytes, d_kinds};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, reverse ? ZK_OP_SCAN_RLC_REV : ZK_OP_SCAN_RLC, &desc, host.data(), d_out, n));
 }
 
 // poly::EvaluationDomain::new(j, k)

@@ -55,6 +55,19 @@ pub struct zk_row_rlc {
     pub d_cols: *const *const c_void,
     pub widths: *const u8,
 }
+/// `zk_field_vec_op` ops: `out[i] = m[kind_i] * out[i - 1] + w[kind_i] * cell[i]` along a typed column (`out[-1] = z0`), and the
+/// same from the last row down (`out[n] = z0`).  For these ops `d_a` is a HOST pointer to a `zk_scan_rlc` and `d_b` a HOST pointer to
+/// `9 x 32 B` Montgomery Fr: `z0`, then `m_0, w_0 .. m_3, w_3`.
+pub const ZK_OP_SCAN_RLC: c_int = 9;
+pub const ZK_OP_SCAN_RLC_REV: c_int = 10;
+/// `zk_scan_rlc`: `d_cells` is a device pointer to `n` cells of `width` bytes (1, 2, 4, 8, 16: packed little-endian unsigned; 32:
+/// Montgomery Fr), `d_kinds` a device pointer to `n` kind bytes (low two bits) or null (every row kind 0).
+#[repr(C)]
+pub struct zk_scan_rlc {
+    pub d_cells: *const c_void,
+    pub width: u32,
+    pub d_kinds: *const u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

@@ -24,6 +24,7 @@ FIELD_FR, FIELD_FQ = 0, 1
 OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
 OP_SCAN_AFFINE, OP_SCAN_AFFINE_REV = 3, 4            # out[i] = a[i] * out[i -+ 1] + b[i] along the column, Fr only
 OP_ROW_RLC = 8                                        # out[i] = c + sum_j w_j * cell_j[i] across typed columns, Fr only (ZK_OP_ROW_RLC)
+OP_SCAN_RLC, OP_SCAN_RLC_REV = 9, 10                 # out[i] = m[kind_i] * out[i -+ 1] + w[kind_i] * cell[i] along a typed column, Fr only
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -77,6 +78,11 @@ def lib():
 class _RowRlc(ctypes.Structure):
     """zk_row_rlc: the column table of ZK_OP_ROW_RLC (host memory)"""
     _fields_ = [("count", ctypes.c_uint32), ("d_cols", ctypes.POINTER(ctypes.c_void_p)), ("widths", ctypes.POINTER(ctypes.c_uint8))]
+
+
+class _ScanRlc(ctypes.Structure):
+    """zk_scan_rlc: the cells and kinds of ZK_OP_SCAN_RLC / ZK_OP_SCAN_RLC_REV (host memory; both pointers are device pointers)"""
+    _fields_ = [("d_cells", ctypes.c_void_p), ("width", ctypes.c_uint32), ("d_kinds", ctypes.c_void_p)]
 
 
 def _host_ptr(a: np.ndarray):
@@ -703,6 +709,21 @@ class Context:
         wd = (ctypes.c_uint8 * max(cnt, 1))(*widths)
         desc = _RowRlc(cnt, ctypes.cast(pp, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(wd, ctypes.POINTER(ctypes.c_uint8)))
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_ROW_RLC, ctypes.byref(desc), _host_ptr(hk), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
+    def scan_rlc(self, cells, width, kinds, table, n, out, z0=None, reverse=False):
+        """out[i] = m[kind_i] * out[i - 1] + w[kind_i] * cell[i] for i < n with out[-1] = z0 (zk_field_vec_op with ZK_OP_SCAN_RLC);
+        reverse: from the last element down, out[i] = m[kind_i] * out[i + 1] + w[kind_i] * cell[i] with out[n] = z0.  cells: DeviceBuffer
+        or device pointer of n cells of `width` bytes -- 1, 2, 4, 8, 16: packed little-endian unsigned cells, read like fr_from_uint;
+        32: Montgomery Fr.  kinds: n bytes on the device (the low two bits of each are the row's kind) or None (every row kind 0).
+        table: four (m, w) pairs, each 4 uint64 Montgomery -- e.g. step (r, 1), start (0, 1), hold (1, 0), clear (0, 0); z0: 4 uint64
+        Montgomery (default 0).  out (DeviceBuffer or pointer, n x 32 B) overlaps neither the cells nor the kinds."""
+        ptr_of = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        hk = np.zeros((9, 4), dtype=np.uint64)
+        if z0 is not None:
+            hk[0] = np.asarray(z0, dtype=np.uint64).reshape(4)
+        hk[1:] = np.asarray(table, dtype=np.uint64).reshape(8, 4)
+        desc = _ScanRlc(ptr_of(cells), width, None if kinds is None else ptr_of(kinds))
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_SCAN_RLC_REV if reverse else OP_SCAN_RLC, ctypes.byref(desc), _host_ptr(hk), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

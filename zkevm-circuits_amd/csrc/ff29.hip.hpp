@@ -751,6 +751,33 @@ __host__ __device__ __forceinline__ F29<P> rlc29_reduce(const Rlc29<P>& t) {
     return r;
 }
 
+// ---- one row of a running RLC: z <- (z M + x K) 2^-261 mod p (the typed scan of csrc/vec.hip, ZK_OP_SCAN_RLC) ---------------------
+// z is the state, normalised and below 2p (a Montgomery image: the integer Z 2^256), x the row's cell as an integer of L limbs, M and
+// K the plain normalised constants of the row's kind: M = m 2^261 and K = w 2^517 (K = w 2^261 where x is itself a Montgomery image)
+// give the image of m Z + w X.  Two terms under one reduction: T < 2p p + 2^128 p < 2^261 p (x < p instead of 2^128: T < 3 p^2), and
+// the fullest column holds 1 + 9 + L <= 19 products, far below RLC29_MAX_LOAD -- rlc29_mac never runs a carry pass here.
+template <int L, class P>
+__host__ __device__ __forceinline__ F29<P> scan_rlc29_step(const F29<P>& z, const uint32_t* x, const uint32_t* M, const uint32_t* K) {
+    Rlc29<P> t;
+    const uint32_t zero[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    rlc29_init(t, zero);
+    rlc29_mac<9>(t, z.l, M);
+    rlc29_mac<L>(t, x, K);
+    return rlc29_reduce(t);
+}
+// The same row as a map z -> A z + B composed onto the rows before it (A, B Montgomery images, normalised, below 2p; the identity
+// is A = 2^256 mod p, B = 0): A <- A M 2^-261, B <- (B M + x K) 2^-261.  A chunk of rows folds into one map by calling this in scan
+// order; applying that map to the entering state equals walking the rows with scan_rlc29_step.
+template <int L, class P>
+__host__ __device__ __forceinline__ void scan_rlc29_fold(F29<P>& A, F29<P>& B, const uint32_t* x, const uint32_t* M, const uint32_t* K) {
+    Rlc29<P> t;
+    const uint32_t zero[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    rlc29_init(t, zero);
+    rlc29_mac<9>(t, A.l, M);
+    A = rlc29_reduce(t);
+    B = scan_rlc29_step<L>(B, x, M, K);
+}
+
 using Fq29 = F29<Fq29P>;
 using Fr29 = F29<Fr29P>;
 

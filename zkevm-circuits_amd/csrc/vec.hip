@@ -912,6 +912,229 @@ int fr_row_rlc_run(zk_ctx* ctx, const zk_row_rlc* desc, const void* h_k, Fr* d_o
     return ZK_OK;
 }
 
+// ---- running RLC of typed cells: out[i] = m[kind_i] out[i-1] + w[kind_i] cell[i] (ZK_OP_SCAN_RLC, ZK_OP_SCAN_RLC_REV) -------------
+// The RLC ALONG a column (Keccak data_rlc, bytecode value_rlc, the copy circuit's reverse rlc_acc), from the packed cells and a
+// one-byte kind column: the affine scan above with its two n x 32 B operand columns replaced by n x (width + 1) bytes.  Tiling,
+// launches and scratch are scan_affine_run's (SCAN_THREADS x SCAN_PER rows a block; A: block maps, k_affine_b: entering values,
+// C: the walk); what differs is how a thread gets its SCAN_PER rows and what a row costs:
+//   * loads.  A thread's chunk is SCAN_PER = 8 consecutive cells in memory (scan position j is element j, or n - 1 - j under REV,
+//     so a reverse chunk is the same eight cells walked downwards).  Kind bytes and byte cells come in as ONE aligned 8-byte word,
+//     halfword cells as two; the caller aligns to the cell width only, so the chunk straddles two aligned words when the column
+//     starts off an 8-byte boundary: the thread loads the next word too and funnel-shifts.  An aligned word that is not wholly
+//     inside the column -- only its first and last can be -- is put together from its valid bytes alone.  Cells of 4, 8 and 16 bytes
+//     are loaded one by one at their natural alignment (4 and 8: all eight before the first product; 16: where they are used,
+//     which keeps the walk out of scratch memory), 32-byte cells as four 8-byte words.
+//   * the row.  The four (M, K) records of the kinds (SrlRec: plain limbs, M = m 2^261, K = w 2^517 or w 2^261 for 32-byte cells)
+//     travel as a kernel argument and are copied to LDS once a block; a lane picks its record by its row's kind.  The fold is
+//     scan_rlc29_fold, the walk scan_rlc29_step (csrc/ff29.hip.hpp): ONE reduction per row in the walk.
+// z0 enters as the constant map in front of block 0 (A: block 0's map becomes z -> map(z0); C: block 0 starts from z0), so
+// k_affine_b runs unchanged.
+struct SrlRec { uint32_t m[9], k[9]; };
+struct SrlArgs { const uint8_t* cells; const uint8_t* kinds; SrlRec rec[4]; Fr z0; };
+static_assert(SCAN_PER == 8, "a chunk of byte cells is one 8-byte word");
+// the aligned 8-byte word at virtual offset a of `base` (8-byte aligned); valid bytes are [lo, hi), the others read as 0 untouched
+__device__ __forceinline__ uint64_t srl_word(const uint8_t* base, int64_t a, int64_t lo, int64_t hi) {
+    if (a >= lo && a + 8 <= hi) return *reinterpret_cast<const uint64_t*>(base + a);
+    uint64_t w = 0;
+    if (a + 8 <= lo || a >= hi) return w;
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+        if (a + t >= lo && a + t < hi) w |= (uint64_t)base[a + t] << (8 * t);
+    return w;
+}
+// out = the 8 NW bytes from byte offset q (any sign) of the column of len bytes at p (any alignment); bytes outside the column are 0
+template <int NW>
+__device__ __forceinline__ void srl_bytes(const uint8_t* p, int64_t q, int64_t len, uint64_t (&out)[NW]) {
+    const int64_t head = (int64_t)((uintptr_t)p & 7u);
+    const uint8_t* base = p - head;
+    const int64_t v = q + head, a0 = v & ~(int64_t)7, hi = head + len;
+    const uint32_t sh = 8u * (uint32_t)(v & 7);
+    uint64_t w[NW + 1];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = srl_word(base, a0 + 8 * i, head, hi);
+    w[NW] = sh ? srl_word(base, a0 + 8 * NW, head, hi) : 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) out[i] = sh ? (w[i] >> sh | w[i + 1] << (64 - sh)) : w[i];
+}
+template <int W>
+struct SrlChunk {
+    static constexpr int L = W <= 2 ? 1 : W == 4 ? 2 : W == 8 ? 3 : W == 16 ? 5 : 9;
+    static constexpr int XW = W <= 2 ? 2 * W : W == 32 ? 1 : W / 4;    // 32-bit words of a row of raw: the whole chunk packed (W <= 2), one cell
+    uint64_t kinds;                                                     // byte c: the kind byte of chunk cell c, in memory order
+    uint32_t raw[W <= 2 || W >= 16 ? 1 : SCAN_PER][XW];                 // W >= 16: unused, the cells are loaded where they are used
+};
+// the chunk whose first cell in memory is element lo (lo > -8; elements outside [0, n) read as 0 and are never used)
+template <int W>
+__device__ __forceinline__ void srl_load(const SrlArgs& g, int64_t lo, uint64_t n, SrlChunk<W>& ch) {
+    uint64_t kw[1] = {0};
+    if (g.kinds) srl_bytes<1>(g.kinds, lo, (int64_t)n, kw);
+    ch.kinds = kw[0];
+    if constexpr (W == 1) {
+        uint64_t cw[1];
+        srl_bytes<1>(g.cells, lo, (int64_t)n, cw);
+        ch.raw[0][0] = (uint32_t)cw[0]; ch.raw[0][1] = (uint32_t)(cw[0] >> 32);
+    } else if constexpr (W == 2) {
+        uint64_t cw[2];
+        srl_bytes<2>(g.cells, lo * 2, (int64_t)n * 2, cw);
+        ch.raw[0][0] = (uint32_t)cw[0]; ch.raw[0][1] = (uint32_t)(cw[0] >> 32);
+        ch.raw[0][2] = (uint32_t)cw[1]; ch.raw[0][3] = (uint32_t)(cw[1] >> 32);
+    } else if constexpr (W <= 8) {
+#pragma unroll
+        for (int c = 0; c < SCAN_PER; ++c) {
+            const int64_t i = lo + c;
+#pragma unroll
+            for (int q = 0; q < SrlChunk<W>::XW; ++q) ch.raw[c][q] = 0;
+            if (i < 0 || i >= (int64_t)n) continue;
+            if constexpr (W == 4) ch.raw[c][0] = *reinterpret_cast<const uint32_t*>(g.cells + i * 4);
+            else { const uint2 p = *reinterpret_cast<const uint2*>(g.cells + i * 8); ch.raw[c][0] = p.x; ch.raw[c][1] = p.y; }
+        }
+    }
+}
+// the limbs of chunk cell c (element i, inside [0, n))
+template <int W>
+__device__ __forceinline__ void srl_cell(const SrlArgs& g, const SrlChunk<W>& ch, int64_t i, int c, uint32_t (&x)[9]) {
+    Fr cell{{0, 0, 0, 0, 0, 0, 0, 0}};
+    if constexpr (W == 1) cell.l[0] = (ch.raw[0][c >> 2] >> (8 * (c & 3))) & 0xffu;
+    else if constexpr (W == 2) cell.l[0] = (ch.raw[0][c >> 1] >> (16 * (c & 1))) & 0xffffu;
+    else if constexpr (W <= 8) {
+#pragma unroll
+        for (int q = 0; q < SrlChunk<W>::XW; ++q) cell.l[q] = ch.raw[c][q];
+    } else if constexpr (W == 16) {
+        const uint4 p = *reinterpret_cast<const uint4*>(g.cells + i * 16);
+        cell.l[0] = p.x; cell.l[1] = p.y; cell.l[2] = p.z; cell.l[3] = p.w;
+    } else {
+        const uint2* src = reinterpret_cast<const uint2*>(g.cells) + i * 4;          // 8-byte aligned
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const uint2 p = src[q]; cell.l[2 * q] = p.x; cell.l[2 * q + 1] = p.y; }
+    }
+    const Fr29 l = unpack29<Fr29P>(cell);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) x[q] = l.l[q];
+}
+__device__ __forceinline__ void srl_table_to_lds(const SrlArgs& g, SrlRec* tab) {
+    if (threadIdx.x < 4) tab[threadIdx.x] = g.rec[threadIdx.x];
+    __syncthreads();
+}
+__device__ __forceinline__ void srl_record(const SrlRec* tab, uint32_t kind, uint32_t (&M)[9], uint32_t (&K)[9]) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) { M[q] = tab[kind].m[q]; K[q] = tab[kind].k[q]; }
+}
+// composite map of this thread's rows from scan position `start` on (positions at or past n are skipped), like aff_chunk
+template <bool REV, int W>
+__device__ __forceinline__ Aff srl_chunk(const SrlArgs& g, const SrlRec* tab, const SrlChunk<W>& ch, int64_t lo, uint64_t start, uint64_t n) {
+    Fr29 A = unpack29<Fr29P>(Fr::one()), B = unpack29<Fr29P>(Fr::zero());
+#pragma unroll
+    for (int k = 0; k < SCAN_PER; ++k) {
+        if (start + k >= n) break;
+        const int c = REV ? SCAN_PER - 1 - k : k;
+        uint32_t x[9], M[9], K[9];
+        srl_cell<W>(g, ch, lo + c, c, x);
+        srl_record(tab, (uint32_t)(ch.kinds >> (8 * c)) & 3u, M, K);
+        scan_rlc29_fold<SrlChunk<W>::L>(A, B, x, M, K);
+    }
+    return Aff{pack29_lt2p(A), pack29_lt2p(B)};
+}
+template <bool REV, int W>
+__global__ void __launch_bounds__(SCAN_THREADS) k_scan_rlc_a(SrlArgs g, Aff* __restrict__ maps, uint64_t n) {
+    __shared__ Aff sh[SCAN_THREADS];
+    __shared__ SrlRec tab[4];
+    srl_table_to_lds(g, tab);
+    const uint64_t start = (uint64_t)blockIdx.x * (SCAN_THREADS * SCAN_PER) + (uint64_t)threadIdx.x * SCAN_PER;
+    const int64_t lo = REV ? (int64_t)n - SCAN_PER - (int64_t)start : (int64_t)start;
+    Aff v = aff_id();
+    if (start < n) {
+        SrlChunk<W> ch;
+        srl_load<W>(g, lo, n, ch);
+        v = srl_chunk<REV, W>(g, tab, ch, lo, start, n);
+    }
+    Aff total = aff_block_total(v, sh);
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == 0) { total.B = aff_apply(total, g.z0); total.A = Fr::zero(); }       // the constant map z0 in front of everything
+        stg(&maps[blockIdx.x].A, total.A);
+        stg(&maps[blockIdx.x].B, total.B);
+    }
+}
+// entering == nullptr: a single block, z0 enters it
+template <bool REV, int W>
+__global__ void __launch_bounds__(SCAN_THREADS) k_scan_rlc_c(SrlArgs g, Fr* __restrict__ out, const Fr* __restrict__ entering, uint64_t n) {
+    __shared__ Aff sh[SCAN_THREADS];
+    __shared__ SrlRec tab[4];
+    srl_table_to_lds(g, tab);
+    const uint64_t start = (uint64_t)blockIdx.x * (SCAN_THREADS * SCAN_PER) + (uint64_t)threadIdx.x * SCAN_PER;
+    const int64_t lo = REV ? (int64_t)n - SCAN_PER - (int64_t)start : (int64_t)start;
+    SrlChunk<W> ch;
+    Aff v = aff_id();
+    if (start < n) {
+        srl_load<W>(g, lo, n, ch);
+        v = srl_chunk<REV, W>(g, tab, ch, lo, start, n);
+    }
+    Aff total;
+    const Aff ex = aff_block_exclusive_scan(v, sh, &total);
+    if (start >= n) return;
+    Fr29 z = unpack29<Fr29P>(aff_apply(ex, entering && blockIdx.x ? ldg(entering + blockIdx.x) : g.z0));
+#pragma unroll
+    for (int k = 0; k < SCAN_PER; ++k) {
+        if (start + k >= n) break;
+        const int c = REV ? SCAN_PER - 1 - k : k;
+        uint32_t x[9], M[9], K[9];
+        srl_cell<W>(g, ch, lo + c, c, x);
+        srl_record(tab, (uint32_t)(ch.kinds >> (8 * c)) & 3u, M, K);
+        z = scan_rlc29_step<SrlChunk<W>::L>(z, x, M, K);
+        stg(out + (lo + c), pack29_lt2p(z));
+    }
+}
+template <bool REV, int W>
+static void scan_rlc_launch(zk_ctx* ctx, const SrlArgs& g, Aff* maps, Fr* entering, Fr* d_out, uint64_t n, unsigned blocks) {
+    if (blocks > 1) {
+        hipLaunchKernelGGL((k_scan_rlc_a<REV, W>), dim3(blocks), dim3(SCAN_THREADS), 0, ctx->stream, g, maps, n);
+        hipLaunchKernelGGL(k_affine_b, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (const Aff*)maps, entering, (uint32_t)blocks);
+    }
+    hipLaunchKernelGGL((k_scan_rlc_c<REV, W>), dim3(blocks), dim3(SCAN_THREADS), 0, ctx->stream, g, d_out, (const Fr*)entering, n);
+}
+// h_tab: z0, then m_0, w_0 .. m_3, w_3, Montgomery Fr in host memory.  Everything is validated before n is looked at and before
+// the first launch, so a refused call has written nothing.
+static int fr_scan_rlc_run(zk_ctx* ctx, bool rev, const zk_scan_rlc* desc, const void* h_tab, Fr* d_out, uint64_t n) {
+    const uint32_t width = desc->width;
+    if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16 && width != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "scan RLC: cell width %u: must be 1, 2, 4, 8, 16 or 32 bytes", width);
+    const uintptr_t p = (uintptr_t)desc->d_cells, kp = (uintptr_t)desc->d_kinds, o = (uintptr_t)d_out, o_end = o + n * sizeof(Fr);
+    if (!p) return ctx->fail(ZK_ERR_INVALID_ARG, "scan RLC: NULL cells");
+    if (p % (width == 32 ? 8 : width)) return ctx->fail(ZK_ERR_INVALID_ARG, "scan RLC: cells of %u bytes at a misaligned address", width);
+    if (n && p < o_end && o < p + n * width) return ctx->fail(ZK_ERR_INVALID_ARG, "scan RLC: the cells overlap the output");
+    if (n && kp && kp < o_end && o < kp + n) return ctx->fail(ZK_ERR_INVALID_ARG, "scan RLC: the kinds overlap the output");
+    if (!n) return ZK_OK;
+    const uint64_t blocks = (n + SCAN_THREADS * SCAN_PER - 1) / (SCAN_THREADS * SCAN_PER);
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many elements for one scan");
+    static const Fr c261 = [] { Fr c = Fr::one(); for (int i = 0; i < 261 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^261 mod r
+    SrlArgs g;
+    memset(&g, 0, sizeof g);
+    g.cells = (const uint8_t*)desc->d_cells;
+    g.kinds = desc->d_kinds;
+    Fr tab[9];
+    memcpy(tab, h_tab, sizeof tab);
+    g.z0 = tab[0] * Fr::one();                                          // times Montgomery one: the value itself, canonical
+    for (int s = 0; s < 4; ++s) {                                       // plain normalised limbs, canonical, like fr_row_rlc_run's
+        const Fr29 M = unpack29<Fr29P>(tab[1 + 2 * s] * c261), K = unpack29<Fr29P>(tab[2 + 2 * s] * (width == 32 ? c261 : fr_c517()));
+        for (int i = 0; i < 9; ++i) { g.rec[s].m[i] = M.l[i]; g.rec[s].k[i] = K.l[i]; }
+    }
+    Aff* maps = nullptr;
+    Fr* entering = nullptr;
+    if (blocks > 1) {                                                   // SC_POLY2 like scan_affine_run
+        maps = (Aff*)ctx->get_scratch(SC_POLY2, (sizeof(Aff) + sizeof(Fr)) * blocks);
+        if (!maps) return ZK_ERR_OOM;
+        entering = (Fr*)(maps + blocks);
+    }
+    ZkProfScope prof(ctx, "fr_scan_rlc");
+    prof.bytes = n * (width + (kp ? 1ull : 0ull) + sizeof(Fr));
+#define ZK_SRL_CASE(W) case W: rev ? scan_rlc_launch<true, W>(ctx, g, maps, entering, d_out, n, (unsigned)blocks) : scan_rlc_launch<false, W>(ctx, g, maps, entering, d_out, n, (unsigned)blocks); break;
+    switch (width) {
+        ZK_SRL_CASE(1) ZK_SRL_CASE(2) ZK_SRL_CASE(4) ZK_SRL_CASE(8) ZK_SRL_CASE(16)
+        default: ZK_SRL_CASE(32)
+    }
+#undef ZK_SRL_CASE
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+
 // ---- sigma columns from the permutation mapping: out[j][i] = delta^j' * omega^i' for mapping[j][i] = (j', i') ------------------------
 // halo2's permutation::keygen::Assembly::mapping names, for cell i of permutation column j, the next cell (j', i') of its cycle; the
 // sigma polynomial's value there is delta^j' * omega^i'.  Up to SM_BATCH columns per launch in the manner of k_fr_from_uint_batch:
@@ -962,6 +1185,10 @@ int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void*
     if (op == ZK_OP_ROW_RLC) {                                          // d_a, d_b: HOST pointers (column table; constant and weights)
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the row RLC is defined over Fr only");
         return fr_row_rlc_run(ctx, (const zk_row_rlc*)d_a, d_b, (Fr*)d_out, n);
+    }
+    if (op == ZK_OP_SCAN_RLC || op == ZK_OP_SCAN_RLC_REV) {             // d_a, d_b: HOST pointers (cells and kinds; z0 and the (m, w) table)
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the scan RLC is defined over Fr only");
+        return fr_scan_rlc_run(ctx, op == ZK_OP_SCAN_RLC_REV, (const zk_scan_rlc*)d_a, d_b, (Fr*)d_out, n);
     }
     if (n == 0) return ZK_OK;
     if (op == ZK_OP_SCAN_AFFINE || op == ZK_OP_SCAN_AFFINE_REV) {
