@@ -56,6 +56,10 @@ typedef struct zk_row_rlc {
 #define ZK_OP_SCAN_RLC 9
 #define ZK_OP_SCAN_RLC_REV 10
 typedef struct zk_scan_rlc { const void* d_cells; uint32_t width; const uint8_t* d_kinds; } zk_scan_rlc;
+/* the inverse-or-zero of a row RLC of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct, whose first three
+ * members are those of zk_row_rlc; d_num is a device pointer or NULL */
+#define ZK_OP_ROW_INV0 12
+typedef struct zk_row_inv0 { uint32_t count; const void* const* d_cols; const uint8_t* widths; const void* d_num; uint32_t num_width; } zk_row_inv0;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -161,6 +165,27 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * nor the kinds.  ZK_FIELD_FQ, any other width, NULL or misaligned d_cells, a forbidden overlap: ZK_ERR_INVALID_ARG before any
  * launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.  Booked under the zk_prof
  * name "fr_scan_rlc" with n * (width + (d_kinds ? 1 : 0) + 32) algorithmic bytes per call.
+ * ZK_OP_ROW_INV0 (a #define, value 12 -- 11 stays refused, as the tests of the ops above require; Fr only) is the inverse-or-zero
+ * witness of a row RLC, straight from packed typed cells -- IsZeroChip's value_inv, IsEqual's inverse of a difference, halo2's
+ * Assigned::Rational(num, den).evaluate() with a denominator that is linear in typed cells:
+ *   d_out[i] = num[i] * inv0(c + sum_j w_j * cell_j[i])  for i < n,      inv0(0) = 0, inv0(x) = 1/x
+ * As for ZK_OP_ROW_RLC, d_a and d_b are HOST pointers, read before the call returns; the call is asynchronous on the context's
+ * stream.  d_a points to a zk_row_inv0 {count, d_cols, widths, d_num, num_width}, d_b to (count + 1) x 32 B Montgomery Fr: c, then
+ * w_0 .. w_(count-1).  count, d_cols and widths mean exactly what they mean in zk_row_rlc (widths, alignment, nothing outside n *
+ * width bytes is read, several columns may name one buffer); count = 0 gives the constant column num[i] * inv0(c).  value_inv of a
+ * cell is count = 1, w = 1; IsEqual's inverse is w = (1, -1); the inverse of a cell minus a constant k is c = -k.  d_num = NULL:
+ * every numerator is one (num_width is ignored); otherwise a device column of num_width in {1, 2, 4, 8, 16, 32} under the same
+ * alignment and read rules.  Results are canonical; a row whose denominator is 0 modulo r gives 0 whatever its numerator.  One
+ * inversion serves the 1024 consecutive rows [1024 k, 1024 k + 1024) of a wave: a 32-byte cell, denominator or numerator, that is
+ * not canonical gives an undefined VALUE in each of the 1024 rows that share its wave's inversion, touches no memory that would not
+ * be touched otherwise, and gives no error.  The overlap rule is ZK_OP_ROW_RLC's: d_out (n x 32 B) overlaps no narrow column; it may BE a
+ * 32-byte column, denominator or numerator, at the same address, but not overlap one partially.  ZK_FIELD_FQ, any other width (of
+ * a column or of a non-NULL numerator), a NULL or misaligned column, NULL d_cols or widths with count > 0, a forbidden overlap:
+ * ZK_ERR_INVALID_ARG before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then
+ * ZK_OK.  64 columns per launch; a longer table runs as further launches -- the earlier ones are the row RLC into d_out (the sum so
+ * far), only the last one inverts, columns that ARE d_out go to the first -- and then d_num may not be d_out (ZK_ERR_INVALID_ARG).
+ * Every launch is booked under the zk_prof name "fr_row_inv0" with n * (sum of its widths, the sum so far counting as 32, + num_width
+ * on the inverting launch when d_num is given, + 32) algorithmic bytes.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

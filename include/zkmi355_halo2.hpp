@@ -157,6 +157,21 @@ inline void scan_rlc(const Context& c, const void* d_cells, uint32_t cell_bytes,
     const zk_scan_rlc desc{d_cells, cell_bytes, d_kinds};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, reverse ? ZK_OP_SCAN_RLC_REV : ZK_OP_SCAN_RLC, &desc, host.data(), d_out, n));
 }
+// d_out[i] = num[i] * inv0(constant + sum_j weights[j] * cell_j[i]) for i < n, inv0(0) = 0, across typed columns on the device
+// (zk_field_vec_op with ZK_OP_ROW_INV0 and a zk_row_inv0; asynchronous on the context's stream) -- halo2's
+// Assigned::Rational(num, den).evaluate() with a denominator that is linear in typed cells, the batch_invert_assigned of such a
+// column.  d_cols, cell_bytes, weights and constant as for row_rlc: IsZeroChip's value_inv is one column with weight one, IsEqual's
+// inverse of a difference the weights (1, -1), the inverse of a cell minus a constant k is constant = -k.  d_num: nullptr (every
+// numerator is one) or n cells of num_bytes bytes (1, 2, 4, 8, 16 packed; 32: Montgomery Fr).  d_out (n x 32 B) may be one of the
+// 32-byte columns or the 32-byte numerator itself and overlaps no other column.
+inline void row_inv0(const Context& c, const std::vector<const void*>& d_cols, const std::vector<uint8_t>& cell_bytes, const std::vector<Fr>& weights, size_t n, void* d_out,
+                     const Fr& constant = Fr{}, const void* d_num = nullptr, uint32_t num_bytes = 32) {
+    if (cell_bytes.size() != d_cols.size() || weights.size() != d_cols.size()) throw Error(ZK_ERR_INVALID_ARG, "row_inv0: one cell width and one weight per column");
+    std::vector<Fr> host(1, constant);                                  // the constant, then the weights: host memory, read by the call
+    host.insert(host.end(), weights.begin(), weights.end());
+    const zk_row_inv0 desc{(uint32_t)d_cols.size(), d_cols.data(), cell_bytes.data(), d_num, num_bytes};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_ROW_INV0, &desc, host.data(), d_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -68,6 +68,20 @@ pub struct zk_scan_rlc {
     pub width: u32,
     pub d_kinds: *const u8,
 }
+/// `zk_field_vec_op` op: `d_out[i] = num[i] * inv0(c + sum_j w_j * cell_j[i])` across typed columns, `inv0(0) = 0` -- the
+/// `Assigned::Rational(num, den)` cells that `batch_invert_assigned` would invert on the host.  For this op `d_a` is a HOST pointer
+/// to a `zk_row_inv0` and `d_b` a HOST pointer to `(count + 1) x 32 B` Montgomery Fr (`c`, then the weights).
+pub const ZK_OP_ROW_INV0: c_int = 12;
+/// `zk_row_inv0`: `count`, `d_cols` and `widths` as in `zk_row_rlc`; `d_num` is null (every numerator is one) or a device pointer to
+/// `n` cells of `num_width` bytes (1, 2, 4, 8, 16: packed little-endian unsigned; 32: Montgomery Fr).
+#[repr(C)]
+pub struct zk_row_inv0 {
+    pub count: u32,
+    pub d_cols: *const *const c_void,
+    pub widths: *const u8,
+    pub d_num: *const c_void,
+    pub num_width: u32,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

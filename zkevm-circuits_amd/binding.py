@@ -25,6 +25,7 @@ OP_ADD, OP_SUB, OP_MUL = 0, 1, 2
 OP_SCAN_AFFINE, OP_SCAN_AFFINE_REV = 3, 4            # out[i] = a[i] * out[i -+ 1] + b[i] along the column, Fr only
 OP_ROW_RLC = 8                                        # out[i] = c + sum_j w_j * cell_j[i] across typed columns, Fr only (ZK_OP_ROW_RLC)
 OP_SCAN_RLC, OP_SCAN_RLC_REV = 9, 10                 # out[i] = m[kind_i] * out[i -+ 1] + w[kind_i] * cell[i] along a typed column, Fr only
+OP_ROW_INV0 = 12                                      # out[i] = num[i] * inv0(c + sum_j w_j * cell_j[i]) across typed columns, Fr only (ZK_OP_ROW_INV0)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -83,6 +84,12 @@ class _RowRlc(ctypes.Structure):
 class _ScanRlc(ctypes.Structure):
     """zk_scan_rlc: the cells and kinds of ZK_OP_SCAN_RLC / ZK_OP_SCAN_RLC_REV (host memory; both pointers are device pointers)"""
     _fields_ = [("d_cells", ctypes.c_void_p), ("width", ctypes.c_uint32), ("d_kinds", ctypes.c_void_p)]
+
+
+class _RowInv0(ctypes.Structure):
+    """zk_row_inv0: the column table and the numerator of ZK_OP_ROW_INV0 (host memory; d_num is a device pointer or NULL)"""
+    _fields_ = [("count", ctypes.c_uint32), ("d_cols", ctypes.POINTER(ctypes.c_void_p)), ("widths", ctypes.POINTER(ctypes.c_uint8)),
+                ("d_num", ctypes.c_void_p), ("num_width", ctypes.c_uint32)]
 
 
 def _host_ptr(a: np.ndarray):
@@ -724,6 +731,27 @@ class Context:
         hk[1:] = np.asarray(table, dtype=np.uint64).reshape(8, 4)
         desc = _ScanRlc(ptr_of(cells), width, None if kinds is None else ptr_of(kinds))
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_SCAN_RLC_REV if reverse else OP_SCAN_RLC, ctypes.byref(desc), _host_ptr(hk), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
+    def row_inv0(self, cols, widths, weights, n, out, constant=None, num=None, num_width=32):
+        """out[i] = num[i] * inv0(constant + sum_j weights[j] * cell_j[i]) for i < n, inv0(0) = 0 (zk_field_vec_op with ZK_OP_ROW_INV0):
+        IsZeroChip's value_inv (one column, weight one), IsEqual's inverse of a difference (weights 1, -1), a rational cell (num).
+        cols, widths, weights, constant: as for row_rlc.  num: None (every numerator is one) or a DeviceBuffer / device pointer of n
+        cells of num_width bytes (1, 2, 4, 8, 16 packed, 32 Montgomery Fr).  A row whose denominator is zero gives zero.  out
+        (DeviceBuffer or pointer, n x 32 B) may be one of the 32-byte columns or the 32-byte numerator itself and must not overlap
+        any other column.  One launch per 64 columns; only the last one inverts."""
+        ptr_of = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        cnt = len(cols)
+        assert len(widths) == cnt
+        hk = np.zeros((cnt + 1, 4), dtype=np.uint64)
+        if constant is not None:
+            hk[0] = np.asarray(constant, dtype=np.uint64).reshape(4)
+        if cnt:
+            hk[1:] = np.asarray(weights, dtype=np.uint64).reshape(cnt, 4)
+        pp = (ctypes.c_void_p * max(cnt, 1))(*[ptr_of(p) for p in cols])
+        wd = (ctypes.c_uint8 * max(cnt, 1))(*widths)
+        desc = _RowInv0(cnt, ctypes.cast(pp, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(wd, ctypes.POINTER(ctypes.c_uint8)),
+                        None if num is None else ptr_of(num), 0 if num is None else num_width)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_ROW_INV0, ctypes.byref(desc), _host_ptr(hk), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

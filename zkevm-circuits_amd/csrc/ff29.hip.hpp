@@ -778,7 +778,73 @@ __host__ __device__ __forceinline__ void scan_rlc29_fold(F29<P>& A, F29<P>& B, c
     B = scan_rlc29_step<L>(B, x, M, K);
 }
 
+// ---- inverse-or-zero of a row sum: out = num * inv0(D), inv0(0) = 0 (the per-lane steps of k_fr_row_inv0, csrc/vec.hip, ZK_OP_ROW_INV0) --
+// Forms.  mul29 is Montgomery by R' = 2^261, the columns are R = 2^256.  Write [x]_e for the residue x 2^e; mul29([x]_e, [y]_f) =
+// [x y]_(e + f - 261), so a factor in R' form ([y]_261) leaves the form of the other factor as it is.
+//   * the denominator: the host hands the inverting launch its constants with a further 2^5 (w 2^522 narrow, w 2^266 for a 32-byte
+//     column, c 2^522), so rlc29_reduce leaves [D]_261 directly -- k_batch_invert's five doublings per element are not paid;
+//   * prefix products, the products over the wave and the back-substitution multiply R' forms only; the ONE inverse of a wave is put
+//     into the form e that the numerator wants by the constant of inv29_rp (2^(e + 522) instead of 2^783), once per wave on lane
+//     63, and every quotient [1/D]_e = iv * pre below inherits it:
+//       no numerator            e = 256: the quotient IS the result, no product by one_r          (constant 2^778)
+//       32-byte numerator [N]_256  e = 261: mul29([1/D]_261, [N]_256) = [N/D]_256, in one_r's place  (constant 2^783)
+//       narrow numerator N = [N]_0  e = 517: mul29([1/D]_517, N) = [N/D]_256                         (constant 2^1039)
+// Bounds.  Every mul29 operand here is normalised (limbs below 2^29) and below 2p: a result of rlc29_reduce / canon29_lt2p / mul29, a
+// canonical constant, a canonical 32-byte numerator (below p) or a narrow integer (below 2^128); every product is below 4 p^2 <
+// 2^261 p, as mul29 assumes, and its result is normalised and below 2p again.
+// Zero.  rlc29_reduce is only below 2p: a denominator that cancels modulo p may arrive as the integer p, so the test is made on the
+// canonical limbs (canon29_lt2p) -- an untested p would enter the wave's product as a zero factor.  `live` has bit s set for a row
+// that takes part: inside n and non-zero.  The others enter the products as one and come out as 0.
+enum { INV0_NUM_ONE = 0, INV0_NUM_UINT = 1, INV0_NUM_FR = 2 };
+// the reduced sum as canonical limbs ([D]_261 with the inverting launch's constants); false: D = 0 mod p
+template <class P>
+__host__ __device__ __forceinline__ bool inv0_29_den(const Rlc29<P>& t, F29<P>& d) {
+    d = canon29_lt2p(rlc29_reduce(t));
+    uint32_t any = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) any |= d.l[i];
+    return any != 0;
+}
+// pre[k] = the product of the live d[j], j < k, starting from one_rp = [1]_261; returns the product of all of them
+template <int K, class P>
+__host__ __device__ __forceinline__ F29<P> inv0_29_prefix(const F29<P> (&d)[K], uint32_t live, const F29<P>& one_rp, F29<P> (&pre)[K]) {
+    F29<P> acc = one_rp;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        pre[k] = acc;
+        if (live >> k & 1u) acc = mul29(acc, d[k]);
+    }
+    return acc;
+}
+// iv = [1 / (the product inv0_29_prefix returned)]_e  ->  q[k] = [1 / D_k]_e for every live k (the others are left alone)
+template <int K, class P>
+__host__ __device__ __forceinline__ void inv0_29_back(F29<P> iv, const F29<P> (&d)[K], const F29<P> (&pre)[K], uint32_t live, F29<P> (&q)[K]) {
+#pragma unroll
+    for (int k = K; k-- > 0;) {
+        if (!(live >> k & 1u)) continue;
+        q[k] = mul29(iv, pre[k]);
+        if (k) iv = mul29(iv, d[k]);
+    }
+}
+// the row's result from its quotient (in the form of its NUM, above) and its numerator: canonical, R = 2^256 form
+template <int NUM, class P>
+__host__ __device__ __forceinline__ Fp<typename P::P32> inv0_29_out(const F29<P>& q, const F29<P>& num) {
+    if constexpr (NUM == INV0_NUM_ONE) return pack29_lt2p(q);
+    else return pack29_lt2p(mul29(q, num));
+}
+
 using Fq29 = F29<Fq29P>;
 using Fr29 = F29<Fr29P>;
+
+// 1 / b for b in R' = 2^261 form, times c 2^-522: the residue as a plain integer X = B 2^261 has X^-1 = B^-1 2^-261 (binary extended
+// Euclid, ff.hip.hpp), and one product by the plain constant c brings it to B^-1 c 2^-522 -- c783 = 2^783 gives R' form again.  A
+// lone lane runs this while its wave waits: the Fermat ladder (381 products, ~95 000 instructions) took 250 us there, this takes a
+// quarter of the instructions.
+__host__ __device__ inline Fr29 inv29_rp(const Fr29& b, const Fr29& c783) {
+    const Fr x = pack29_lt2p(b);
+    Fr y;
+    inv_xgcd<FrP>(y.l, x.l);
+    return mul29(unpack29<Fr29P>(y), c783);
+}
 
 }  // namespace zk

@@ -4,6 +4,7 @@
 //   prefix product / prefix sum         permutation & lookup grand product (K7, K8)
 //   affine scan z = a z + b             running RLCs with resets (challenge-phase witness columns)
 //   row RLC z = c + sum w_j cell_j      rlc::value / RwRow::rlc across typed columns, one reduction per row
+//   row inverse z = num * inv0(row RLC) IsZeroChip::value_inv, Assigned::Rational(num, den).evaluate() over typed columns (K12)
 //   eval_polynomial, kate_division      halo2_proofs::arithmetic           (K9, K10, K11)
 // All kernels read/write 32-byte elements as two 16-byte transactions per lane, consecutive
 // lanes on consecutive elements (fully coalesced), grid-stride where a fixed grid is needed.
@@ -68,15 +69,7 @@ __device__ __forceinline__ Fr29 shfl29(const Fr29& v, int src) {
     for (int k = 0; k < 9; ++k) r.l[k] = __shfl(v.l[k], src);
     return r;
 }
-// 1 / b for b in R' = 2^261 form, result in R' form: the residue as a plain integer X = B 2^261 has X^-1 = B^-1 2^-261 (binary
-// extended Euclid, ff.hip.hpp), and one product by c783 = 2^783 brings it to B^-1 2^261.  A lone lane runs this while its wave
-// waits: the Fermat ladder (381 products, ~95 000 instructions) took 250 us there, this takes a quarter of the instructions.
-__device__ inline Fr29 inv29_rp(const Fr29& b, const Fr29& c783) {
-    const Fr x = pack29_lt2p(b);
-    Fr y;
-    inv_xgcd<FrP>(y.l, x.l);
-    return mul29(unpack29<Fr29P>(y), c783);
-}
+// inv29_rp (csrc/ff29.hip.hpp): 1 / b for b in R' form, result in R' form with c783 = 2^783
 __global__ void __launch_bounds__(256) k_batch_invert(Fr* __restrict__ a, uint64_t n, uint64_t nt, Fr c783_plain) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;                       // nt is a multiple of 64: whole waves leave
@@ -812,101 +805,296 @@ __device__ __forceinline__ uint32_t row_rlc_terms(const RrBatch& b, uint32_t j, 
         return g;
     }
 }
+// the sums of a wave's rows over the whole table, unreduced: acc[s] is the row wave * FU_CELLS * 64 + s * 64 + lane.  A macro, not a
+// function: with the accumulators handed on by reference the compiler spills them (k_fr_row_rlc: 414 registers and no scratch as
+// written here, 512 and 196 B of scratch per lane through a function).
+#define ZK_ROW_RLC_SUMS(b, n, wave, acc)                                                                                   \
+    _Pragma("unroll") for (int s = 0; s < FU_CELLS; ++s) rlc29_init(acc[s], b.k0);                                         \
+    for (uint32_t j = 0; j < b.count;) {                                /* wave-uniform, and so is the width */            \
+        switch (b.col[j].width) {                                                                                          \
+            case 1: j += row_rlc_terms<1>(b, j, n, wave, acc); break;                                                      \
+            case 2: j += row_rlc_terms<2>(b, j, n, wave, acc); break;                                                      \
+            case 4: j += row_rlc_terms<4>(b, j, n, wave, acc); break;                                                      \
+            case 8: j += row_rlc_terms<8>(b, j, n, wave, acc); break;                                                      \
+            case 16: j += row_rlc_terms<16>(b, j, n, wave, acc); break;                                                    \
+            default: j += row_rlc_terms<32>(b, j, n, wave, acc); break;                                                    \
+        }                                                                                                                  \
+    }
 __global__ void __launch_bounds__(256) k_fr_row_rlc(RrBatch b, uint64_t n, Fr* out) {
     const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (wave * (FU_CELLS * 64) >= n) return;                            // whole waves only: the shuffles stay inside a wave
     const uint32_t lane = threadIdx.x & 63u;
     Rlc29<Fr29P> acc[FU_CELLS];
-#pragma unroll
-    for (int s = 0; s < FU_CELLS; ++s) rlc29_init(acc[s], b.k0);
-    for (uint32_t j = 0; j < b.count;) {                                // wave-uniform, and so is the width
-        switch (b.col[j].width) {
-            case 1: j += row_rlc_terms<1>(b, j, n, wave, acc); break;
-            case 2: j += row_rlc_terms<2>(b, j, n, wave, acc); break;
-            case 4: j += row_rlc_terms<4>(b, j, n, wave, acc); break;
-            case 8: j += row_rlc_terms<8>(b, j, n, wave, acc); break;
-            case 16: j += row_rlc_terms<16>(b, j, n, wave, acc); break;
-            default: j += row_rlc_terms<32>(b, j, n, wave, acc); break;
-        }
-    }
+    ZK_ROW_RLC_SUMS(b, n, wave, acc)
 #pragma unroll
     for (int s = 0; s < FU_CELLS; ++s) {
         const uint64_t row = wave * (FU_CELLS * 64) + (uint64_t)s * 64 + lane;
         if (row < n) stg(out + row, pack29_lt2p(rlc29_reduce(acc[s])));
     }
 }
-// desc->count columns, RR_BATCH per launch; everything is validated before the first launch, so a refused call has written nothing.
-// h_k: the constant and the count weights, Montgomery Fr in host memory.
-int fr_row_rlc_run(zk_ctx* ctx, const zk_row_rlc* desc, const void* h_k, Fr* d_out, uint64_t n) {
-    const size_t count = desc->count;
-    if (count && (!desc->d_cols || !desc->widths)) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC: NULL column or width table");
-    const uintptr_t o = (uintptr_t)d_out, o_end = o + n * sizeof(Fr);
-    for (size_t c = 0; c < count; ++c) {
-        const uint32_t width = desc->widths[c];
-        const uintptr_t p = (uintptr_t)desc->d_cols[c], p_end = p + n * width;
-        if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16 && width != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu: cell width %u: must be 1, 2, 4, 8, 16 or 32 bytes", c, width);
-        if (!p) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu: NULL pointer", c);
-        if (p % (width == 32 ? 8 : width)) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu: cells of %u bytes at a misaligned address", c, width);
-        // a lane reads its rows of every column before it writes them: the output may BE a 32-byte column (taken by the first
-        // launch, below), and nothing else
-        if (n && !(width == 32 && p == o) && p < o_end && o < p_end) return ctx->fail(ZK_ERR_INVALID_ARG, "row RLC column %zu overlaps the output", c);
+// ---- inverse-or-zero of a row RLC: out[i] = num[i] * inv0(c + sum_j w_j * cell_j[i]) (ZK_OP_ROW_INV0) ----------------------------------
+// IsZeroChip's value_inv, IsEqual's inverse of a difference, halo2's Assigned::Rational(num, den).evaluate() with a denominator that is
+// linear in typed cells, in ONE launch that writes only d_out.  A wave takes RI_TILES consecutive tiles of FU_CELLS * 64 rows, each in
+// the wave, sweep and store shape of k_fr_row_rlc and by its column walk (ZK_ROW_RLC_SUMS over row_rlc_terms); a tile's FU_CELLS Rlc29
+// records are dead once its denominators are reduced, and the lane's RI_ROWS = RI_TILES * FU_CELLS denominators then go the way of
+// k_batch_invert's BI_K values: zeros skipped, prefix products in the lane, products over the wave from both ends by shuffles, ONE
+// inv29_rp per wave on lane 63, back-substitution -- one inversion per RI_TILES * 256 rows.  The arithmetic of a lane, the forms and
+// the operand bounds are inv0_29_* in csrc/ff29.hip.hpp (a host harness runs exactly that code).  Rows at or past n and zero rows
+// enter the products as one (`live`); a wave whose rows are all zero inverts the constant one; whole waves past n have left before
+// any shuffle, and a tile past n is skipped by the whole wave.  A lane reads all its rows of every column, the numerator included,
+// before its first store, and the shuffles move values between lanes, never rows: d_out may be a 32-byte column of this launch,
+// denominator or numerator.
+// Rows per inversion.  inv_xgcd runs on one lane while its wave waits, and at one wave per SIMD (the column walk needs 414
+// registers) nothing else runs on that SIMD meanwhile: the kernel's time is (waves / wave slots) rounds of one inversion each, about
+// 130 us a round on an MI355X, so the rows of a wave are what counts.  Measured at 2^20 rows (profiles/r23_row_inv0.md): 256 rows
+// 0.59 ms, 512 rows 0.34 ms, 1024 rows 0.20 ms (one round on 1024 wave slots; the composition of three calls it replaces: 0.195 ms).
+// RI_TILES = 4 it is.  A tile's denominators wait in LDS (144 KB of the CU's 160 KB for the one resident workgroup), not in registers,
+// because the tiles have to be a loop; see there.  ZK_ROW_INV0_TILES = 1, 2 build the other forms (A/B builds: make VARIANT=...
+// EXTRA=-DZK_ROW_INV0_TILES=...).
+// NUM: how a numerator is read -- INV0_NUM_ONE none, INV0_NUM_UINT packed cells of num_width bytes (loaded like a column of the
+// table), INV0_NUM_FR canonical Montgomery elements; cinv is the plain constant of inv29_rp that puts the wave's inverse into the form
+// that NUM wants (fr_row_inv0_run), one_rp the integer 2^261 mod r.
+#ifndef ZK_ROW_INV0_TILES
+#define ZK_ROW_INV0_TILES 4
+#endif
+constexpr int RI_TILES = ZK_ROW_INV0_TILES, RI_ROWS = RI_TILES * FU_CELLS;
+static_assert(RI_TILES == 1 || RI_TILES == 2 || RI_TILES == 4, "256, 512 or 1024 rows per inversion");
+struct RiArgs { const void* num; uint32_t num_width; uint32_t one_rp[9]; uint32_t cinv[9]; };
+static_assert(sizeof(RrBatch) + sizeof(RiArgs) < 4096 - 64, "kernel argument size");
+template <int W>
+__device__ __forceinline__ void row_inv0_num(const void* num, uint64_t n, uint64_t tile, Fr29* x29) {
+    constexpr uint32_t load_bytes = W < 4 ? W * FU_CELLS : W;
+    const uint8_t* src = (const uint8_t*)num;
+    const uint32_t head = (uint32_t)((uintptr_t)src % load_bytes) / W;
+    uint32_t x[FU_CELLS][4];
+    fu_load_wave<W>(src - (size_t)head * W, head, n, tile, head, x);
+#pragma unroll
+    for (int s = 0; s < FU_CELLS; ++s) x29[s] = unpack29<Fr29P>(Fr{{x[s][0], x[s][1], x[s][2], x[s][3], 0, 0, 0, 0}});
+}
+template <int NUM>
+__global__ void __launch_bounds__(256) k_fr_row_inv0(RrBatch b, RiArgs a, uint64_t n, Fr* out) {
+    const uint64_t tile0 = (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * RI_TILES;     // this wave's first tile of 256 rows
+    if (tile0 * (FU_CELLS * 64) >= n) return;                           // whole waves only: the shuffles stay inside a wave
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t row0 = tile0 * (FU_CELLS * 64) + lane;               // this lane's rows: row0 + 64 k, k < RI_ROWS
+    Fr29 d[RI_ROWS], num[RI_ROWS];
+    uint32_t live = 0;
+    if constexpr (RI_TILES == 1) {
+        Rlc29<Fr29P> acc[FU_CELLS];
+        ZK_ROW_RLC_SUMS(b, n, tile0, acc)
+#pragma unroll
+        for (int s = 0; s < FU_CELLS; ++s)
+            if (inv0_29_den(acc[s], d[s]) && row0 + 64u * s < n) live |= 1u << s;
+    } else {
+        // ONE copy of the column walk in a loop that is not unrolled (two copies in line spill 3 KB per lane), so a tile's
+        // denominators cannot go to registers named by the loop variable: they are parked in LDS, limb k of row r of thread T at
+        // [r][k][T] (no bank conflicts, no barrier: a lane reads back what it wrote), and fetched once all tiles are done
+        __shared__ uint32_t park[RI_ROWS][9][256];
+#pragma unroll 1
+        for (int t = 0; t < RI_TILES; ++t) {
+            if ((tile0 + t) * (FU_CELLS * 64) >= n) break;              // wave-uniform
+            Rlc29<Fr29P> acc[FU_CELLS];
+            ZK_ROW_RLC_SUMS(b, n, (tile0 + t), acc)
+#pragma unroll
+            for (int s = 0; s < FU_CELLS; ++s) {
+                Fr29 ds;
+                if (inv0_29_den(acc[s], ds) && row0 + 64u * (t * FU_CELLS + s) < n) live |= 1u << (t * FU_CELLS + s);
+#pragma unroll
+                for (int k = 0; k < 9; ++k) park[t * FU_CELLS + s][k][threadIdx.x] = ds.l[k];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RI_ROWS; ++r)                               // rows of a skipped tile are not live: whatever is there is not used
+#pragma unroll
+            for (int k = 0; k < 9; ++k) d[r].l[k] = park[r][k][threadIdx.x];
     }
-    if (!n) return ZK_OK;
-    const uint64_t per_block = (uint64_t)FU_CELLS * 256, blocks = (n + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many rows for one launch");
-    static const Fr c261 = [] { Fr c = Fr::one(); for (int i = 0; i < 261 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^261 mod r
-    const uint8_t* hk = (const uint8_t*)h_k;
-    auto limbs_of = [](uint32_t* k, const Fr& mont, const Fr& by) {     // plain normalised limbs of (value of mont) * by: canonical, below 2^29 each
-        const Fr29 l = unpack29<Fr29P>(mont * by);
-        for (int i = 0; i < 9; ++i) k[i] = l.l[i];
-    };
-    // The terms in launch order.  "A lane reads its rows before it writes them" holds inside ONE launch only: the first launch
-    // overwrites d_out, so every column that IS d_out must be read by it.  All of them (there may be several) become one term with
-    // the sum of their constants, at the head of the list; the others follow in table order.
-    struct Term { RrColumn col; uint32_t booked; };
-    std::vector<Term> terms;
+    if constexpr (NUM == INV0_NUM_FR) {
+        const uint2* src = (const uint2*)a.num;                         // 8-byte aligned
+        uint2 v[RI_ROWS][4];
+#pragma unroll
+        for (int k = 0; k < RI_ROWS; ++k)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[k][q] = row0 + 64u * k < n ? src[(row0 + 64u * k) * 4 + q] : make_uint2(0, 0);
+#pragma unroll
+        for (int k = 0; k < RI_ROWS; ++k) num[k] = unpack29<Fr29P>(Fr{{v[k][0].x, v[k][0].y, v[k][1].x, v[k][1].y, v[k][2].x, v[k][2].y, v[k][3].x, v[k][3].y}});
+    } else if constexpr (NUM == INV0_NUM_UINT) {
+#define ZK_ROW_INV0_NUM(t)                                                                                                 \
+    if ((tile0 + t) * (FU_CELLS * 64) < n) {                            /* wave-uniform, and so is the width */            \
+        switch (a.num_width) {                                                                                             \
+            case 1: row_inv0_num<1>(a.num, n, tile0 + t, num + t * FU_CELLS); break;                                       \
+            case 2: row_inv0_num<2>(a.num, n, tile0 + t, num + t * FU_CELLS); break;                                       \
+            case 4: row_inv0_num<4>(a.num, n, tile0 + t, num + t * FU_CELLS); break;                                       \
+            case 8: row_inv0_num<8>(a.num, n, tile0 + t, num + t * FU_CELLS); break;                                       \
+            default: row_inv0_num<16>(a.num, n, tile0 + t, num + t * FU_CELLS); break;                                     \
+        }                                                                                                                  \
+    }
+        ZK_ROW_INV0_NUM(0)
+        if constexpr (RI_TILES > 1) { ZK_ROW_INV0_NUM(1) }
+        if constexpr (RI_TILES > 2) { ZK_ROW_INV0_NUM(2) ZK_ROW_INV0_NUM(3) }
+#undef ZK_ROW_INV0_NUM
+    }
+    Fr29 one_rp, cinv, pre[RI_ROWS];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { one_rp.l[k] = a.one_rp[k]; cinv.l[k] = a.cinv[k]; }
+    const Fr29 mine = inv0_29_prefix(d, live, one_rp, pre);
+    // inclusive products over the lanes from both ends
+    Fr29 up = mine, down = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const Fr29 u = shfl_up29(up, off), dn = shfl_down29(down, off);
+        if (lane >= (uint32_t)off) up = mul29(up, u);
+        if (lane + off < 64u) down = mul29(down, dn);
+    }
+    // one inversion per wave: of the product of all its lanes, into the form the numerator wants
+    Fr29 inv_total = one_rp;
+    if (lane == 63u) inv_total = inv29_rp(up, cinv);
+    inv_total = shfl29(inv_total, 63);
+    // 1 / (this lane's product) = 1 / total x (product of the lanes below) x (product of the lanes above)
+    const Fr29 below = shfl_up29(up, 1), above = shfl_down29(down, 1);
+    Fr29 iv = inv_total;
+    if (lane > 0u) iv = mul29(iv, below);
+    if (lane < 63u) iv = mul29(iv, above);
+    Fr29 q[RI_ROWS];
+    inv0_29_back(iv, d, pre, live, q);
+#pragma unroll
+    for (int k = 0; k < RI_ROWS; ++k) {
+        if (row0 + 64u * k >= n) continue;
+        stg(out + row0 + 64u * k, live >> k & 1u ? inv0_29_out<NUM>(q[k], num[k]) : Fr::zero());
+    }
+}
+
+// ---- the host side of both row ops --------------------------------------------------------------------------------------------------
+// One typed column (of the table, or the numerator of ZK_OP_ROW_INV0) against the op's output: width, pointer, alignment, and the
+// overlap rule -- a lane reads its rows of every column before it writes them: the output may BE a 32-byte column, and nothing else.
+static int rr_check_column(zk_ctx* ctx, const char* op, const char* what, size_t c, const void* col, uint32_t width, const Fr* d_out, uint64_t n) {
+    const uintptr_t o = (uintptr_t)d_out, o_end = o + n * sizeof(Fr), p = (uintptr_t)col, p_end = p + n * width;
+    if (width != 1 && width != 2 && width != 4 && width != 8 && width != 16 && width != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "%s %s %zu: cell width %u: must be 1, 2, 4, 8, 16 or 32 bytes", op, what, c, width);
+    if (!p) return ctx->fail(ZK_ERR_INVALID_ARG, "%s %s %zu: NULL pointer", op, what, c);
+    if (p % (width == 32 ? 8 : width)) return ctx->fail(ZK_ERR_INVALID_ARG, "%s %s %zu: cells of %u bytes at a misaligned address", op, what, c, width);
+    if (n && !(width == 32 && p == o) && p < o_end && o < p_end) return ctx->fail(ZK_ERR_INVALID_ARG, "%s %s %zu overlaps the output", op, what, c);
+    return ZK_OK;
+}
+// the column table of a row op: everything is validated before the first launch, so a refused call has written nothing
+static int rr_validate(zk_ctx* ctx, const char* op, size_t count, const void* const* d_cols, const uint8_t* widths, const Fr* d_out, uint64_t n) {
+    if (count && (!d_cols || !widths)) return ctx->fail(ZK_ERR_INVALID_ARG, "%s: NULL column or width table", op);
+    for (size_t c = 0; c < count; ++c)
+        if (int e = rr_check_column(ctx, op, "column", c, d_cols[c], widths[c], d_out, n)) return e;
+    return ZK_OK;
+}
+static Fr fr_pow2(int e) {                                              // the integer 2^e mod r, e >= 256 (Fr::one() holds 2^256)
+    Fr c = Fr::one();
+    for (int i = 256; i < e; ++i) c = dbl(c);
+    return c;
+}
+static void rr_limbs(uint32_t* k, const Fr& mont, const Fr& by) {       // plain normalised limbs of (value of mont) * by: canonical, below 2^29 each
+    const Fr29 l = unpack29<Fr29P>(mont * by);
+    for (int i = 0; i < 9; ++i) k[i] = l.l[i];
+}
+// The terms in launch order.  "A lane reads its rows before it writes them" holds inside ONE launch only: the first launch
+// overwrites d_out, so every column that IS d_out must be read by it.  All of them (there may be several) become one term with
+// the sum of their weights, at the head of the list; the others follow in table order.
+struct RrTerm { const void* src; uint32_t width; Fr w; uint32_t booked; };
+static std::vector<RrTerm> rr_terms(size_t count, const void* const* d_cols, const uint8_t* widths, const uint8_t* hk, const Fr* d_out) {
+    std::vector<RrTerm> terms;
     terms.reserve(count + 1);
-    Fr alias_k = Fr::zero();
+    Fr alias_w = Fr::zero();
     uint32_t alias_bytes = 0;
     for (size_t c = 0; c < count; ++c) {
         Fr w;
         memcpy(&w, hk + (1 + c) * sizeof(Fr), sizeof w);
-        const uint32_t width = desc->widths[c];
-        if (width == 32 && (uintptr_t)desc->d_cols[c] == o) { alias_k = alias_k + w * c261; alias_bytes += 32; continue; }   // products are canonical: the sum is
-        Term t{{desc->d_cols[c], width, {}}, width};
-        limbs_of(t.col.k, w, width == 32 ? c261 : fr_c517());
-        terms.push_back(t);
+        if (widths[c] == 32 && d_cols[c] == (const void*)d_out) { alias_w = alias_w + w; alias_bytes += 32; continue; }
+        terms.push_back({d_cols[c], widths[c], w, widths[c]});
     }
-    if (alias_bytes) {
-        Term t{{d_out, 32, {}}, alias_bytes};                           // booked as the table states it: 32 B per aliased column
-        limbs_of(t.col.k, alias_k, Fr::one());                          // times Montgomery one: the value itself
-        terms.insert(terms.begin(), t);
+    if (alias_bytes) terms.insert(terms.begin(), {d_out, 32, alias_w, alias_bytes});   // booked as the table states it: 32 B per aliased column
+    return terms;
+}
+// The next launch's table: the constant (first launch) or the sum so far as a 32-byte column of weight one (k0 stays 0), then the
+// terms from c0 on, RR_BATCH in all.  K = w 2^(517 + up) for a narrow column and the constant, w 2^(261 + up) for a 32-byte one: up = 0
+// leaves the Montgomery image of the sum, up = 5 its R' = 2^261 form (the inverting launch).  Returns the launch's booked widths.
+static uint64_t rr_fill(RrBatch& b, const std::vector<RrTerm>& terms, size_t& c0, const uint8_t* hk, const Fr* d_out, bool up) {
+    static const Fr by[2][2] = {{fr_pow2(517), fr_pow2(261)}, {fr_pow2(522), fr_pow2(266)}};      // [up][32-byte]
+    memset(&b, 0, sizeof b);
+    uint64_t width_sum = 0;
+    uint32_t cnt = 0;
+    if (c0 == 0) {
+        Fr c;
+        memcpy(&c, hk, sizeof c);
+        rr_limbs(b.k0, c, by[up][0]);
+    } else {
+        b.col[cnt] = {d_out, 32, {}};
+        rr_limbs(b.col[cnt].k, Fr::one(), by[up][1]);
+        width_sum += 32;
+        ++cnt;
     }
+    for (; cnt < RR_BATCH && c0 < terms.size(); ++cnt, ++c0) {
+        b.col[cnt] = {terms[c0].src, terms[c0].width, {}};
+        rr_limbs(b.col[cnt].k, terms[c0].w, by[up][terms[c0].width == 32]);
+        width_sum += terms[c0].booked;
+    }
+    b.count = cnt;
+    std::stable_sort(b.col, b.col + cnt, [](const RrColumn& x, const RrColumn& y) { return x.width < y.width; });   // runs of one width for the kernel
+    return width_sum;
+}
+// desc->count columns, RR_BATCH per launch.  h_k: the constant and the count weights, Montgomery Fr in host memory.
+int fr_row_rlc_run(zk_ctx* ctx, const zk_row_rlc* desc, const void* h_k, Fr* d_out, uint64_t n) {
+    if (int e = rr_validate(ctx, "row RLC", desc->count, desc->d_cols, desc->widths, d_out, n)) return e;
+    if (!n) return ZK_OK;
+    const uint64_t per_block = (uint64_t)FU_CELLS * 256, blocks = (n + per_block - 1) / per_block;
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many rows for one launch");
+    const uint8_t* hk = (const uint8_t*)h_k;
+    const std::vector<RrTerm> terms = rr_terms(desc->count, desc->d_cols, desc->widths, hk, d_out);
     size_t c0 = 0;
     do {
         RrBatch b;
-        memset(&b, 0, sizeof b);
         ZkProfScope prof(ctx, "fr_row_rlc");
-        uint64_t width_sum = 0;
-        uint32_t cnt = 0;
-        if (c0 == 0) {
-            Fr c;
-            memcpy(&c, hk, sizeof c);
-            limbs_of(b.k0, c, fr_c517());
-        } else {                                                        // the sum so far: a 32-byte column of weight one (k0 stays 0)
-            b.col[cnt] = {d_out, 32, {}};
-            limbs_of(b.col[cnt].k, Fr::one(), c261);
-            width_sum += 32;
-            ++cnt;
-        }
-        for (; cnt < RR_BATCH && c0 < terms.size(); ++cnt, ++c0) {
-            b.col[cnt] = terms[c0].col;
-            width_sum += terms[c0].booked;
-        }
-        b.count = cnt;
-        std::stable_sort(b.col, b.col + cnt, [](const RrColumn& x, const RrColumn& y) { return x.width < y.width; });   // runs of one width for the kernel
-        prof.bytes = n * (width_sum + 32ull);
+        prof.bytes = n * (rr_fill(b, terms, c0, hk, d_out, false) + 32ull);
         hipLaunchKernelGGL(k_fr_row_rlc, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, b, n, d_out);
+    } while (c0 < terms.size());
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+// The same table under an inversion.  More than RR_BATCH terms: the earlier launches are k_fr_row_rlc itself into d_out (the sum so
+// far) and only the last one inverts; d_out then holds that sum, so it cannot also be the numerator -- refused, like any overlap.
+int fr_row_inv0_run(zk_ctx* ctx, const zk_row_inv0* desc, const void* h_k, Fr* d_out, uint64_t n) {
+    if (int e = rr_validate(ctx, "row inverse", desc->count, desc->d_cols, desc->widths, d_out, n)) return e;
+    if (desc->d_num)
+        if (int e = rr_check_column(ctx, "row inverse", "numerator", 0, desc->d_num, desc->num_width, d_out, n)) return e;
+    if (!n) return ZK_OK;
+    const uint64_t per_block = (uint64_t)FU_CELLS * 256, blocks = (n + per_block - 1) / per_block;                   // k_fr_row_rlc's
+    const uint64_t inv_blocks = (n + per_block * RI_TILES - 1) / (per_block * RI_TILES);                              // a wave takes RI_TILES tiles
+    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many rows for one launch");
+    const uint8_t* hk = (const uint8_t*)h_k;
+    const std::vector<RrTerm> terms = rr_terms(desc->count, desc->d_cols, desc->widths, hk, d_out);
+    if (terms.size() > RR_BATCH && desc->d_num == (const void*)d_out) return ctx->fail(ZK_ERR_INVALID_ARG, "row inverse: the output holds the sum so far of more than %d columns and cannot be the numerator", RR_BATCH);
+    // the constant of inv29_rp by numerator: the quotients come out as [1/D]_256 (they are the result), [1/D]_261 (times [N]_256) or
+    // [1/D]_517 (times the integer N) -- csrc/ff29.hip.hpp
+    static const Fr c261 = fr_pow2(261), cinv[3] = {fr_pow2(778), fr_pow2(1039), fr_pow2(783)};
+    const int num = !desc->d_num ? INV0_NUM_ONE : desc->num_width == 32 ? INV0_NUM_FR : INV0_NUM_UINT;
+    RiArgs a;
+    memset(&a, 0, sizeof a);
+    a.num = desc->d_num;
+    a.num_width = desc->d_num ? desc->num_width : 0;
+    const Fr29 one_l = unpack29<Fr29P>(c261), cinv_l = unpack29<Fr29P>(cinv[num]);
+    for (int i = 0; i < 9; ++i) { a.one_rp[i] = one_l.l[i]; a.cinv[i] = cinv_l.l[i]; }
+    size_t c0 = 0;
+    do {
+        RrBatch b;
+        ZkProfScope prof(ctx, "fr_row_inv0");
+        const bool last = terms.size() - c0 <= (size_t)RR_BATCH - (c0 ? 1 : 0);
+        const uint64_t width_sum = rr_fill(b, terms, c0, hk, d_out, last);
+        const dim3 g((unsigned)blocks), t(256);
+        if (!last) {
+            prof.bytes = n * (width_sum + 32ull);
+            hipLaunchKernelGGL(k_fr_row_rlc, g, t, 0, ctx->stream, b, n, d_out);
+            continue;
+        }
+        prof.bytes = n * (width_sum + a.num_width + 32ull);
+        const dim3 gi((unsigned)inv_blocks);
+        switch (num) {
+            case INV0_NUM_ONE: hipLaunchKernelGGL(k_fr_row_inv0<INV0_NUM_ONE>, gi, t, 0, ctx->stream, b, a, n, d_out); break;
+            case INV0_NUM_UINT: hipLaunchKernelGGL(k_fr_row_inv0<INV0_NUM_UINT>, gi, t, 0, ctx->stream, b, a, n, d_out); break;
+            default: hipLaunchKernelGGL(k_fr_row_inv0<INV0_NUM_FR>, gi, t, 0, ctx->stream, b, a, n, d_out); break;
+        }
     } while (c0 < terms.size());
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
@@ -1186,7 +1374,11 @@ int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void*
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the row RLC is defined over Fr only");
         return fr_row_rlc_run(ctx, (const zk_row_rlc*)d_a, d_b, (Fr*)d_out, n);
     }
-    if (op == ZK_OP_SCAN_RLC || op == ZK_OP_SCAN_RLC_REV) {             // d_a, d_b: HOST pointers (cells and kinds; z0 and the (m, w) table)
+    if (op == ZK_OP_ROW_INV0) {                                         // d_a, d_b: HOST pointers (column table and numerator; constant and weights)
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the row inverse is defined over Fr only");
+        return fr_row_inv0_run(ctx, (const zk_row_inv0*)d_a, d_b, (Fr*)d_out, n);
+    }
+    if (op == ZK_OP_SCAN_RLC || op == ZK_OP_SCAN_RLC_REV) {           // d_a, d_b: HOST pointers (cells and kinds; z0 and the (m, w) table)
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the scan RLC is defined over Fr only");
         return fr_scan_rlc_run(ctx, op == ZK_OP_SCAN_RLC_REV, (const zk_scan_rlc*)d_a, d_b, (Fr*)d_out, n);
     }
