@@ -60,6 +60,17 @@ typedef struct zk_scan_rlc { const void* d_cells; uint32_t width; const uint8_t*
  * members are those of zk_row_rlc; d_num is a device pointer or NULL */
 #define ZK_OP_ROW_INV0 12
 typedef struct zk_row_inv0 { uint32_t count; const void* const* d_cols; const uint8_t* widths; const void* d_num; uint32_t num_width; } zk_row_inv0;
+/* the width-3 Poseidon hash columns of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct, whose pointers
+ * are device pointers */
+#define ZK_OP_POSEIDON 14
+#define ZK_POSEIDON_FINAL 1
+typedef struct zk_poseidon {
+    const void* d_in0; const void* d_in1; const void* d_cap;
+    const uint8_t* d_kinds;
+    void* d_word0; void* d_word1;
+    uint8_t width0, width1, cap_width;
+    uint8_t flags;
+} zk_poseidon;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -186,6 +197,33 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * far), only the last one inverts, columns that ARE d_out go to the first -- and then d_num may not be d_out (ZK_ERR_INVALID_ARG).
  * Every launch is booked under the zk_prof name "fr_row_inv0" with n * (sum of its widths, the sum so far counting as 32, + num_width
  * on the inverting launch when d_num is given, + 32) algorithmic bytes.
+ * ZK_OP_POSEIDON (a #define, value 14 -- 13 stays refused, like 11; Fr only) makes the width-3 Poseidon hash columns of the
+ * reference's PoseidonTable -- hash_id, input0, input1 -- from packed typed cells: zktrie's hash_with_domain([a, b], domain), one
+ * permutation per row, and the Poseidon code hash, a rate-2 sponge over 31-byte big-endian words with capacity len * 2^64.  The
+ * permutation is that of zk_host_poseidon_permute_width3 (x^5, R_F = 8, R_P = 57, the plain round schedule).  As for the other typed
+ * ops, d_a and d_b are HOST pointers, read before the call returns; the call is asynchronous on the context's stream.  d_a points to
+ * a zk_poseidon {d_in0, d_in1, d_cap, d_kinds, d_word0, d_word1, width0, width1, cap_width, flags} whose pointers are device
+ * pointers, d_b to 32 B: one Montgomery Fr cap_scale (2^64 for the code hash, where the capacity cell is the byte length; 1 where it
+ * is the zktrie domain).  Widths 1, 2, 4, 8, 16: packed little-endian unsigned cells at stride = width, read exactly like
+ * zk_fr_from_uint, aligned to the width, nothing outside n * width bytes is read; 32: canonical Montgomery Fr, 8-byte aligned; 31
+ * (width0, width1 only; cap_width = 31 is refused): cell i is the 31 bytes at ptr + 62 * i, BIG-endian, any alignment, exactly those
+ * bytes are read -- the rows of unroll_to_hash_input_default: bytecodes laid end to end, each zero-padded to a multiple of 62 bytes,
+ * d_in1 = d_in0 + 31.  d_cap = NULL: capacity 0 (cap_width is ignored).  d_kinds: n bytes, any alignment, row kind = d_kinds[i] & 3;
+ * NULL: every row is a head.
+ *   0 head      s = (cap_scale * cap[i], in0[i], in1[i])
+ *   1 continue  s = s'(i-1) + (0, in0[i], in1[i]), s'(i-1) the full three-word state row i-1 left; cap[i] is not read; at row 0 or
+ *               behind an off row it continues from the zero state
+ *   2, 3 off    the row writes 0 (to d_out and to the word outputs) and ends the message
+ * Then s' = permute(s) and d_out[i] = s'[0], canonical Montgomery Fr: the running hash.  With ZK_POSEIDON_FINAL in flags, d_out[i]
+ * is the s'[0] of the LAST row of the message row i belongs to, on every row of that message (the table's hash_id).  d_word0 and
+ * d_word1 (n x 32 B each, or NULL) receive the Montgomery images of in0[i] and in1[i] (the table's input0, input1).  A 32-byte cell
+ * that is not canonical gives an undefined VALUE from its row to the end of its message, touches no memory that would not be touched
+ * otherwise, and gives no error.  ZK_FIELD_FQ, any other width, a NULL or misaligned d_in0 or d_in1 (or misaligned d_cap), unknown
+ * flag bits, any overlap between an output (d_out, d_word0, d_word1) and any input or another output: ZK_ERR_INVALID_ARG before any
+ * launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.  One lane walks one message;
+ * with d_kinds the first rows of the messages are first gathered into a list on the device (no host synchronisation), and more than
+ * 2^32 - 1 rows are refused.  Booked under the zk_prof name "fr_poseidon" with n * (width0 + width1 + (d_cap ? cap_width : 0) +
+ * (d_kinds ? 1 : 0) + 32 + 32 per word output given) algorithmic bytes per call.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

@@ -172,6 +172,19 @@ inline void row_inv0(const Context& c, const std::vector<const void*>& d_cols, c
     const zk_row_inv0 desc{(uint32_t)d_cols.size(), d_cols.data(), cell_bytes.data(), d_num, num_bytes};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_ROW_INV0, &desc, host.data(), d_out, n));
 }
+// d_out[i] = permute(s)[0] for i < n: the width-3 Poseidon hash columns of the PoseidonTable from typed cells on the device
+// (zk_field_vec_op with ZK_OP_POSEIDON and a zk_poseidon; asynchronous on the context's stream) -- Fr::hash_with_domain([a, b], domain)
+// per row (d_kinds = nullptr, d_cap = the domain column, cap_scale = one) and the Poseidon code hash (cells of 31 bytes: cell i is the
+// 31 big-endian bytes at ptr + 62 i, d_in1 = d_in0 + 31; d_cap = the byte lengths, cap_scale = 2^64; d_kinds: 0 head, 1 continue, 2 off;
+// final_hash: every row of a message holds the hash of its last row, the table's hash_id).  d_word0 / d_word1: optional n x 32 B
+// outputs, the Montgomery images of the inputs (input0, input1).  No output overlaps an input or another output.
+inline void poseidon(const Context& c, const void* d_in0, uint8_t bytes0, const void* d_in1, uint8_t bytes1, size_t n, void* d_out, const void* d_cap = nullptr, uint8_t cap_bytes = 8,
+                     const Fr* cap_scale = nullptr, const uint8_t* d_kinds = nullptr, bool final_hash = false, void* d_word0 = nullptr, void* d_word1 = nullptr) {
+    const Fr one{{0xac96341c4ffffffbULL, 0x36fc76959f60cd29ULL, 0x666ea36f7879462eULL, 0x0e0a77c19a07df2fULL}};           // 2^256 mod r: Montgomery one
+    const Fr scale = cap_scale ? *cap_scale : one;                      // host memory, read by the call
+    const zk_poseidon desc{d_in0, d_in1, d_cap, d_kinds, d_word0, d_word1, bytes0, bytes1, (uint8_t)(d_cap ? cap_bytes : 0), (uint8_t)(final_hash ? ZK_POSEIDON_FINAL : 0)};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_POSEIDON, &desc, &scale, d_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -82,6 +82,29 @@ pub struct zk_row_inv0 {
     pub d_num: *const c_void,
     pub num_width: u32,
 }
+/// `zk_field_vec_op` op: the width-3 Poseidon hash columns of the `PoseidonTable` (`hash_id`, `input0`, `input1`) from typed cells --
+/// `Fr::hash_with_domain([a, b], domain)` per row and the Poseidon code hash over 31-byte big-endian words.  For this op `d_a` is a
+/// HOST pointer to a `zk_poseidon` and `d_b` a HOST pointer to 32 B, the Montgomery Fr `cap_scale` (2^64 for the code hash).
+pub const ZK_OP_POSEIDON: c_int = 14;
+/// `zk_poseidon.flags`: every row of a message holds the hash of its last row.
+pub const ZK_POSEIDON_FINAL: u8 = 1;
+/// `zk_poseidon`: device pointers.  `d_cap` may be null (capacity 0), `d_kinds` may be null (every row is a head; otherwise `n`
+/// bytes, kind = byte & 3: 0 head, 1 continue, 2 / 3 off), `d_word0` / `d_word1` are optional `n x 32 B` outputs.  Widths 1, 2, 4, 8,
+/// 16 (packed little-endian unsigned), 32 (Montgomery Fr) or, for `width0` / `width1`, 31: cell `i` is the 31 big-endian bytes at
+/// `ptr + 62 * i`.
+#[repr(C)]
+pub struct zk_poseidon {
+    pub d_in0: *const c_void,
+    pub d_in1: *const c_void,
+    pub d_cap: *const c_void,
+    pub d_kinds: *const u8,
+    pub d_word0: *mut c_void,
+    pub d_word1: *mut c_void,
+    pub width0: u8,
+    pub width1: u8,
+    pub cap_width: u8,
+    pub flags: u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

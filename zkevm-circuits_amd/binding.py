@@ -26,6 +26,8 @@ OP_SCAN_AFFINE, OP_SCAN_AFFINE_REV = 3, 4            # out[i] = a[i] * out[i -+ 
 OP_ROW_RLC = 8                                        # out[i] = c + sum_j w_j * cell_j[i] across typed columns, Fr only (ZK_OP_ROW_RLC)
 OP_SCAN_RLC, OP_SCAN_RLC_REV = 9, 10                 # out[i] = m[kind_i] * out[i -+ 1] + w[kind_i] * cell[i] along a typed column, Fr only
 OP_ROW_INV0 = 12                                      # out[i] = num[i] * inv0(c + sum_j w_j * cell_j[i]) across typed columns, Fr only (ZK_OP_ROW_INV0)
+OP_POSEIDON = 14                                      # out[i] = permute(state of row i)[0], width-3 Poseidon over typed cells, Fr only (ZK_OP_POSEIDON)
+POSEIDON_FINAL = 1                                    # zk_poseidon.flags: every row of a message holds the hash of its last row
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -90,6 +92,13 @@ class _RowInv0(ctypes.Structure):
     """zk_row_inv0: the column table and the numerator of ZK_OP_ROW_INV0 (host memory; d_num is a device pointer or NULL)"""
     _fields_ = [("count", ctypes.c_uint32), ("d_cols", ctypes.POINTER(ctypes.c_void_p)), ("widths", ctypes.POINTER(ctypes.c_uint8)),
                 ("d_num", ctypes.c_void_p), ("num_width", ctypes.c_uint32)]
+
+
+class _Poseidon(ctypes.Structure):
+    """zk_poseidon: the columns of ZK_OP_POSEIDON (host memory; every pointer is a device pointer or NULL)"""
+    _fields_ = [("d_in0", ctypes.c_void_p), ("d_in1", ctypes.c_void_p), ("d_cap", ctypes.c_void_p), ("d_kinds", ctypes.c_void_p),
+                ("d_word0", ctypes.c_void_p), ("d_word1", ctypes.c_void_p),
+                ("width0", ctypes.c_uint8), ("width1", ctypes.c_uint8), ("cap_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
 
 
 def _host_ptr(a: np.ndarray):
@@ -752,6 +761,24 @@ class Context:
         desc = _RowInv0(cnt, ctypes.cast(pp, ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(wd, ctypes.POINTER(ctypes.c_uint8)),
                         None if num is None else ptr_of(num), 0 if num is None else num_width)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_ROW_INV0, ctypes.byref(desc), _host_ptr(hk), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
+    def poseidon(self, in0, width0, in1, width1, n, out, cap=None, cap_width=8, cap_scale=None, kinds=None, final=False, word0=None, word1=None):
+        """out[i] = permute(s)[0] for i < n, the width-3 Poseidon permutation of host_poseidon_permute_width3 over typed cells
+        (zk_field_vec_op with ZK_OP_POSEIDON).  in0, in1, cap, kinds, out, word0, word1: DeviceBuffers or device pointers.  Widths 1, 2,
+        4, 8, 16 (packed little-endian), 32 (Montgomery Fr) or, for in0 and in1, 31: cell i is the 31 BIG-endian bytes at ptr + 62 i.
+        kinds: None (every row is a head) or n bytes, kind = byte & 3: 0 head, s = (cap_scale * cap[i], in0[i], in1[i]); 1 continue,
+        s = the state row i - 1 left + (0, in0[i], in1[i]); 2, 3 off, the row writes 0.  cap None: capacity 0; cap_scale: (4,) u64
+        Montgomery Fr, None: one.  final: every row of a message holds the value of its last row.  word0, word1: optional n x 32 B
+        outputs, the Montgomery images of in0 and in1.  No output may overlap an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        scale = np.zeros(4, dtype=np.uint64)
+        if cap_scale is None:
+            scale[:] = (0xac96341c4ffffffb, 0x36fc76959f60cd29, 0x666ea36f7879462e, 0x0e0a77c19a07df2f)      # 2^256 mod r: Montgomery one
+        else:
+            scale[:] = np.asarray(cap_scale, dtype=np.uint64).reshape(4)
+        desc = _Poseidon(ptr_of(in0), ptr_of(in1), ptr_of(cap), ptr_of(kinds), ptr_of(word0), ptr_of(word1), width0, width1, cap_width if cap is not None else 0,
+                         POSEIDON_FINAL if final else 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_POSEIDON, ctypes.byref(desc), _host_ptr(scale), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

@@ -72,6 +72,7 @@ struct zk_ctx {
     uint32_t comm_rank = 0, comm_world = 1;
     std::map<uint64_t, std::shared_ptr<zk::NttDomain>> domains;   // key: log_n | kind << 8
     std::map<uint64_t, void*> pow_tables;                         // cached two-level power tables of the coset generators
+    void* poseidon_tab = nullptr;                                 // the width-3 Poseidon constants as limb records (poseidon.hip), built on first use
     std::map<const void*, void*> loop_records;                    // measurement only (ZK_QUOTIENT_LOOP_RECORDS, quotient.hip): column buffer -> its image as a coset record buffer
     std::vector<void*> pinned;   // small pinned host staging buffers
     // Device block pool for the prover's column buffers: a proof allocates and frees hundreds of
@@ -239,6 +240,7 @@ int fr_powers_fmt(zk_ctx* ctx, const Fr& base, const Fr& mul, void* d_out, size_
 int quotient_eval_fmt(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr, const void* const* h_col_ptrs, uint32_t num_cols, const void* h_consts, uint32_t num_consts, uint32_t k, uint32_t ext_k,
                       int divide_by_vanishing, void* d_out, bool records);
 int fr_scale_run(zk_ctx* ctx, Fr* d_a, const Fr& s, uint64_t n);
+int fr_poseidon_run(zk_ctx* ctx, const zk_poseidon* desc, const void* h_scale, Fr* d_out, uint64_t n);   // poseidon.hip: ZK_OP_POSEIDON of zk_field_vec_op
 // G1 encodings read on the device (params.hip k_g1_decode): 32 B compressed, 64 B Montgomery limbs, 64 B big-endian x || y (EVM)
 enum G1Enc : int { G1_ENC_COMPRESSED = 0, G1_ENC_RAW = 1, G1_ENC_BE_XY = 2 };
 int g1_decode_run(zk_ctx* ctx, const void* d_in, int enc, G1Affine* d_out, uint64_t n, uint32_t* d_bad, uint8_t* d_bad_at);
