@@ -71,6 +71,19 @@ typedef struct zk_poseidon {
     uint8_t width0, width1, cap_width;
     uint8_t flags;
 } zk_poseidon;
+/* the Keccak-256 table columns of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct, whose pointers are
+ * device pointers */
+#define ZK_OP_KECCAK 16
+typedef struct zk_keccak {
+    const void* d_bytes;      /* device: the bytes the messages live in */
+    uint64_t    total_bytes;  /* bytes readable at d_bytes */
+    const void* d_offsets;    /* device: n unsigned little-endian offsets into d_bytes */
+    const void* d_lens;       /* device: n unsigned little-endian byte lengths */
+    void*       d_digest;     /* device, n x 32 B, or NULL: the digests, in digest byte order */
+    void*       d_input_rlc;  /* device, n x 32 B Montgomery Fr, or NULL */
+    uint8_t     index_width;  /* 4 or 8: width of an offset and of a length */
+    uint8_t     flags;        /* must be 0 */
+} zk_keccak;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -224,6 +237,32 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * with d_kinds the first rows of the messages are first gathered into a list on the device (no host synchronisation), and more than
  * 2^32 - 1 rows are refused.  Booked under the zk_prof name "fr_poseidon" with n * (width0 + width1 + (d_cap ? cap_width : 0) +
  * (d_kinds ? 1 : 0) + 32 + 32 per word output given) algorithmic bytes per call.
+ * ZK_OP_KECCAK (a #define, value 16 -- 15 stays refused, like 11 and 13; Fr only) makes the hash columns of the reference's
+ * KeccakTable (zkevm-circuits/src/table.rs: is_final, input_rlc, input_len, output_rlc) from message bytes that live on the device:
+ * Keccak-256 (pad byte 0x01, rate 136, the function of zk_host_keccak256) of n messages, one per row, and the two challenge-phase
+ * columns.  As for the other typed ops, d_a and d_b are HOST pointers, read before the call returns; the call is asynchronous on the
+ * context's stream.  d_a points to a zk_keccak {d_bytes, total_bytes, d_offsets, d_lens, d_digest, d_input_rlc, index_width, flags}
+ * whose pointers are device pointers, d_b to 2 x 32 B of Montgomery Fr: r_out (the reference's evm_word challenge), then r_in
+ * (keccak_input); r_in is used only when d_input_rlc is given, all 64 bytes are always read.  index_width 4 or 8: d_offsets and
+ * d_lens are n unsigned little-endian integers of that width, aligned to it.  Message i is the len_i bytes at d_bytes + off_i;
+ * messages may overlap, repeat, and start at any byte address.  For i < n:
+ *   digest_i       = Keccak-256 of message i
+ *   d_out[i]       = sum_(k<32) digest_i[k] * r_out^(31-k), canonical Montgomery Fr: rlc::value(Word::from_big_endian(digest)
+ *                    .to_le_bytes(), evm_word), the table's output_rlc and the Keccak circuit's hash_rlc
+ *   d_digest[i]    (n x 32 B at any alignment, or NULL) the 32 digest bytes, in digest order
+ *   d_input_rlc[i] (n x 32 B, or NULL) = sum_(k<len) m[k] * r_in^(len-1-k), rlc::value(input.iter().rev(), keccak_input); 0 for the
+ *                    empty message
+ * The d_lens buffer itself IS the table's input_len column: a 4- or 8-byte typed cell column, ready for
+ * zk_proof_advice_phase_typed_dev.  The offsets and lengths are device data that the host never sees: a message with off_i >
+ * total_bytes or len_i > total_bytes - off_i (computed so that it cannot wrap) writes 0 to every output of its row and reads nothing,
+ * and no error is reported for it, because there is no host synchronisation.  No byte outside [d_bytes, d_bytes + total_bytes) is
+ * ever read, whatever the device data hold.  ZK_FIELD_FQ, an index_width other than 4 or 8, NULL or misaligned d_offsets or d_lens,
+ * NULL d_bytes with total_bytes > 0, nonzero flags, NULL d_out, d_out or d_input_rlc at an address that is no multiple of 16, any
+ * overlap between an output (d_out, d_digest, d_input_rlc) and any input or another output, more rows than one launch grid takes
+ * (2^31 - 1 workgroups of 256): ZK_ERR_INVALID_ARG before any launch, nothing is written; the arguments are validated before n is
+ * looked at, n = 0 is then ZK_OK.  One lane walks one message, so a wave takes as long as its longest message.  Booked under the
+ * zk_prof name "fr_keccak" with n * (2 * index_width + 32 + 32 per optional output given) + total_bytes algorithmic bytes per call:
+ * the host cannot know the sum of the lengths, total_bytes stands in for the message bytes read.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

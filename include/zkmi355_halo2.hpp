@@ -185,6 +185,18 @@ inline void poseidon(const Context& c, const void* d_in0, uint8_t bytes0, const 
     const zk_poseidon desc{d_in0, d_in1, d_cap, d_kinds, d_word0, d_word1, bytes0, bytes1, (uint8_t)(d_cap ? cap_bytes : 0), (uint8_t)(final_hash ? ZK_POSEIDON_FINAL : 0)};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_POSEIDON, &desc, &scale, d_out, n));
 }
+// d_out[i] = sum_k digest_i[k] r_out^(31-k) for i < n, digest_i = Keccak-256 of the len_i bytes at d_bytes + off_i: the hash columns
+// of the KeccakTable from message bytes on the device (zk_field_vec_op with ZK_OP_KECCAK and a zk_keccak; asynchronous on the
+// context's stream) -- output_rlc = rlc::value(Word::from_big_endian(digest).to_le_bytes(), evm_word) in d_out, and optionally the
+// digest bytes (d_digest, n x 32 B) and input_rlc = rlc::value(input.iter().rev(), keccak_input) (d_input_rlc, n x 32 B, under r_in).
+// d_offsets, d_lens: n unsigned integers of index_bytes (4 or 8) each; d_lens is the input_len column as it stands.  A message that
+// does not lie inside the total_bytes at d_bytes writes zeros and reads nothing.  No output overlaps an input or another output.
+inline void keccak(const Context& c, const void* d_bytes, uint64_t total_bytes, const void* d_offsets, const void* d_lens, uint8_t index_bytes, size_t n, void* d_out, const Fr& r_out,
+                   const Fr& r_in = Fr{}, void* d_digest = nullptr, void* d_input_rlc = nullptr) {
+    const Fr host[2] = {r_out, r_in};                                   // host memory, read by the call
+    const zk_keccak desc{d_bytes, total_bytes, d_offsets, d_lens, d_digest, d_input_rlc, index_bytes, 0};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_KECCAK, &desc, host, d_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -105,6 +105,24 @@ pub struct zk_poseidon {
     pub cap_width: u8,
     pub flags: u8,
 }
+/// `zk_field_vec_op` op: the hash columns of the `KeccakTable` from message bytes on the device -- `d_out[i]` is `output_rlc`, the
+/// Keccak-256 digest of message `i` under the `evm_word` challenge.  For this op `d_a` is a HOST pointer to a `zk_keccak` and `d_b` a
+/// HOST pointer to `2 x 32 B` Montgomery Fr: `r_out` (`evm_word`), then `r_in` (`keccak_input`, used with `d_input_rlc`).
+pub const ZK_OP_KECCAK: c_int = 16;
+/// `zk_keccak`: device pointers.  Message `i` is the `d_lens[i]` bytes at `d_bytes + d_offsets[i]`; offsets and lengths are unsigned
+/// little-endian integers of `index_width` (4 or 8) bytes; `d_lens` is the table's `input_len` column as it stands.  `d_digest` and
+/// `d_input_rlc` are optional `n x 32 B` outputs.  `flags` must be 0.
+#[repr(C)]
+pub struct zk_keccak {
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub d_offsets: *const c_void,
+    pub d_lens: *const c_void,
+    pub d_digest: *mut c_void,
+    pub d_input_rlc: *mut c_void,
+    pub index_width: u8,
+    pub flags: u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

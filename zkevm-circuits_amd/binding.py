@@ -28,6 +28,7 @@ OP_SCAN_RLC, OP_SCAN_RLC_REV = 9, 10                 # out[i] = m[kind_i] * out[
 OP_ROW_INV0 = 12                                      # out[i] = num[i] * inv0(c + sum_j w_j * cell_j[i]) across typed columns, Fr only (ZK_OP_ROW_INV0)
 OP_POSEIDON = 14                                      # out[i] = permute(state of row i)[0], width-3 Poseidon over typed cells, Fr only (ZK_OP_POSEIDON)
 POSEIDON_FINAL = 1                                    # zk_poseidon.flags: every row of a message holds the hash of its last row
+OP_KECCAK = 16                                        # out[i] = output_rlc of Keccak-256(message i), messages as bytes on the device, Fr only (ZK_OP_KECCAK)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -99,6 +100,12 @@ class _Poseidon(ctypes.Structure):
     _fields_ = [("d_in0", ctypes.c_void_p), ("d_in1", ctypes.c_void_p), ("d_cap", ctypes.c_void_p), ("d_kinds", ctypes.c_void_p),
                 ("d_word0", ctypes.c_void_p), ("d_word1", ctypes.c_void_p),
                 ("width0", ctypes.c_uint8), ("width1", ctypes.c_uint8), ("cap_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+class _Keccak(ctypes.Structure):
+    """zk_keccak: the messages and optional outputs of ZK_OP_KECCAK (host memory; every pointer is a device pointer or NULL)"""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p), ("d_lens", ctypes.c_void_p),
+                ("d_digest", ctypes.c_void_p), ("d_input_rlc", ctypes.c_void_p), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
 
 
 def _host_ptr(a: np.ndarray):
@@ -779,6 +786,23 @@ class Context:
         desc = _Poseidon(ptr_of(in0), ptr_of(in1), ptr_of(cap), ptr_of(kinds), ptr_of(word0), ptr_of(word1), width0, width1, cap_width if cap is not None else 0,
                          POSEIDON_FINAL if final else 0)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_POSEIDON, ctypes.byref(desc), _host_ptr(scale), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
+    def keccak(self, data, total_bytes, offsets, lens, index_width, n, out, r_out, r_in=None, digest=None, input_rlc=None):
+        """out[i] = sum_k digest_i[k] r_out^(31-k) for i < n, digest_i = Keccak-256 (the function of host_keccak256) of the lens[i]
+        bytes at data + offsets[i]: the KeccakTable's output_rlc (zk_field_vec_op with ZK_OP_KECCAK).  data, offsets, lens, out, digest,
+        input_rlc: DeviceBuffers or device pointers.  data: total_bytes readable bytes; offsets, lens: n unsigned little-endian
+        integers of index_width (4 or 8) bytes, aligned to it -- lens is the table's input_len column as it stands.  Messages may
+        overlap, repeat and start at any byte address; a message that does not lie inside the total_bytes writes 0 to every output
+        of its row and reads nothing, without an error.  r_out, r_in: (4,) u64 Montgomery Fr (r_in None: zero; it is used only with
+        input_rlc).  digest: optional n x 32 B, the digest bytes; input_rlc: optional n x 32 B, sum_k m[k] r_in^(len-1-k), 0 for
+        the empty message.  No output may overlap an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        r = np.zeros((2, 4), dtype=np.uint64)
+        r[0] = np.asarray(r_out, dtype=np.uint64).reshape(4)
+        if r_in is not None:
+            r[1] = np.asarray(r_in, dtype=np.uint64).reshape(4)
+        desc = _Keccak(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_KECCAK, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))
