@@ -84,6 +84,19 @@ typedef struct zk_keccak {
     uint8_t     index_width;  /* 4 or 8: width of an offset and of a length */
     uint8_t     flags;        /* must be 0 */
 } zk_keccak;
+/* the SHA-256 table columns of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct, whose pointers are device
+ * pointers; the members are zk_keccak's in name, type and order */
+#define ZK_OP_SHA256 18
+typedef struct zk_sha256 {
+    const void* d_bytes;      /* device: the bytes the messages live in */
+    uint64_t    total_bytes;  /* bytes readable at d_bytes; below 2^61 */
+    const void* d_offsets;    /* device: n unsigned little-endian offsets into d_bytes */
+    const void* d_lens;       /* device: n unsigned little-endian byte lengths */
+    void*       d_digest;     /* device, n x 32 B, or NULL: the digests, in digest byte order */
+    void*       d_input_rlc;  /* device, n x 32 B Montgomery Fr, or NULL */
+    uint8_t     index_width;  /* 4 or 8: width of an offset and of a length */
+    uint8_t     flags;        /* must be 0 */
+} zk_sha256;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -263,6 +276,27 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * looked at, n = 0 is then ZK_OK.  One lane walks one message, so a wave takes as long as its longest message.  Booked under the
  * zk_prof name "fr_keccak" with n * (2 * index_width + 32 + 32 per optional output given) + total_bytes algorithmic bytes per call:
  * the host cannot know the sum of the lengths, total_bytes stands in for the message bytes read.
+ * ZK_OP_SHA256 (a #define, value 18 -- 17 stays refused, like 11, 13 and 15; Fr only) makes the hash columns of the reference's
+ * SHA256Table (zkevm-circuits/src/table.rs: is_final, input_rlc, input_len, output_rlc; what the SHA-256 precompile looks up) in the
+ * same way: SHA-256 (FIPS 180-4) of n messages, one per row, and the two challenge-phase columns.  d_a is a HOST pointer to a
+ * zk_sha256, whose eight members are zk_keccak's in name, type and order {d_bytes, total_bytes, d_offsets, d_lens, d_digest,
+ * d_input_rlc, index_width, flags}, d_b a HOST pointer to 2 x 32 B of Montgomery Fr, r_out then r_in, both read before the call
+ * returns; r_in is used only when d_input_rlc is given, all 64 bytes are always read.  In the reference BOTH RLCs of this table are
+ * taken under keccak_input: a caller that builds the reference's table passes the same challenge twice.  For i < n:
+ *   digest_i       = SHA-256 of message i, the len_i bytes at d_bytes + off_i
+ *   d_out[i]       = sum_(k<32) digest_i[k] * r_out^(31-k), canonical Montgomery Fr: rlc::value(Word::from_big_endian(output)
+ *                    .to_le_bytes(), challenge), the table's output_rlc and the SHA-256 circuit's hashes_rlc
+ *   d_digest[i]    (n x 32 B at any alignment, or NULL) the 32 digest bytes in digest order, H0's most significant byte first
+ *   d_input_rlc[i] (n x 32 B, or NULL) = sum_(k<len) m[k] * r_in^(len-1-k), rlc::value(input.iter().rev(), challenge); 0 for the
+ *                    empty message
+ * The d_lens buffer itself IS the table's input_len column, ready for zk_proof_advice_phase_typed_dev.  Every other rule is
+ * ZK_OP_KECCAK's: messages may overlap, repeat and start at any byte address; a message with off_i > total_bytes or len_i >
+ * total_bytes - off_i (computed so that it cannot wrap) writes 0 to every output of its row and reads nothing, without an error; no
+ * byte outside [d_bytes, d_bytes + total_bytes) is ever read; the same arguments are ZK_ERR_INVALID_ARG before any launch with
+ * nothing written, validated before n is looked at, n = 0 is then ZK_OK.  One refusal more: total_bytes of 2^61 or above, because a
+ * message's length in bits would not fit the 64-bit length field of the padding.  One lane walks one message, so a wave takes as
+ * long as its longest message.  Booked under the zk_prof name "fr_sha256" with n * (2 * index_width + 32 + 32 per optional output
+ * given) + total_bytes algorithmic bytes per call.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

@@ -197,6 +197,16 @@ inline void keccak(const Context& c, const void* d_bytes, uint64_t total_bytes, 
     const zk_keccak desc{d_bytes, total_bytes, d_offsets, d_lens, d_digest, d_input_rlc, index_bytes, 0};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_KECCAK, &desc, host, d_out, n));
 }
+// The same for the SHA256Table: digest_i = SHA-256 (FIPS 180-4) of the len_i bytes at d_bytes + off_i, d_out[i] = output_rlc =
+// rlc::value(Word::from_big_endian(output).to_le_bytes(), challenge), optionally the digest bytes and input_rlc (zk_field_vec_op with
+// ZK_OP_SHA256 and a zk_sha256; asynchronous on the context's stream).  The reference takes BOTH RLCs of this table under
+// keccak_input: r_in = nullptr means r_in = r_out.  total_bytes stays below 2^61; every other rule is keccak()'s.
+inline void sha256(const Context& c, const void* d_bytes, uint64_t total_bytes, const void* d_offsets, const void* d_lens, uint8_t index_bytes, size_t n, void* d_out, const Fr& r_out,
+                   const Fr* r_in = nullptr, void* d_digest = nullptr, void* d_input_rlc = nullptr) {
+    const Fr host[2] = {r_out, r_in ? *r_in : r_out};                   // host memory, read by the call
+    const zk_sha256 desc{d_bytes, total_bytes, d_offsets, d_lens, d_digest, d_input_rlc, index_bytes, 0};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_SHA256, &desc, host, d_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -123,6 +123,23 @@ pub struct zk_keccak {
     pub index_width: u8,
     pub flags: u8,
 }
+/// `zk_field_vec_op` op: the hash columns of the `SHA256Table` from message bytes on the device -- `d_out[i]` is `output_rlc`, the
+/// SHA-256 digest of message `i` under `r_out`.  For this op `d_a` is a HOST pointer to a `zk_sha256` and `d_b` a HOST pointer to
+/// `2 x 32 B` Montgomery Fr: `r_out`, then `r_in` (used with `d_input_rlc`).  The reference takes both RLCs of this table under
+/// `keccak_input`: pass that challenge twice.
+pub const ZK_OP_SHA256: c_int = 18;
+/// `zk_sha256`: member for member `zk_keccak`.  `total_bytes` stays below `2^61`.  `flags` must be 0.
+#[repr(C)]
+pub struct zk_sha256 {
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub d_offsets: *const c_void,
+    pub d_lens: *const c_void,
+    pub d_digest: *mut c_void,
+    pub d_input_rlc: *mut c_void,
+    pub index_width: u8,
+    pub flags: u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

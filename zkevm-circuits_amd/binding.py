@@ -29,6 +29,7 @@ OP_ROW_INV0 = 12                                      # out[i] = num[i] * inv0(c
 OP_POSEIDON = 14                                      # out[i] = permute(state of row i)[0], width-3 Poseidon over typed cells, Fr only (ZK_OP_POSEIDON)
 POSEIDON_FINAL = 1                                    # zk_poseidon.flags: every row of a message holds the hash of its last row
 OP_KECCAK = 16                                        # out[i] = output_rlc of Keccak-256(message i), messages as bytes on the device, Fr only (ZK_OP_KECCAK)
+OP_SHA256 = 18                                        # out[i] = output_rlc of SHA-256(message i), messages as bytes on the device, Fr only (ZK_OP_SHA256)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -104,6 +105,13 @@ class _Poseidon(ctypes.Structure):
 
 class _Keccak(ctypes.Structure):
     """zk_keccak: the messages and optional outputs of ZK_OP_KECCAK (host memory; every pointer is a device pointer or NULL)"""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p), ("d_lens", ctypes.c_void_p),
+                ("d_digest", ctypes.c_void_p), ("d_input_rlc", ctypes.c_void_p), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+class _Sha256(ctypes.Structure):
+    """zk_sha256: the messages and optional outputs of ZK_OP_SHA256, member for member zk_keccak (host memory; every pointer is a
+    device pointer or NULL)"""
     _fields_ = [("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p), ("d_lens", ctypes.c_void_p),
                 ("d_digest", ctypes.c_void_p), ("d_input_rlc", ctypes.c_void_p), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
 
@@ -803,6 +811,23 @@ class Context:
             r[1] = np.asarray(r_in, dtype=np.uint64).reshape(4)
         desc = _Keccak(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_KECCAK, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
+    def sha256(self, data, total_bytes, offsets, lens, index_width, n, out, r_out, r_in=None, digest=None, input_rlc=None):
+        """out[i] = sum_k digest_i[k] r_out^(31-k) for i < n, digest_i = SHA-256 (FIPS 180-4) of the lens[i] bytes at data +
+        offsets[i]: the SHA256Table's output_rlc (zk_field_vec_op with ZK_OP_SHA256).  The arguments and rules are keccak()'s: data,
+        offsets, lens, out, digest, input_rlc are DeviceBuffers or device pointers; data holds total_bytes (below 2^61) readable
+        bytes; offsets, lens are n unsigned little-endian integers of index_width (4 or 8) bytes, aligned to it -- lens is the
+        table's input_len column as it stands.  Messages may overlap, repeat and start at any byte address; a message that does not
+        lie inside the total_bytes writes 0 to every output of its row and reads nothing, without an error.  r_out, r_in: (4,) u64
+        Montgomery Fr; r_in None means r_in = r_out, because the reference's table takes both RLCs under one challenge
+        (keccak_input); r_in is used only with input_rlc.  digest: optional n x 32 B, the digest bytes in digest order; input_rlc:
+        optional n x 32 B, sum_k m[k] r_in^(len-1-k), 0 for the empty message.  No output may overlap an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        r = np.zeros((2, 4), dtype=np.uint64)
+        r[0] = np.asarray(r_out, dtype=np.uint64).reshape(4)
+        r[1] = r[0] if r_in is None else np.asarray(r_in, dtype=np.uint64).reshape(4)
+        desc = _Sha256(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_SHA256, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

@@ -242,6 +242,7 @@ int quotient_eval_fmt(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr
 int fr_scale_run(zk_ctx* ctx, Fr* d_a, const Fr& s, uint64_t n);
 int fr_poseidon_run(zk_ctx* ctx, const zk_poseidon* desc, const void* h_scale, Fr* d_out, uint64_t n);   // poseidon.hip: ZK_OP_POSEIDON of zk_field_vec_op
 int fr_keccak_run(zk_ctx* ctx, const zk_keccak* desc, const void* h_challenges, Fr* d_out, uint64_t n);   // keccak.hip: ZK_OP_KECCAK of zk_field_vec_op
+int fr_sha256_run(zk_ctx* ctx, const zk_sha256* desc, const void* h_challenges, Fr* d_out, uint64_t n);   // sha256.hip: ZK_OP_SHA256 of zk_field_vec_op
 // G1 encodings read on the device (params.hip k_g1_decode): 32 B compressed, 64 B Montgomery limbs, 64 B big-endian x || y (EVM)
 enum G1Enc : int { G1_ENC_COMPRESSED = 0, G1_ENC_RAW = 1, G1_ENC_BE_XY = 2 };
 int g1_decode_run(zk_ctx* ctx, const void* d_in, int enc, G1Affine* d_out, uint64_t n, uint32_t* d_bad, uint8_t* d_bad_at);

@@ -1390,6 +1390,10 @@ int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void*
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the Keccak op is defined over Fr only");
         return fr_keccak_run(ctx, (const zk_keccak*)d_a, d_b, (Fr*)d_out, n);
     }
+    if (op == ZK_OP_SHA256) {                                           // d_a, d_b: HOST pointers (the zk_sha256; r_out and r_in)
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the SHA-256 op is defined over Fr only");
+        return fr_sha256_run(ctx, (const zk_sha256*)d_a, d_b, (Fr*)d_out, n);
+    }
     if (n == 0) return ZK_OK;
     if (op == ZK_OP_SCAN_AFFINE || op == ZK_OP_SCAN_AFFINE_REV) {
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the scan ops are defined over Fr only");
