@@ -268,7 +268,26 @@ int commit_batch_staged(zk_ctx* ctx, const zk_srs* srs, int basis, const void* c
 void sample_narrow(const void* const* h_cols, size_t count, size_t n, uint8_t* narrow);   // host sampling of Montgomery-form columns: 1 = at most a quarter of the sampled values are >= 2^64
 int sample_narrow_dev(zk_ctx* ctx, const void* const* d_cols, size_t count, size_t n, uint8_t* narrow);   // the same for columns resident on the device
 int sample_narrow_dev_typed(zk_ctx* ctx, const void* const* d_cols, const uint8_t* widths, size_t count, size_t n, size_t rows, uint8_t* narrow);   // typed columns on the device: <= 8 bytes small by construction, 16 judged over `rows` packed cells, 32 as sample_narrow_dev
-int lookup_multiplicities_enqueue(zk_ctx* ctx, const Fr* const* d_inputs, size_t num_inputs, const Fr* d_table, size_t usable_rows, Fr* d_m, size_t n, uint32_t* d_status, bool reuse_hash = false);   // lookup.hip, no sync
+int lookup_multiplicities_enqueue(zk_ctx* ctx, const Fr* const* d_inputs, size_t num_inputs, const Fr* d_table, size_t usable_rows, Fr* d_m, size_t n, uint32_t* d_status, bool reuse_hash = false,
+                                  bool one_launch = false);   // lookup.hip, no sync
+// One theta-compressed tuple of a lookup argument (lookup.hip k_lk_compress_many): `width` elements, most significant power of theta first.
+// Element i is col[i] read at rotation rot[i] (LK_ELEM_CONST: col[i] points at ONE value on the device), times fac[i] at frot[i] where fac[i]
+// is set; common: every element carries fac[0] / frot[0], applied once to the sum.
+constexpr uint32_t LK_TUPLE_MAX = 16, LK_ELEM_CONST = 1;
+struct LkTuple {
+    const Fr* col[LK_TUPLE_MAX];
+    const Fr* fac[LK_TUPLE_MAX];
+    int32_t rot[LK_TUPLE_MAX], frot[LK_TUPLE_MAX];
+    uint32_t flags[LK_TUPLE_MAX];
+    Fr* dst;
+    uint32_t width, common;
+};
+int lookup_compress_many_enqueue(zk_ctx* ctx, const LkTuple* d_descs, size_t count, const void* h_theta, size_t n);   // lookup.hip, no sync
+// The logUp running sums of a batch of arguments (vec.hip).  Argument a: phi[0] = 0, phi[i + 1] = phi[i] + sum_j inv_f[j n + i] - m[i] inv_t[i],
+// with inv_f its N inverted input columns, one behind the other.
+struct LkSum { const Fr* m; const Fr* inv_t; const Fr* inv_f; Fr* phi; uint64_t N; };
+int fr_batch_invert_from(zk_ctx* ctx, const Fr* const* d_src, const void* h_beta, uint32_t log_n, Fr* d_inv, size_t slots);   // d_inv[s n + i] = 1 / (d_src[s][i] + beta), zero where that is zero; d_src on the device
+int lookup_sums_enqueue(zk_ctx* ctx, const LkSum* d_args, size_t count, size_t n);   // d_args on the device; enqueued, no sync
 // row checks of zk_mock_verify (lookup.hip; enqueued on the context's stream, no sync)
 struct MockFail { uint32_t kind, index, sub, row; };          // == zk_mock_failure
 int mock_hash_build(zk_ctx* ctx, const Fr* d_table, size_t rows, int scratch_slot, const uint32_t** slots_out, uint32_t* mask_out);

@@ -12,6 +12,8 @@
 // with that value, settled with atomicCAS / atomicMax), then one probe sequence per input row
 // (atomicAdd on the owning row's counter).  Values are canonical Montgomery residues, so equality
 // of the eight limbs is equality in Fr.  2 n slots for n rows: expected probe length < 1.5.
+#include <algorithm>
+
 #include "ctx.hpp"
 
 namespace zk {
@@ -70,9 +72,13 @@ __global__ void __launch_bounds__(256) k_lk_insert(const Fr* __restrict__ table,
 constexpr int LK_COUNT_THREADS = 1024;
 constexpr int LK_BLOCK_SLOT_BITS = 11;
 constexpr uint32_t LK_BLOCK_SLOTS = 1u << LK_BLOCK_SLOT_BITS;     // 2 x LK_COUNT_THREADS
+// the input vectors of one launch: blockIdx.y picks one (the pointers travel as kernel arguments: no table upload)
+constexpr size_t LK_COUNT_INPUTS = 16;
+struct LkInputs { const Fr* p[LK_COUNT_INPUTS]; };
 // status[0] = lowest input row whose value is not in the table (LK_EMPTY if none)
-__global__ void __launch_bounds__(LK_COUNT_THREADS) k_lk_count(const Fr* __restrict__ inputs, const Fr* __restrict__ table, uint32_t rows, const uint32_t* __restrict__ slots, uint32_t mask,
+__global__ void __launch_bounds__(LK_COUNT_THREADS) k_lk_count(LkInputs in, const Fr* __restrict__ table, uint32_t rows, const uint32_t* __restrict__ slots, uint32_t mask,
                                                   uint32_t* __restrict__ counts, uint32_t* __restrict__ status) {
+    const Fr* __restrict__ inputs = in.p[blockIdx.y];
     const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t owner = LK_EMPTY;
     if (row < rows) {
@@ -129,7 +135,9 @@ __global__ void __launch_bounds__(256) k_lk_to_fr(const uint32_t* __restrict__ c
 // reuse_hash: the previous call on this context was for the SAME table values and row count (consecutive lookup arguments into
 // one table -- what chunk_lookups() leaves when a table has more inputs than one argument's degree allows): its hash is still in
 // the scratch, only the counters start over.
-int lookup_multiplicities_enqueue(zk_ctx* ctx, const Fr* const* d_inputs, size_t num_inputs, const Fr* d_table, size_t usable_rows, Fr* d_m, size_t n, uint32_t* d_status, bool reuse_hash) {
+// one_launch: the inputs of the argument are counted by one launch per LK_COUNT_INPUTS of them (the input on a grid dimension)
+// instead of one launch each; the counters are atomic sums either way.
+int lookup_multiplicities_enqueue(zk_ctx* ctx, const Fr* const* d_inputs, size_t num_inputs, const Fr* d_table, size_t usable_rows, Fr* d_m, size_t n, uint32_t* d_status, bool reuse_hash, bool one_launch) {
     uint32_t cap = 16;
     while (cap < 2 * usable_rows) cap <<= 1;
     // scratch: slots[cap] | counts[usable_rows]   (reused by the next enqueue: same stream, so ordered)
@@ -141,12 +149,62 @@ int lookup_multiplicities_enqueue(zk_ctx* ctx, const Fr* const* d_inputs, size_t
     const uint32_t rows = (uint32_t)usable_rows;
     if (rows) {
         if (!reuse_hash) hipLaunchKernelGGL(k_lk_insert, dim3((rows + 255) / 256), dim3(256), 0, ctx->stream, d_table, rows, slots, cap - 1);
-        for (size_t i = 0; i < num_inputs; ++i)
-            hipLaunchKernelGGL(k_lk_count, dim3((rows + LK_COUNT_THREADS - 1) / LK_COUNT_THREADS), dim3(LK_COUNT_THREADS), 0, ctx->stream, d_inputs[i], d_table, rows,
+        const size_t per = one_launch ? LK_COUNT_INPUTS : 1;
+        for (size_t i = 0; i < num_inputs; i += per) {
+            const size_t cnt = std::min(per, num_inputs - i);
+            LkInputs in{};
+            for (size_t j = 0; j < cnt; ++j) in.p[j] = d_inputs[i + j];
+            hipLaunchKernelGGL(k_lk_count, dim3((rows + LK_COUNT_THREADS - 1) / LK_COUNT_THREADS, (unsigned)cnt), dim3(LK_COUNT_THREADS), 0, ctx->stream, in, d_table, rows,
                                (const uint32_t*)slots, cap - 1, counts, d_status);
+        }
         ZK_CHECK_LAUNCH(ctx);
     }
     hipLaunchKernelGGL(k_lk_to_fr, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)counts, rows, d_m, (uint64_t)n);
+    ZK_CHECK_LAUNCH(ctx);
+    return ZK_OK;
+}
+
+
+// ---- theta-compression of every tuple of a stage in one launch (stage_lookup_multiplicities, prover.hip) ---------------------
+// A descriptor is one tuple ((e0 theta + e1) theta + e2) ... whose elements are column reads at a rotation, constants, or
+// products F x column with F a column read (prover.hip: recognise_tuple).  Grid: row tiles x descriptor.  Where every element
+// carries the same F (the q_enable of a zkEVM lookup) the sum is multiplied by F once.  Plain Montgomery arithmetic on canonical
+// residues, so the output is the canonical residue the evaluator's program gives: the hash join compares limbs.
+static_assert(sizeof(LkTuple) % 8 == 0, "descriptor rows are read as an array");
+__device__ __forceinline__ Fr lk_tuple_elem(const LkTuple& d, uint32_t i, uint32_t row, uint32_t mask, bool own_factor) {
+    // a constant is a one-row column (LK_ELEM_CONST: the row index is dropped)
+    Fr e = ldg(d.col[i] + ((d.flags[i] & LK_ELEM_CONST) ? 0u : ((row + (uint32_t)d.rot[i]) & mask)));
+    if (own_factor && d.fac[i]) e = e * ldg(d.fac[i] + ((row + (uint32_t)d.frot[i]) & mask));
+    return e;
+}
+__global__ void __launch_bounds__(256) k_lk_compress_many(const LkTuple* __restrict__ descs, Fr theta, uint32_t n) {
+    const LkTuple& d = descs[blockIdx.y];
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x, mask = n - 1u;          // n is a power of two
+    if (row >= n) return;
+    const uint32_t w = d.width;
+    const bool common = d.common != 0;
+    Fr acc = lk_tuple_elem(d, 0, row, mask, !common);
+    for (uint32_t i = 1; i < w; i += 2) {           // two elements in flight per Horner step
+        const Fr e0 = lk_tuple_elem(d, i, row, mask, !common);
+        if (i + 1 < w) {
+            const Fr e1 = lk_tuple_elem(d, i + 1, row, mask, !common);
+            acc = (acc * theta + e0) * theta + e1;
+        } else acc = acc * theta + e0;
+    }
+    if (common) acc = acc * ldg(d.fac[0] + ((row + (uint32_t)d.frot[0]) & mask));
+    stg(d.dst + row, acc);
+}
+// d_descs: `count` descriptors on the device (the caller uploaded them with the constants they point to); enqueued, no sync
+int lookup_compress_many_enqueue(zk_ctx* ctx, const LkTuple* d_descs, size_t count, const void* h_theta, size_t n) {
+    if (!count || !n) return ZK_OK;
+    if (n > ((size_t)1 << 31) || (n & (n - 1))) return ctx->fail(ZK_ERR_INVALID_ARG, "lookup compression: %zu rows are not a power of two below 2^32", n);
+    Fr theta;
+    memcpy(&theta, h_theta, sizeof theta);
+    ZkProfScope prof(ctx, "lookup_compress_many");
+    for (size_t c0 = 0; c0 < count; c0 += 65535) {          // gridDim.y
+        const size_t cnt = std::min<size_t>(65535, count - c0);
+        hipLaunchKernelGGL(k_lk_compress_many, dim3((unsigned)((n + 255) / 256), (unsigned)cnt), dim3(256), 0, ctx->stream, d_descs + c0, theta, (uint32_t)n);
+    }
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
@@ -258,7 +316,7 @@ extern "C" int zk_lookup_multiplicities(zk_ctx* ctx, const void* d_inputs, const
     if (!status) return ZK_ERR_OOM;
     ZK_HIP(ctx, hipMemsetAsync(status, 0xFF, 4, ctx->stream));
     const Fr* one_input = (const Fr*)d_inputs;
-    int rc = lookup_multiplicities_enqueue(ctx, &one_input, 1, (const Fr*)d_table, usable_rows, (Fr*)d_m, n, status, false);
+    int rc = lookup_multiplicities_enqueue(ctx, &one_input, 1, (const Fr*)d_table, usable_rows, (Fr*)d_m, n, status, false, false);
     if (rc) return rc;
     uint32_t st = LK_EMPTY;
     ZK_HIP(ctx, hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, ctx->stream));

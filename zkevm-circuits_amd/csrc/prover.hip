@@ -1400,6 +1400,7 @@ struct Finish {
     // ZK_SHARD_LOOKUPS=0: every rank works on every argument, as before.
     const bool shard_args;
     std::vector<uint32_t> act;                // the arguments this rank works on, in order
+    std::vector<uint32_t> lk_order;           // `act` in the order the two lookup stages take them: arguments into one table side by side (stage_lookup_multiplicities)
     bool late_cosets = false;                 // the auxiliary stream holds coset transforms of this session's advice columns
     bool records = false;                     // the cosets of this session are coset records (finish_coset_format)
     // lookups: compressed inputs and tables (until the grand sums have read them), m and phi in Lagrange form
@@ -1539,6 +1540,62 @@ static int exchange_owned(Finish& f, std::vector<DevBuf>& cols) {
     return ZK_OK;
 }
 
+// ZK_LOOKUP_FUSED (default on; =0: the path before it): the two lookup stages compress every tuple they recognise in one launch,
+// count an argument's inputs in one launch, invert the denominators out of place and form the running sums of a batch of arguments
+// in one launch chain (lookup.hip, vec.hip).  Read at the top of each stage: the tests flip it inside one process.
+static bool lookup_fused() { const char* e = getenv("ZK_LOOKUP_FUSED"); return !(e && atoi(e) == 0); }
+
+// The tuples k_lk_compress_many takes (what push_compressed would emit for them is the same polynomial): every element is a column
+// read at any rotation, a constant, or F * column / column * F with F a single column read.  Of two column reads under a product the
+// factor is the one all elements share (the first operands are tried before the second ones, as push_compressed does), else the
+// first.  Constants are appended to `consts`; the element's pointer is set once they have an address (flags: LK_ELEM_CONST, rot =
+// index into consts).  false: the tuple keeps run_program.
+static bool recognise_tuple(const Env& e, const std::vector<Prog>& exprs, LkTuple* d, std::vector<F4>* consts) {
+    if (exprs.empty() || exprs.size() > LK_TUPLE_MAX) return false;
+    const size_t consts0 = consts->size();
+    auto decline = [&] { consts->resize(consts0); return false; };
+    const size_t w = exprs.size();
+    bool all_products = true;
+    for (const Prog& g : exprs) {
+        const bool leaf = g.size() == 1 && (g[0].op == Q_PUSH_COL || g[0].op == Q_PUSH_CONST);
+        const bool product = g.size() == 3 && g[0].op == Q_PUSH_COL && g[1].op == Q_PUSH_COL && g[2].op == Q_MUL;
+        if (!leaf && !product) return false;
+        all_products = all_products && product;
+    }
+    int common = -1;          // operand (0 / 1) that is the same column read in every element
+    if (all_products && w >= 2)
+        for (int side = 0; side < 2 && common < 0; ++side) {
+            bool same = true;
+            for (size_t i = 1; i < w && same; ++i) same = exprs[i][side].a == exprs[0][side].a && exprs[i][side].b == exprs[0][side].b;
+            if (same) common = side;
+        }
+    memset((void*)d, 0, sizeof *d);
+    d->width = (uint32_t)w;
+    d->common = common >= 0;
+    for (size_t i = 0; i < w; ++i) {
+        const Prog& g = exprs[i];
+        if (g.size() == 1 && g[0].op == Q_PUSH_CONST) {
+            F4 v;
+            if (!resolve_const(e, g[0].a, &v)) return decline();
+            d->flags[i] = LK_ELEM_CONST;
+            d->rot[i] = (int32_t)consts->size();
+            consts->push_back(v);
+            continue;
+        }
+        const int fside = g.size() == 3 ? (common >= 0 ? common : 0) : -1;
+        const Instr& c = g.size() == 3 ? g[1 - fside] : g[0];
+        d->col[i] = (const Fr*)resolve_col(e, c.a);
+        d->rot[i] = (int32_t)c.b;
+        if (!d->col[i]) return decline();
+        if (fside >= 0) {
+            d->fac[i] = (const Fr*)resolve_col(e, g[fside].a);
+            d->frot[i] = (int32_t)g[fside].b;
+            if (!d->fac[i]) return decline();
+        }
+    }
+    return true;
+}
+
 // ---- lookups, round 1 (mv_lookup::prover::Argument::prepare): theta-compressed table and input tuples,
 // multiplicities m over ALL input tuples of the argument.  Every lookup is enqueued back to back
 // (compression programs, device hash join); one download of the status words, one pipelined batch
@@ -1555,33 +1612,73 @@ static int stage_lookup_multiplicities(Finish& f) {
             PK_ALLOC(ctx, f.lk_m[l], n * 32);
             mptrs[l] = f.lk_m[l].p;
         }
+        const bool fused = lookup_fused();
         uint32_t prev_l = 0;
         bool have_prev = false;
-        for (const uint32_t l : f.act) {
+        // every tuple the stage compresses: the recognised ones become descriptor rows (one upload, one launch), the others programs
+        std::vector<LkTuple> descs;
+        std::vector<F4> dconsts;
+        std::vector<Prog> table_prog(pk->L);
+        std::vector<std::vector<uint8_t>> by_program(pk->L);      // [l][0]: the table, [l][1 + a]: input a -- still to be compressed by run_program
+        for (const uint32_t l : f.act) { PB pt; push_compressed(pt, pk->lookups[l].tables); pt.fold(C_ONE); table_prog[l] = std::move(pt.g); }
+        // An argument reads the compressed table, the hash and the inverted denominators of the one taken before it when both name the
+        // same table.  The fused path takes the arguments table by table, so that holds for EVERY argument into a table, not only for
+        // neighbours (100 lookups into 3 tables, interleaved: 3 tables compressed, hashed and inverted instead of 100).  Every argument's m and
+        // phi depend on its own tuples alone, and commitments, blinding rows and checks go by argument index: the order is free.
+        f.lk_order = f.act;
+        if (fused) std::stable_sort(f.lk_order.begin(), f.lk_order.end(), [&](uint32_t x, uint32_t y) {
+            auto key = [](const Instr& in) { return std::make_tuple(in.op, in.a, in.b); };
+            return std::lexicographical_compare(table_prog[x].begin(), table_prog[x].end(), table_prog[y].begin(), table_prog[y].end(), [&](const Instr& p, const Instr& q) { return key(p) < key(q); });
+        });
+        for (const uint32_t l : f.lk_order) {
             const auto& lk = pk->lookups[l];
-            PB pt;
-            push_compressed(pt, lk.tables); pt.fold(C_ONE);
+            const Prog& tg = table_prog[l];
             // consecutive arguments into the same table (chunk_lookups() splits a table's inputs over as many arguments as the
             // degree bound needs; the EVM circuit's 80-odd lookups go into a dozen tables): one compressed table, one hash
             static const bool share_tables = !(getenv("ZK_LOOKUP_SHARE") && atoi(getenv("ZK_LOOKUP_SHARE")) == 0);      // measurement knob
-            f.same_table[l] = share_tables && have_prev && pt.g.size() == prev_table.size() && memcmp(pt.g.data(), prev_table.data(), pt.g.size() * sizeof(Instr)) == 0;
+            f.same_table[l] = share_tables && have_prev && tg.size() == prev_table.size() && memcmp(tg.data(), prev_table.data(), tg.size() * sizeof(Instr)) == 0;
             f.table_owner[l] = f.same_table[l] ? f.table_owner[prev_l] : l;
-            prev_table = pt.g;
+            prev_table = tg;
             prev_l = l; have_prev = true;
+            by_program[l].assign(1 + lk.inputs.size(), 1);
+            LkTuple d;
             if (!f.same_table[l]) {
                 PK_ALLOC(ctx, f.lk_t[l], n * 32);
-                PK_TRY(run_program(ctx, f.lag, pt.g, f.lk_t[l].p));
+                if (fused && recognise_tuple(f.lag, lk.tables, &d, &dconsts)) { d.dst = f.lk_t[l].fr(); descs.push_back(d); by_program[l][0] = 0; }
             }
             f.lk_f[l].resize(lk.inputs.size());
+            for (size_t a = 0; a < lk.inputs.size(); ++a) {
+                PK_ALLOC(ctx, f.lk_f[l][a], n * 32);
+                if (fused && recognise_tuple(f.lag, lk.inputs[a], &d, &dconsts)) { d.dst = f.lk_f[l][a].fr(); descs.push_back(d); by_program[l][1 + a] = 0; }
+            }
+        }
+        DevBuf dtab;
+        if (!descs.empty()) {          // descriptors and the constants they name: one upload for the stage
+            const size_t consts_at = descs.size() * sizeof(LkTuple);
+            PK_ALLOC(ctx, dtab, consts_at + dconsts.size() * 32 + 32);
+            const Fr* d_consts = (const Fr*)((const char*)dtab.p + consts_at);
+            for (LkTuple& d : descs)
+                for (uint32_t i = 0; i < d.width; ++i)
+                    if (d.flags[i] & LK_ELEM_CONST) { d.col[i] = d_consts + d.rot[i]; d.rot[i] = 0; }
+            std::vector<uint8_t> host(consts_at + dconsts.size() * 32);
+            memcpy(host.data(), descs.data(), consts_at);
+            if (!dconsts.empty()) memcpy(host.data() + consts_at, dconsts.data(), dconsts.size() * 32);
+            PK_TRY(zk_h2d(ctx, dtab.p, host.data(), host.size()));
+            PK_TRY(lookup_compress_many_enqueue(ctx, (const LkTuple*)dtab.p, descs.size(), &f.lag.theta, n));
+        }
+        for (const uint32_t l : f.lk_order) {
+            const auto& lk = pk->lookups[l];
+            if (!f.same_table[l] && by_program[l][0]) PK_TRY(run_program(ctx, f.lag, table_prog[l], f.lk_t[l].p));
             std::vector<const Fr*> fptrs;
             for (size_t a = 0; a < lk.inputs.size(); ++a) {
-                PB pf;
-                push_compressed(pf, lk.inputs[a]); pf.fold(C_ONE);
-                PK_ALLOC(ctx, f.lk_f[l][a], n * 32);
-                PK_TRY(run_program(ctx, f.lag, pf.g, f.lk_f[l][a].p));
+                if (by_program[l][1 + a]) {
+                    PB pf;
+                    push_compressed(pf, lk.inputs[a]); pf.fold(C_ONE);
+                    PK_TRY(run_program(ctx, f.lag, pf.g, f.lk_f[l][a].p));
+                }
                 fptrs.push_back(f.lk_f[l][a].fr());
             }
-            PK_TRY(lookup_multiplicities_enqueue(ctx, fptrs.data(), fptrs.size(), f.lk_t[f.table_owner[l]].fr(), pk->u, f.lk_m[l].fr(), n, (uint32_t*)status.p + l, f.same_table[l]));
+            PK_TRY(lookup_multiplicities_enqueue(ctx, fptrs.data(), fptrs.size(), f.lk_t[f.table_owner[l]].fr(), pk->u, f.lk_m[l].fr(), n, (uint32_t*)status.p + l, f.same_table[l], fused));
         }
         std::vector<uint32_t> st(pk->L);
         PK_TRY(zk_d2h(ctx, st.data(), status.p, (size_t)pk->L * 4));
@@ -1664,7 +1761,7 @@ static int stage_lookup_grand_sums(Finish& f) {
         // memory the arguments are processed in several such batches.
         std::vector<size_t> slot0(pk->L), tslot(pk->L), nslots(pk->L);
         DevBuf g, closing_d;
-        PK_ALLOC(ctx, g, n * 32); PK_ALLOC(ctx, closing_d, (size_t)pk->L * 32);
+        PK_ALLOC(ctx, closing_d, (size_t)pk->L * 32);
         std::vector<F4> blind((size_t)pk->L * pk->bf);
         for (size_t q = 0; q < blind.size(); ++q) blind[q] = rng.next_fr();            // argument by argument, row by row: the order they were always drawn in, on every rank
         std::vector<const void*> pptrs(pk->L);
@@ -1674,29 +1771,57 @@ static int stage_lookup_grand_sums(Finish& f) {
         }
         ZK_HIP(ctx, hipMemsetAsync(closing_d.p, 0, (size_t)pk->L * 32, ctx->stream));
         const size_t free_b = device_free_bytes();          // unknown counts as none: batches of four slots
-        const size_t max_slots = std::max<size_t>(4, (free_b + ctx->pool_bytes) / 4 / (n * 32));
-        const size_t NA = f.act.size();
+        size_t max_slots = std::max<size_t>(4, (free_b + ctx->pool_bytes) / 4 / (n * 32));
+        if (const char* e = getenv("ZK_LOOKUP_PHI_SLOTS")) { if (atol(e) > 0) max_slots = (size_t)atol(e); }      // test knob: several batches at small n
+        const bool fused = lookup_fused();
+        if (!fused) PK_ALLOC(ctx, g, n * 32);
+        const std::vector<uint32_t>& ord = f.lk_order;          // the order the multiplicities stage settled who shares whose table in
+        const size_t NA = ord.size();
         for (size_t j0 = 0; j0 < NA;) {
             // arguments act[j0 .. j1) share one inversion; an argument is never separated from the owner of its table
             size_t slots = 0;
             size_t j1 = j0;
             while (j1 < NA) {
-                const uint32_t l1 = f.act[j1];
+                const uint32_t l1 = ord[j1];
                 const size_t need = f.lk_f[l1].size() + (f.same_table[l1] && j1 > j0 ? 0 : 1);
                 if (j1 > j0 && slots + need > max_slots && !f.same_table[l1]) break;
                 slot0[l1] = slots;
-                tslot[l1] = (f.same_table[l1] && j1 > j0) ? tslot[f.act[j1 - 1]] : slots;
+                tslot[l1] = (f.same_table[l1] && j1 > j0) ? tslot[ord[j1 - 1]] : slots;
                 nslots[l1] = need;
                 slots += need;
                 ++j1;
             }
             DevBuf inv;
             PK_ALLOC(ctx, inv, slots * n * 32);
+            if (fused) {
+                // the denominators are inverted out of place (beta added at the load: no copy of the compressed columns), then ONE launch
+                // chain forms g and its running sum for every argument of the batch; both tables travel in one upload
+                std::vector<const void*> asrc(slots);
+                std::vector<LkSum> sums;
+                for (size_t j = j0; j < j1; ++j) {
+                    const uint32_t l = ord[j];
+                    const size_t N = f.lk_f[l].size();
+                    const bool own_t = tslot[l] == slot0[l];
+                    if (own_t) asrc[tslot[l]] = f.lk_t[f.table_owner[l]].p;
+                    for (size_t a = 0; a < N; ++a) asrc[slot0[l] + (own_t ? 1 : 0) + a] = f.lk_f[l][a].p;
+                    sums.push_back(LkSum{f.lk_m[l].fr(), (const Fr*)inv.p + tslot[l] * n, (const Fr*)inv.p + (slot0[l] + (own_t ? 1 : 0)) * n, f.lk_phi[l].fr(), (uint64_t)N});
+                }
+                const size_t sums_at = (slots * sizeof(void*) + 15) & ~(size_t)15;
+                std::vector<uint8_t> host(sums_at + sums.size() * sizeof(LkSum));
+                memcpy(host.data(), asrc.data(), slots * sizeof(void*));
+                memcpy(host.data() + sums_at, sums.data(), sums.size() * sizeof(LkSum));
+                DevBuf dtab;
+                PK_ALLOC(ctx, dtab, host.size());
+                PK_TRY(zk_h2d(ctx, dtab.p, host.data(), host.size()));
+                ZkProfScope prof(ctx, "lookup_phi_fused");
+                PK_TRY(fr_batch_invert_from(ctx, (const Fr* const*)dtab.p, &f.lag.beta, f.k, (Fr*)inv.p, slots));
+                PK_TRY(lookup_sums_enqueue(ctx, (const LkSum*)((const char*)dtab.p + sums_at), sums.size(), n));
+            } else {
             {   // t + beta and every f_a + beta of the batch, into their slots: ONE kind of launch for all of them (fr_add_const_many; each used to be a program of its own)
                 std::vector<const void*> asrc;
                 std::vector<void*> adst;
                 for (size_t j = j0; j < j1; ++j) {
-                    const uint32_t l = f.act[j];
+                    const uint32_t l = ord[j];
                     const size_t N = f.lk_f[l].size();
                     const bool own_t = tslot[l] == slot0[l];
                     for (size_t a = own_t ? 0 : 1; a <= N; ++a) {
@@ -1708,22 +1833,25 @@ static int stage_lookup_grand_sums(Finish& f) {
                 PK_TRY(fr_add_const_many(ctx, asrc.data(), adst.data(), asrc.size(), &f.lag.beta, n));
             }
             PK_TRY(zk_fr_batch_invert(ctx, inv.p, slots * n));
+            }
             for (size_t j = j0; j < j1; ++j) {
-                const uint32_t l = f.act[j];
+                const uint32_t l = ord[j];
                 DevBuf& phi = f.lk_phi[l];
                 const size_t N = f.lk_f[l].size();
                 const bool own_t = tslot[l] == slot0[l];
                 const char* inv_t = (const char*)inv.p + tslot[l] * n * 32;
                 const char* inv_f = (const char*)inv.p + (slot0[l] + (own_t ? 1 : 0)) * n * 32;
-                // g = sum_a inv_f_a - m * inv_t
-                PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_MUL, f.lk_m[l].p, inv_t, g.p, n));
-                PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_SUB, inv_f, g.p, g.p, n));
-                for (size_t a = 1; a < N; ++a) PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_ADD, g.p, inv_f + a * n * 32, g.p, n));
-                PK_TRY(zk_fr_prefix_sum(ctx, g.p, phi.p, n));                       // phi[0] = 0, phi[i+1] = phi[i] + g[i]
+                if (!fused) {
+                    // g = sum_a inv_f_a - m * inv_t
+                    PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_MUL, f.lk_m[l].p, inv_t, g.p, n));
+                    PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_SUB, inv_f, g.p, g.p, n));
+                    for (size_t a = 1; a < N; ++a) PK_TRY(zk_field_vec_op(ctx, ZK_FIELD_FR, ZK_OP_ADD, g.p, inv_f + a * n * 32, g.p, n));
+                    PK_TRY(zk_fr_prefix_sum(ctx, g.p, phi.p, n));                       // phi[0] = 0, phi[i+1] = phi[i] + g[i]
+                }
                 ZK_HIP(ctx, hipMemcpyAsync((char*)closing_d.p + (size_t)l * 32, (char*)phi.p + (size_t)pk->u * 32, 32, hipMemcpyDeviceToDevice, ctx->stream));
                 ZK_HIP(ctx, hipMemcpyAsync((char*)phi.p + (n - pk->bf) * 32, blind.data() + (size_t)l * pk->bf, (size_t)pk->bf * 32, hipMemcpyHostToDevice, ctx->stream));
                 f.lk_f[l].clear();                                                    // f, t are not needed again (the quotient recomputes them on its cosets)
-                if (j + 1 == NA || !f.same_table[f.act[j + 1]]) f.lk_t[f.table_owner[l]].release();      // the table's last reader
+                if (j + 1 == NA || !f.same_table[ord[j + 1]]) f.lk_t[f.table_owner[l]].release();      // the table's last reader
             }
             j0 = j1;
         }

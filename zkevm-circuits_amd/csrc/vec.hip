@@ -70,7 +70,11 @@ __device__ __forceinline__ Fr29 shfl29(const Fr29& v, int src) {
     return r;
 }
 // inv29_rp (csrc/ff29.hip.hpp): 1 / b for b in R' form, result in R' form with c783 = 2^783
-__global__ void __launch_bounds__(256) k_batch_invert(Fr* __restrict__ a, uint64_t n, uint64_t nt, Fr c783_plain) {
+// FROM: out of place -- element i of `a` is read as src[i >> log_n][i mod 2^log_n] + beta (the logUp denominators: the compressed
+// columns stay where they are, no copy with beta added is made first); the lanes' elements, the products and the one inversion
+// per wave are the same either way.
+template <bool FROM>
+__global__ void __launch_bounds__(256) k_batch_invert(Fr* __restrict__ a, uint64_t n, uint64_t nt, Fr c783_plain, const Fr* const* __restrict__ src, uint32_t log_n, Fr beta) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;                       // nt is a multiple of 64: whole waves leave
     const uint32_t lane = threadIdx.x & 63u;
@@ -80,7 +84,12 @@ __global__ void __launch_bounds__(256) k_batch_invert(Fr* __restrict__ a, uint64
 #pragma unroll
     for (int k = 0; k < BI_K; ++k) {           // every load in flight before the first product
         const uint64_t i = (uint64_t)k * nt + t;
-        x[k] = i < n ? ldg(a + i) : Fr::zero();
+        if (FROM) x[k] = i < n ? ldg(src[i >> log_n] + (i & (((uint64_t)1 << log_n) - 1))) : Fr::zero();
+        else x[k] = i < n ? ldg(a + i) : Fr::zero();
+    }
+    if (FROM) {
+#pragma unroll
+        for (int k = 0; k < BI_K; ++k) if ((uint64_t)k * nt + t < n) x[k] = x[k] + beta;
     }
     Fr29 v[BI_K], pre[BI_K];
     Fr29 acc = one_rp;
@@ -109,8 +118,11 @@ __global__ void __launch_bounds__(256) k_batch_invert(Fr* __restrict__ a, uint64
     const Fr29 one_r = unpack29<Fr29P>(Fr::one());                     // x 2^256 / 2^261: R' -> R on the way out
 #pragma unroll
     for (int k = BI_K; k-- > 0;) {
-        if (x[k].is_zero()) continue;
         const uint64_t i = (uint64_t)k * nt + t;
+        if (x[k].is_zero()) {                  // stays zero: in place it is there already
+            if (FROM && i < n) stg(a + i, Fr::zero());
+            continue;
+        }
         stg(a + i, pack29_lt2p(mul29(mul29(iv, pre[k]), one_r)));
         iv = mul29(iv, v[k]);
     }
@@ -209,6 +221,128 @@ static int scan_run(zk_ctx* ctx, const Fr* d_a, Fr* d_z, uint64_t n) {
         hipLaunchKernelGGL((k_scan_c<Op>), dim3(blocks), dim3(SCAN_THREADS), 0, ctx->stream, d_z, totals, n);
         ZK_CHECK_LAUNCH(ctx);
     }
+    return ZK_OK;
+}
+
+// ---- the logUp running sums of a batch of lookup arguments (stage_lookup_grand_sums, prover.hip) ---------------------------
+// phi[0] = 0, phi[i + 1] = phi[i] + g[i] with g = sum_a inv_f_a - m inv_t formed on the fly: the N + 2 input arrays are read
+// once and phi is written once (as vector ops and a scan of their result that was N + 1 passes of two reads and a write, then
+// the scan's four).  Three launches for ALL arguments of the batch, the argument on a grid dimension:
+//   A: a block takes a segment of SCAN_THREADS * SCAN_PER rows in SCAN_PER sweeps, thread t the row sweep * SCAN_THREADS + t --
+//      neighbouring lanes on neighbouring rows, every load coalesced; a shuffle scan inside each wave, the SCAN_PER x 4 wave
+//      totals scanned by the first wave; writes the locally prefixed phi and the segment's total
+//   B: one block per argument scans its segment totals
+//   C: phi[i] += offset of its segment
+__device__ __forceinline__ Fr shfl_up_fr(const Fr& v, int off) {
+    Fr r;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r.l[k] = __shfl_up(v.l[k], off);
+    return r;
+}
+// inclusive sums over the lanes of a wave
+__device__ __forceinline__ Fr wave_inclusive_sum(Fr v, uint32_t lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const Fr u = shfl_up_fr(v, off);
+        if (lane >= (uint32_t)off) v = v + u;
+    }
+    return v;
+}
+constexpr int LKS_WAVES = SCAN_THREADS / 64;
+__global__ void __launch_bounds__(SCAN_THREADS) k_lk_sum_a(const LkSum* __restrict__ args, Fr* __restrict__ totals, uint32_t blocks, uint64_t n) {
+    __shared__ Fr wtot[SCAN_PER * LKS_WAVES], woff[SCAN_PER * LKS_WAVES];
+    static_assert(SCAN_PER * LKS_WAVES <= 64, "one wave scans the wave totals");
+    const LkSum d = args[blockIdx.y];
+    const uint64_t seg = (uint64_t)blockIdx.x * (SCAN_THREADS * SCAN_PER);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    Fr ex[SCAN_PER];
+#pragma unroll
+    for (int k = 0; k < SCAN_PER; ++k) {
+        const uint64_t i = seg + (uint64_t)k * SCAN_THREADS + threadIdx.x;
+        Fr g = Fr::zero();
+        if (i < n) {
+            const Fr mt = ldg(d.m + i), it = ldg(d.inv_t + i);
+            g = ldg(d.inv_f + i);
+            for (uint64_t a = 1; a < d.N; ++a) g = g + ldg(d.inv_f + a * n + i);
+            g = g - mt * it;
+        }
+        const Fr inc = wave_inclusive_sum(g, lane);
+        ex[k] = inc - g;                              // exclusive inside the wave
+        if (lane == 63u) wtot[k * LKS_WAVES + wave] = inc;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const Fr v = lane < SCAN_PER * LKS_WAVES ? wtot[lane] : Fr::zero();
+        const Fr inc = wave_inclusive_sum(v, lane);
+        if (lane < SCAN_PER * LKS_WAVES) woff[lane] = inc - v;
+        if (lane == 63u) stg(totals + (size_t)blockIdx.y * blocks + blockIdx.x, inc);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SCAN_PER; ++k) {
+        const uint64_t i = seg + (uint64_t)k * SCAN_THREADS + threadIdx.x;
+        if (i < n) stg(d.phi + i, woff[k * LKS_WAVES + wave] + ex[k]);
+    }
+}
+// exclusive scan of every argument's `cnt` segment totals in place (k_scan_b, one block per argument)
+__global__ void __launch_bounds__(SCAN_THREADS) k_lk_sum_b(Fr* totals, uint32_t cnt) {
+    __shared__ Fr sh[SCAN_THREADS];
+    totals += (size_t)blockIdx.x * cnt;
+    Fr carry = Fr::zero();
+    for (uint32_t base = 0; base < cnt; base += SCAN_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        Fr v = i < cnt ? ldg(totals + i) : Fr::zero();
+        Fr total;
+        Fr ex = block_exclusive_scan<OpAdd>(v, sh, &total);
+        if (i < cnt) stg(totals + i, carry + ex);
+        carry = carry + total;
+    }
+}
+__global__ void __launch_bounds__(SCAN_THREADS) k_lk_sum_c(const LkSum* __restrict__ args, const Fr* __restrict__ offs, uint32_t blocks, uint64_t n) {
+    if (blockIdx.x == 0) return;   // the first segment's offset is zero
+    Fr* __restrict__ z = args[blockIdx.y].phi;
+    const Fr off = ldg(offs + (size_t)blockIdx.y * blocks + blockIdx.x);
+    const uint64_t seg = (uint64_t)blockIdx.x * (SCAN_THREADS * SCAN_PER);
+#pragma unroll
+    for (int k = 0; k < SCAN_PER; ++k) {
+        const uint64_t i = seg + (uint64_t)k * SCAN_THREADS + threadIdx.x;
+        if (i < n) stg(z + i, off + ldg(z + i));
+    }
+}
+int lookup_sums_enqueue(zk_ctx* ctx, const LkSum* d_args, size_t count, size_t n) {
+    if (!count || !n) return ZK_OK;
+    const uint64_t blocks64 = ((uint64_t)n + SCAN_THREADS * SCAN_PER - 1) / (SCAN_THREADS * SCAN_PER);
+    if (blocks64 > 0x7FFFFFFFull) return ctx->fail(ZK_ERR_INVALID_ARG, "lookup sums: %zu rows exceed one launch", n);
+    const uint32_t blocks = (uint32_t)blocks64;
+    for (size_t c0 = 0; c0 < count; c0 += 65535) {          // gridDim.y; the totals are reused by the next chunk: same stream, so ordered
+        const unsigned cnt = (unsigned)std::min<size_t>(65535, count - c0);
+        Fr* totals = (Fr*)ctx->get_scratch(SC_POLY2, sizeof(Fr) * (size_t)blocks * cnt);
+        if (!totals) return ZK_ERR_OOM;
+        hipLaunchKernelGGL(k_lk_sum_a, dim3(blocks, cnt), dim3(SCAN_THREADS), 0, ctx->stream, d_args + c0, totals, blocks, (uint64_t)n);
+        ZK_CHECK_LAUNCH(ctx);
+        if (blocks > 1) {
+            hipLaunchKernelGGL(k_lk_sum_b, dim3(cnt), dim3(SCAN_THREADS), 0, ctx->stream, totals, blocks);
+            ZK_CHECK_LAUNCH(ctx);
+            hipLaunchKernelGGL(k_lk_sum_c, dim3(blocks, cnt), dim3(SCAN_THREADS), 0, ctx->stream, d_args + c0, (const Fr*)totals, blocks, (uint64_t)n);
+            ZK_CHECK_LAUNCH(ctx);
+        }
+    }
+    return ZK_OK;
+}
+// d_inv[s 2^log_n + i] = 1 / (d_src[s][i] + beta) for `slots` columns of 2^log_n rows (zero where the sum is zero); d_src lies on the device
+int fr_batch_invert_from(zk_ctx* ctx, const Fr* const* d_src, const void* h_beta, uint32_t log_n, Fr* d_inv, size_t slots) {
+    if (!slots) return ZK_OK;
+    if (log_n > 31) return ctx->fail(ZK_ERR_INVALID_ARG, "batch inversion: 2^%u rows per column", log_n);
+    const uint64_t n = (uint64_t)slots << log_n;
+    uint64_t nt = (n + BI_K - 1) / BI_K;
+    nt = (nt + 63) / 64 * 64;
+    if ((nt + 255) / 256 > 0x7FFFFFFFull) return ctx->fail(ZK_ERR_INVALID_ARG, "batch inversion: %zu columns of 2^%u rows exceed one launch", slots, log_n);
+    Fr beta;
+    memcpy(&beta, h_beta, sizeof beta);
+    Fr c783 = Fr::one();                                           // the integer 2^783 mod r (Fr::one() holds 2^256)
+    for (int i = 0; i < 783 - 256; ++i) c783 = dbl(c783);
+    hipLaunchKernelGGL(k_batch_invert<true>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, d_inv, n, nt, c783, d_src, log_n, beta);
+    ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
 
@@ -1451,7 +1585,7 @@ int zk_fr_batch_invert(zk_ctx* ctx, void* d_a, size_t n) {
     uint64_t nt = (n + BI_K - 1) / BI_K;
     nt = (nt + 63) / 64 * 64;
     static const Fr c783 = [] { Fr c = Fr::one(); for (int i = 0; i < 783 - 256; ++i) c = dbl(c); return c; }();      // the integer 2^783 mod r (Fr::one() holds 2^256)
-    hipLaunchKernelGGL(k_batch_invert, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, (Fr*)d_a, (uint64_t)n, nt, c783);
+    hipLaunchKernelGGL(k_batch_invert<false>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, ctx->stream, (Fr*)d_a, (uint64_t)n, nt, c783, (const Fr* const*)nullptr, 0u, Fr::zero());
     ZK_CHECK_LAUNCH(ctx);
     return ZK_OK;
 }
