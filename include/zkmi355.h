@@ -97,6 +97,31 @@ typedef struct zk_sha256 {
     uint8_t     index_width;  /* 4 or 8: width of an offset and of a length */
     uint8_t     flags;        /* must be 0 */
 } zk_sha256;
+/* the stable sort of 64-byte key records of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct, whose pointers
+ * are device pointers */
+#define ZK_OP_KEY_SORT 20
+typedef struct zk_key_sort {
+    const void* d_keys;    /* device: n records of 64 B, 8-byte aligned */
+    void*       d_sorted;  /* device, n x 64 B, 8-byte aligned, or NULL: the records in sorted order */
+    uint8_t     flags;     /* must be 0 */
+} zk_key_sort;
+/* the ordering witness of adjacent key records of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct; cols and
+ * d_cols are HOST arrays, every other pointer is a device pointer */
+#define ZK_OP_KEY_ORDER 22
+typedef struct zk_key_col { uint8_t offset; uint8_t width; } zk_key_col;   /* key bytes [offset, offset + width), width 1, 2 or 4 */
+typedef struct zk_key_order {
+    const void* d_keys;        /* device: n records of 64 B, 8-byte aligned */
+    const void* d_perm;        /* device: n x uint32, 4-byte aligned, or NULL; row i is record d_perm[i] (NULL: record i) */
+    void*       d_diff;        /* device, n x 32 B Montgomery Fr, or NULL: limb_difference */
+    void*       d_index;       /* device, n bytes, or NULL: first_different_limb, 0..31 */
+    void*       d_bits;        /* device, 5 x n bytes, or NULL: plane b (n bytes at d_bits + b * n) holds bit (4 - b) of the index */
+    void*       d_not_first;   /* device, n bytes, or NULL: index >= group_limbs ? 1 : 0 */
+    uint32_t    group_limbs;   /* 0..32; 30 for the state circuit: a difference in RwCounter1 or RwCounter0 alone is not a first access */
+    uint32_t    count;         /* gathered columns, at most 64 */
+    const zk_key_col* cols;    /* HOST array of count entries */
+    void* const* d_cols;       /* HOST array of count device pointers: n cells of cols[j].width bytes, aligned to that width */
+    uint8_t     flags;         /* must be 0 */
+} zk_key_order;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -297,6 +322,49 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * message's length in bits would not fit the 64-bit length field of the padding.  One lane walks one message, so a wave takes as
  * long as its longest message.  Booked under the zk_prof name "fr_sha256" with n * (2 * index_width + 32 + 32 per optional output
  * given) + total_bytes algorithmic bytes per call.
+ * ZK_OP_KEY_SORT and ZK_OP_KEY_ORDER (#defines, values 20 and 22 -- 19 and 21 stay refused, like 11, 13, 15 and 17; Fr only) put the
+ * rows of the reference's RW table into the state circuit's order and make the ordering witness of adjacent rows, on the device.
+ * Both work on n KEY RECORDS of 64 bytes at d_keys (8-byte aligned), compared as big-endian 512-bit integers, byte 0 most significant;
+ * limb j (0..31) of a record is the big-endian 16-bit number in bytes 2j, 2j + 1.  The ops give no byte a meaning.  For the state
+ * circuit a record is what rw_to_be_limbs packs (state_circuit/lexicographic_ordering.rs): byte 0 zero, 1 tag, 2-5 id (big-endian),
+ * 6-25 address, 26 zero, 27 field_tag, 28-59 storage_key (big-endian), 60-63 rw_counter (big-endian); the limb index is then the
+ * reference's LimbIndex, Tag = 0, Id1 = 1, ..., RwCounter1 = 30, RwCounter0 = 31.  d_a is a HOST pointer to the descriptor, read
+ * before the call returns; the calls are asynchronous on the context's stream and never wait for the device.
+ * ZK_OP_KEY_SORT: d_a points to a zk_key_sort {d_keys, d_sorted, flags}; d_b is NULL or a HOST pointer to a 64-byte mask, key byte j
+ * takes part in the comparison if and only if mask[j] != 0 (NULL: all 64 take part); d_out is n x 4 B, 4-byte aligned, and d_out[i] is
+ * the uint32 index of the record that stands at place i of the order; d_sorted (n x 64 B, 8-byte aligned, or NULL) receives the
+ * records themselves in that order.  The sort is stable: records that agree in every compared byte keep their input order, and the
+ * result is a pure function of the input (no placement depends on the order in which atomics arrive).  A mask without bytes 60-63
+ * gives the reference's sort_by_cached_key(Rw::as_key) over rows handed over in rw_counter order; the full mask gives the same order
+ * whenever the counters are distinct.  It is a least-significant-digit radix sort of the permutation, one key byte per pass from byte
+ * 63 up to byte 0 over the bytes the mask keeps; a byte position at which all records agree is found on the device and its pass does
+ * nothing.  Temporaries (two index buffers and 256 counts per 2048 records) come from the context's scratch, which grows on demand.
+ * Booked under the zk_prof name "key_sort" with n * (76 + 14 per kept mask byte + 128 with d_sorted) algorithmic bytes per call: 64 +
+ * 4 for the first look at the records, per pass an index and a key byte read twice and an index written, 4 + 4 for d_out, 64 + 64 for
+ * d_sorted.
+ * ZK_OP_KEY_ORDER: d_a points to a zk_key_order {d_keys, d_perm, d_diff, d_index, d_bits, d_not_first, group_limbs, count, cols,
+ * d_cols, flags}; d_b must be NULL; d_out is n x 32 B.  Row i is record d_perm[i] (d_perm NULL: record i).  For 1 <= i < n, with j the
+ * first limb at which the records of rows i and i - 1 differ:
+ *   d_index[i]     (n bytes, or NULL) = j, the reference's first_different_limb
+ *   d_bits         (5 x n bytes, or NULL) plane b, the n bytes at d_bits + b * n, holds bit (4 - b) of j: the BinaryNumberChip's five
+ *                  columns, plane 0 the most significant bit (AsBits<5>)
+ *   d_diff[i]      (n x 32 B, or NULL) = cur_j - prev_j in Fr, limb_difference; r - d when the rows are out of order
+ *   d_out[i]       = d_diff[i]^-1, limb_difference_inverse
+ *   d_not_first[i] (n bytes, or NULL) = j >= group_limbs ? 1 : 0; group_limbs 30 gives the state circuit's not_first_access
+ * All Fr outputs are canonical Montgomery.  Two equal records give index 31, difference 0, inverse 0 and not_first 1 for group_limbs
+ * <= 31, without an error.  Row 0 has no predecessor and writes 0 to every one of these outputs.  d_perm is device data that the host
+ * never sees: a row whose index, or whose predecessor's index, is >= n writes 0 to every one of these outputs and reads no record;
+ * nothing outside [d_keys, d_keys + 64 n) is ever read.  The gathered columns: cols and d_cols are HOST arrays of count <= 64 entries;
+ * cell i of column c is the big-endian integer of key bytes [cols[c].offset, cols[c].offset + cols[c].width) of row i's record, stored
+ * little-endian at width (1, 2 or 4) bytes at d_cols[c], a typed cell column ready for zk_proof_advice_phase_typed_dev.  Row 0 is
+ * included; a row whose own index is >= n writes 0.  The inverse is a lookup in the inverses of 1..65535, which the context makes on
+ * the device at the first call and keeps (2 MB).  Booked under the zk_prof name "key_order" with n * (192 + 8 with d_perm + 32 with
+ * d_diff + 1 with d_index + 5 with d_bits + 1 with d_not_first + the sum of the column widths) algorithmic bytes per call.
+ * For both ops ZK_FIELD_FQ, nonzero flags, NULL d_a, d_keys or d_out, a misaligned pointer (d_keys, d_sorted 8; d_out of the sort and
+ * d_perm 4; d_out of the order and d_diff 16; a gathered column its width), n >= 2^32, a zk_key_col with a width other than 1, 2 or 4
+ * or offset + width > 64, count > 64, NULL cols or d_cols with count > 0, a NULL entry of d_cols, group_limbs > 32, a non-NULL d_b for
+ * ZK_OP_KEY_ORDER, any overlap between an output and any input or another output (d_sorted may not be d_keys): ZK_ERR_INVALID_ARG
+ * before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

@@ -207,6 +207,26 @@ inline void sha256(const Context& c, const void* d_bytes, uint64_t total_bytes, 
     const zk_sha256 desc{d_bytes, total_bytes, d_offsets, d_lens, d_digest, d_input_rlc, index_bytes, 0};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_SHA256, &desc, host, d_out, n));
 }
+// The state circuit's row order: d_perm_out[i] = the uint32 index of the record at place i when the n 64-byte key records at d_keys
+// (what rw_to_be_limbs packs of an RW row) are sorted as big-endian integers, stably (zk_field_vec_op with ZK_OP_KEY_SORT and a
+// zk_key_sort; asynchronous on the context's stream).  mask: nullptr (all 64 bytes take part) or 64 host bytes, key byte j takes part
+// iff mask[j] != 0 -- without bytes 60..63 this is sort_by_cached_key(Rw::as_key) over rows in rw_counter order.  d_sorted: optional
+// n x 64 B, the records in that order.
+inline void key_sort(const Context& c, const void* d_keys, size_t n, void* d_perm_out, const uint8_t* mask = nullptr, void* d_sorted = nullptr) {
+    const zk_key_sort desc{d_keys, d_sorted, 0};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_KEY_SORT, &desc, mask, d_perm_out, n));
+}
+// The ordering witness of adjacent rows, row i = record d_perm[i] (nullptr: record i): d_inv_out = limb_difference_inverse, and
+// optionally limb_difference, first_different_limb as bytes and as the BinaryNumberChip's five bit planes, not_first_access
+// (first_different_limb >= group_limbs) and `count` gathered typed columns -- cell i of column j is the big-endian integer of key
+// bytes [cols[j].offset, cols[j].offset + cols[j].width) of row i's record (zk_field_vec_op with ZK_OP_KEY_ORDER and a zk_key_order).
+// cols and d_cols are host arrays.  No output overlaps an input or another output.
+inline void key_order(const Context& c, const void* d_keys, size_t n, void* d_inv_out, const void* d_perm = nullptr, void* d_diff = nullptr, void* d_index = nullptr,
+                      void* d_bits = nullptr, void* d_not_first = nullptr, uint32_t group_limbs = 30, uint32_t count = 0, const zk_key_col* cols = nullptr,
+                      void* const* d_cols = nullptr) {
+    const zk_key_order desc{d_keys, d_perm, d_diff, d_index, d_bits, d_not_first, group_limbs, count, cols, d_cols, 0};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_KEY_ORDER, &desc, nullptr, d_inv_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -140,6 +140,42 @@ pub struct zk_sha256 {
     pub index_width: u8,
     pub flags: u8,
 }
+/// `zk_field_vec_op` op: the stable sort of `n` 64-byte key records (what `rw_to_be_limbs` packs of an RW row), as a permutation --
+/// `d_out[i]` is the `u32` index of the record at place `i`.  For this op `d_a` is a HOST pointer to a `zk_key_sort` and `d_b` is
+/// null or a HOST pointer to a 64-byte mask: key byte `j` takes part iff `mask[j] != 0`.
+pub const ZK_OP_KEY_SORT: c_int = 20;
+/// `zk_key_sort`: `d_sorted` may be null.  `flags` must be 0.
+#[repr(C)]
+pub struct zk_key_sort {
+    pub d_keys: *const c_void,
+    pub d_sorted: *mut c_void,
+    pub flags: u8,
+}
+/// `zk_field_vec_op` op: the ordering witness of adjacent key records -- `d_out[i]` is `limb_difference_inverse` of rows `i` and
+/// `i - 1`.  For this op `d_a` is a HOST pointer to a `zk_key_order` and `d_b` must be null.
+pub const ZK_OP_KEY_ORDER: c_int = 22;
+/// `zk_key_col`: key bytes `[offset, offset + width)` of a gathered column, width 1, 2 or 4.
+#[repr(C)]
+pub struct zk_key_col {
+    pub offset: u8,
+    pub width: u8,
+}
+/// `zk_key_order`: `cols` and `d_cols` are HOST arrays of `count <= 64` entries; every other pointer is a device pointer, and all
+/// but `d_keys` may be null.  `group_limbs` is 30 for the state circuit.  `flags` must be 0.
+#[repr(C)]
+pub struct zk_key_order {
+    pub d_keys: *const c_void,
+    pub d_perm: *const c_void,
+    pub d_diff: *mut c_void,
+    pub d_index: *mut c_void,
+    pub d_bits: *mut c_void,
+    pub d_not_first: *mut c_void,
+    pub group_limbs: u32,
+    pub count: u32,
+    pub cols: *const zk_key_col,
+    pub d_cols: *const *mut c_void,
+    pub flags: u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

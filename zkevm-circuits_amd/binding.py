@@ -30,6 +30,8 @@ OP_POSEIDON = 14                                      # out[i] = permute(state o
 POSEIDON_FINAL = 1                                    # zk_poseidon.flags: every row of a message holds the hash of its last row
 OP_KECCAK = 16                                        # out[i] = output_rlc of Keccak-256(message i), messages as bytes on the device, Fr only (ZK_OP_KECCAK)
 OP_SHA256 = 18                                        # out[i] = output_rlc of SHA-256(message i), messages as bytes on the device, Fr only (ZK_OP_SHA256)
+OP_KEY_SORT = 20                                      # out[i] = index of the 64-byte key record at place i of the stable order (ZK_OP_KEY_SORT)
+OP_KEY_ORDER = 22                                     # out[i] = limb_difference_inverse of key records i and i - 1 in row order (ZK_OP_KEY_ORDER)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -114,6 +116,24 @@ class _Sha256(ctypes.Structure):
     device pointer or NULL)"""
     _fields_ = [("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p), ("d_lens", ctypes.c_void_p),
                 ("d_digest", ctypes.c_void_p), ("d_input_rlc", ctypes.c_void_p), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+class _KeySort(ctypes.Structure):
+    """zk_key_sort: the records and the optional sorted copy of ZK_OP_KEY_SORT (host memory; both pointers are device pointers)"""
+    _fields_ = [("d_keys", ctypes.c_void_p), ("d_sorted", ctypes.c_void_p), ("flags", ctypes.c_uint8)]
+
+
+class _KeyCol(ctypes.Structure):
+    """zk_key_col: key bytes [offset, offset + width) of a gathered column of ZK_OP_KEY_ORDER"""
+    _fields_ = [("offset", ctypes.c_uint8), ("width", ctypes.c_uint8)]
+
+
+class _KeyOrder(ctypes.Structure):
+    """zk_key_order: the records, the row order and the outputs of ZK_OP_KEY_ORDER (host memory; cols and d_cols are host arrays, every
+    other pointer is a device pointer or NULL)"""
+    _fields_ = [("d_keys", ctypes.c_void_p), ("d_perm", ctypes.c_void_p), ("d_diff", ctypes.c_void_p), ("d_index", ctypes.c_void_p),
+                ("d_bits", ctypes.c_void_p), ("d_not_first", ctypes.c_void_p), ("group_limbs", ctypes.c_uint32), ("count", ctypes.c_uint32),
+                ("cols", ctypes.POINTER(_KeyCol)), ("d_cols", ctypes.POINTER(ctypes.c_void_p)), ("flags", ctypes.c_uint8)]
 
 
 def _host_ptr(a: np.ndarray):
@@ -828,6 +848,40 @@ class Context:
         r[1] = r[0] if r_in is None else np.asarray(r_in, dtype=np.uint64).reshape(4)
         desc = _Sha256(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_SHA256, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
+    def key_sort(self, keys, n, perm_out, mask=None, sorted_keys=None):
+        """perm_out[i] = the uint32 index of the record that stands at place i when the n 64-byte key records at keys are sorted as
+        big-endian 512-bit integers, stably (zk_field_vec_op with ZK_OP_KEY_SORT).  keys, perm_out, sorted_keys: DeviceBuffers or
+        device pointers; keys and sorted_keys 8-byte aligned, perm_out n x 4 B.  mask: None (all 64 bytes take part) or 64 bytes,
+        key byte j takes part if and only if mask[j] != 0; without bytes 60-63 the order is the reference's
+        sort_by_cached_key(Rw::as_key) over rows handed over in rw_counter order.  sorted_keys: optional n x 64 B, the records in
+        sorted order.  No output may overlap the records or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        desc = _KeySort(ptr_of(keys), ptr_of(sorted_keys), 0)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.frombuffer(bytes(mask), dtype=np.uint8) if isinstance(mask, (bytes, bytearray)) else np.asarray(mask, dtype=np.uint8))
+            if m.shape != (64,):
+                raise ValueError("the key mask has 64 bytes")
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_KEY_SORT, ctypes.byref(desc), None if m is None else _host_ptr(m), ctypes.c_void_p(ptr_of(perm_out)), ctypes.c_size_t(n)))
+
+    def key_order(self, keys, n, inv_out, perm=None, diff=None, index=None, bits=None, not_first=None, group_limbs=30, cols=None):
+        """The ordering witness of adjacent key records (zk_field_vec_op with ZK_OP_KEY_ORDER).  Row i is record perm[i] (perm None:
+        record i); for 1 <= i < n, with j the first 16-bit big-endian limb at which the records of rows i and i - 1 differ: index[i] = j
+        (n bytes), bits plane b (n bytes at bits + b * n) = bit (4 - b) of j, diff[i] = cur_j - prev_j (n x 32 B Montgomery Fr),
+        inv_out[i] = diff[i]^-1 (n x 32 B), not_first[i] = j >= group_limbs (n bytes; 30: the state circuit's not_first_access).
+        Equal records give index 31, difference and inverse 0; row 0, and a row whose index or whose predecessor's index is >= n,
+        writes 0 to all of these.  cols: a list of (offset, width, buffer): cell i of the buffer (n cells of width 1, 2 or 4 bytes)
+        becomes the big-endian integer of key bytes [offset, offset + width) of row i's record, stored little-endian -- a typed cell
+        column; a row whose own index is >= n writes 0.  keys, inv_out, perm, diff, index, bits, not_first and the column buffers:
+        DeviceBuffers or device pointers.  No output may overlap an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        cols = list(cols or [])
+        table = (_KeyCol * max(1, len(cols)))(*[_KeyCol(off, width) for off, width, _ in cols])
+        ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[ptr_of(buf) for _, _, buf in cols])
+        desc = _KeyOrder(ptr_of(keys), ptr_of(perm), ptr_of(diff), ptr_of(index), ptr_of(bits), ptr_of(not_first), group_limbs, len(cols),
+                         table if cols else None, ptrs if cols else None, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_KEY_ORDER, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(inv_out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

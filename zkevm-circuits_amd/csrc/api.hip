@@ -98,6 +98,7 @@ void zk_ctx_destroy(zk_ctx* ctx) {
     ctx->domains.clear();
     for (auto& kv : ctx->pow_tables) (void)hipFree(kv.second);
     if (ctx->poseidon_tab) (void)hipFree(ctx->poseidon_tab);
+    if (ctx->key_inv_tab) (void)hipFree(ctx->key_inv_tab);
     for (auto& kv : ctx->loop_records) (void)hipFree(kv.second);
     ctx->pool_trim();
     ctx->prof_resolve();

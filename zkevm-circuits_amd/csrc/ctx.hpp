@@ -33,7 +33,7 @@ struct zk_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipDeviceProp_t prop{};
     // scratch arenas, grown on demand (never shrunk): index = purpose
-    zk::Scratch scratch[19];
+    zk::Scratch scratch[20];
     // side stream + events for pipelining consecutive MSMs (msm.hip): created on first use
     hipStream_t stream2 = nullptr, stream2b = nullptr, stream2c = nullptr;
     std::vector<hipStream_t> owned_streams;      // every stream zk_ctx_create made (roles may share one; 'd' entries of the layout have no role at all)
@@ -73,6 +73,7 @@ struct zk_ctx {
     std::map<uint64_t, std::shared_ptr<zk::NttDomain>> domains;   // key: log_n | kind << 8
     std::map<uint64_t, void*> pow_tables;                         // cached two-level power tables of the coset generators
     void* poseidon_tab = nullptr;                                 // the width-3 Poseidon constants as limb records (poseidon.hip), built on first use
+    void* key_inv_tab = nullptr;                                  // the inverses of 0..65535 as Montgomery Fr (keysort.hip: ZK_OP_KEY_ORDER), made on the device at first use
     std::map<const void*, void*> loop_records;                    // measurement only (ZK_QUOTIENT_LOOP_RECORDS, quotient.hip): column buffer -> its image as a coset record buffer
     std::vector<void*> pinned;   // small pinned host staging buffers
     // Device block pool for the prover's column buffers: a proof allocates and frees hundreds of
@@ -214,7 +215,7 @@ struct zk_srs {
     } while (0)
 
 namespace zk {
-enum ScratchSlot { SC_NTT = 0, SC_MSM_KEYS = 1, SC_MSM_BUCKETS = 2, SC_MSM_MISC = 3, SC_POLY = 4, SC_POLY2 = 5, SC_TMP = 6, SC_TMP2 = 7, SC_MSM_BUCKETS2 = 8, SC_MSM_RESULTS = 9, SC_QTMP = 10, SC_COMM = 11, SC_MSM_BUCKETS3 = 12, SC_MSM_BUCKETS4 = 13, SC_MSM_DESC = 14, SC_MSM_TAILS = 15, SC_NTT_AUX = 16, SC_QACC = 17, SC_QSLICE = 18 };
+enum ScratchSlot { SC_NTT = 0, SC_MSM_KEYS = 1, SC_MSM_BUCKETS = 2, SC_MSM_MISC = 3, SC_POLY = 4, SC_POLY2 = 5, SC_TMP = 6, SC_TMP2 = 7, SC_MSM_BUCKETS2 = 8, SC_MSM_RESULTS = 9, SC_QTMP = 10, SC_COMM = 11, SC_MSM_BUCKETS3 = 12, SC_MSM_BUCKETS4 = 13, SC_MSM_DESC = 14, SC_MSM_TAILS = 15, SC_NTT_AUX = 16, SC_QACC = 17, SC_QSLICE = 18, SC_KEYSORT = 19 };
 
 // host-side field helpers (slow path, used for constants / tables only)
 Fr fr_from_u64(uint64_t v);
@@ -243,6 +244,8 @@ int fr_scale_run(zk_ctx* ctx, Fr* d_a, const Fr& s, uint64_t n);
 int fr_poseidon_run(zk_ctx* ctx, const zk_poseidon* desc, const void* h_scale, Fr* d_out, uint64_t n);   // poseidon.hip: ZK_OP_POSEIDON of zk_field_vec_op
 int fr_keccak_run(zk_ctx* ctx, const zk_keccak* desc, const void* h_challenges, Fr* d_out, uint64_t n);   // keccak.hip: ZK_OP_KECCAK of zk_field_vec_op
 int fr_sha256_run(zk_ctx* ctx, const zk_sha256* desc, const void* h_challenges, Fr* d_out, uint64_t n);   // sha256.hip: ZK_OP_SHA256 of zk_field_vec_op
+int key_sort_run(zk_ctx* ctx, const zk_key_sort* desc, const void* h_mask, void* d_out, uint64_t n);   // keysort.hip: ZK_OP_KEY_SORT of zk_field_vec_op
+int key_order_run(zk_ctx* ctx, const zk_key_order* desc, void* d_out, uint64_t n);                     // keysort.hip: ZK_OP_KEY_ORDER of zk_field_vec_op
 // G1 encodings read on the device (params.hip k_g1_decode): 32 B compressed, 64 B Montgomery limbs, 64 B big-endian x || y (EVM)
 enum G1Enc : int { G1_ENC_COMPRESSED = 0, G1_ENC_RAW = 1, G1_ENC_BE_XY = 2 };
 int g1_decode_run(zk_ctx* ctx, const void* d_in, int enc, G1Affine* d_out, uint64_t n, uint32_t* d_bad, uint8_t* d_bad_at);

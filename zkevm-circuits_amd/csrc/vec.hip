@@ -1503,6 +1503,17 @@ extern "C" {
 
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n) {
     if (!ctx) return ZK_ERR_INVALID_ARG;
+    if (op == ZK_OP_KEY_SORT) {                                         // d_a, d_b: HOST pointers (the zk_key_sort; the 64-byte mask or NULL)
+        ZK_REQUIRE(ctx, d_a && d_out, "null pointer");
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the key ops are defined over Fr only");
+        return key_sort_run(ctx, (const zk_key_sort*)d_a, d_b, d_out, n);
+    }
+    if (op == ZK_OP_KEY_ORDER) {                                        // d_a: HOST pointer (the zk_key_order); d_b: NULL
+        ZK_REQUIRE(ctx, d_a && d_out, "null pointer");
+        ZK_REQUIRE(ctx, !d_b, "the key order takes no second operand");
+        ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the key ops are defined over Fr only");
+        return key_order_run(ctx, (const zk_key_order*)d_a, d_out, n);
+    }
     ZK_REQUIRE(ctx, d_a && d_b && d_out, "null device pointer");
     if (op == ZK_OP_ROW_RLC) {                                          // d_a, d_b: HOST pointers (column table; constant and weights)
         ZK_REQUIRE(ctx, field == ZK_FIELD_FR, "the row RLC is defined over Fr only");
