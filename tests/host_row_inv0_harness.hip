@@ -1,7 +1,7 @@
 // Test harness: the per-lane arithmetic of the inverse-or-zero row op (csrc/ff29.hip.hpp: inv0_29_den / inv0_29_prefix / inv29_rp /
 // inv0_29_back / inv0_29_out over rlc29_init / rlc29_mac / rlc29_reduce) compiled for the HOST as a stand-alone program, run directly by
 // tests/test_row_inv0_host.py (once plain, once under the address and undefined-behaviour sanitizers).  It does to the rows of one
-// lane -- 4 (one tile of the kernel) or 16 (the four tiles a wave takes) -- what a lane of k_fr_row_inv0 (csrc/vec.hip) does, the
+// lane -- 4 (one tile of the kernel) or 16 (the four tiles a wave takes) -- what a lane of k_fr_row_inv0 (csrc/typed_rows.hip) does, the
 // wave being this lane alone: the product that inv29_rp inverts is the lane's own.
 // Input (file named by argv[1]), all numbers little-endian integers in hex:
 //   lane <num kind: 0 none, 1 narrow, 2 Fr> <rows: 4 | 16> <2^261 mod p> <constant of inv29_rp>

@@ -1,6 +1,6 @@
 // Test harness: the row RLC's limb routine (csrc/ff29.hip.hpp: rlc29_init / rlc29_mac / rlc29_carry / rlc29_reduce) compiled for the
 // HOST as a stand-alone program, run directly by tests/test_row_rlc_host.py (once plain, once under the address and
-// undefined-behaviour sanitizers).  It does to one row what a lane of k_fr_row_rlc (csrc/vec.hip) does: cells become limbs by
+// undefined-behaviour sanitizers).  It does to one row what a lane of k_fr_row_rlc (csrc/typed_rows.hip) does: cells become limbs by
 // unpack29 (1, 1, 2, 3, 5 or 9 of them by width), every term goes through rlc29_mac, one rlc29_reduce, pack29_lt2p.
 // Input (file named by argv[1]), all numbers little-endian integers in hex:
 //   case <count>

@@ -815,6 +815,15 @@ class Context:
                          POSEIDON_FINAL if final else 0)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_POSEIDON, ctypes.byref(desc), _host_ptr(scale), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
 
+    def _byte_hash(self, op, desc_type, data, total_bytes, offsets, lens, index_width, n, out, r_out, r_in, digest, input_rlc):
+        """keccak() and sha256(): one descriptor layout, the two challenges behind each other"""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        r = np.zeros((2, 4), dtype=np.uint64)
+        r[0] = np.asarray(r_out, dtype=np.uint64).reshape(4)
+        r[1] = np.asarray(r_in, dtype=np.uint64).reshape(4)
+        desc = desc_type(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, op, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+
     def keccak(self, data, total_bytes, offsets, lens, index_width, n, out, r_out, r_in=None, digest=None, input_rlc=None):
         """out[i] = sum_k digest_i[k] r_out^(31-k) for i < n, digest_i = Keccak-256 (the function of host_keccak256) of the lens[i]
         bytes at data + offsets[i]: the KeccakTable's output_rlc (zk_field_vec_op with ZK_OP_KECCAK).  data, offsets, lens, out, digest,
@@ -824,13 +833,7 @@ class Context:
         of its row and reads nothing, without an error.  r_out, r_in: (4,) u64 Montgomery Fr (r_in None: zero; it is used only with
         input_rlc).  digest: optional n x 32 B, the digest bytes; input_rlc: optional n x 32 B, sum_k m[k] r_in^(len-1-k), 0 for
         the empty message.  No output may overlap an input or another output."""
-        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
-        r = np.zeros((2, 4), dtype=np.uint64)
-        r[0] = np.asarray(r_out, dtype=np.uint64).reshape(4)
-        if r_in is not None:
-            r[1] = np.asarray(r_in, dtype=np.uint64).reshape(4)
-        desc = _Keccak(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
-        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_KECCAK, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+        self._byte_hash(OP_KECCAK, _Keccak, data, total_bytes, offsets, lens, index_width, n, out, r_out, np.zeros(4, dtype=np.uint64) if r_in is None else r_in, digest, input_rlc)
 
     def sha256(self, data, total_bytes, offsets, lens, index_width, n, out, r_out, r_in=None, digest=None, input_rlc=None):
         """out[i] = sum_k digest_i[k] r_out^(31-k) for i < n, digest_i = SHA-256 (FIPS 180-4) of the lens[i] bytes at data +
@@ -842,12 +845,7 @@ class Context:
         Montgomery Fr; r_in None means r_in = r_out, because the reference's table takes both RLCs under one challenge
         (keccak_input); r_in is used only with input_rlc.  digest: optional n x 32 B, the digest bytes in digest order; input_rlc:
         optional n x 32 B, sum_k m[k] r_in^(len-1-k), 0 for the empty message.  No output may overlap an input or another output."""
-        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
-        r = np.zeros((2, 4), dtype=np.uint64)
-        r[0] = np.asarray(r_out, dtype=np.uint64).reshape(4)
-        r[1] = r[0] if r_in is None else np.asarray(r_in, dtype=np.uint64).reshape(4)
-        desc = _Sha256(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(digest), ptr_of(input_rlc), index_width, 0)
-        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_SHA256, ctypes.byref(desc), _host_ptr(r), ctypes.c_void_p(ptr_of(out)), ctypes.c_size_t(n)))
+        self._byte_hash(OP_SHA256, _Sha256, data, total_bytes, offsets, lens, index_width, n, out, r_out, r_out if r_in is None else r_in, digest, input_rlc)
 
     def key_sort(self, keys, n, perm_out, mask=None, sorted_keys=None):
         """perm_out[i] = the uint32 index of the record that stands at place i when the n 64-byte key records at keys are sorted as

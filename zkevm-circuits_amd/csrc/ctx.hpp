@@ -241,6 +241,8 @@ int fr_powers_fmt(zk_ctx* ctx, const Fr& base, const Fr& mul, void* d_out, size_
 int quotient_eval_fmt(zk_ctx* ctx, const uint32_t* h_program, uint32_t num_instr, const void* const* h_col_ptrs, uint32_t num_cols, const void* h_consts, uint32_t num_consts, uint32_t k, uint32_t ext_k,
                       int divide_by_vanishing, void* d_out, bool records);
 int fr_scale_run(zk_ctx* ctx, Fr* d_a, const Fr& s, uint64_t n);
+int fr_row_rlc_run(zk_ctx* ctx, const zk_row_rlc* desc, const void* h_k, Fr* d_out, uint64_t n);       // typed_rows.hip: ZK_OP_ROW_RLC of zk_field_vec_op
+int fr_row_inv0_run(zk_ctx* ctx, const zk_row_inv0* desc, const void* h_k, Fr* d_out, uint64_t n);     // typed_rows.hip: ZK_OP_ROW_INV0 of zk_field_vec_op
 int fr_poseidon_run(zk_ctx* ctx, const zk_poseidon* desc, const void* h_scale, Fr* d_out, uint64_t n);   // poseidon.hip: ZK_OP_POSEIDON of zk_field_vec_op
 int fr_keccak_run(zk_ctx* ctx, const zk_keccak* desc, const void* h_challenges, Fr* d_out, uint64_t n);   // keccak.hip: ZK_OP_KECCAK of zk_field_vec_op
 int fr_sha256_run(zk_ctx* ctx, const zk_sha256* desc, const void* h_challenges, Fr* d_out, uint64_t n);   // sha256.hip: ZK_OP_SHA256 of zk_field_vec_op
@@ -300,8 +302,8 @@ int mock_probe_enqueue(zk_ctx* ctx, const Fr* d_inputs, const Fr* d_table, const
 int mock_perm_enqueue(zk_ctx* ctx, const Fr* const* d_sigma, const Fr* const* d_cols, const Fr* d_ids, const uint32_t* d_slots, uint32_t mask, uint32_t num_cols, uint32_t k,
                       uint32_t kind, MockFail* d_out, uint32_t cap, uint32_t* d_counter);
 int fr_add_const_many(zk_ctx* ctx, const void* const* d_src, void* const* d_dst, size_t count, const void* h_k, size_t n);   // vec.hip: dst[c] = src[c] + k, any number of columns, no upload / sync
-int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint32_t width, uint64_t n, Fr* d_out);   // vec.hip: zk_fr_from_uint on any stream of the context (validates width and alignment)
-int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_packed, const uint8_t* widths, size_t count, uint64_t n, Fr* const* d_out);   // vec.hip: count columns of n cells each, sixteen per launch (validates every width and alignment before the first launch)
+int fr_from_uint_run(zk_ctx* ctx, hipStream_t stream, const void* d_packed, uint32_t width, uint64_t n, Fr* d_out);   // typed_rows.hip: zk_fr_from_uint on any stream of the context (validates width and alignment)
+int fr_from_uint_batch_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_packed, const uint8_t* widths, size_t count, uint64_t n, Fr* const* d_out);   // typed_rows.hip: count columns of n cells each, sixteen per launch (validates every width and alignment before the first launch)
 int sigma_from_mapping_run(zk_ctx* ctx, hipStream_t stream, const void* const* d_map, size_t count, uint64_t n, uint32_t P, const Fr* d_omega, const Fr* d_delta, uint32_t* d_bad, Fr* const* d_out);   // vec.hip: count sigma columns of n cells from halo2's permutation mapping, (u32 j', u32 i') per cell, sixteen per launch; a pair outside [0, P) x [0, n) stores zero and sets *d_bad
 int g_to_lagrange(zk_ctx* ctx, const G1Affine* d_g, uint32_t k, G1Affine* d_out);   // ecntt.hip: inverse FFT over G1
 bool comm_ready(const zk_ctx* ctx);                                                              // comm.hip: in-library RCCL collectives

@@ -674,7 +674,7 @@ __host__ __device__ inline Fp<typename P29::P32> inv_via29(const Fp<typename P29
     return pack29_lt2p(mul29(r, unpack29<P29>(F::one())));                 // x 2^256 / 2^261: R' -> R
 }
 
-// ---- sum of short products under ONE reduction: T = sum_j x_j K_j, then T 2^-261 mod p (the row RLC of csrc/vec.hip) ---------
+// ---- sum of short products under ONE reduction: T = sum_j x_j K_j, then T 2^-261 mod p (the row RLC of csrc/typed_rows.hip) ---------
 // x_j is an integer of L_j <= 9 limbs and K_j a plain normalised constant below p; both have limbs below 2^29, so every product
 // is below 2^58.  The sum is kept as 18 integer column sums c[k] of weight 2^(29 k) (x_i K_j goes to column i + j <= 16, column 17
 // only ever takes carries), in 64-bit words, and nothing is reduced until rlc29_reduce.  Plain C on the host and on the device
@@ -686,7 +686,7 @@ __host__ __device__ inline Fp<typename P29::P32> inv_via29(const Fp<typename P29
 //       less than 2^35 into the next one.  Bytes (L = 1) get 53 terms between passes, 16-byte cells 10, full elements 5.
 //   (2) the sum.  rlc29_reduce needs T < 2^261 p, like mul29; its result is then normalised and below 2p.  A narrow term (x below
 //       2^128) is below 2^128 p, so their number does not matter; a full-size one (x < p) is below p^2 and 2^261 / p = 169.2 of
-//       those fit in Fr (147.6 in Fq).  The caller counts them: csrc/vec.hip puts at most RR_BATCH = 64 terms under one reduction.
+//       those fit in Fr (147.6 in Fq).  The caller counts them: csrc/typed_rows.hip puts at most RR_BATCH = 64 terms under one reduction.
 // rlc29_room(t, need) makes room for `need` products ahead of a run of terms whose limb counts add up to `need`: the tests that
 // rlc29_mac still makes for every term of the run then cannot fire.  `load` is a runtime value; where the run is unrolled with a
 // constant `need`, the compiler's range propagation (load <= MAX - need after the call) can remove those tests and their copies
@@ -778,7 +778,7 @@ __host__ __device__ __forceinline__ void scan_rlc29_fold(F29<P>& A, F29<P>& B, c
     B = scan_rlc29_step<L>(B, x, M, K);
 }
 
-// ---- inverse-or-zero of a row sum: out = num * inv0(D), inv0(0) = 0 (the per-lane steps of k_fr_row_inv0, csrc/vec.hip, ZK_OP_ROW_INV0) --
+// ---- inverse-or-zero of a row sum: out = num * inv0(D), inv0(0) = 0 (the per-lane steps of k_fr_row_inv0, csrc/typed_rows.hip, ZK_OP_ROW_INV0) --
 // Forms.  mul29 is Montgomery by R' = 2^261, the columns are R = 2^256.  Write [x]_e for the residue x 2^e; mul29([x]_e, [y]_f) =
 // [x y]_(e + f - 261), so a factor in R' form ([y]_261) leaves the form of the other factor as it is.
 //   * the denominator: the host hands the inverting launch its constants with a further 2^5 (w 2^522 narrow, w 2^266 for a 32-byte
@@ -845,6 +845,26 @@ __host__ __device__ inline Fr29 inv29_rp(const Fr29& b, const Fr29& c783) {
     Fr y;
     inv_xgcd<FrP>(y.l, x.l);
     return mul29(unpack29<Fr29P>(y), c783);
+}
+
+// a limb record from another lane of the wave
+__device__ __forceinline__ Fr29 shfl_up29(const Fr29& v, int off) {
+    Fr29 r;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r.l[k] = __shfl_up(v.l[k], off);
+    return r;
+}
+__device__ __forceinline__ Fr29 shfl_down29(const Fr29& v, int off) {
+    Fr29 r;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r.l[k] = __shfl_down(v.l[k], off);
+    return r;
+}
+__device__ __forceinline__ Fr29 shfl29(const Fr29& v, int src) {
+    Fr29 r;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r.l[k] = __shfl(v.l[k], src);
+    return r;
 }
 
 }  // namespace zk

@@ -3,7 +3,8 @@
 //   digest_i = Keccak-256(the len_i bytes at d_bytes + off_i);  d_out[i] = sum_k digest_i[k] r_out^(31-k)  (output_rlc, hash_rlc);
 //   d_digest[i] = the 32 digest bytes;  d_input_rlc[i] = sum_k m[k] r_in^(len-1-k).
 // The per-lane code is csrc/keccak64.hip.hpp (absorbing at any alignment, the permutation with the state in registers, the RLCs eight
-// bytes per reduction); this file holds the two kernels and the host side.
+// bytes per reduction); the row, the checks and the launch are csrc/bytehash.hip.hpp, shared with ZK_OP_SHA256; this file holds the
+// trait and the two kernels.
 // Launch: one, lane = row.  k_keccak<false> is the plain call; k_keccak<true> also walks input_rlc and is a separate instantiation
 // so that the plain call does not carry its registers.  The 16 + 16 limb records of the two challenges are made on the host per
 // call and travel as kernel arguments: wave-uniform, fetched by scalar loads.  No LDS, no scratch, no host synchronisation: the
@@ -13,26 +14,18 @@
 // k_keccak<true> 90, five waves per SIMD either way.
 // Lanes of a wave have different lengths and a wave takes as long as its longest message -- the trade ZK_OP_POSEIDON made; one long
 // message among short ones costs its own blocks once per wave it sits in (profiles/r25_keccak.md has that measured).
-#include "ctx.hpp"
-#include "keccak64.hip.hpp"
+#include "bytehash.hip.hpp"
 
 namespace zk {
 
-struct KckArgs {
-    const uint8_t* bytes;
-    uint64_t total;
-    const void* offs;
-    const void* lens;
-    uint8_t* digest;                    // NULL: not wanted
-    Fr* out;
-    Fr* in_rlc;                         // k_keccak<true> only
-    uint64_t n;
-    uint32_t index_width;
-    KckPow pout;
+struct KeccakHash {
+    using Desc = zk_keccak;
+    static constexpr const char *name = "Keccak", *prof = "fr_keccak";
+    static constexpr int TOTAL_LOG2 = 64;
 };
 
 template <bool RLC>
-__global__ void __launch_bounds__(256) k_keccak(const KckArgs g, const KckPow pin) {
+__global__ void __launch_bounds__(256) k_keccak(const HashArgs g, const KckPow pin) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= g.n) return;
     const uint64_t off = kck_index(g.offs, g.index_width, i), len = kck_index(g.lens, g.index_width, i);
@@ -57,61 +50,6 @@ __global__ void __launch_bounds__(256) k_keccak(const KckArgs g, const KckPow pi
     if constexpr (RLC) stg(g.in_rlc + i, in);
 }
 
-struct KckSpan { uintptr_t lo, hi; const char* what; bool out; };
-
-// h_challenges: r_out, then r_in, Montgomery Fr in host memory.  Everything is validated before n is looked at and before the
-// launch, so a refused call has written nothing.
-int fr_keccak_run(zk_ctx* ctx, const zk_keccak* desc, const void* h_challenges, Fr* d_out, uint64_t n) {
-    const uint32_t iw = desc->index_width;
-    if (desc->flags) return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: flags 0x%x: must be 0", desc->flags);
-    if (iw != 4 && iw != 8) return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: index width %u: must be 4 or 8 bytes", iw);
-    if (!desc->d_offsets || !desc->d_lens) return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: NULL offsets or lengths");
-    if ((uintptr_t)desc->d_offsets % iw || (uintptr_t)desc->d_lens % iw) return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: offsets or lengths of %u bytes at a misaligned address", iw);
-    if (!desc->d_bytes && desc->total_bytes) return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: NULL d_bytes with %llu bytes", (unsigned long long)desc->total_bytes);
-    if ((uintptr_t)d_out % 16 || (uintptr_t)desc->d_input_rlc % 16) return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: an Fr output at an address that is no multiple of 16");
-    const uint64_t blocks = n / 256 + (n % 256 ? 1 : 0);
-    if (blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many rows for one launch");
-    // no output overlaps an input or another output
-    KckSpan span[6];
-    int spans = 0;
-    auto add = [&](const void* p, uint64_t len, const char* what, bool out) { if (p && len) span[spans++] = {(uintptr_t)p, (uintptr_t)p + len, what, out}; };
-    add(d_out, n * sizeof(Fr), "d_out", true);
-    add(desc->d_digest, n * 32, "d_digest", true);
-    add(desc->d_input_rlc, n * sizeof(Fr), "d_input_rlc", true);
-    add(desc->d_bytes, desc->total_bytes, "d_bytes", false);
-    add(desc->d_offsets, n * iw, "d_offsets", false);
-    add(desc->d_lens, n * iw, "d_lens", false);
-    for (int a = 0; a < spans; ++a)
-        for (int b = a + 1; b < spans; ++b)
-            if ((span[a].out || span[b].out) && span[a].lo < span[b].hi && span[b].lo < span[a].hi)
-                return ctx->fail(ZK_ERR_INVALID_ARG, "Keccak: %s overlaps %s", span[a].what, span[b].what);
-    if (!n) return ZK_OK;
-
-    Fr r[2];
-    memcpy(r, h_challenges, sizeof r);                  // all 64 bytes, whether r_in is used or not
-    KckArgs g;
-    memset(&g, 0, sizeof g);
-    g.bytes = (const uint8_t*)desc->d_bytes;
-    g.total = desc->total_bytes;
-    g.offs = desc->d_offsets;
-    g.lens = desc->d_lens;
-    g.digest = (uint8_t*)desc->d_digest;
-    g.out = d_out;
-    g.in_rlc = (Fr*)desc->d_input_rlc;
-    g.n = n;
-    g.index_width = iw;
-    g.pout = kck_pow_table(r[0]);
-    KckPow pin;
-    memset(&pin, 0, sizeof pin);
-    if (g.in_rlc) pin = kck_pow_table(r[1]);
-
-    ZkProfScope prof(ctx, "fr_keccak");
-    // the host cannot know the sum of the lengths: total_bytes stands in for the message bytes read
-    prof.bytes = n * (2ull * iw + 32 + (g.digest ? 32 : 0) + (g.in_rlc ? 32 : 0)) + desc->total_bytes;
-    if (g.in_rlc) hipLaunchKernelGGL(k_keccak<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, g, pin);
-    else hipLaunchKernelGGL(k_keccak<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, g, pin);
-    ZK_CHECK_LAUNCH(ctx);
-    return ZK_OK;
-}
+int fr_keccak_run(zk_ctx* ctx, const zk_keccak* desc, const void* h_challenges, Fr* d_out, uint64_t n) { return byte_hash_run<KeccakHash>(ctx, desc, h_challenges, d_out, n, k_keccak<false>, k_keccak<true>); }
 
 }  // namespace zk

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "ff29.hip.hpp"
+#include "op_check.hpp"
 
 namespace zk {
 
@@ -81,10 +82,7 @@ struct KckPow {
 };
 // from the Montgomery image of r; host side, once per call
 inline KckPow kck_pow_table(const Fr& r) {
-    Fr c261 = Fr::one(), c517;                          // the integers 2^261 and 2^517 mod p
-    for (int i = 256; i < 261; ++i) c261 = dbl(c261);
-    c517 = c261;
-    for (int i = 261; i < 517; ++i) c517 = dbl(c517);
+    const Fr c261 = fr_pow2(261), c517 = fr_pow2(517);  // the integers 2^261 and 2^517 mod p
     KckPow t;
     Fr pw = Fr::one();
     for (int e = 0; e <= 8; ++e) {

@@ -26,11 +26,12 @@
 // count-leading-zeros, the difference a signed integer in +-65535.  The inverse is a LOOKUP: the context caches the inverses of
 // 0..65535 (2 MB, made on the device at the first call by 65536 lanes of Fermat inversion, no host data and no wait), the entry of |d|
 // is negated for a negative difference.  The per-wave batch inversion of ZK_OP_ROW_INV0 would put one inv_xgcd per 64 rows on lane
-// 63 while its wave waits (130 us a round, csrc/vec.hip) and carry 9-limb prefix products through twelve shuffled multiplications;
+// 63 while its wave waits (130 us a round, csrc/typed_rows.hip) and carry 9-limb prefix products through twelve shuffled multiplications;
 // the table costs one 32-byte load per row from a table that stays in L2, and no multiplication.  The gathered columns run in the
 // same launch, out of the record the lane already holds: word selects (ko_word), no second pass over the records.
 #include "ctx.hpp"
 #include "keyorder.hip.hpp"
+#include "op_check.hpp"
 
 namespace zk {
 
@@ -210,14 +211,6 @@ __global__ void __launch_bounds__(256) k_ks_finish(const KsArgs g, uint32_t* out
     }
 }
 
-struct KeySpan { uintptr_t lo, hi; const char* what; bool out; };
-static const char* key_overlap(const KeySpan* span, int spans, const char** other) {
-    for (int a = 0; a < spans; ++a)
-        for (int b = a + 1; b < spans; ++b)
-            if ((span[a].out || span[b].out) && span[a].lo < span[b].hi && span[b].lo < span[a].hi) { *other = span[b].what; return span[a].what; }
-    return nullptr;
-}
-
 // h_mask: NULL or 64 bytes in host memory.  Everything is validated before n is looked at and before the first launch.
 int key_sort_run(zk_ctx* ctx, const zk_key_sort* desc, const void* h_mask, void* d_out, uint64_t n) {
     if (desc->flags) return ctx->fail(ZK_ERR_INVALID_ARG, "key sort: flags 0x%x: must be 0", desc->flags);
@@ -226,14 +219,12 @@ int key_sort_run(zk_ctx* ctx, const zk_key_sort* desc, const void* h_mask, void*
     if ((uintptr_t)d_out % 4) return ctx->fail(ZK_ERR_INVALID_ARG, "key sort: d_out at an address that is no multiple of 4");
     if (n >> 32) return ctx->fail(ZK_ERR_INVALID_ARG, "key sort: %llu records: 2^32 or more", (unsigned long long)n);
     if (desc->d_sorted == desc->d_keys) return ctx->fail(ZK_ERR_INVALID_ARG, "key sort: d_sorted is d_keys");
-    KeySpan span[3];
-    int spans = 0;
-    auto add = [&](const void* p, uint64_t len, const char* what, bool out) { if (p && len) span[spans++] = {(uintptr_t)p, (uintptr_t)p + len, what, out}; };
-    add(d_out, n * 4, "d_out", true);
-    add(desc->d_sorted, n * 64, "d_sorted", true);
-    add(desc->d_keys, n * 64, "d_keys", false);
-    const char* other = nullptr;
-    if (const char* what = key_overlap(span, spans, &other)) return ctx->fail(ZK_ERR_INVALID_ARG, "key sort: %s overlaps %s", what, other);
+    SpanList<3> spans;
+    spans.add(d_out, n * 4, "d_out", true);
+    spans.add(desc->d_sorted, n * 64, "d_sorted", true);
+    spans.add(desc->d_keys, n * 64, "d_keys", false);
+    const char *what, *other;
+    if (spans.overlap(&what, &other)) return ctx->fail(ZK_ERR_INVALID_ARG, "key sort: %s overlaps %s", what, other);
     if (!n) return ZK_OK;
 
     uint64_t keep = 0;
@@ -365,27 +356,25 @@ int key_order_run(zk_ctx* ctx, const zk_key_order* desc, void* d_out, uint64_t n
     if (desc->group_limbs > 32) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: group_limbs %u: at most 32", desc->group_limbs);
     if (desc->count > KO_MAX_COLS) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: %u gathered columns: at most 64", desc->count);
     if (desc->count && (!desc->cols || !desc->d_cols)) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: NULL cols or d_cols with %u columns", desc->count);
-    KeySpan span[7 + KO_MAX_COLS];
-    int spans = 0;
-    auto add = [&](const void* p, uint64_t len, const char* what, bool out) { if (p && len) span[spans++] = {(uintptr_t)p, (uintptr_t)p + len, what, out}; };
-    add(d_out, n * sizeof(Fr), "d_out", true);
-    add(desc->d_diff, n * sizeof(Fr), "d_diff", true);
-    add(desc->d_index, n, "d_index", true);
-    add(desc->d_bits, 5 * n, "d_bits", true);
-    add(desc->d_not_first, n, "d_not_first", true);
+    SpanList<7 + KO_MAX_COLS> spans;
+    spans.add(d_out, n * sizeof(Fr), "d_out", true);
+    spans.add(desc->d_diff, n * sizeof(Fr), "d_diff", true);
+    spans.add(desc->d_index, n, "d_index", true);
+    spans.add(desc->d_bits, 5 * n, "d_bits", true);
+    spans.add(desc->d_not_first, n, "d_not_first", true);
     uint64_t col_bytes = 0;
     for (uint32_t c = 0; c < desc->count; ++c) {
         const uint32_t offset = desc->cols[c].offset, width = desc->cols[c].width;
         if (!key_col_ok(offset, width)) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: column %u: key bytes [%u, %u + %u): width 1, 2 or 4 inside the 64 bytes", c, offset, offset, width);
         if (!desc->d_cols[c]) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: column %u: NULL", c);
-        if ((uintptr_t)desc->d_cols[c] % width) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: column %u: cells of %u bytes at a misaligned address", c, width);
-        add(desc->d_cols[c], n * width, "a gathered column", true);
+        if ((uintptr_t)desc->d_cols[c] % typed_cell_align(width)) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: column %u: cells of %u bytes at a misaligned address", c, width);
+        spans.add(desc->d_cols[c], n * width, "a gathered column", true);
         col_bytes += width;
     }
-    add(desc->d_keys, n * 64, "d_keys", false);
-    add(desc->d_perm, n * 4, "d_perm", false);
-    const char* other = nullptr;
-    if (const char* what = key_overlap(span, spans, &other)) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: %s overlaps %s", what, other);
+    spans.add(desc->d_keys, n * 64, "d_keys", false);
+    spans.add(desc->d_perm, n * 4, "d_perm", false);
+    const char *what, *other;
+    if (spans.overlap(&what, &other)) return ctx->fail(ZK_ERR_INVALID_ARG, "key order: %s overlaps %s", what, other);
     if (!n) return ZK_OK;
 
     KoArgs g;

@@ -19,6 +19,7 @@
 //                     in a second sweep.  A wave takes as long as its longest message (profiles/r24_poseidon.md has that measured).
 #include "ctx.hpp"
 #include "host_hash.hpp"
+#include "op_check.hpp"
 #include "poseidon29.hip.hpp"
 
 namespace zk {
@@ -115,8 +116,7 @@ __global__ void __launch_bounds__(256) k_poseidon_walk(const PsdArgs g, const ui
 static int poseidon_table(zk_ctx* ctx, const uint32_t** out) {
     if (!ctx->poseidon_tab) {
         const host::PoseidonWidth3& spec = host::PoseidonWidth3::get();
-        auto pow2 = [](int e) { Fr c = Fr::one(); for (int i = 256; i < e; ++i) c = dbl(c); return c; };      // the integer 2^e mod r
-        const Fr c261 = pow2(261), c522 = pow2(522);
+        const Fr c261 = fr_pow2(261), c522 = fr_pow2(522);
         std::vector<uint32_t> h((size_t)PSD_TAB_WORDS);
         auto put = [&](int rec, const host::F4& mont, const Fr& by) {    // plain canonical limbs of (value of mont) * by
             Fr v;
@@ -139,49 +139,41 @@ static int poseidon_table(zk_ctx* ctx, const uint32_t** out) {
     return ZK_OK;
 }
 
-struct PsdSpan { uintptr_t lo, hi; const char* what; bool out; };
-
 // h_scale: one Montgomery Fr in host memory.  Everything is validated before n is looked at and before the first launch, so a
 // refused call has written nothing.
 int fr_poseidon_run(zk_ctx* ctx, const zk_poseidon* desc, const void* h_scale, Fr* d_out, uint64_t n) {
-    auto narrow = [](uint32_t w) { return w == 1 || w == 2 || w == 4 || w == 8 || w == 16; };
     auto bytes = [](uint32_t w, uint64_t rows) -> uint64_t { return !rows ? 0 : w == 31 ? 62 * (rows - 1) + 31 : (uint64_t)w * rows; };
     if (desc->flags & ~(uint32_t)ZK_POSEIDON_FINAL) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: unknown flag bits 0x%x", desc->flags);
     const void* in[2] = {desc->d_in0, desc->d_in1};
     const uint32_t width[2] = {desc->width0, desc->width1};
     for (int c = 0; c < 2; ++c) {
-        if (!narrow(width[c]) && width[c] != 31 && width[c] != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: input %d: cell width %u: must be 1, 2, 4, 8, 16, 31 or 32 bytes", c, width[c]);
+        if (!typed_cell_width_ok(width[c], true) && width[c] != 31) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: input %d: cell width %u: must be 1, 2, 4, 8, 16, 31 or 32 bytes", c, width[c]);
         if (!in[c]) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: input %d: NULL pointer", c);
-        if (width[c] != 31 && (uintptr_t)in[c] % (width[c] == 32 ? 8 : width[c])) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: input %d: cells of %u bytes at a misaligned address", c, width[c]);
+        if (width[c] != 31 && (uintptr_t)in[c] % typed_cell_align(width[c])) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: input %d: cells of %u bytes at a misaligned address", c, width[c]);
     }
     const uint32_t cap_width = desc->d_cap ? desc->cap_width : 0;
     if (desc->d_cap) {
-        if (!narrow(cap_width) && cap_width != 32) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: capacity cell width %u: must be 1, 2, 4, 8, 16 or 32 bytes", cap_width);
-        if ((uintptr_t)desc->d_cap % (cap_width == 32 ? 8 : cap_width)) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: capacity cells of %u bytes at a misaligned address", cap_width);
+        if (!typed_cell_width_ok(cap_width, true)) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: capacity cell width %u: must be 1, 2, 4, 8, 16 or 32 bytes", cap_width);
+        if ((uintptr_t)desc->d_cap % typed_cell_align(cap_width)) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: capacity cells of %u bytes at a misaligned address", cap_width);
     }
     // no output overlaps an input or another output
-    PsdSpan span[7];
-    int spans = 0;
-    auto add = [&](const void* p, uint64_t len, const char* what, bool out) { if (p && len) span[spans++] = {(uintptr_t)p, (uintptr_t)p + len, what, out}; };
-    add(d_out, n * sizeof(Fr), "d_out", true);
-    add(desc->d_word0, n * sizeof(Fr), "d_word0", true);
-    add(desc->d_word1, n * sizeof(Fr), "d_word1", true);
-    add(desc->d_in0, bytes(width[0], n), "d_in0", false);
-    add(desc->d_in1, bytes(width[1], n), "d_in1", false);
-    add(desc->d_cap, bytes(cap_width, n), "d_cap", false);
-    add(desc->d_kinds, n, "d_kinds", false);
-    for (int a = 0; a < spans; ++a)
-        for (int b = a + 1; b < spans; ++b)
-            if ((span[a].out || span[b].out) && span[a].lo < span[b].hi && span[b].lo < span[a].hi)
-                return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: %s overlaps %s", span[a].what, span[b].what);
+    SpanList<7> spans;
+    spans.add(d_out, n * sizeof(Fr), "d_out", true);
+    spans.add(desc->d_word0, n * sizeof(Fr), "d_word0", true);
+    spans.add(desc->d_word1, n * sizeof(Fr), "d_word1", true);
+    spans.add(desc->d_in0, bytes(width[0], n), "d_in0", false);
+    spans.add(desc->d_in1, bytes(width[1], n), "d_in1", false);
+    spans.add(desc->d_cap, bytes(cap_width, n), "d_cap", false);
+    spans.add(desc->d_kinds, n, "d_kinds", false);
+    const char *what, *other;
+    if (spans.overlap(&what, &other)) return ctx->fail(ZK_ERR_INVALID_ARG, "Poseidon: %s overlaps %s", what, other);
     if (!n) return ZK_OK;
     const uint64_t blocks = (n + 255) / 256;
     if ((desc->d_kinds && n > 0xffffffffull) || blocks > 0x7fffffffull) return ctx->fail(ZK_ERR_INVALID_ARG, "too many rows for one launch");   // the list holds 32-bit row numbers
     const uint32_t* tab = nullptr;
     if (int e = poseidon_table(ctx, &tab)) return e;
 
-    static const Fr c522 = [] { Fr c = Fr::one(); for (int i = 256; i < 522; ++i) c = dbl(c); return c; }();   // the integers 2^522, 2^266 mod r
-    static const Fr c266 = [] { Fr c = Fr::one(); for (int i = 256; i < 266; ++i) c = dbl(c); return c; }();
+    static const Fr c522 = fr_pow2(522), c266 = fr_pow2(266);           // the integers 2^522, 2^266 mod r
     PsdArgs g;
     memset(&g, 0, sizeof g);
     g.in0 = (const uint8_t*)desc->d_in0;

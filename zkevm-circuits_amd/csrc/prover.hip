@@ -530,7 +530,7 @@ F4 eval_small(const std::vector<F4>& c, const F4& at) { F4 acc = host::fr_zero()
 // narrow fixed columns, k_sigma_from_mapping for the sigma columns (Montgomery fixed columns go straight to their buffer) --
 // while the commitments of the previous columns run: the staging callback of commit_batch_staged fences each group.  `tables`
 // receives the delta^j table and, behind it, the kernel's flag word; the caller reads the flag once the device is drained.
-constexpr size_t V4_GROUP = 16;                    // columns per expansion launch (FU_BATCH, SM_BATCH of vec.hip)
+constexpr size_t V4_GROUP = 16;                    // columns per expansion launch (FU_BATCH of typed_rows.hip, SM_BATCH of vec.hip)
 int load_columns_v4(zk_ctx* ctx, zk_pk* pk, Reader& r, DevBuf* tables) {
     const size_t n = (size_t)1 << pk->k, F = pk->F, P = pk->P;
     struct Stage {
