@@ -122,6 +122,28 @@ typedef struct zk_key_order {
     void* const* d_cols;       /* HOST array of count device pointers: n cells of cols[j].width bytes, aligned to that width */
     uint8_t     flags;         /* must be 0 */
 } zk_key_order;
+/* the rows of the bytecode circuit of zk_field_vec_op (described there): its d_a is a HOST pointer to this struct, whose pointers are
+ * device pointers; d_bytes, total_bytes, d_offsets, d_lens and index_width are those of zk_keccak */
+#define ZK_OP_BYTECODE_ROWS 26
+typedef struct zk_bytecode_rows {
+    const void* d_bytes;          /* device: the bytes the bytecodes live in */
+    uint64_t    total_bytes;      /* bytes readable at d_bytes */
+    const void* d_offsets;        /* device: count unsigned little-endian offsets into d_bytes */
+    const void* d_lens;           /* device: count unsigned little-endian byte lengths */
+    const void* d_hashes;         /* device, count x 32 B Montgomery Fr, or NULL: code hash of each bytecode */
+    void* d_tag;                  /* n x 1 B or NULL */
+    void* d_index;                /* n x 4 B or NULL */
+    void* d_value;                /* n x 4 B or NULL */
+    void* d_is_code;              /* n x 1 B or NULL */
+    void* d_push_data_left;       /* n x 1 B or NULL */
+    void* d_push_data_size;       /* n x 1 B or NULL */
+    void* d_length;               /* n x 4 B or NULL */
+    void* d_acc_kinds;            /* n x 1 B or NULL: kind column for push_acc (ZK_OP_SCAN_RLC) */
+    void* d_rlc_kinds;            /* n x 1 B or NULL: kind column for push_rlc (ZK_OP_SCAN_RLC_REV) */
+    uint32_t count;               /* bytecodes */
+    uint8_t  index_width;         /* 4 or 8 */
+    uint8_t  flags;               /* must be 0 */
+} zk_bytecode_rows;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -365,6 +387,42 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * or offset + width > 64, count > 64, NULL cols or d_cols with count > 0, a NULL entry of d_cols, group_limbs > 32, a non-NULL d_b for
  * ZK_OP_KEY_ORDER, any overlap between an output and any input or another output (d_sorted may not be d_keys): ZK_ERR_INVALID_ARG
  * before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.
+ * ZK_OP_BYTECODE_ROWS (a #define, value 26 -- 23, 24, 25 and 27 stay refused; Fr only) makes the rows of the reference's bytecode
+ * circuit (bytecode_circuit/bytecode_unroller.rs unroll_with_codehash, circuit.rs assign_bytecode and set_padding_row) from code bytes
+ * that live on the device.  d_a is a HOST pointer to a zk_bytecode_rows {d_bytes, total_bytes, d_offsets, d_lens, d_hashes, d_tag,
+ * d_index, d_value, d_is_code, d_push_data_left, d_push_data_size, d_length, d_acc_kinds, d_rlc_kinds, count, index_width, flags},
+ * d_b a HOST pointer to 32 B, one Montgomery Fr empty_hash (the code hash of the padding rows: POSEIDON_CODE_HASH_EMPTY, or the RLC
+ * of EMPTY_CODE_HASH_LE), both read before the call returns; the call is asynchronous on the context's stream and never waits for
+ * the device.  d_bytes, total_bytes, d_offsets, d_lens and index_width mean exactly what they mean in zk_keccak, with count entries:
+ * one set of device buffers feeds this op, the code hash (ZK_OP_POSEIDON) and ZK_OP_KECCAK.  Bytecode b of L_b = len_b bytes B owns
+ * the L_b + 1 consecutive rows from start_b = sum_(c<b) (L_c + 1); with P(v) = v - 0x5f for 0x60 <= v <= 0x7f and 0 otherwise:
+ *   header row start_b           tag 0, index 0, value L_b, is_code 0, push_data_left 0, push_data_size 0, length L_b
+ *   byte row start_b + 1 + p     tag 1, index p, value B[p], length L_b, push_data_size P(B[p]) (data bytes included),
+ *                                push_data_left s_p with s_0 = 0 and s_(p+1) = s_p == 0 ? P(B[p]) : s_p - 1, is_code = (s_p == 0)
+ *   padding rows, up to n        every typed output 0 (tag 0 is Header)
+ *   d_out[i]       (n x 32 B) d_hashes[b] on every row of bytecode b (0 there when d_hashes is NULL), empty_hash on padding rows
+ *   d_acc_kinds[i] 1 on a data row (tag 1 and push_data_left > 0), else 0: ZK_OP_SCAN_RLC over the value column with z0 = 0 and the
+ *                  table {0: (0, 0), 1: (r, 1)} is push_acc
+ *   d_rlc_kinds[i] 1 on the last data row of an instruction (a data row with push_data_left == 1 or index == length - 1), 2 on every
+ *                  other data row and on a code row with push_data_size > 0 and index < length - 1, else 0: ZK_OP_SCAN_RLC_REV over
+ *                  the push_acc column with z0 = 0 and the table {0: (0, 0), 1: (0, 1), 2: (1, 0)} is push_rlc
+ * Each typed output may be NULL.  The cells are little-endian at the width the struct names (value and length hold L mod 2^32),
+ * aligned to it -- the 1-byte columns at any address --, ready for zk_proof_advice_phase_typed_dev.  Rows at or after n are not
+ * written: a bytecode that does not fit is cut there without an error (the reference returns Error::Synthesis), and the kinds of the
+ * cut instruction then describe a push_rlc nobody should use.  The offsets and lengths are device data that the host never sees: an
+ * entry with off > total_bytes or len > total_bytes - off (computed so that it cannot wrap) counts as an empty bytecode everywhere in
+ * this op and reads nothing; no byte outside [d_bytes, d_bytes + total_bytes) is ever read.  start_b is exact while it is <= n and
+ * saturates there.  Bytecodes may overlap, repeat, and start at any address; the result is a pure function of the input.  No lane
+ * walks a bytecode: the work is laid out by rows.  start is a device scan into the context's scratch; push_data_left is a state in
+ * 0..32 whose 33-entry transition maps are made per tile of 1024 rows, composed up a 64-ary hierarchy and pushed down again, so a
+ * single long bytecode costs what many short ones cost.  Stages whose outputs are all NULL are not launched: a call with only
+ * d_hashes and d_out (the second call of a Keccak-code-hash build, in the challenge phase) never reads d_bytes.  ZK_FIELD_FQ, an
+ * index_width other than 4 or 8, nonzero flags, NULL or misaligned d_offsets or d_lens with count > 0, NULL d_bytes with total_bytes
+ * > 0, d_hashes at an address that is no multiple of 8, d_out at one that is no multiple of 16, d_index, d_value or d_length at one
+ * that is no multiple of 4, n >= 2^32, total_bytes >= 2^61, any overlap between an output and any input or another output:
+ * ZK_ERR_INVALID_ARG before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.
+ * Booked under the zk_prof name "bytecode_rows" with count * (2 * index_width + 32 with d_hashes) + total_bytes (only if an output
+ * reads the bytes) + n * (32 + the widths of the outputs given) algorithmic bytes per call.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

@@ -227,6 +227,13 @@ inline void key_order(const Context& c, const void* d_keys, size_t n, void* d_in
     const zk_key_order desc{d_keys, d_perm, d_diff, d_index, d_bits, d_not_first, group_limbs, count, cols, d_cols, 0};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_KEY_ORDER, &desc, nullptr, d_inv_out, n));
 }
+// The rows of the bytecode circuit from code bytes on the device (zk_field_vec_op with ZK_OP_BYTECODE_ROWS; asynchronous on the
+// context's stream).  desc: a zk_bytecode_rows -- the bytes, offsets and lengths as for keccak(), the code hashes, and the outputs
+// wanted (tag, index, value, is_code, push_data_left, push_data_size, length, the kind columns of push_acc and push_rlc), each a
+// device pointer or nullptr.  d_hash_out[i] (n x 32 B) = the code hash of the bytecode of row i, empty_hash on the padding rows.
+inline void bytecode_rows(const Context& c, const zk_bytecode_rows& desc, const Fr& empty_hash, size_t n, void* d_hash_out) {
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_BYTECODE_ROWS, &desc, &empty_hash, d_hash_out, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -176,6 +176,33 @@ pub struct zk_key_order {
     pub d_cols: *const *mut c_void,
     pub flags: u8,
 }
+/// `zk_field_vec_op` op: the rows of the bytecode circuit from code bytes on the device -- `d_out[i]` is the code hash of the bytecode
+/// row `i` belongs to, `empty_hash` on padding rows.  For this op `d_a` is a HOST pointer to a `zk_bytecode_rows` and `d_b` a HOST
+/// pointer to `32 B`, one Montgomery Fr `empty_hash`.
+pub const ZK_OP_BYTECODE_ROWS: c_int = 26;
+/// `zk_bytecode_rows`: `d_bytes`, `total_bytes`, `d_offsets`, `d_lens` and `index_width` are those of `zk_keccak`, with `count`
+/// entries; `d_hashes` and every output may be null.  `d_acc_kinds` and `d_rlc_kinds` are the kind columns of `ZK_OP_SCAN_RLC`
+/// (`push_acc`) and `ZK_OP_SCAN_RLC_REV` (`push_rlc`).  `flags` must be 0.
+#[repr(C)]
+pub struct zk_bytecode_rows {
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub d_offsets: *const c_void,
+    pub d_lens: *const c_void,
+    pub d_hashes: *const c_void,
+    pub d_tag: *mut c_void,
+    pub d_index: *mut c_void,
+    pub d_value: *mut c_void,
+    pub d_is_code: *mut c_void,
+    pub d_push_data_left: *mut c_void,
+    pub d_push_data_size: *mut c_void,
+    pub d_length: *mut c_void,
+    pub d_acc_kinds: *mut c_void,
+    pub d_rlc_kinds: *mut c_void,
+    pub count: u32,
+    pub index_width: u8,
+    pub flags: u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

@@ -32,6 +32,7 @@ OP_KECCAK = 16                                        # out[i] = output_rlc of K
 OP_SHA256 = 18                                        # out[i] = output_rlc of SHA-256(message i), messages as bytes on the device, Fr only (ZK_OP_SHA256)
 OP_KEY_SORT = 20                                      # out[i] = index of the 64-byte key record at place i of the stable order (ZK_OP_KEY_SORT)
 OP_KEY_ORDER = 22                                     # out[i] = limb_difference_inverse of key records i and i - 1 in row order (ZK_OP_KEY_ORDER)
+OP_BYTECODE_ROWS = 26                                 # out[i] = the code hash of the bytecode that row i of the bytecode circuit belongs to (ZK_OP_BYTECODE_ROWS)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -134,6 +135,16 @@ class _KeyOrder(ctypes.Structure):
     _fields_ = [("d_keys", ctypes.c_void_p), ("d_perm", ctypes.c_void_p), ("d_diff", ctypes.c_void_p), ("d_index", ctypes.c_void_p),
                 ("d_bits", ctypes.c_void_p), ("d_not_first", ctypes.c_void_p), ("group_limbs", ctypes.c_uint32), ("count", ctypes.c_uint32),
                 ("cols", ctypes.POINTER(_KeyCol)), ("d_cols", ctypes.POINTER(ctypes.c_void_p)), ("flags", ctypes.c_uint8)]
+
+
+class _BytecodeRows(ctypes.Structure):
+    """zk_bytecode_rows: the code bytes, the code hashes and the outputs of ZK_OP_BYTECODE_ROWS (host memory; every pointer is a device
+    pointer or NULL)"""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p), ("d_lens", ctypes.c_void_p),
+                ("d_hashes", ctypes.c_void_p), ("d_tag", ctypes.c_void_p), ("d_index", ctypes.c_void_p), ("d_value", ctypes.c_void_p),
+                ("d_is_code", ctypes.c_void_p), ("d_push_data_left", ctypes.c_void_p), ("d_push_data_size", ctypes.c_void_p),
+                ("d_length", ctypes.c_void_p), ("d_acc_kinds", ctypes.c_void_p), ("d_rlc_kinds", ctypes.c_void_p),
+                ("count", ctypes.c_uint32), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
 
 
 def _host_ptr(a: np.ndarray):
@@ -880,6 +891,24 @@ class Context:
         desc = _KeyOrder(ptr_of(keys), ptr_of(perm), ptr_of(diff), ptr_of(index), ptr_of(bits), ptr_of(not_first), group_limbs, len(cols),
                          table if cols else None, ptrs if cols else None, 0)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_KEY_ORDER, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(inv_out)), ctypes.c_size_t(n)))
+
+    def bytecode_rows(self, data, total_bytes, offsets, lens, index_width, count, n, hash_out, empty_hash, hashes=None, tag=None, index=None, value=None,
+                      is_code=None, push_data_left=None, push_data_size=None, length=None, acc_kinds=None, rlc_kinds=None):
+        """The n rows of the bytecode circuit from `count` bytecodes, bytecode b the lens[b] bytes at data + offsets[b] (zk_field_vec_op
+        with ZK_OP_BYTECODE_ROWS).  data, offsets, lens, index_width mean what they mean for keccak(), with count entries.  A bytecode
+        of L bytes owns L + 1 rows, a header row (tag 0, value L) and a row per byte (tag 1, index, value, push_data_size, push_data_left
+        and is_code of the unroller); the rows behind the last bytecode, up to n, are padding, all zero.  hash_out (n x 32 B) receives
+        hashes[b] (count x 32 B Montgomery Fr; None: zero) on every row of bytecode b and empty_hash ((4,) u64 Montgomery Fr) on the
+        padding rows.  tag, is_code, push_data_left, push_data_size, acc_kinds, rlc_kinds: optional n x 1 B at any address; index,
+        value, length: optional n x 4 B.  acc_kinds and rlc_kinds are the kind columns from which scan_rlc makes push_acc (forward, over
+        value) and push_rlc (reverse, over push_acc).  An entry that does not lie inside the total_bytes counts as an empty bytecode;
+        a bytecode that does not fit into the n rows is cut.  Every buffer: a DeviceBuffer or a device pointer.  No output may overlap
+        an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        empty = np.ascontiguousarray(np.asarray(empty_hash, dtype=np.uint64).reshape(4))
+        desc = _BytecodeRows(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(hashes), ptr_of(tag), ptr_of(index), ptr_of(value), ptr_of(is_code),
+                             ptr_of(push_data_left), ptr_of(push_data_size), ptr_of(length), ptr_of(acc_kinds), ptr_of(rlc_kinds), count, index_width, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_BYTECODE_ROWS, ctypes.byref(desc), _host_ptr(empty), ctypes.c_void_p(ptr_of(hash_out)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

@@ -932,6 +932,8 @@ static const DescOp DESC_OPS[] = {
     // h_b: the 64-byte mask or NULL; none
     {ZK_OP_KEY_SORT, "the key ops are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(key_sort_run(ctx, (const zk_key_sort*)a, b, o, n))},
     {ZK_OP_KEY_ORDER, "the key ops are defined over Fr only", DescOp::B_NONE, ZK_DESC_RUN(key_order_run(ctx, (const zk_key_order*)a, o, n))},
+    // h_b: the code hash of the padding rows
+    {ZK_OP_BYTECODE_ROWS, "the bytecode rows are defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(bytecode_rows_run(ctx, (const zk_bytecode_rows*)a, b, o, n))},
     // h_b: the constant and the weights
     {ZK_OP_ROW_RLC, "the row RLC is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_rlc_run(ctx, (const zk_row_rlc*)a, b, (Fr*)o, n))},
     {ZK_OP_ROW_INV0, "the row inverse is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_inv0_run(ctx, (const zk_row_inv0*)a, b, (Fr*)o, n))},
