@@ -144,6 +144,61 @@ typedef struct zk_bytecode_rows {
     uint8_t  index_width;         /* 4 or 8 */
     uint8_t  flags;               /* must be 0 */
 } zk_bytecode_rows;
+/* the rows of the copy circuit and of the copy table of zk_field_vec_op (described there): d_a is a HOST pointer to a zk_copy_rows
+ * (ZK_OP_COPY_ROWS, the integer columns) or a zk_copy_rlc (ZK_OP_COPY_RLC, the challenge-phase columns), whose pointers are device
+ * pointers; the first five members of the two structs are the same in name, type and order.  zk_copy_event is the 88-byte
+ * little-endian record d_events holds per copy event: device data that the host never reads */
+#define ZK_OP_COPY_ROWS 28
+#define ZK_OP_COPY_RLC 30
+#define ZK_COPY_MEMORY_COPY 1
+typedef struct zk_copy_event {
+    uint64_t src_addr, src_addr_end, dst_addr;
+    uint64_t dst_addr_bias;   /* added (mod 2^64) to the addr column on writer rows only */
+    uint64_t rw_counter;      /* rw_counter_start() */
+    uint64_t src_off, dst_off, prev_off;   /* offsets into d_bytes of three runs of `length` bytes */
+    uint32_t length;          /* full_length(): steps; the event owns 2 * length rows */
+    uint32_t src_front, src_back, dst_front, dst_back;   /* masked steps at the front / back of each thread */
+    uint8_t  src_tag, dst_tag;   /* CopyDataType: 1 Bytecode, 2 Memory, 3 TxCalldata, 4 TxLog, 5 RlcAcc */
+    uint8_t  flags;              /* bit 0 ZK_COPY_MEMORY_COPY: src_id == dst_id and both Memory */
+    uint8_t  reserved;           /* 0 */
+} zk_copy_event;
+typedef struct zk_copy_rows {
+    const void* d_events;     /* device: count records of 88 B (zk_copy_event), 8-byte aligned */
+    uint32_t    count;
+    const void* d_bytes;      /* device: the byte heap */
+    uint64_t    total_bytes;  /* below 2^61 */
+    uint8_t     flags;        /* must be 0 */
+    void* d_is_first;         /* n x 1 B or NULL */
+    void* d_is_last;          /* n x 1 B or NULL */
+    void* d_tag;              /* n x 1 B or NULL */
+    void* d_tag_bits;         /* 3 x n B or NULL: plane b (n bytes at d_tag_bits + b * n) holds bit (2 - b) of the tag */
+    void* d_value;            /* n x 1 B or NULL */
+    void* d_value_prev;       /* n x 1 B or NULL */
+    void* d_mask;             /* n x 1 B or NULL */
+    void* d_front_mask;       /* n x 1 B or NULL */
+    void* d_word_index;       /* n x 1 B or NULL */
+    void* d_src_addr_end;     /* n x 8 B or NULL */
+    void* d_is_pad;           /* n x 1 B or NULL */
+    void* d_non_pad_non_mask; /* n x 1 B or NULL */
+    void* d_real_bytes_left;  /* n x 8 B or NULL */
+    void* d_rw_counter;       /* n x 8 B or NULL */
+    void* d_rwc_inc_left;     /* n x 8 B or NULL */
+    void* d_types;            /* 5 x n B or NULL: planes is_bytecode, is_memory, is_tx_calldata, is_tx_log, is_memory_copy */
+    void* d_src_end_rows;     /* n x 1 B or NULL: the d_num of ZK_OP_ROW_INV0 for is_src_end's inverse */
+} zk_copy_rows;
+typedef struct zk_copy_rlc {
+    const void* d_events;     /* device: count records of 88 B (zk_copy_event), 8-byte aligned */
+    uint32_t    count;
+    const void* d_bytes;      /* device: the byte heap */
+    uint64_t    total_bytes;  /* below 2^61 */
+    uint8_t     flags;        /* must be 0 */
+    const void* d_ids;        /* device, count x 2 x 32 B Montgomery Fr, or NULL: src id, then dst id of each event */
+    void* d_id;               /* n x 32 B or NULL */
+    void* d_id_other;         /* n x 32 B or NULL */
+    void* d_rlc_acc;          /* n x 32 B or NULL */
+    void* d_word_rlc;         /* n x 32 B or NULL */
+    void* d_word_rlc_prev;    /* n x 32 B or NULL */
+} zk_copy_rlc;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -423,6 +478,67 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * ZK_ERR_INVALID_ARG before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.
  * Booked under the zk_prof name "bytecode_rows" with count * (2 * index_width + 32 with d_hashes) + total_bytes (only if an output
  * reads the bytes) + n * (32 + the widths of the outputs given) algorithmic bytes per call.
+ * ZK_OP_COPY_ROWS and ZK_OP_COPY_RLC (#defines, values 28 and 30 -- 27 and 29 stay refused; Fr only) make the rows of the reference's
+ * copy circuit and copy table (table.rs CopyTable::assignments, copy_circuit.rs assign_copy_event and assign_padding_row) from one
+ * zk_copy_event record per copy event and the byte heap, both on the device: ZK_OP_COPY_ROWS the integer columns as typed cells ready
+ * for zk_proof_advice_phase_typed_dev, ZK_OP_COPY_RLC the challenge-phase columns.  d_a is a HOST pointer to a zk_copy_rows or a
+ * zk_copy_rlc, read before the call returns; the first five members {d_events, count, d_bytes, total_bytes, flags} are the same in
+ * both; the calls are asynchronous on the context's stream and never wait for the device.  A zk_copy_event {src_addr, src_addr_end,
+ * dst_addr, dst_addr_bias, rw_counter, src_off, dst_off, prev_off, length, src_front, src_back, dst_front, dst_back, src_tag,
+ * dst_tag, flags, reserved} is 88 little-endian bytes of device data that the host never reads: the run at src_off is the reader's
+ * bytes (copy_bytes.bytes), the run at dst_off the writer's (aux_bytes, else src_off again), the run at prev_off bytes_write_prev
+ * (else dst_off again), each of length bytes; dst_addr_bias carries build_tx_log_address, (TxLogFieldTag::Data << 32) + (log_id << 48)
+ * for a log and 0 otherwise; the masks are counts of masked steps at the front and at the back of each thread, which is all that the
+ * circuit's constrain_mask allows.  Event e of L = length steps owns the 2 L rows from start_e = sum_(c<e) 2 L_c; row j of it is step
+ * s = j >> 1 of thread t = j & 1 (0 the reader, 1 the writer).  With (f, b) the front and back counts of the thread -- a thread whose
+ * masks cover the whole event, f + b >= L, keeps front_mask = 1 and never advances its address: (f, b) := (L, 0) --, R = (src_tag ==
+ * 2), W = (dst_tag == 2 or 4), delta = (R + W) (L / 32), cl = max(L - src_front - src_back, 0), q = s / 32, adv = max(0, s - f):
+ *   is_first, is_last            j == 0, j == 2 L - 1
+ *   tag, d_tag_bits, d_types     src_tag on reader rows, dst_tag on writer rows; the three planes of n bytes hold bit 2, 1, 0 of it; the
+ *                                five planes tag == 1, tag == 2, tag == 3, tag == 4 and ZK_COPY_MEMORY_COPY (both rows)
+ *   value, value_prev            d_bytes[src_off + s] (reader) or d_bytes[dst_off + s] (writer); value (reader) or d_bytes[prev_off + s]
+ *   mask, front_mask             s < f or s >= L - b;  s < f
+ *   word_index                   s mod 32
+ *   addr (d_out, n x 8 B)        src_addr + adv (reader), dst_addr + adv + dst_addr_bias (writer), mod 2^64
+ *   src_addr_end                 src_addr_end (reader), dst_addr + L (writer)
+ *   is_pad, non_pad_non_mask     reader only: src_addr + adv >= src_addr_end;  !is_pad && !mask
+ *   real_bytes_left              cl - min(adv, L - f - b), mod 2^64
+ *   rw_counter, rwc_inc_left     memory copy: rw_counter + q and delta - q (reader), rw_counter + delta / 2 + q and delta - delta / 2 - q
+ *                                (writer); otherwise, with inc = q (R + W) + (t == 1 && s mod 32 == 31 ? R : 0): rw_counter + inc, delta - inc
+ *   d_src_end_rows               1 on reader rows and on padding rows, the rows on which the reference assigns is_src_end's inverse:
+ *                                the d_num of ZK_OP_ROW_INV0 over (addr, src_addr_end)
+ * The rows from start_count up to n are padding rows: is_last = i & 1, src_addr_end = 1, mask = front_mask = d_src_end_rows = 1, every
+ * other typed output 0 (tag 0 is Padding).  Each typed output may be NULL; 1-byte columns and planes may stand at any address, 8-byte
+ * columns at a multiple of 8.  ZK_OP_COPY_ROWS takes no second operand: d_b must be NULL.
+ * ZK_OP_COPY_RLC: d_b is a HOST pointer to 2 x 32 B, Montgomery Fr r_word (evm_word) then r_in (keccak_input), all 64 bytes read
+ * before the call returns.  Every output is n x 32 B canonical Montgomery Fr at a multiple of 16, d_out is value_acc, the others may
+ * be NULL.  With A_t(-1) = 0, and W_t and V reset to 0 at every s mod 32 == 0:
+ *   value_acc (d_out)            A_t(s) = mask ? A_t(s - 1) : A_t(s - 1) r_in + (is_pad ? 0 : value)
+ *   d_word_rlc                   W_t(s) = W_t(s - 1) r_word + value
+ *   d_word_rlc_prev              W_0(s) on reader rows; on writer rows V(s) = V(s - 1) r_word + value_prev
+ *   d_rlc_acc                    on every row of the event A_1(L - 1) if src_tag == 5 or dst_tag == 5 or dst_tag == 1, else 0; 0 for an
+ *                                event cut at n.  This is the value constrain_event_rlc_acc forces; it equals the reference's sum over
+ *                                the reader's unmasked bytes whenever the writer's run and masks are the reader's, which holds for every
+ *                                event with an RLC that the reference builds
+ *   d_id, d_id_other             d_ids[2 e + t], d_ids[2 e + 1 - t] (d_ids: count x 2 x 32 B Montgomery Fr at a multiple of 8, the src id
+ *                                then the dst id of each event as number_or_hash_to_field gives them; NULL: 0 for both).  ZK_OP_ROW_INV0
+ *                                over (id, id_other) with the weights (1, -1) is the is_id_unchange inverse of every row
+ * On padding rows every output is 0 except id_other, which is 1 (that inverse is -1 there).  An event counts as an empty event
+ * everywhere in both ops and reads nothing when a tag lies outside 1..5, reserved is nonzero, flag bits other than bit 0 are set or one
+ * of its three runs does not lie inside [0, total_bytes) (off > total_bytes or length > total_bytes - off: it cannot wrap).  Rows at
+ * or after n are not written: an event that does not fit is cut there without an error.  start_e is exact while it
+ * is <= n and saturates there.  No byte outside the two input buffers is ever read, whatever the device data hold; runs may overlap
+ * and repeat; the result is a pure function of the input.  No lane walks an event: the work is laid out by rows.  start is a device
+ * scan into the context's scratch; ZK_OP_COPY_ROWS evaluates the closed forms above per tile of 1024 rows; value_acc is an affine scan
+ * in step space that carries both threads (a masked step is the identity map, an event's first step a constant map, so no segment
+ * flags), the word RLCs look at most 31 steps back, rlc_acc and the ids are gathers behind the scan.  Stages whose outputs are all
+ * NULL are not launched; ZK_OP_COPY_ROWS without d_value and d_value_prev never reads d_bytes.  ZK_FIELD_FQ, nonzero descriptor flags,
+ * NULL or misaligned (8) d_events with count > 0, NULL d_bytes with total_bytes > 0, total_bytes >= 2^61, n >= 2^32, a misaligned
+ * output or d_ids, a non-NULL d_b for ZK_OP_COPY_ROWS, any overlap between an output and any input or another output:
+ * ZK_ERR_INVALID_ARG before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK.
+ * Booked under the zk_prof names "copy_rows" with count * 88 + total_bytes (only with d_value or d_value_prev) + n * (8 + the widths of
+ * the outputs given; d_tag_bits 3, d_types 5) and "copy_rlc" with count * (88 + 64 with d_ids) + total_bytes + n * 32 * (1 + the outputs
+ * given) algorithmic bytes per call.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

@@ -234,6 +234,18 @@ inline void key_order(const Context& c, const void* d_keys, size_t n, void* d_in
 inline void bytecode_rows(const Context& c, const zk_bytecode_rows& desc, const Fr& empty_hash, size_t n, void* d_hash_out) {
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_BYTECODE_ROWS, &desc, &empty_hash, d_hash_out, n));
 }
+// The integer columns of the copy circuit and the copy table from copy events on the device (zk_field_vec_op with ZK_OP_COPY_ROWS;
+// asynchronous on the context's stream).  desc: a zk_copy_rows -- the zk_copy_event records, the byte heap, and the typed outputs
+// wanted, each a device pointer or nullptr.  d_addr (n x 8 B) receives the addr column.
+inline void copy_rows(const Context& c, const zk_copy_rows& desc, size_t n, void* d_addr) {
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_COPY_ROWS, &desc, nullptr, d_addr, n));
+}
+// The challenge-phase columns of the same rows (ZK_OP_COPY_RLC).  desc: a zk_copy_rlc -- events and heap as above, the ids, and
+// id, id_other, rlc_acc, word_rlc, word_rlc_prev, each n x 32 B or nullptr.  d_value_acc (n x 32 B) receives value_acc.
+inline void copy_rlc(const Context& c, const zk_copy_rlc& desc, const Fr& r_word, const Fr& r_in, size_t n, void* d_value_acc) {
+    const Fr challenges[2] = {r_word, r_in};
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_COPY_RLC, &desc, challenges, d_value_acc, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

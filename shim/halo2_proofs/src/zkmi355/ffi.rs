@@ -203,6 +203,77 @@ pub struct zk_bytecode_rows {
     pub index_width: u8,
     pub flags: u8,
 }
+/// `zk_field_vec_op` ops: the rows of the copy circuit and the copy table from copy events on the device.  `ZK_OP_COPY_ROWS` writes
+/// the integer columns (`d_out` is the 8-byte `addr` column; `d_a` a HOST pointer to a `zk_copy_rows`, `d_b` null), `ZK_OP_COPY_RLC`
+/// the challenge-phase columns (`d_out` is `value_acc`; `d_a` a HOST pointer to a `zk_copy_rlc`, `d_b` a HOST pointer to `2 x 32 B`,
+/// Montgomery Fr `r_word` then `r_in`).
+pub const ZK_OP_COPY_ROWS: c_int = 28;
+pub const ZK_OP_COPY_RLC: c_int = 30;
+/// bit 0 of `zk_copy_event::flags`: `src_id == dst_id` and both tags Memory
+pub const ZK_COPY_MEMORY_COPY: u8 = 1;
+/// `zk_copy_event`: the 88-byte record of one copy event, device data.  The three offsets name runs of `length` bytes in the byte
+/// heap; the masks are counts of masked steps at the front and the back of each thread; tags are `CopyDataType` values 1..5.
+#[repr(C)]
+pub struct zk_copy_event {
+    pub src_addr: u64,
+    pub src_addr_end: u64,
+    pub dst_addr: u64,
+    pub dst_addr_bias: u64,
+    pub rw_counter: u64,
+    pub src_off: u64,
+    pub dst_off: u64,
+    pub prev_off: u64,
+    pub length: u32,
+    pub src_front: u32,
+    pub src_back: u32,
+    pub dst_front: u32,
+    pub dst_back: u32,
+    pub src_tag: u8,
+    pub dst_tag: u8,
+    pub flags: u8,
+    pub reserved: u8,
+}
+/// `zk_copy_rows`: the events, the byte heap and the typed outputs of `ZK_OP_COPY_ROWS`; every output may be null.  `flags` must be 0.
+#[repr(C)]
+pub struct zk_copy_rows {
+    pub d_events: *const c_void,
+    pub count: u32,
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub flags: u8,
+    pub d_is_first: *mut c_void,
+    pub d_is_last: *mut c_void,
+    pub d_tag: *mut c_void,
+    pub d_tag_bits: *mut c_void,
+    pub d_value: *mut c_void,
+    pub d_value_prev: *mut c_void,
+    pub d_mask: *mut c_void,
+    pub d_front_mask: *mut c_void,
+    pub d_word_index: *mut c_void,
+    pub d_src_addr_end: *mut c_void,
+    pub d_is_pad: *mut c_void,
+    pub d_non_pad_non_mask: *mut c_void,
+    pub d_real_bytes_left: *mut c_void,
+    pub d_rw_counter: *mut c_void,
+    pub d_rwc_inc_left: *mut c_void,
+    pub d_types: *mut c_void,
+    pub d_src_end_rows: *mut c_void,
+}
+/// `zk_copy_rlc`: the first five members are those of `zk_copy_rows`; `d_ids` (`count x 2 x 32 B`) and every output may be null.
+#[repr(C)]
+pub struct zk_copy_rlc {
+    pub d_events: *const c_void,
+    pub count: u32,
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub flags: u8,
+    pub d_ids: *const c_void,
+    pub d_id: *mut c_void,
+    pub d_id_other: *mut c_void,
+    pub d_rlc_acc: *mut c_void,
+    pub d_word_rlc: *mut c_void,
+    pub d_word_rlc_prev: *mut c_void,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

@@ -33,6 +33,8 @@ OP_SHA256 = 18                                        # out[i] = output_rlc of S
 OP_KEY_SORT = 20                                      # out[i] = index of the 64-byte key record at place i of the stable order (ZK_OP_KEY_SORT)
 OP_KEY_ORDER = 22                                     # out[i] = limb_difference_inverse of key records i and i - 1 in row order (ZK_OP_KEY_ORDER)
 OP_BYTECODE_ROWS = 26                                 # out[i] = the code hash of the bytecode that row i of the bytecode circuit belongs to (ZK_OP_BYTECODE_ROWS)
+OP_COPY_ROWS = 28                                     # out[i] = the addr cell (8 bytes) of row i of the copy circuit, from copy events on the device (ZK_OP_COPY_ROWS)
+OP_COPY_RLC = 30                                      # out[i] = value_acc of row i of the copy circuit (ZK_OP_COPY_RLC)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -145,6 +147,32 @@ class _BytecodeRows(ctypes.Structure):
                 ("d_is_code", ctypes.c_void_p), ("d_push_data_left", ctypes.c_void_p), ("d_push_data_size", ctypes.c_void_p),
                 ("d_length", ctypes.c_void_p), ("d_acc_kinds", ctypes.c_void_p), ("d_rlc_kinds", ctypes.c_void_p),
                 ("count", ctypes.c_uint32), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+COPY_ROWS_OUTPUTS = ("is_first", "is_last", "tag", "tag_bits", "value", "value_prev", "mask", "front_mask", "word_index", "src_addr_end", "is_pad", "non_pad_non_mask",
+                     "real_bytes_left", "rw_counter", "rwc_inc_left", "types", "src_end_rows")
+COPY_RLC_OUTPUTS = ("id", "id_other", "rlc_acc", "word_rlc", "word_rlc_prev")
+
+
+class _CopyEvent(ctypes.Structure):
+    """zk_copy_event: the 88-byte record of one copy event (device data; the host never reads it)"""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("src_addr", "src_addr_end", "dst_addr", "dst_addr_bias", "rw_counter", "src_off", "dst_off", "prev_off")] + \
+               [(name, ctypes.c_uint32) for name in ("length", "src_front", "src_back", "dst_front", "dst_back")] + \
+               [(name, ctypes.c_uint8) for name in ("src_tag", "dst_tag", "flags", "reserved")]
+
+
+_COPY_SHARED = [("d_events", ctypes.c_void_p), ("count", ctypes.c_uint32), ("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("flags", ctypes.c_uint8)]
+
+
+class _CopyRows(ctypes.Structure):
+    """zk_copy_rows: the events, the byte heap and the typed outputs of ZK_OP_COPY_ROWS (host memory; every pointer is a device pointer
+    or NULL)"""
+    _fields_ = _COPY_SHARED + [("d_" + name, ctypes.c_void_p) for name in COPY_ROWS_OUTPUTS]
+
+
+class _CopyRlc(ctypes.Structure):
+    """zk_copy_rlc: the events, the byte heap, the ids and the outputs of ZK_OP_COPY_RLC"""
+    _fields_ = _COPY_SHARED + [("d_ids", ctypes.c_void_p)] + [("d_" + name, ctypes.c_void_p) for name in COPY_RLC_OUTPUTS]
 
 
 def _host_ptr(a: np.ndarray):
@@ -909,6 +937,36 @@ class Context:
         desc = _BytecodeRows(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), ptr_of(hashes), ptr_of(tag), ptr_of(index), ptr_of(value), ptr_of(is_code),
                              ptr_of(push_data_left), ptr_of(push_data_size), ptr_of(length), ptr_of(acc_kinds), ptr_of(rlc_kinds), count, index_width, 0)
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_BYTECODE_ROWS, ctypes.byref(desc), _host_ptr(empty), ctypes.c_void_p(ptr_of(hash_out)), ctypes.c_size_t(n)))
+
+    def copy_rows(self, events, count, data, total_bytes, n, addr, **outputs):
+        """The integer columns of the n rows of the copy circuit and the copy table from `count` copy events (zk_field_vec_op with
+        ZK_OP_COPY_ROWS).  events: count records of 88 bytes (zk_copy_event) on the device, 8-byte aligned; data: the byte heap of
+        total_bytes bytes that the events' three runs point into.  An event of L steps owns 2 L rows, a reader row and a writer row per
+        step; the rows behind the last event, up to n, are padding rows.  addr (n x 8 B) receives the addr column; outputs: any of
+        COPY_ROWS_OUTPUTS -- 1-byte columns at any address, tag_bits 3 and types 5 planes of n bytes, src_addr_end, real_bytes_left,
+        rw_counter and rwc_inc_left n x 8 B at a multiple of 8.  An event that does not count (a tag outside 1..5, a nonzero reserved
+        byte, unknown flag bits, a run outside the heap) is an empty event; an event that does not fit into the n rows is cut.  Every
+        buffer: a DeviceBuffer or a device pointer.  No output may overlap an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        unknown = set(outputs) - set(COPY_ROWS_OUTPUTS)
+        if unknown:
+            raise TypeError(f"copy_rows: unknown outputs {sorted(unknown)}")
+        desc = _CopyRows(ptr_of(events), count, ptr_of(data), total_bytes, 0, *(ptr_of(outputs.get(name)) for name in COPY_ROWS_OUTPUTS))
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_COPY_ROWS, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(addr)), ctypes.c_size_t(n)))
+
+    def copy_rlc(self, events, count, data, total_bytes, n, value_acc, r_word, r_in, ids=None, **outputs):
+        """The challenge-phase columns of the same n rows (zk_field_vec_op with ZK_OP_COPY_RLC).  events, count, data, total_bytes: as
+        for copy_rows.  r_word (evm_word) and r_in (keccak_input): (4,) u64 Montgomery Fr.  value_acc (n x 32 B) receives the running
+        RLC of each thread's unmasked bytes; outputs: any of COPY_RLC_OUTPUTS, n x 32 B at a multiple of 16 -- word_rlc and
+        word_rlc_prev restart every 32 steps, rlc_acc is the writer's last value_acc on every row of an event with an RLC, id and
+        id_other are ids[2 e + t] and ids[2 e + 1 - t] (ids: count x 2 x 32 B Montgomery Fr or None) and 0 and 1 on padding rows."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        unknown = set(outputs) - set(COPY_RLC_OUTPUTS)
+        if unknown:
+            raise TypeError(f"copy_rlc: unknown outputs {sorted(unknown)}")
+        ch = np.ascontiguousarray(np.concatenate([np.asarray(r_word, dtype=np.uint64).reshape(4), np.asarray(r_in, dtype=np.uint64).reshape(4)]))
+        desc = _CopyRlc(ptr_of(events), count, ptr_of(data), total_bytes, 0, ptr_of(ids), *(ptr_of(outputs.get(name)) for name in COPY_RLC_OUTPUTS))
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_COPY_RLC, ctypes.byref(desc), _host_ptr(ch), ctypes.c_void_p(ptr_of(value_acc)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

@@ -368,8 +368,8 @@ __global__ void __launch_bounds__(256) k_bc_rows(const BcArgs g) {
     }
 }
 
-// exclusive saturating scan of w[0 .. count) in place; tmp: room for the sums of every level
-static void bc_scan(zk_ctx* ctx, uint32_t* w, uint64_t count, uint32_t* tmp, uint32_t cap) {
+// exclusive saturating scan of w[0 .. count) in place; tmp: room for the sums of every level (copy_rows.hip scans its row starts with it too)
+void bc_scan(zk_ctx* ctx, uint32_t* w, uint64_t count, uint32_t* tmp, uint32_t cap) {
     const uint64_t tiles = (count + BC_SCAN_TILE - 1) / BC_SCAN_TILE;
     if (tiles <= 1) {
         hipLaunchKernelGGL(k_bc_scan_down, dim3(1), dim3(256), 0, ctx->stream, w, count, (const uint32_t*)nullptr, cap);

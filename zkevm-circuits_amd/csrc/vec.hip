@@ -8,6 +8,7 @@
 // and zk_field_vec_op, which dispatches the descriptor ops of the other units.
 // All kernels read/write 32-byte elements as two 16-byte transactions per lane, consecutive
 // lanes on consecutive elements (fully coalesced), grid-stride where a fixed grid is needed.
+#include "affine.hip.hpp"
 #include "ctx.hpp"
 #include "ff29.hip.hpp"
 #include "op_check.hpp"
@@ -117,8 +118,6 @@ __global__ void __launch_bounds__(256) k_batch_invert(Fr* __restrict__ a, uint64
 //      + LDS Hillis-Steele over the 256 thread totals), writes locally-prefixed z, block total
 //   B: one block scans the block totals
 //   C: z[i] = off[block] (op) z[i]
-constexpr int SCAN_THREADS = 256;
-constexpr int SCAN_PER = 8;
 struct OpMul { __device__ static Fr id() { return Fr::one(); } __device__ static Fr f(const Fr& a, const Fr& b) { return a * b; } };
 struct OpAdd { __device__ static Fr id() { return Fr::zero(); } __device__ static Fr f(const Fr& a, const Fr& b) { return a + b; } };
 
@@ -339,10 +338,7 @@ int fr_batch_invert_from(zk_ctx* ctx, const Fr* const* d_src, const void* h_beta
 //   C: each block folds its thread chunks again, scans the thread maps in LDS, applies the exclusive map to the entering value and
 //      walks its elements: z = a[i] z + b[i], stored as it goes.  a and b are read twice, out is written once.
 // REV mirrors the memory index (scan position j is element n - 1 - j) and nothing else: ZK_OP_SCAN_AFFINE_REV.
-struct Aff { Fr A, B; };
-__device__ __forceinline__ Aff aff_id() { return Aff{Fr::one(), Fr::zero()}; }
-__device__ __forceinline__ Aff aff_then(const Aff& p, const Aff& q) { return Aff{q.A * p.A, q.A * p.B + q.B}; }   // first p, then q
-__device__ __forceinline__ Fr aff_apply(const Aff& p, const Fr& z) { return p.A * z + p.B; }
+// Aff, aff_then, aff_apply, aff_block_total and aff_block_exclusive_scan are csrc/affine.hip.hpp, which copy_rows.hip shares.
 
 // composite map of this thread's SCAN_PER elements from scan position `start` on; positions at or past n are the identity and
 // are skipped.  Scan position j is element j, or n - 1 - j under REV.
@@ -360,37 +356,6 @@ __device__ __forceinline__ Aff aff_chunk(const Fr* __restrict__ a, const Fr* __r
         acc.B = x * acc.B + ldg(b + i);
     }
     return acc;
-}
-// composite of the block's SCAN_THREADS maps in thread order (valid in thread 0): neighbours pair up, the earlier one first
-__device__ __forceinline__ Aff aff_block_total(const Aff& v, Aff* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int m = SCAN_THREADS / 2; m > 0; m >>= 1) {
-        Aff x;
-        if (t < m) x = aff_then(sh[2 * t], sh[2 * t + 1]);
-        __syncthreads();
-        if (t < m) sh[t] = x;
-        __syncthreads();
-    }
-    return sh[0];
-}
-// block_exclusive_scan over maps: returns the composite of the threads before this one; *total = the whole block's
-__device__ __forceinline__ Aff aff_block_exclusive_scan(const Aff& v, Aff* sh, Aff* total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-        Aff x = sh[t];
-        if (t >= off) x = aff_then(sh[t - off], x);
-        __syncthreads();
-        sh[t] = x;
-        __syncthreads();
-    }
-    *total = sh[SCAN_THREADS - 1];
-    Aff ex = t ? sh[t - 1] : aff_id();
-    __syncthreads();
-    return ex;
 }
 
 template <bool REV>
@@ -412,6 +377,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_affine_b(const Aff* __restrict
         if (i < cnt) stg(entering + i, aff_apply(ex, carry));
         carry = aff_apply(total, carry);
     }
+}
+void affine_b_launch(zk_ctx* ctx, const Aff* maps, Fr* entering, uint32_t cnt) {
+    hipLaunchKernelGGL(k_affine_b, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, maps, entering, cnt);
 }
 // entering == nullptr: a single block, nothing enters it
 template <bool REV>
@@ -934,6 +902,9 @@ static const DescOp DESC_OPS[] = {
     {ZK_OP_KEY_ORDER, "the key ops are defined over Fr only", DescOp::B_NONE, ZK_DESC_RUN(key_order_run(ctx, (const zk_key_order*)a, o, n))},
     // h_b: the code hash of the padding rows
     {ZK_OP_BYTECODE_ROWS, "the bytecode rows are defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(bytecode_rows_run(ctx, (const zk_bytecode_rows*)a, b, o, n))},
+    // h_b: must be NULL (copy_rows_run says so in its own words); r_word and r_in
+    {ZK_OP_COPY_ROWS, "the copy rows are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(copy_rows_run(ctx, (const zk_copy_rows*)a, b, o, n))},
+    {ZK_OP_COPY_RLC, "the copy rows are defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(copy_rlc_run(ctx, (const zk_copy_rlc*)a, b, o, n))},
     // h_b: the constant and the weights
     {ZK_OP_ROW_RLC, "the row RLC is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_rlc_run(ctx, (const zk_row_rlc*)a, b, (Fr*)o, n))},
     {ZK_OP_ROW_INV0, "the row inverse is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_inv0_run(ctx, (const zk_row_inv0*)a, b, (Fr*)o, n))},
