@@ -15,24 +15,11 @@
 #include <algorithm>
 
 #include "ctx.hpp"
+#include "lkhash.hip.hpp"            // fr_hash, fr_same
 
 namespace zk {
 
 constexpr uint32_t LK_EMPTY = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t fr_hash(const Fr& a) {
-    uint32_t h = a.l[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) h = (h ^ a.l[i]) * 0x9E3779B1u + (h >> 15);
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;   // murmur3 finaliser
-    return h;
-}
-__device__ __forceinline__ bool fr_same(const Fr& a, const Fr& b) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d |= a.l[i] ^ b.l[i];
-    return d == 0;
-}
 
 __global__ void __launch_bounds__(256) k_lk_insert(const Fr* __restrict__ table, uint32_t rows, uint32_t* slots, uint32_t mask) {
     // Rows are taken from the top down: the workgroups that start first carry the highest rows, so when a value repeats over a
