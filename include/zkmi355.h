@@ -199,6 +199,29 @@ typedef struct zk_copy_rlc {
     void* d_word_rlc;         /* n x 32 B or NULL */
     void* d_word_rlc_prev;    /* n x 32 B or NULL */
 } zk_copy_rlc;
+/* the rows of the exponentiation circuit and of the exponentiation table of zk_field_vec_op (described there): d_a is a HOST pointer
+ * to a zk_exp_rows, whose pointers are device pointers.  zk_exp_event is the 64-byte little-endian record d_events holds per
+ * exponentiation event: device data that the host never reads */
+#define ZK_OP_EXP_ROWS 32
+typedef struct zk_exp_event {
+    uint64_t base[4];         /* little-endian 64-bit limbs */
+    uint64_t exponent[4];
+} zk_exp_event;
+typedef struct zk_exp_rows {
+    const void* d_events;      /* device: count records of 64 B, 8-byte aligned */
+    uint32_t    count;
+    uint8_t     flags;         /* must be 0 */
+    void* d_is_last;           /* n x 1 B or NULL */
+    void* d_base_limb;         /* n x 8 B or NULL */
+    void* d_exponent_lo_hi;    /* n x 16 B or NULL */
+    void* d_mul_cols;          /* 4 x n x 16 B or NULL: plane c (at + c * n * 16) is mul_gadget col c */
+    void* d_mul_u16_64;        /* 4 x n x 2 B or NULL: planes of range_check_64.u16_repr */
+    void* d_mul_u16_128;       /* 8 x n x 2 B or NULL */
+    void* d_parity_cols;       /* as d_mul_cols */
+    void* d_parity_u16_64;     /* as d_mul_u16_64 */
+    void* d_parity_u16_128;    /* as d_mul_u16_128 */
+    void* d_rows_needed;       /* one uint64_t, 8-byte aligned, or NULL */
+} zk_exp_rows;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -539,6 +562,44 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * Booked under the zk_prof names "copy_rows" with count * 88 + total_bytes (only with d_value or d_value_prev) + n * (8 + the widths of
  * the outputs given; d_tag_bits 3, d_types 5) and "copy_rlc" with count * (88 + 64 with d_ids) + total_bytes + n * 32 * (1 + the outputs
  * given) algorithmic bytes per call.
+ * ZK_OP_EXP_ROWS (#define, value 32 -- 31 stays refused; Fr only) makes the rows of the reference's exponentiation circuit and
+ * exponentiation table (exp_circuit.rs assign_exp_events, table.rs ExpTable::assignments, gadgets MulAddChip::assign and
+ * UIntRangeCheckChip::assign) from one zk_exp_event {base[4], exponent[4]} per event, 64 little-endian bytes of device data that the
+ * host never reads: every cell is an integer of at most 128 bits, written as a typed cell ready for zk_proof_advice_phase_typed_dev.
+ * d_a is a HOST pointer to a zk_exp_rows, read before the call returns; d_b must be NULL; the call is asynchronous on the context's
+ * stream and never waits for the device.  d_out is exponentiation_lo_hi, n x 16 B at a multiple of 16; every other output may be
+ * NULL, 16-byte cells at a multiple of 16, d_base_limb at one of 8, the u16 planes at one of 2, d_is_last anywhere.  An event with
+ * exponent x < 2 has no steps and no rows; otherwise it has S = (bitlen(x) - 1) + (popcount(x) - 1) <= 510 steps of 8 rows from
+ * start_e = sum_(c<e) 8 S_c, in the reference's reversed order (exp_by_squaring's steps, last first), all products mod 2^256.  With
+ * P(i) = i + popcount(x mod 2^i) and i the largest index with P(i) <= j, step j holds x_j = x >> i, bit 0 cleared when j - P(i) == 1,
+ * d_j = base^(x_j); x_j odd: a_j = base^(x_j - 1), b_j = base; x_j even: a_j = b_j = base^(x_j / 2).  The rows of step j at row o:
+ *   d_is_last                    1 on row o of step S - 1, else 0
+ *   d_base_limb                  the 64-bit limbs 0..3 of base on rows o .. o + 3, 0 on rows o + 4 .. o + 7
+ *   d_exponent_lo_hi, d_out      the low and the high 128 bits of x_j, of d_j, on rows o and o + 1, 0 below
+ *   d_mul_cols, d_parity_cols    MulAddChip::assign of [a_j, b_j, 0, d_j] and of [2, x_j >> 1, x_j & 1, x_j]: plane c (n x 16 B at
+ *                                + c * n * 16) is the chip's col c.  Row o: the 64-bit limbs of a; o + 1: of b; o + 2: c_lo, c_hi,
+ *                                d_lo, d_hi; o + 3 and col 0 of o + 4: the five u16 digits of carry_lo = (t0 + t1 2^64 + c_lo - d_lo)
+ *                                >> 128; o + 5 and col 0 of o + 6: of carry_hi = (t2 + t3 2^64 + c_hi + carry_lo - d_hi) >> 128, with
+ *                                t_k = sum_(i<=k) a_i b_(k-i); every other cell 0
+ *   d_*_u16_64                   range_check_64.u16_repr: plane c (n x 2 B at + c * n * 2) holds digit c of a_0 .. a_3, b_0 .. b_3 on
+ *                                rows o .. o + 7
+ *   d_*_u16_128                  range_check_128.u16_repr: plane c of eight holds digit c of c_lo, c_hi, d_lo, d_hi on rows o .. o + 3,
+ *                                0 below
+ * Behind the events' rows the default event (base 2, exponent 2: one step, a = b = 2, d = 4, is_last = 1) is repeated while
+ * offset + 8 <= n - 10, and every row behind that is 0 in every output; n is the caller's max_exp_rows, need not be a multiple of 8
+ * and may be below 10 (all zeros).  Where the reference asserts that the events fit, the op writes whole steps only: a step whose 8
+ * rows do not lie below n - 10 is not written and neither is anything behind it, zeros take over.  d_rows_needed, one uint64_t on the
+ * device at a multiple of 8 or NULL, receives 8 sum S + 10, exact and unsaturated, for the caller to compare with n later; start_e is
+ * exact while it is <= n and saturates there.  The fixed columns q_enable, is_step and is_final_step are key material, constant for
+ * a given n, and not part of the op; the u16 cells are in range by construction.  No lane walks an event to find x_j, a_j or b_j:
+ * start is a device scan into the context's scratch, one lane per event runs the chain d_(S - 1) .. d_0 of truncated multiplies into
+ * (n / 8 + 1) x 32 B of scratch, and the rows are closed forms per tile of 1024 rows.  No atomics; no byte outside d_events is read
+ * whatever the records hold; the result is a pure function of the input.  ZK_FIELD_FQ, nonzero flags, NULL or misaligned (8)
+ * d_events with count > 0, n >= 2^32, a misaligned output, a non-NULL d_b, any overlap of an output with the events or another
+ * output: ZK_ERR_INVALID_ARG before any launch, nothing is written; the arguments are validated before n is looked at, n = 0 is then
+ * ZK_OK and writes nothing, d_rows_needed included.  Booked under the zk_prof name "exp_rows" with count * 64 + n * (16 + the widths of the outputs given: 1, 8, 16, 64, 8, 16,
+ * 64, 8, 16) algorithmic bytes per call; inside it k_exp_chain and k_exp_rows are timed on their own under "exp_rows_chain" and
+ * "exp_rows_tiles", with no bytes.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

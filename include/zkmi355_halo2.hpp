@@ -246,6 +246,13 @@ inline void copy_rlc(const Context& c, const zk_copy_rlc& desc, const Fr& r_word
     const Fr challenges[2] = {r_word, r_in};
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_COPY_RLC, &desc, challenges, d_value_acc, n));
 }
+// The rows of the exponentiation circuit and the exponentiation table from (base, exponent) events on the device (zk_field_vec_op
+// with ZK_OP_EXP_ROWS; asynchronous on the context's stream).  desc: a zk_exp_rows -- the zk_exp_event records and the typed outputs
+// wanted, each a device pointer or nullptr; d_rows_needed receives 8 x the steps of all events + 10 for the caller to compare with n.
+// d_exponentiation_lo_hi (n x 16 B) receives that column.
+inline void exp_rows(const Context& c, const zk_exp_rows& desc, size_t n, void* d_exponentiation_lo_hi) {
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_EXP_ROWS, &desc, nullptr, d_exponentiation_lo_hi, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -274,6 +274,33 @@ pub struct zk_copy_rlc {
     pub d_word_rlc: *mut c_void,
     pub d_word_rlc_prev: *mut c_void,
 }
+/// `zk_field_vec_op` op: the rows of the exponentiation circuit and the exponentiation table from `(base, exponent)` events on the
+/// device (`d_out` is the 16-byte `exponentiation_lo_hi` column; `d_a` a HOST pointer to a `zk_exp_rows`, `d_b` null).
+pub const ZK_OP_EXP_ROWS: c_int = 32;
+/// `zk_exp_event`: the 64-byte record of one exponentiation event, device data: little-endian 64-bit limbs.
+#[repr(C)]
+pub struct zk_exp_event {
+    pub base: [u64; 4],
+    pub exponent: [u64; 4],
+}
+/// `zk_exp_rows`: the events and the typed outputs of `ZK_OP_EXP_ROWS`; every output may be null.  `flags` must be 0.
+/// `d_rows_needed` receives `8 x steps + 10` as one `u64` for the caller to compare with `n`.
+#[repr(C)]
+pub struct zk_exp_rows {
+    pub d_events: *const c_void,
+    pub count: u32,
+    pub flags: u8,
+    pub d_is_last: *mut c_void,
+    pub d_base_limb: *mut c_void,
+    pub d_exponent_lo_hi: *mut c_void,
+    pub d_mul_cols: *mut c_void,
+    pub d_mul_u16_64: *mut c_void,
+    pub d_mul_u16_128: *mut c_void,
+    pub d_parity_cols: *mut c_void,
+    pub d_parity_u16_64: *mut c_void,
+    pub d_parity_u16_128: *mut c_void,
+    pub d_rows_needed: *mut c_void,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

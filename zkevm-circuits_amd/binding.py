@@ -35,6 +35,7 @@ OP_KEY_ORDER = 22                                     # out[i] = limb_difference
 OP_BYTECODE_ROWS = 26                                 # out[i] = the code hash of the bytecode that row i of the bytecode circuit belongs to (ZK_OP_BYTECODE_ROWS)
 OP_COPY_ROWS = 28                                     # out[i] = the addr cell (8 bytes) of row i of the copy circuit, from copy events on the device (ZK_OP_COPY_ROWS)
 OP_COPY_RLC = 30                                      # out[i] = value_acc of row i of the copy circuit (ZK_OP_COPY_RLC)
+OP_EXP_ROWS = 32                                      # out[i] = the exponentiation_lo_hi cell (16 bytes) of row i of the exponentiation circuit (ZK_OP_EXP_ROWS)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -173,6 +174,19 @@ class _CopyRows(ctypes.Structure):
 class _CopyRlc(ctypes.Structure):
     """zk_copy_rlc: the events, the byte heap, the ids and the outputs of ZK_OP_COPY_RLC"""
     _fields_ = _COPY_SHARED + [("d_ids", ctypes.c_void_p)] + [("d_" + name, ctypes.c_void_p) for name in COPY_RLC_OUTPUTS]
+
+
+EXP_ROWS_OUTPUTS = ("is_last", "base_limb", "exponent_lo_hi", "mul_cols", "mul_u16_64", "mul_u16_128", "parity_cols", "parity_u16_64", "parity_u16_128", "rows_needed")
+
+
+class _ExpEvent(ctypes.Structure):
+    """zk_exp_event: the 64-byte record of one exponentiation event (device data; the host never reads it)"""
+    _fields_ = [("base", ctypes.c_uint64 * 4), ("exponent", ctypes.c_uint64 * 4)]
+
+
+class _ExpRows(ctypes.Structure):
+    """zk_exp_rows: the events and the typed outputs of ZK_OP_EXP_ROWS (host memory; every pointer is a device pointer or NULL)"""
+    _fields_ = [("d_events", ctypes.c_void_p), ("count", ctypes.c_uint32), ("flags", ctypes.c_uint8)] + [("d_" + name, ctypes.c_void_p) for name in EXP_ROWS_OUTPUTS]
 
 
 def _host_ptr(a: np.ndarray):
@@ -967,6 +981,23 @@ class Context:
         ch = np.ascontiguousarray(np.concatenate([np.asarray(r_word, dtype=np.uint64).reshape(4), np.asarray(r_in, dtype=np.uint64).reshape(4)]))
         desc = _CopyRlc(ptr_of(events), count, ptr_of(data), total_bytes, 0, ptr_of(ids), *(ptr_of(outputs.get(name)) for name in COPY_RLC_OUTPUTS))
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_COPY_RLC, ctypes.byref(desc), _host_ptr(ch), ctypes.c_void_p(ptr_of(value_acc)), ctypes.c_size_t(n)))
+
+    def exp_rows(self, events, count, n, exponentiation_lo_hi, **outputs):
+        """The n rows of the exponentiation circuit and the exponentiation table from `count` events (zk_field_vec_op with
+        ZK_OP_EXP_ROWS).  events: count records of 64 bytes (zk_exp_event: base, then exponent, four little-endian u64 each) on the
+        device, 8-byte aligned.  An event with exponent x >= 2 owns 8 rows for each of its (bitlen(x) - 1) + (popcount(x) - 1) steps,
+        last step of exp_by_squaring first; behind the events the default event (2, 2) is repeated while a step fits below the
+        n - 10 rows in use, and the rest is zero.  exponentiation_lo_hi (n x 16 B at a multiple of 16) receives that column; outputs:
+        any of EXP_ROWS_OUTPUTS -- is_last n x 1 B, base_limb n x 8 B, exponent_lo_hi n x 16 B, mul_cols and parity_cols 4 planes of
+        n x 16 B, the u16_64 and u16_128 outputs 4 and 8 planes of n x 2 B, rows_needed one uint64 that receives 8 x the steps of
+        all events + 10 for the caller to compare with n (events that do not fit are cut at a whole step, without an error).  Every
+        buffer: a DeviceBuffer or a device pointer.  No output may overlap the events or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        unknown = set(outputs) - set(EXP_ROWS_OUTPUTS)
+        if unknown:
+            raise TypeError(f"exp_rows: unknown outputs {sorted(unknown)}")
+        desc = _ExpRows(ptr_of(events), count, 0, *(ptr_of(outputs.get(name)) for name in EXP_ROWS_OUTPUTS))
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_EXP_ROWS, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(exponentiation_lo_hi)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

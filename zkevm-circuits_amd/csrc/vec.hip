@@ -905,6 +905,8 @@ static const DescOp DESC_OPS[] = {
     // h_b: must be NULL (copy_rows_run says so in its own words); r_word and r_in
     {ZK_OP_COPY_ROWS, "the copy rows are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(copy_rows_run(ctx, (const zk_copy_rows*)a, b, o, n))},
     {ZK_OP_COPY_RLC, "the copy rows are defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(copy_rlc_run(ctx, (const zk_copy_rlc*)a, b, o, n))},
+    // h_b: must be NULL (exp_rows_run says so in its own words)
+    {ZK_OP_EXP_ROWS, "the exponentiation rows are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(exp_rows_run(ctx, (const zk_exp_rows*)a, b, o, n))},
     // h_b: the constant and the weights
     {ZK_OP_ROW_RLC, "the row RLC is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_rlc_run(ctx, (const zk_row_rlc*)a, b, (Fr*)o, n))},
     {ZK_OP_ROW_INV0, "the row inverse is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_inv0_run(ctx, (const zk_row_inv0*)a, b, (Fr*)o, n))},
