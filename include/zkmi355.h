@@ -222,6 +222,43 @@ typedef struct zk_exp_rows {
     void* d_parity_u16_128;    /* as d_mul_u16_128 */
     void* d_rows_needed;       /* one uint64_t, 8-byte aligned, or NULL */
 } zk_exp_rows;
+/* the columns the Poseidon-hash extension adds to the bytecode circuit, and the code-hash rows of the Poseidon table, of
+ * zk_field_vec_op (described there): d_a is a HOST pointer to a zk_code_hash_rows (ZK_OP_CODE_HASH_ROWS) or a zk_code_hash_table
+ * (ZK_OP_CODE_HASH_TABLE), whose pointers are device pointers; d_bytes, total_bytes, d_offsets, d_lens and index_width are those of
+ * zk_keccak and zk_bytecode_rows, the first four members of the two structs are the same in name, type and order */
+#define ZK_OP_CODE_HASH_ROWS 34
+#define ZK_OP_CODE_HASH_TABLE 36
+typedef struct zk_code_hash_rows {
+    const void* d_bytes;            /* device: the bytes the bytecodes live in */
+    uint64_t    total_bytes;        /* bytes readable at d_bytes; below 2^61 */
+    const void* d_offsets;          /* device: count unsigned little-endian offsets into d_bytes */
+    const void* d_lens;             /* device: count unsigned little-endian byte lengths */
+    void* d_control_length;         /* n x 4 B or NULL */
+    void* d_bytes_in_field_index;   /* n x 1 B or NULL */
+    void* d_bytes_in_field_inv;     /* n x 32 B Montgomery Fr, 16-byte aligned, or NULL */
+    void* d_is_field_border;        /* n x 1 B or NULL */
+    void* d_padding_shift;          /* n x 32 B Montgomery Fr, 16-byte aligned, or NULL */
+    void* d_field_index;            /* n x 1 B or NULL */
+    void* d_field_index_inv;        /* n x 1 B or NULL */
+    uint32_t count;                 /* bytecodes */
+    uint8_t  index_width;           /* 4 or 8 */
+    uint8_t  flags;                 /* must be 0 */
+} zk_code_hash_rows;
+typedef struct zk_code_hash_table {
+    const void* d_bytes;            /* device: the bytes the bytecodes live in */
+    uint64_t    total_bytes;        /* bytes readable at d_bytes; below 2^61 */
+    const void* d_offsets;          /* device: count unsigned little-endian offsets into d_bytes */
+    const void* d_lens;             /* device: count unsigned little-endian byte lengths */
+    void* d_input1;                 /* n x 32 B Montgomery Fr, 16-byte aligned, or NULL */
+    void* d_control;                /* n x 16 B, 16-byte aligned, or NULL */
+    void* d_heading_mark;           /* n x 1 B or NULL */
+    void* d_kinds;                  /* n x 1 B or NULL: the kinds column of ZK_OP_POSEIDON */
+    void* d_cap;                    /* n x 8 B, 8-byte aligned, or NULL: the d_cap of ZK_OP_POSEIDON */
+    void* d_rows_needed;            /* one uint64_t, 8-byte aligned, or NULL */
+    uint32_t count;                 /* bytecodes */
+    uint8_t  index_width;           /* 4 or 8 */
+    uint8_t  flags;                 /* must be 0 */
+} zk_code_hash_table;
 
 /* ---- context / memory ----------------------------------------------------------------------- */
 int zk_ctx_create(int device, zk_ctx** out);
@@ -600,6 +637,51 @@ int zk_selftest_products(zk_ctx* ctx, int field, uint32_t operand_sets, uint32_t
  * ZK_OK and writes nothing, d_rows_needed included.  Booked under the zk_prof name "exp_rows" with count * 64 + n * (16 + the widths of the outputs given: 1, 8, 16, 64, 8, 16,
  * 64, 8, 16) algorithmic bytes per call; inside it k_exp_chain and k_exp_rows are timed on their own under "exp_rows_chain" and
  * "exp_rows_tiles", with no bytes.
+ * ZK_OP_CODE_HASH_ROWS and ZK_OP_CODE_HASH_TABLE (#defines, values 34 and 36 -- 33 and 35 stay refused; Fr only) make, from the code
+ * bytes ZK_OP_KECCAK and ZK_OP_BYTECODE_ROWS read, the eight advice columns that the Poseidon-hash extension adds to the bytecode
+ * circuit (bytecode_circuit/circuit/to_poseidon_hash.rs assign_extended_row, set_header_row) and the code-hash rows of the Poseidon
+ * table (table.rs PoseidonTable::dev_load over unroll_to_hash_input_default) in the shape ZK_OP_POSEIDON reads.  d_a is a
+ * HOST pointer to a zk_code_hash_rows or a zk_code_hash_table, read before the call returns; d_b must be NULL; the calls are asynchronous
+ * on the context's stream, never wait for the device and allocate nothing once the context's scratch has grown to the size of the
+ * call.  d_bytes, total_bytes, d_offsets, d_lens and index_width mean exactly what they mean in zk_keccak and zk_bytecode_rows,
+ * with count entries and the same rule: an entry with off > total_bytes or len > total_bytes - off is an empty bytecode, and no
+ * byte outside [d_bytes, d_bytes + total_bytes) -- indeed none outside a bytecode's own [off, off + len) -- is ever read.  With L
+ * the length of a bytecode and B its bytes, 31 = HASHBLOCK_BYTES_IN_FIELD bytes to a field and two fields to a block:
+ * ZK_OP_CODE_HASH_ROWS works in the row space of ZK_OP_BYTECODE_ROWS: bytecode b owns the L_b + 1 rows from start_b = sum_(c<b)
+ * (L_c + 1), the scan saturates at n, a bytecode that does not fit is cut at n without an error, rows at or after n are not written.
+ *   header row of b              control_length L, field_input 0, bytes_in_field_index 0, bytes_in_field_inv 0, is_field_border 0,
+ *                                padding_shift 256^31, field_index 1, field_index_inv 0 (the reference's set_header_row, although
+ *                                1 / (2 - 1) = 1)
+ *   byte row p, m = p mod 31     control_length L - 62 (p div 62), field_input sum_(t=0..m) B[p - m + t] 256^(30 - t),
+ *                                bytes_in_field_index m + 1, bytes_in_field_inv 1 / (30 - m) or 0, is_field_border (m == 30 or
+ *                                p + 1 == L), padding_shift 256^(30 - m), field_index (p div 31) mod 2 + 1, field_index_inv
+ *                                1 - (p div 31) mod 2
+ *   padding rows, up to n        a header row of length 0
+ * field_input is d_out, n x 32 B canonical Montgomery Fr at a multiple of 16, as are d_bytes_in_field_inv and d_padding_shift;
+ * d_control_length is n x 4 B (L mod 2^32, as the bytecode op's length) at a multiple of 4; the four 1-byte columns stand at any
+ * address; every typed output may be NULL, and the typed cells are ready for zk_proof_advice_phase_typed_dev.
+ * ZK_OP_CODE_HASH_TABLE works in the row space of the table: bytecode b owns the K_b = ceil(L_b / 62) rows from tstart_b = sum_(c<b)
+ * K_c -- an empty bytecode owns none --, under the same saturating scan.  Row j of b:
+ *   d_out, d_input1              n x 32 B Montgomery Fr at a multiple of 16: the big-endian integers of B[62 j .. 62 j + 31) and
+ *                                B[62 j + 31 .. 62 j + 62), bytes at or behind L read as 0 (and are not read from memory)
+ *   d_control                    n x 16 B little-endian at a multiple of 16: (L - 62 j) 2^64 = HASHABLE_DOMAIN_SPEC * control_len,
+ *                                the low eight bytes 0
+ *   d_heading_mark, d_kinds      n x 1 B each: j == 0; 0 on j == 0 and 1 otherwise, the head and continue kinds of ZK_OP_POSEIDON
+ *   d_cap                        n x 8 B at a multiple of 8: L
+ * The rows from sum K_b up to n hold 0 in every output and kind 2 (off).  d_rows_needed, one uint64_t on the device at a multiple
+ * of 8 or NULL, receives the unsaturated sum K_b: one store, no atomics.  The reference's two leading table rows are the caller's
+ * pointer offset; domain_spec is always 0 and not written.  ZK_OP_POSEIDON over d_out and d_input1 with width0 = width1 = 32, d_cap
+ * with cap_width = 8, cap_scale = 2^64, d_kinds and ZK_POSEIDON_FINAL gives the table's hash_id with no host re-packing.
+ * No lane walks a bytecode: the starts are a device scan (that of ZK_OP_BYTECODE_ROWS) into a scratch slot of the two ops' own, a
+ * workgroup takes a tile of 1024 rows and finds the bytecodes of its first and last row by one search each, each lane its own inside
+ * that window; a field's bytes come as up to nine aligned dwords per lane, single bytes at the two ends of a bytecode; the powers
+ * of 256 and the inverses of 1 .. 30 are compile-time constants.  No atomics; the result is a pure function of the input.  For both
+ * ops ZK_FIELD_FQ, nonzero flags, a non-NULL d_b, an index_width other than 4 or 8, NULL or misaligned d_offsets or d_lens with
+ * count > 0, NULL d_bytes with total_bytes > 0, an output at an address that is no multiple of its alignment above, n >= 2^32,
+ * total_bytes >= 2^61, any overlap between an output and any input or another output: ZK_ERR_INVALID_ARG before any launch, nothing
+ * is written; the arguments are validated before n is looked at, n = 0 is then ZK_OK and writes nothing, d_rows_needed included.
+ * Booked under the zk_prof names "code_hash_rows" and "code_hash_table" with count * 2 * index_width + total_bytes + n * (32 + the
+ * widths of the outputs given) algorithmic bytes per call, + 8 with d_rows_needed.
  * Other op values (5, 6, 7, 11, ...) are refused. */
 int zk_field_vec_op(zk_ctx* ctx, int field, int op, const void* d_a, const void* d_b, void* d_out, size_t n);
 /* out[i] = a[i] * s  (s: host pointer to one element) */

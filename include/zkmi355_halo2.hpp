@@ -253,6 +253,18 @@ inline void copy_rlc(const Context& c, const zk_copy_rlc& desc, const Fr& r_word
 inline void exp_rows(const Context& c, const zk_exp_rows& desc, size_t n, void* d_exponentiation_lo_hi) {
     c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_EXP_ROWS, &desc, nullptr, d_exponentiation_lo_hi, n));
 }
+// The eight columns the Poseidon-hash extension adds to the rows of the bytecode circuit (zk_field_vec_op with ZK_OP_CODE_HASH_ROWS;
+// asynchronous on the context's stream).  desc: a zk_code_hash_rows -- the bytes, offsets and lengths as for bytecode_rows(), and the
+// typed outputs wanted, each a device pointer or nullptr.  d_field_input (n x 32 B) receives field_input.
+inline void code_hash_rows(const Context& c, const zk_code_hash_rows& desc, size_t n, void* d_field_input) {
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_CODE_HASH_ROWS, &desc, nullptr, d_field_input, n));
+}
+// The code-hash rows of the Poseidon table from the same bytes (ZK_OP_CODE_HASH_TABLE).  desc: a zk_code_hash_table -- input1, control,
+// heading_mark, the kinds and the capacity column of ZK_OP_POSEIDON, each a device pointer or nullptr; d_rows_needed receives the rows
+// of all bytecodes for the caller to compare with n.  d_input0 (n x 32 B) receives input0.
+inline void code_hash_table(const Context& c, const zk_code_hash_table& desc, size_t n, void* d_input0) {
+    c.check(zk_field_vec_op(c.raw(), ZK_FIELD_FR, ZK_OP_CODE_HASH_TABLE, &desc, nullptr, d_input0, n));
+}
 
 // poly::EvaluationDomain::new(j, k)
 class EvaluationDomain {

@@ -301,6 +301,48 @@ pub struct zk_exp_rows {
     pub d_parity_u16_128: *mut c_void,
     pub d_rows_needed: *mut c_void,
 }
+/// `zk_field_vec_op` ops: the eight columns the Poseidon-hash extension adds to the bytecode circuit (`d_out` is `field_input`) and
+/// the code-hash rows of the Poseidon table (`d_out` is `input0`), from the code bytes of `zk_bytecode_rows`.  For both `d_a` is a
+/// HOST pointer to the struct below and `d_b` null.
+pub const ZK_OP_CODE_HASH_ROWS: c_int = 34;
+pub const ZK_OP_CODE_HASH_TABLE: c_int = 36;
+/// `zk_code_hash_rows`: `d_bytes`, `total_bytes`, `d_offsets`, `d_lens` and `index_width` are those of `zk_keccak`, with `count`
+/// entries; every output may be null.  `flags` must be 0.
+#[repr(C)]
+pub struct zk_code_hash_rows {
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub d_offsets: *const c_void,
+    pub d_lens: *const c_void,
+    pub d_control_length: *mut c_void,
+    pub d_bytes_in_field_index: *mut c_void,
+    pub d_bytes_in_field_inv: *mut c_void,
+    pub d_is_field_border: *mut c_void,
+    pub d_padding_shift: *mut c_void,
+    pub d_field_index: *mut c_void,
+    pub d_field_index_inv: *mut c_void,
+    pub count: u32,
+    pub index_width: u8,
+    pub flags: u8,
+}
+/// `zk_code_hash_table`: the same inputs; `d_kinds` and `d_cap` are the kinds and the capacity column of `ZK_OP_POSEIDON`,
+/// `d_rows_needed` receives the rows of all bytecodes as one `u64` for the caller to compare with `n`.
+#[repr(C)]
+pub struct zk_code_hash_table {
+    pub d_bytes: *const c_void,
+    pub total_bytes: u64,
+    pub d_offsets: *const c_void,
+    pub d_lens: *const c_void,
+    pub d_input1: *mut c_void,
+    pub d_control: *mut c_void,
+    pub d_heading_mark: *mut c_void,
+    pub d_kinds: *mut c_void,
+    pub d_cap: *mut c_void,
+    pub d_rows_needed: *mut c_void,
+    pub count: u32,
+    pub index_width: u8,
+    pub flags: u8,
+}
 
 /// `zk_transcript_vtable`: every transcript operation of a proving session is forwarded to the
 /// caller's `T: TranscriptWrite<G1Affine, _>` (see `transcript.rs`).

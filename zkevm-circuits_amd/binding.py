@@ -36,6 +36,8 @@ OP_BYTECODE_ROWS = 26                                 # out[i] = the code hash o
 OP_COPY_ROWS = 28                                     # out[i] = the addr cell (8 bytes) of row i of the copy circuit, from copy events on the device (ZK_OP_COPY_ROWS)
 OP_COPY_RLC = 30                                      # out[i] = value_acc of row i of the copy circuit (ZK_OP_COPY_RLC)
 OP_EXP_ROWS = 32                                      # out[i] = the exponentiation_lo_hi cell (16 bytes) of row i of the exponentiation circuit (ZK_OP_EXP_ROWS)
+OP_CODE_HASH_ROWS = 34                                # out[i] = field_input of row i of the bytecode circuit's Poseidon-hash extension (ZK_OP_CODE_HASH_ROWS)
+OP_CODE_HASH_TABLE = 36                               # out[i] = input0 of code-hash row i of the Poseidon table (ZK_OP_CODE_HASH_TABLE)
 # quotient-program opcodes (csrc/quotient.hip)
 Q_END, Q_PUSH_COL, Q_PUSH_CONST, Q_ADD, Q_SUB, Q_MUL, Q_NEG, Q_SQUARE, Q_DOUBLE, Q_FOLD, Q_MUL_CONST, Q_ADD_CONST, Q_TEE_TMP, Q_PUSH_TMP = range(14)
 
@@ -187,6 +189,23 @@ class _ExpEvent(ctypes.Structure):
 class _ExpRows(ctypes.Structure):
     """zk_exp_rows: the events and the typed outputs of ZK_OP_EXP_ROWS (host memory; every pointer is a device pointer or NULL)"""
     _fields_ = [("d_events", ctypes.c_void_p), ("count", ctypes.c_uint32), ("flags", ctypes.c_uint8)] + [("d_" + name, ctypes.c_void_p) for name in EXP_ROWS_OUTPUTS]
+
+
+CODE_HASH_ROWS_OUTPUTS = ("control_length", "bytes_in_field_index", "bytes_in_field_inv", "is_field_border", "padding_shift", "field_index", "field_index_inv")
+CODE_HASH_TABLE_OUTPUTS = ("input1", "control", "heading_mark", "kinds", "cap", "rows_needed")
+_CODE_HASH_SHARED = [("d_bytes", ctypes.c_void_p), ("total_bytes", ctypes.c_uint64), ("d_offsets", ctypes.c_void_p), ("d_lens", ctypes.c_void_p)]
+_CODE_HASH_TAIL = [("count", ctypes.c_uint32), ("index_width", ctypes.c_uint8), ("flags", ctypes.c_uint8)]
+
+
+class _CodeHashRows(ctypes.Structure):
+    """zk_code_hash_rows: the code bytes and the typed outputs of ZK_OP_CODE_HASH_ROWS (host memory; every pointer is a device pointer
+    or NULL)"""
+    _fields_ = _CODE_HASH_SHARED + [("d_" + name, ctypes.c_void_p) for name in CODE_HASH_ROWS_OUTPUTS] + _CODE_HASH_TAIL
+
+
+class _CodeHashTable(ctypes.Structure):
+    """zk_code_hash_table: the code bytes and the outputs of ZK_OP_CODE_HASH_TABLE"""
+    _fields_ = _CODE_HASH_SHARED + [("d_" + name, ctypes.c_void_p) for name in CODE_HASH_TABLE_OUTPUTS] + _CODE_HASH_TAIL
 
 
 def _host_ptr(a: np.ndarray):
@@ -998,6 +1017,36 @@ class Context:
             raise TypeError(f"exp_rows: unknown outputs {sorted(unknown)}")
         desc = _ExpRows(ptr_of(events), count, 0, *(ptr_of(outputs.get(name)) for name in EXP_ROWS_OUTPUTS))
         self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_EXP_ROWS, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(exponentiation_lo_hi)), ctypes.c_size_t(n)))
+
+    def code_hash_rows(self, data, total_bytes, offsets, lens, index_width, count, n, field_input, **outputs):
+        """The eight columns the Poseidon-hash extension adds to the n rows of the bytecode circuit (zk_field_vec_op with
+        ZK_OP_CODE_HASH_ROWS).  data, total_bytes, offsets, lens, index_width, count and the rows are those of bytecode_rows(): a
+        bytecode of L bytes owns a header row and a row per byte, the rows behind the last bytecode are padding.  field_input
+        (n x 32 B at a multiple of 16) receives the big-endian integer of the bytes of the row's 31-byte field up to the row's own;
+        outputs: any of CODE_HASH_ROWS_OUTPUTS -- bytes_in_field_inv and padding_shift n x 32 B Montgomery Fr at a multiple of 16,
+        control_length n x 4 B, bytes_in_field_index, is_field_border, field_index and field_index_inv n x 1 B at any address.  An
+        entry that does not lie inside the total_bytes counts as an empty bytecode; a bytecode that does not fit into the n rows is
+        cut.  Every buffer: a DeviceBuffer or a device pointer.  No output may overlap an input or another output."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        unknown = set(outputs) - set(CODE_HASH_ROWS_OUTPUTS)
+        if unknown:
+            raise TypeError(f"code_hash_rows: unknown outputs {sorted(unknown)}")
+        desc = _CodeHashRows(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), *(ptr_of(outputs.get(name)) for name in CODE_HASH_ROWS_OUTPUTS), count, index_width, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_CODE_HASH_ROWS, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(field_input)), ctypes.c_size_t(n)))
+
+    def code_hash_table(self, data, total_bytes, offsets, lens, index_width, count, n, input0, **outputs):
+        """The code-hash rows of the Poseidon table from the same code bytes (zk_field_vec_op with ZK_OP_CODE_HASH_TABLE): a bytecode
+        of L bytes owns ceil(L / 62) of the n rows, an empty one none.  input0 (n x 32 B at a multiple of 16) receives the first
+        31-byte word of each block; outputs: any of CODE_HASH_TABLE_OUTPUTS -- input1 n x 32 B, control n x 16 B ((L - 62 j) 2^64),
+        heading_mark and kinds n x 1 B, cap n x 8 B (L), rows_needed one uint64 that receives the rows of all bytecodes for the caller
+        to compare with n.  The rows behind the last bytecode hold 0 and kind 2.  poseidon(input0, 32, input1, 32, n, hash_id, cap=cap,
+        cap_width=8, cap_scale=2^64 as Montgomery Fr, kinds=kinds, final=True) then is the table's hash_id."""
+        ptr_of = lambda b: None if b is None else b.ptr if isinstance(b, DeviceBuffer) else b
+        unknown = set(outputs) - set(CODE_HASH_TABLE_OUTPUTS)
+        if unknown:
+            raise TypeError(f"code_hash_table: unknown outputs {sorted(unknown)}")
+        desc = _CodeHashTable(ptr_of(data), total_bytes, ptr_of(offsets), ptr_of(lens), *(ptr_of(outputs.get(name)) for name in CODE_HASH_TABLE_OUTPUTS), count, index_width, 0)
+        self._ck(lib().zk_field_vec_op(self.h, FIELD_FR, OP_CODE_HASH_TABLE, ctypes.byref(desc), None, ctypes.c_void_p(ptr_of(input0)), ctypes.c_size_t(n)))
 
     def fr_scale(self, a: DeviceBuffer, s: np.ndarray, n: int):
         self._ck(lib().zk_fr_scale(self.h, ctypes.c_void_p(a.ptr), _host_ptr(np.ascontiguousarray(s)), ctypes.c_size_t(n)))

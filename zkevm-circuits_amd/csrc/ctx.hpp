@@ -33,7 +33,7 @@ struct zk_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipDeviceProp_t prop{};
     // scratch arenas, grown on demand (never shrunk): index = purpose
-    zk::Scratch scratch[23];
+    zk::Scratch scratch[24];
     // side stream + events for pipelining consecutive MSMs (msm.hip): created on first use
     hipStream_t stream2 = nullptr, stream2b = nullptr, stream2c = nullptr;
     std::vector<hipStream_t> owned_streams;      // every stream zk_ctx_create made (roles may share one; 'd' entries of the layout have no role at all)
@@ -215,7 +215,7 @@ struct zk_srs {
     } while (0)
 
 namespace zk {
-enum ScratchSlot { SC_NTT = 0, SC_MSM_KEYS = 1, SC_MSM_BUCKETS = 2, SC_MSM_MISC = 3, SC_POLY = 4, SC_POLY2 = 5, SC_TMP = 6, SC_TMP2 = 7, SC_MSM_BUCKETS2 = 8, SC_MSM_RESULTS = 9, SC_QTMP = 10, SC_COMM = 11, SC_MSM_BUCKETS3 = 12, SC_MSM_BUCKETS4 = 13, SC_MSM_DESC = 14, SC_MSM_TAILS = 15, SC_NTT_AUX = 16, SC_QACC = 17, SC_QSLICE = 18, SC_KEYSORT = 19, SC_BYTECODE = 20, SC_COPY = 21, SC_EXP = 22 };
+enum ScratchSlot { SC_NTT = 0, SC_MSM_KEYS = 1, SC_MSM_BUCKETS = 2, SC_MSM_MISC = 3, SC_POLY = 4, SC_POLY2 = 5, SC_TMP = 6, SC_TMP2 = 7, SC_MSM_BUCKETS2 = 8, SC_MSM_RESULTS = 9, SC_QTMP = 10, SC_COMM = 11, SC_MSM_BUCKETS3 = 12, SC_MSM_BUCKETS4 = 13, SC_MSM_DESC = 14, SC_MSM_TAILS = 15, SC_NTT_AUX = 16, SC_QACC = 17, SC_QSLICE = 18, SC_KEYSORT = 19, SC_BYTECODE = 20, SC_COPY = 21, SC_EXP = 22, SC_CODE_HASH = 23 };
 
 // host-side field helpers (slow path, used for constants / tables only)
 Fr fr_from_u64(uint64_t v);
@@ -253,6 +253,8 @@ void bc_scan(zk_ctx* ctx, uint32_t* w, uint64_t count, uint32_t* tmp, uint32_t c
 int copy_rows_run(zk_ctx* ctx, const zk_copy_rows* desc, const void* h_b, void* d_out, uint64_t n);   // copy_rows.hip: ZK_OP_COPY_ROWS of zk_field_vec_op
 int copy_rlc_run(zk_ctx* ctx, const zk_copy_rlc* desc, const void* h_challenges, void* d_out, uint64_t n);   // copy_rows.hip: ZK_OP_COPY_RLC of zk_field_vec_op
 int exp_rows_run(zk_ctx* ctx, const zk_exp_rows* desc, const void* h_b, void* d_out, uint64_t n);   // exp_rows.hip: ZK_OP_EXP_ROWS of zk_field_vec_op
+int code_hash_rows_run(zk_ctx* ctx, const zk_code_hash_rows* desc, const void* h_b, void* d_out, uint64_t n);     // code_hash_rows.hip: ZK_OP_CODE_HASH_ROWS of zk_field_vec_op
+int code_hash_table_run(zk_ctx* ctx, const zk_code_hash_table* desc, const void* h_b, void* d_out, uint64_t n);   // code_hash_rows.hip: ZK_OP_CODE_HASH_TABLE of zk_field_vec_op
 // G1 encodings read on the device (params.hip k_g1_decode): 32 B compressed, 64 B Montgomery limbs, 64 B big-endian x || y (EVM)
 enum G1Enc : int { G1_ENC_COMPRESSED = 0, G1_ENC_RAW = 1, G1_ENC_BE_XY = 2 };
 int g1_decode_run(zk_ctx* ctx, const void* d_in, int enc, G1Affine* d_out, uint64_t n, uint32_t* d_bad, uint8_t* d_bad_at);

@@ -907,6 +907,9 @@ static const DescOp DESC_OPS[] = {
     {ZK_OP_COPY_RLC, "the copy rows are defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(copy_rlc_run(ctx, (const zk_copy_rlc*)a, b, o, n))},
     // h_b: must be NULL (exp_rows_run says so in its own words)
     {ZK_OP_EXP_ROWS, "the exponentiation rows are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(exp_rows_run(ctx, (const zk_exp_rows*)a, b, o, n))},
+    // h_b: must be NULL (the two say so in their own words)
+    {ZK_OP_CODE_HASH_ROWS, "the code hash rows are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(code_hash_rows_run(ctx, (const zk_code_hash_rows*)a, b, o, n))},
+    {ZK_OP_CODE_HASH_TABLE, "the code hash rows are defined over Fr only", DescOp::B_OPTIONAL, ZK_DESC_RUN(code_hash_table_run(ctx, (const zk_code_hash_table*)a, b, o, n))},
     // h_b: the constant and the weights
     {ZK_OP_ROW_RLC, "the row RLC is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_rlc_run(ctx, (const zk_row_rlc*)a, b, (Fr*)o, n))},
     {ZK_OP_ROW_INV0, "the row inverse is defined over Fr only", DescOp::B_REQUIRED, ZK_DESC_RUN(fr_row_inv0_run(ctx, (const zk_row_inv0*)a, b, (Fr*)o, n))},
