@@ -199,6 +199,42 @@ __host__ __device__ __forceinline__ G1Xyzz29 add29pt(const G1Xyzz29& p, const G1
     return r;
 }
 
+// ---- the group FFT's butterfly (ecntt.hip; compiled for the host by tests/host_ecntt_harness.hip) ---------------------
+__host__ __device__ __forceinline__ int clz32(uint32_t v) {         // v != 0
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __clz(v);
+#else
+    return __builtin_clz(v);
+#endif
+}
+// k * P, k a canonical 256-bit integer, MSB-first double-and-add
+__host__ __device__ inline G1Xyzz29 mul_scalar29(const G1Xyzz29& p, const Fr& k) {
+    int top = -1;
+#pragma unroll 1
+    for (int w = 7; w >= 0; --w) if (k.l[w]) { top = 32 * w + 31 - clz32(k.l[w]); break; }
+    G1Xyzz29 acc = identity29();
+#pragma unroll 1
+    for (int bit = top; bit >= 0; --bit) {
+        acc = dbl29pt(acc);
+        if ((k.l[bit >> 5] >> (bit & 31)) & 1) acc = add29pt(acc, p);
+    }
+    return acc;
+}
+// -P for a point that keeps the stored invariant (0 < y < 8p: no 2-torsion on G1)
+__host__ __device__ __forceinline__ G1Xyzz29 neg29pt(const G1Xyzz29& p) {
+    if (is_identity29(p)) return p;
+    G1Xyzz29 r = p;
+    r.y = sub_n<8>(zero29(), p.y);
+    return r;
+}
+// one radix-2 DIT butterfly: (u, v) -> (lo, hi) = (u + w v, u - w v); w a canonical 256-bit integer, has_w = 0 stands for w = 1
+__host__ __device__ __forceinline__ void ecntt_butterfly29(const G1Xyzz29& u, const G1Xyzz29& v, const Fr& w_canonical, bool has_w, G1Xyzz29* lo, G1Xyzz29* hi) {
+    G1Xyzz29 wv = v;
+    if (has_w) wv = mul_scalar29(v, w_canonical);
+    *lo = add29pt(u, wv);
+    *hi = add29pt(u, neg29pt(wv));
+}
+
 // ---- conversions ------------------------------------------------------------------------------
 // canonical 8x32 affine in R' form -> limbs
 __device__ __forceinline__ G1Affine29 load_affine29(const G1Affine* p) {

@@ -32,38 +32,19 @@ __global__ void __launch_bounds__(256) k_ecntt_load(const G1Affine* __restrict__
     stg29(pts + bitrev32((uint32_t)i, log_n), q);
 }
 
-// k * P, k a canonical 256-bit integer, MSB-first double-and-add
-__device__ inline G1Xyzz29 mul_scalar29(const G1Xyzz29& p, const Fr& k) {
-    int top = -1;
-#pragma unroll 1
-    for (int w = 7; w >= 0; --w) if (k.l[w]) { top = 32 * w + 31 - __clz(k.l[w]); break; }
-    G1Xyzz29 acc = identity29();
-#pragma unroll 1
-    for (int bit = top; bit >= 0; --bit) {
-        acc = dbl29pt(acc);
-        if ((k.l[bit >> 5] >> (bit & 31)) & 1) acc = add29pt(acc, p);
-    }
-    return acc;
-}
-// -P for a point that keeps the stored invariant (0 < y < 8p: no 2-torsion on G1)
-__device__ __forceinline__ G1Xyzz29 neg29pt(const G1Xyzz29& p) {
-    if (is_identity29(p)) return p;
-    G1Xyzz29 r = p;
-    r.y = sub_n<8>(zero29(), p.y);
-    return r;
-}
-
 // one DIT stage: (u, v) -> (u + w v, u - w v), w = tw[j << (log_n - 1 - s)] (Montgomery Fr)
 __global__ void __launch_bounds__(256) k_ecntt_stage(G1Xyzz29* __restrict__ pts, const Fr* __restrict__ tw, int log_n, int s) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= (1ull << (log_n - 1))) return;
     const uint64_t half = 1ull << s, j = b & (half - 1);
     const uint64_t i0 = ((b >> s) << (s + 1)) | j, i1 = i0 + half;
-    const G1Xyzz29 u = ldg29(pts + i0);
-    G1Xyzz29 v = ldg29(pts + i1);
-    if (j) v = mul_scalar29(v, from_mont(ldg(tw + (j << (log_n - 1 - s)))));
-    stg29(pts + i0, add29pt(u, v));
-    stg29(pts + i1, add29pt(u, neg29pt(v)));
+    const G1Xyzz29 u = ldg29(pts + i0), v = ldg29(pts + i1);
+    Fr w = Fr::zero();
+    if (j) w = from_mont(ldg(tw + (j << (log_n - 1 - s))));
+    G1Xyzz29 lo, hi;
+    ecntt_butterfly29(u, v, w, j != 0, &lo, &hi);               // ec29.hip.hpp: mul_scalar29, add29pt, neg29pt
+    stg29(pts + i0, lo);
+    stg29(pts + i1, hi);
 }
 
 // out[i] = affine, R form, of scale * P[i]
